@@ -27,9 +27,21 @@ runs (so it is a kernel duration, always <= ms_per_step; the rocprofv3 average o
 kernel under profiles/ must agree); the span of the same kernel inside the pipelined timed
 region, where it shares the chip with the previous MSM's tail, is reported separately.
 
-The oracle (oracle/) is used only by the cpu_baseline leg: as the checker of the GPU result
-and as the timed CPU port (oracle/cpu_msm_fast.c on every host core the process may use).
-bench.py exits non-zero if either check fails.
+A plain run (no --full) sets up, warms up, times the --steps steps, writes --dump-outputs and
+prints the line: `value` (pairs/s) and `ms_per_step` of the timed steps, nothing else measured.
+--full adds everything else the line has carried: the kernels alone and the roofline, one
+synchronous call, host slices, resident / kept bases, the verifies/s leg, the CPU baseline, the
+size table, the adversarial families, config 5 and (N > 1) the multi-GPU figures.
+
+The oracle (oracle/) is used only by the cpu_baseline leg of --full: as the checker of the GPU
+result and as the timed CPU port (oracle/cpu_msm_fast.c on every host core the process may
+use).  bench.py exits non-zero if either check fails.
+
+--dump-outputs DIR writes what the last timed step returned -- the G1 point of the MSM (or of
+this rank's window range with --emulate-world) as the library hands it back, 18 uint64 limbs =
+X, Y, Z in Montgomery form -- as DIR/msm_g1.npy: float64[3, 12], each coordinate as twelve
+little-endian 32-bit words (exact in float64).  The inputs are seeded: the same arguments give
+the same inputs, and so the same file, on every run and build.
 """
 import argparse
 import json
@@ -42,12 +54,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "go-curdleproofs_amd"))
-# The library keeps up to 10 HIP streams busy (sort, accumulate, one tail per MSM in flight);
-# ROCm's default of 4 hardware queues per process makes some of them share a queue and
-# serialise.  Must be set before the HIP runtime initialises -- under rocprofv3 the profiler's
-# preload initialises HIP before Python runs, so export it in the shell there
-# (tools/refresh_profiles.sh does).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# The HIP runtime's hardware queue count is the environment's: the library's streams (sort,
+# accumulate, one tail per MSM in flight) share the queues it grants.
 
 R_MOD = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 R_INV = pow(1 << 256, -1, R_MOD)
@@ -142,7 +150,18 @@ def main():
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="diagnostic: on ONE GPU, run only the share rank 0 of an N-rank job would run "
                          "(no collective); prints the per-rank step time, not a bench line")
+    ap.add_argument("--full", action="store_true",
+                    help="msm mode: after the timed steps, also everything beyond the headline -- kernels alone and roofline, "
+                         "single call, host slices, resident / kept bases, verifies/s, CPU baseline and result checks, size "
+                         "table, adversarial families, config 5, multi-GPU figures (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="msm mode: write the last timed step's result to DIR/msm_g1.npy (float64[3, 12]: X, Y, Z as the "
+                         "library returns them, Montgomery form, twelve little-endian 32-bit words each)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and (args.sweep or args.mode != "msm"):
+        ap.error("--dump-outputs writes the MSM line's result: --mode msm without --sweep")
 
     import torch
     import curdlemsm as cm
@@ -364,32 +383,38 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     value = n * args.steps / elapsed
     host_ms = {k_: round(v * 1e3 / args.steps, 4) for k_, v in host_t.items()}   # host time per step in submit / wait
+    if args.dump_outputs is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        words = np.ascontiguousarray(result, dtype=np.uint64).view(np.uint32)     # little-endian: low word first
+        np.save(os.path.join(args.dump_outputs, "msm_g1.npy"), words.astype(np.float64).reshape(3, 12))
 
-    # After the timed region, with nothing else in flight: every kernel's own duration (HIP
-    # events, same streams), the sorted-entry and fragment counts, and the latency of one
+    # After the timed region, with nothing else in flight (--full): every kernel's own duration
+    # (HIP events, same streams), the sorted-entry and fragment counts, and the latency of one
     # isolated synchronous call (the entry point a single caller uses).
-    solo_ms, counts = {}, {}
-    cm.profile_enable(1)
-    for _ in range(5):
-        barrier()
-        collect(submit())
-        if dist is not None:
-            flush()
-        pr = cm.profile_last()
-        for name, ms in pr["kernels"].items():
-            solo_ms.setdefault(name, []).append(ms)
-        counts = {"entries": pr["entries"], "fragments": pr["fragments"]}
-    lat = []
+    solo_ms, counts, single_call_ms = {}, {}, None
+    if args.full:
+        cm.profile_enable(1)
+        for _ in range(5):
+            barrier()
+            collect(submit())
+            if dist is not None:
+                flush()
+            pr = cm.profile_last()
+            for name, ms in pr["kernels"].items():
+                solo_ms.setdefault(name, []).append(ms)
+            counts = {"entries": pr["entries"], "fragments": pr["fragments"]}
+        lat = []
+        cm.profile_enable(0)
+        for _ in range(5):
+            barrier()
+            t1 = time.perf_counter()
+            if args.split == "windows":
+                cm.msm_g1_device(pts_ptr, sc_ptr, n_mine, window_bits=c_mine, win_begin=wb, win_end=we, flags=msm_flags)
+            else:
+                cm.msm_g1_device(pts_ptr, sc_ptr, n_mine)
+            lat.append((time.perf_counter() - t1) * 1e3)
+        single_call_ms = float(np.median(lat))
     cm.profile_enable(0)
-    for _ in range(5):
-        barrier()
-        t1 = time.perf_counter()
-        if args.split == "windows":
-            cm.msm_g1_device(pts_ptr, sc_ptr, n_mine, window_bits=c_mine, win_begin=wb, win_end=we, flags=msm_flags)
-        else:
-            cm.msm_g1_device(pts_ptr, sc_ptr, n_mine)
-        lat.append((time.perf_counter() - t1) * 1e3)
-    single_call_ms = float(np.median(lat))
 
     # What an N > 1 line must say beside `value`: the pipelined figure is a THROUGHPUT (6 window-range
     # calls in flight per rank, the exchange of step i finished during step i + 1); one synchronous call -- what
@@ -397,7 +422,7 @@ def main():
     # (barrier, every rank's synchronous window-range call, all_gather, sum; MAX over ranks), the exchange alone, and the
     # SAME contract at one rank (the whole MSM with the flag on this rank's own GPU: the baseline a speed-up is a ratio to).
     multi = None
-    if dist is not None and not args.emulate_world:   # (--emulate-world with --force-dist: one rank's share WITH the exchange, at world size 1)
+    if args.full and dist is not None and not args.emulate_world:   # (--emulate-world with --force-dist: one rank's share WITH the exchange, at world size 1)
         from curdlemsm.distributed import msm_g1_distributed
         on_gpu = dist.get_backend() == "nccl"
 
@@ -462,7 +487,7 @@ def main():
     # split otherwise converts ALL points again).  Beside the headline at every N, never `value`, which stays
     # on gnark-layout inputs.  All ranks run it (the steps exchange their partials like the timed ones).
     resident = None
-    if args.logn <= 22 and not args.no_verify and not bases_box["on"] and not args.emulate_world:
+    if args.full and args.logn <= 22 and not args.no_verify and not bases_box["on"] and not args.emulate_world:
         bases_box["on"] = True
         try:
             run_steps(depth + 1)
@@ -500,7 +525,8 @@ def main():
     # ... and with CURDLE_MSM_BASES_UNCHANGED on the SAME gnark-layout device array (the library keeps its converted copy):
     # the one-rank figure of the contract every rank of an N > 1 window split runs under -- the scaling baseline.
     kept = None
-    if dist is None and args.logn <= 22 and not args.no_verify and not keep_bases and not args.emulate_world and not args.resident_bases:
+    if args.full and dist is None and args.logn <= 22 and not args.no_verify and not keep_bases and not args.emulate_world \
+            and not args.resident_bases:
         msm_flags = cm.MSM_BASES_UNCHANGED
         try:
             run_steps(depth + 1)
@@ -529,7 +555,8 @@ def main():
     # 1 / 2 / 4 / 8 GPUs" table by themselves): every size through ONE synchronous distributed call on ALL ranks (window
     # ranges under the line's contract; barrier, call, MAX over the ranks; median of 7); rank 0 adds the CPU port below.
     dsweep = None
-    if dist is not None and not args.emulate_world and args.logn == 20 and not args.no_cpu_baseline and args.split == "windows":
+    if args.full and dist is not None and not args.emulate_world and args.logn == 20 and not args.no_cpu_baseline \
+            and args.split == "windows":
         from curdlemsm.distributed import msm_g1_distributed
         on_gpu = dist.get_backend() == "nccl"
         dsweep = []
@@ -606,16 +633,18 @@ def main():
             "dtype": "u32", "data": "synthetic",
             "config": {"workload": f"single G1 MSM, N=2^{args.logn} random Fr scalars x walk points, inputs resident in HBM",
                        "n_pairs": n, "window_bits": c, "num_windows": W, "in_flight": depth,
-                       "single_call_ms": round(single_call_ms, 4), "host_ms_per_step": host_ms,
+                       "host_ms_per_step": host_ms,
                        "parallelism": "single GPU" if dist is None else
                        (f"Pippenger windows split x{world}" if args.split == "windows" else f"point ranges x{world}")
                        + f", all_gather of 144 B partials over {dist.get_backend()}"},
             "roofline": roofline,
         }
+        if single_call_ms is not None:
+            out["config"]["single_call_ms"] = round(single_call_ms, 4)
         # the verification leg BEFORE the CPU baseline: sixteen saturated host threads right in
         # front of a latency measurement run into the box's CPU quota (observed: 12 % fewer
         # verifies/s)
-        if world == 1 and args.logn <= 22 and not args.no_verify:
+        if args.full and world == 1 and args.logn <= 22 and not args.no_verify:
             # PCIe-inclusive: the entry point a cgo caller binds takes HOST slices (pageable memory);
             # reported beside the headline, never as `value`
             pts_h = d_pts.cpu().numpy().view(np.uint64)
@@ -644,9 +673,9 @@ def main():
         if multi is not None:
             out["config"]["multi_gpu"] = multi
             out["config"]["bases_unchanged_flag"] = keep_bases
-        if world == 1 and not args.no_verify and args.logn == 20:
+        if args.full and world == 1 and not args.no_verify and args.logn == 20:
             out["verify"] = verify_leg(cm, 200, 20)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # on rank 0 at every N (north_star: the CPU "in the same run"); the other ranks wait at the
             # barrier below -- seconds, far inside the collective's timeout
             out["cpu_baseline"] = cpu_baseline(cm, k, q, n, sc, result, d_pts)
@@ -680,13 +709,13 @@ def main():
     # BASELINE config 5 beside the headline at every N (replicas: every rank verifies its share of
     # 1,024 Whisk shuffle proofs; collective calls, so all ranks take part)
     c5 = None
-    if not args.no_verify and args.logn == 20 and not args.emulate_world:
+    if args.full and not args.no_verify and args.logn == 20 and not args.emulate_world:
         c5 = whisk_batch_leg(cm, torch, dist, dev, rank, world, 1024, 3, 1)
     if rank == 0:
         # One process, several GPUs through the C ABI (curdle_init_devices) -- in a CHILD process with
         # a timeout, after everything above is measured, so that nothing in it can take this line
         # down: only when a one-rank run sees more than one GPU (never on a one-GPU lease).
-        if world == 1 and not args.no_verify and args.logn == 20 and torch.cuda.device_count() > 1 \
+        if args.full and world == 1 and not args.no_verify and args.logn == 20 and torch.cuda.device_count() > 1 \
                 and os.environ.get("CURDLE_BENCH_MULTI_DEVICE", "1") != "0":
             try:
                 cp = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_multi_device.py")], capture_output=True,

@@ -13,7 +13,7 @@ def test_bench_help_lists_the_modes():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0
     for word in ("--gpus", "--steps", "--warmup", "--sweep", "whisk-batch", "verify", "--emulate-world", "--bases-unchanged",
-                 "--convert-per-call"):
+                 "--convert-per-call", "--full", "--dump-outputs"):
         assert word in p.stdout, word
 
 
@@ -55,7 +55,7 @@ def _run_forced_dist(extra, timeout=600):
 @pytest.mark.gpu
 def test_the_nccl_path_of_the_bench_runs_at_world_size_one(gpu):
     # (--exchange-batch 3 with 6 steps: two full batches through the lagged finish, and the flush at the end)
-    line = _run_forced_dist(["--steps", "6", "--warmup", "2", "--logn", "16", "--no-verify", "--exchange-batch", "3"])
+    line = _run_forced_dist(["--steps", "6", "--warmup", "2", "--logn", "16", "--no-verify", "--exchange-batch", "3", "--full"])
     assert line["n_gpus"] == 1 and line["value"] and line["value"] > 0
     assert "over nccl" in line["config"]["parallelism"]            # the partials went through RCCL's all_gather
     assert "exchange" in line["config"]["host_ms_per_step"]
@@ -92,7 +92,7 @@ def test_two_ranks_over_gloo_print_the_multi_gpu_keys(gpu):
     env = dict(os.environ, CURDLE_DIST_BACKEND="gloo")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-                        "--warmup", "2", "--logn", "16", "--no-verify", "--exchange-batch", "4"], env=env, capture_output=True, text=True,
+                        "--warmup", "2", "--logn", "16", "--no-verify", "--exchange-batch", "4", "--full"], env=env, capture_output=True, text=True,
                        timeout=600)      # (4 of 6 steps in one all_gather, the other two by the flush)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -108,7 +108,7 @@ def test_a_distributed_line_carries_the_size_table_too(gpu):
     """north_star wants N in {2^10 .. 2^20} at 1 / 2 / 4 / 8 GPUs: an N > 1 line (here: the N > 1 path at world size 1
     over nccl) carries the table itself -- one synchronous distributed call per size on all ranks, the CPU port beside
     it on rank 0, bit-compared -- so that the driver's multi-GPU runs fill it without another command."""
-    line = _run_forced_dist(["--steps", "3", "--warmup", "1", "--no-verify"])
+    line = _run_forced_dist(["--steps", "3", "--warmup", "1", "--no-verify", "--full"])
     rows = line["sweep"]
     assert [r["logn"] for r in rows] == [10, 12, 14, 16, 18, 20] and "msm_g1_distributed" in line["sweep_what"]
     assert all(r["gpu_matches_cpu"] and r["wall_ms"] > 0 and r["cpu_port_pairs_per_s"] > 0 for r in rows)
@@ -137,9 +137,9 @@ def test_the_distributed_sweep_runs_on_every_rank(gpu):
 
 @pytest.mark.gpu
 def test_the_default_line_carries_the_size_table(gpu):
-    """north_star's N = 2^10 .. 2^20 table is part of the line the driver records -- wall time,
+    """north_star's N = 2^10 .. 2^20 table is part of the --full line -- wall time,
     pairs/s, the dominant kernel's HBM and multiply-issue fractions, the CPU port on the same inputs, bit-compared."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-verify"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-verify", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -160,3 +160,35 @@ def test_the_default_line_carries_the_size_table(gpu):
     for r in adv["rows"]:
         if r["family"] != "uniform" and r["logn"] >= 16:
             assert r["ratio_sync"] < 1.5 and r["ratio_host_slices"] < 1.5, r      # the bar is 1.25; boxes jitter
+
+
+@pytest.mark.gpu
+def test_a_plain_line_times_the_steps_and_dumps_the_result(gpu, tmp_path):
+    """A plain run (no --full) times exactly the steps it is given and measures nothing beyond them; --dump-outputs
+    writes the last step's point, which must be the closed form (k sum s_i + q sum i s_i) G of the seeded inputs
+    (P_i = (k + i q) G, scalars from the same seed as the run's)."""
+    import numpy as np
+    import bench
+    import coracle as co
+    n = 1 << 14
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--logn", "14",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-1500:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - n) < 1e-6 * n
+    assert line["unit"] == "pairs/s" and line["higher_is_better"] is True and line["dtype"] == "u32" and "N=2^14" in line["metric"]
+    for key in ("cpu_baseline", "verify", "sweep", "adversarial", "config5"):
+        assert key not in line, key
+    got = np.load(tmp_path / "msm_g1.npy")
+    assert got.dtype == np.float64 and got.shape == (3, 12)
+    limbs = got.reshape(-1).astype(np.uint32).view(np.uint64)
+    r1 = gpu.Rand(1)
+    k = bench.limbs_to_int(r1.get_fr()) * bench.R_INV % bench.R_MOD
+    q = bench.limbs_to_int(r1.get_fr()) * bench.R_INV % bench.R_MOD
+    s = [bench.limbs_to_int(row) * bench.R_INV % bench.R_MOD for row in bench.uniform_scalars(np.random.default_rng(2), n)]
+    e = (k * sum(s) + q * sum(i * v for i, v in enumerate(s))) % bench.R_MOD
+    exp = co.jac_normalise(np.concatenate([co.scalar_mul_gen(e), np.array(bench.cm_one_limbs(), dtype=np.uint64)]))
+    assert (limbs == exp).all()

@@ -7,6 +7,8 @@ mutation fuzz of every parser -- the counterpart of the reference CI's `go test 
 (.github/workflows/buildlintcheck.yml:21).  CPU only (GPU AddressSanitizer is not available
 on this pool); any sanitizer report aborts the binary and fails the test."""
 import os
+import platform
+import shutil
 import subprocess
 
 import pytest
@@ -32,8 +34,13 @@ def _run(exe, *args):
 
 @pytest.fixture(scope="module")
 def tsan_harness():
+    """The ThreadSanitizer harness as a command prefix.  GCC's TSan runtime maps its shadow memory at fixed addresses and
+    stops with "FATAL: ThreadSanitizer: unexpected memory mapping" (or a segfault) when a mapping lands there, which
+    the wider mmap randomisation of newer kernels (vm.mmap_rnd_bits = 32) makes happen; the harness therefore runs with address-space randomisation off for
+    itself alone (setarch -R), which changes nothing the sanitizer checks."""
     subprocess.run(["make", "-C", HB, "tsan"], check=True, capture_output=True, timeout=600)
-    return os.path.join(HB, "host_flow_tsan")
+    exe = os.path.join(HB, "host_flow_tsan")
+    return ["setarch", platform.machine(), "-R", exe] if shutil.which("setarch") else [exe]
 
 
 def test_batch_threads_under_tsan(tsan_harness):
@@ -42,7 +49,7 @@ def test_batch_threads_under_tsan(tsan_harness):
     ThreadSanitizer, over the test-only backend."""
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1")
     for args in (("flow", "12"), ("whisk", "0")):
-        p = subprocess.run([tsan_harness, *args], capture_output=True, text=True, timeout=900, env=env)
+        p = subprocess.run([*tsan_harness, *args], capture_output=True, text=True, timeout=900, env=env)
         assert p.returncode == 0, p.stdout + p.stderr
         assert "ThreadSanitizer" not in p.stderr, p.stderr
         assert "ok" in p.stdout
@@ -57,7 +64,7 @@ def test_batch_workers_never_wait_for_a_decoding_while_holding_a_slot(tsan_harne
     killed after the timeout otherwise) with exact accept bits and every slot returned."""
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1", CURDLE_STUB_SLOTS="1", CURDLE_TWO_KERNEL_MAX="0",
                CURDLE_BATCH_GROUP="1", CURDLE_BATCH_CHUNK="1", CURDLE_STUB_DECODE_DELAY_MS="20")
-    p = subprocess.run([tsan_harness, "slots", "12"], capture_output=True, text=True, timeout=600, env=env)
+    p = subprocess.run([*tsan_harness, "slots", "12"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "ThreadSanitizer" not in p.stderr, p.stderr
     assert "over 8 slots: ok" in p.stdout
@@ -69,7 +76,7 @@ def test_batch_is_sharded_over_the_configured_devices(tsan_harness):
     its device first, each posed device sees work, the accept bits are exact -- under
     ThreadSanitizer."""
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1", CURDLE_STUB_DEVICES="3", CURDLE_BATCH_CHUNK="2", CURDLE_BATCH_GROUP="3")
-    p = subprocess.run([tsan_harness, "devices", "12"], capture_output=True, text=True, timeout=600, env=env)
+    p = subprocess.run([*tsan_harness, "devices", "12"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "ThreadSanitizer" not in p.stderr, p.stderr
     assert "sharded over 3 devices: ok" in p.stdout

@@ -269,7 +269,9 @@ def test_the_suite_above_with_two_logical_devices(gpu, tmp_path):
     shim = str(tmp_path / "logical_devices_shim.so")
     subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-Wno-deprecated-declarations", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
                            os.path.join(ROOT, "tools", "logical_devices_shim.cpp"), "-o", shim, "-ldl"])
-    env = dict(os.environ, LD_PRELOAD=shim, CURDLE_TEST_DEVICES="0,1", CURDLE_LOGICAL_DEVICES="2")
+    # in front of whatever the environment already preloads, which stays
+    preload = ":".join(p for p in (shim, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, CURDLE_TEST_DEVICES="0,1", CURDLE_LOGICAL_DEVICES="2")
     p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_multi_device.py"), "-x", "-q",
                         "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     tail = p.stdout[-2500:] + p.stderr[-2500:]
