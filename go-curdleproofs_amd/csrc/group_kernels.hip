@@ -17,6 +17,7 @@
 
 #include "fp28.h"
 #include "quad28.h"
+#include "glv_quad.h"
 #include "msm_kernels.h"
 
 namespace curdle {
@@ -25,19 +26,6 @@ using d28::F28;
 using d28::X28;
 
 static constexpr int kBlock = 256;
-
-// gnark affine point -> internal affine; false for (0, 0) = infinity
-__device__ __forceinline__ bool load_affine(F28& x, F28& y, const uint4* __restrict__ points, size_t i) {
-  u32 w[24];
-  d28::load_words<24>(w, points + i * 6);
-  u32 any = 0;
-#pragma unroll
-  for (int j = 0; j < 24; j++) any |= w[j];
-  if (!any) return false;
-  d28::from_gnark(x, w);
-  d28::from_gnark(y, w + 12);
-  return true;
-}
 
 // One quad per element (quad28.h): the point lives spread over four lanes.
 __global__ void __launch_bounds__(kBlock, 2)
@@ -61,43 +49,22 @@ __global__ void __launch_bounds__(kBlock, 2)
   glv_split(k, a, b, neg_a, neg_b);
   F28 x, y, p, acc;
   q28::set_inf(acc);
-  if (load_affine(x, y, points, i)) {  // s * inf = inf
-    F28 yn, z, beta, bx, p1, p2, p3;
-    d28::set_zero(z);
-    d28::sub<4>(yn, z, y);  // 4p - y
-#pragma unroll
-    for (int j = 0; j < d28::N; j++) beta.l[j] = d28::kBeta(j);
-    d28::mul(bx, x, beta);
-    q28::from_affine(p1, x, neg_a ? yn : y);
-    q28::from_affine(p2, bx, neg_b ? yn : y);
-    p3 = p1;
-    q28::add(p3, p2);
-    // bit 126 of each half in the top bit of its top word
-#pragma unroll
-    for (int j = 3; j > 0; j--) {
-      a[j] = (a[j] << 1) | (a[j - 1] >> 31);
-      b[j] = (b[j] << 1) | (b[j - 1] >> 31);
-    }
-    a[0] <<= 1;
-    b[0] <<= 1;
+  if (glvq::load_affine(x, y, points, i)) {  // s * inf = inf
+    F28 p1, p2, p3;
+    glvq::table(p1, p2, p3, x, y, neg_a, neg_b);
+    glvq::shift(a, b);
     for (int bit = 126; bit >= 0; bit--) {
       q28::dbl(acc);
-      const bool ba = a[3] >> 31, bb = b[3] >> 31;
+      const bool ba = glvq::top_bit(a), bb = glvq::top_bit(b);
       if (ba || bb) {
         q28::sel(p, ba, p1, p2);
         q28::sel(p, ba && bb, p3, p);
         q28::add(acc, p);
       }
-#pragma unroll
-      for (int j = 3; j > 0; j--) {
-        a[j] = (a[j] << 1) | (a[j - 1] >> 31);
-        b[j] = (b[j] << 1) | (b[j - 1] >> 31);
-      }
-      a[0] <<= 1;
-      b[0] <<= 1;
+      glvq::shift(a, b);
     }
   }
-  if (addends && load_affine(x, y, addends, i)) {
+  if (addends && glvq::load_affine(x, y, addends, i)) {
     q28::from_affine(p, x, y);
     q28::add(acc, p);
   }

@@ -198,4 +198,12 @@ hipError_t launch_dacc_scalars(const void* d_checks, uint32_t n_checks, const vo
 hipError_t launch_scalar_mul_batch(const void* points, const void* scalars, int shared_scalar, const void* addends,
                                    uint32_t n, void* out_xyzz, hipStream_t stream);
 
+// tracker_kernels.hip: the two equations of n Whisk tracker proofs (whisk.go:136-146), one byte
+// per member.  points: 5 n gnark affine records (rG, krG, kG, A, B per member) with their
+// CURDLE_DECODE_* status bytes; scalars: s, c per member, canonical, 8 little-endian words each;
+// skip[i] != 0 marks a member not to check; gen: the G1 generator.
+static constexpr uint8_t kTrackerReject = 0, kTrackerAccept = 1, kTrackerError = 2;  // error: a record did not decode, or skip
+hipError_t launch_tracker_check(const void* points, const uint8_t* status, const void* scalars, const uint8_t* skip,
+                                const G1Affine& gen, uint32_t n, uint8_t* out, hipStream_t stream);
+
 }  // namespace curdle

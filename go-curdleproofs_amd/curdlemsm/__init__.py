@@ -62,7 +62,7 @@ SYMBOLS = [
     "curdle_verify_batch", "curdle_verify_set_eager",
     "curdle_whisk_is_valid_shuffle_proof", "curdle_whisk_is_valid_shuffle_proof_batch",
     "curdle_whisk_generate_shuffle_proof",
-    "curdle_whisk_is_valid_tracker_proof", "curdle_whisk_generate_tracker_proof", "curdle_proof_reencode", "curdle_merlin_test_vector", "curdle_g1_decompress_batch", "curdle_g1_decompress_begin", "curdle_g1_decompress_finish", "curdle_g1_decompress_start", "curdle_g1_decompress_points",
+    "curdle_whisk_is_valid_tracker_proof", "curdle_whisk_is_valid_tracker_proof_batch", "curdle_whisk_generate_tracker_proof", "curdle_proof_reencode", "curdle_merlin_test_vector", "curdle_g1_decompress_batch", "curdle_g1_decompress_begin", "curdle_g1_decompress_finish", "curdle_g1_decompress_start", "curdle_g1_decompress_points",
     "curdle_g1_scalar_mul_batch",
     "curdle_g1_compress", "curdle_g1_decompress", "curdle_set_last_error", "curdle_fr_inner_product",
     "curdle_dbases_create", "curdle_dbases_free", "curdle_dbases_size", "curdle_dbases_valid",
@@ -168,6 +168,7 @@ _whisk_valid_shuffle_batch = _sig("curdle_whisk_is_valid_shuffle_proof_batch", C
                                   _vp, _vp, C.c_int, _vp)
 _whisk_gen_shuffle = _sig("curdle_whisk_generate_shuffle_proof", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, _vp)
 _whisk_valid_tracker = _sig("curdle_whisk_is_valid_tracker_proof", C.c_int, _vp, _vp, _vp, C.POINTER(C.c_int))
+_whisk_valid_tracker_batch = _sig("curdle_whisk_is_valid_tracker_proof_batch", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp)
 _whisk_gen_tracker = _sig("curdle_whisk_generate_tracker_proof", C.c_int, _vp, _vp, _vp, _vp)
 _verify_set_eager = _sig("curdle_verify_set_eager", C.c_int, C.c_int)
 _reencode = _sig("curdle_proof_reencode", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t))
@@ -776,6 +777,24 @@ def whisk_is_valid_tracker_proof(tracker: bytes, k_commitment: bytes, proof: byt
     ok = C.c_int(0)
     _check(_whisk_valid_tracker(_ptr(t), _ptr(kc), _ptr(pb), C.byref(ok)))
     return bool(ok.value)
+
+
+def whisk_is_valid_tracker_proof_batch(trackers, k_commitments, proofs) -> np.ndarray:
+    """k tracker proofs at once on the GPU (curdle_whisk_is_valid_tracker_proof_batch): lists of
+    96-byte trackers, 48-byte k commitments and 128-byte proofs.  Returns int32[k]: 1 accept,
+    0 reject, EINVAL where whisk_is_valid_tracker_proof raises CurdleError with EINVAL."""
+    k = len(trackers)
+    if len(k_commitments) != k or len(proofs) != k:
+        raise ValueError("trackers, k commitments and proofs need the same count")
+    if (any(len(t) != 96 for t in trackers) or any(len(c) != 48 for c in k_commitments)
+            or any(len(p) != WHISK_TRACKER_PROOF_SIZE for p in proofs)):
+        raise ValueError("tracker 96 B, k commitment 48 B, tracker proof 128 B")
+    out = np.zeros(k, dtype=np.int32)
+    if k == 0:
+        return out
+    t, kc, pb = _bytes_arr(b"".join(trackers)), _bytes_arr(b"".join(k_commitments)), _bytes_arr(b"".join(proofs))
+    _check(_whisk_valid_tracker_batch(_ptr(t), _ptr(kc), _ptr(pb), k, _ptr(out)))
+    return out
 
 
 def whisk_generate_tracker_proof(tracker: bytes, k, rand: Rand) -> bytes:

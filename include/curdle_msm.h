@@ -382,6 +382,17 @@ int curdle_whisk_generate_shuffle_proof(const curdle_crs* crs, const uint8_t* pr
 /* IsValidWhiskTrackerProof, whisk.go:116 (host only: four scalar multiplications) */
 int curdle_whisk_is_valid_tracker_proof(const uint8_t tracker[CURDLE_WHISK_TRACKER_SIZE], const uint8_t k_commitment[48],
                                         const uint8_t proof[CURDLE_WHISK_TRACKER_PROOF_SIZE], int* ok);
+/* k tracker proofs at once, each answered as curdle_whisk_is_valid_tracker_proof answers it
+ * (IsValidWhiskTrackerProof, whisk.go:116).  trackers: k x 96 bytes, k_commitments: k x 48,
+ * proofs: k x 128, back to back.  The 5 k points are decoded (curve and subgroup checked) and both
+ * equations of every member are checked on the GPU; the transcripts are hashed on the host.
+ * results[i] = 1 (accept), 0 (reject: (false, nil)) or CURDLE_EINVAL where the single call
+ * returns CURDLE_EINVAL ((false, err): a record that is not a point of the subgroup, S >= r).
+ * k = 0: CURDLE_OK, nothing read or written, no device needed.  On a negative return every
+ * results[i] holds that code: "could not compute" never reads as a verdict.  No host fallback:
+ * without a device the call fails with CURDLE_ENODEV. */
+int curdle_whisk_is_valid_tracker_proof_batch(const uint8_t* trackers, const uint8_t* k_commitments,
+                                              const uint8_t* proofs, size_t k, int* results);
 /* GenerateWhiskTrackerProof, whisk.go:149 */
 int curdle_whisk_generate_tracker_proof(const uint8_t tracker[CURDLE_WHISK_TRACKER_SIZE], const uint64_t k[4],
                                         curdle_rand* rand, uint8_t proof_out[CURDLE_WHISK_TRACKER_PROOF_SIZE]);
