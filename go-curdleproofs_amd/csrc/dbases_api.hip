@@ -184,7 +184,14 @@ extern "C" int curdle_msm_g1_dbases_windows(const curdle_dbases* bases, const vo
   void* d28 = nullptr;
   if ((rc = dbases_acquire(cur(), set, &d28))) return rc;  // this context's copy, made on first use
   const uint32_t off[2] = {0, (uint32_t)n};
-  rc = run_device(nullptr, d_scalars, off, 1, window_bits, win_begin, win_end, out_jac, nullptr, d28);
+  MsmCall call{off};
+  call.c = window_bits;
+  call.win_begin = win_begin;
+  call.win_end = win_end;
+  MsmInputs in;
+  in.scalars = d_scalars;
+  in.points28 = d28;
+  rc = run_device(call, in, out_jac);
   dbases_release(set);
   return rc;
 }
@@ -217,10 +224,14 @@ extern "C" int curdle_msm_g1_dbases_host(const curdle_dbases* bases, const uint6
     HIP_TRY(hipSetDevice(cx.device));
     int r;
     if ((r = ensure(S.scalars, n * 32))) return r;
-    const SyncStreams st = sync_streams(cx, S);
+    const Streams st = sync_streams(cx, S);
     HIP_TRY(hipMemcpyAsync(S.scalars.p, scalars, n * 32, hipMemcpyHostToDevice, st.pre));
     const uint32_t off[2] = {0, (uint32_t)n};
-    return run_passes(cx, S, nullptr, S.scalars.p, off, 1, 0, 0, -1, st.pre, st.main, st.tail, out_jac, d28);
+    MsmCall call{off};
+    MsmInputs in;
+    in.scalars = S.scalars.p;
+    in.points28 = d28;
+    return run_passes(cx, S, call, in, st, out_jac);
   };
   rc = body();
   if (rc) drain_slot(cx, S);
@@ -259,8 +270,15 @@ extern "C" int curdle_msm_g1_dbases_submit(const curdle_dbases* bases, const voi
   hipStream_t main = turn == 0 ? cx.main_stream : cx.main_extra[turn - 1];
   const bool partial = win_begin > 0 || (win_end >= 0 && win_end < curdle_msm_num_windows(n, window_bits));
   hipStream_t pre = partial && cx.pre_streams == 2 && (seq & 1u) ? cx.pre_stream2 : cx.pre_stream;
-  rc = enqueue_slot(cx, S, nullptr, d_scalars, off, 1, window_bits, win_begin, win_end, pre, main, S.stream,
-                    /*latency_mode=*/false, false, 1, false, nullptr, d28);
+  MsmCall call{off};
+  call.c = window_bits;
+  call.win_begin = win_begin;
+  call.win_end = win_end;
+  call.pipelined = true;
+  MsmInputs in;
+  in.scalars = d_scalars;
+  in.points28 = d28;
+  rc = enqueue_slot(cx, S, call, in, {pre, main, S.stream});
   if (rc) {
     drain_slot(cx, S);
     release_slot(cx, idx);
@@ -434,9 +452,13 @@ int dacc_submit_impl(curdle_dacc* acc, const curdle_dacc_check* checks, size_t n
     df.n_inst = (uint32_t)n_inst;
     df.n_extra = (uint32_t)n_extra;
     const uint32_t off[2] = {0, (uint32_t)n};
-    if ((r = enqueue_slot(cx, S, nullptr, S.scalars.p, off, 1, 0, 0, -1, st, st, st, /*latency_mode=*/true,
-                          /*points28_ready=*/true, 1, false, nullptr, nullptr, /*light_host=*/queued, true, fused ? &df : nullptr)))
-      return r;
+    MsmCall call{off};
+    call.light_host = queued;
+    MsmInputs in;
+    in.scalars = S.scalars.p;
+    in.points28_ready = true;
+    in.dfront = fused ? &df : nullptr;
+    if ((r = enqueue_slot(cx, S, call, in, {st, st, st}))) return r;
     if (fused && export_scalars && n_res)  // (tests: behind the whole call on the stream, read at the wait)
       HIP_TRY(hipMemcpyAsync(h + bytes, S.scalars.p, n_res * 32, hipMemcpyDeviceToHost, st));
     acc->export_off = bytes;

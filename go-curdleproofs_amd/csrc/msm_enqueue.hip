@@ -16,71 +16,23 @@ extern "C" int curdle_debug_skip(unsigned mask) {  // (tools/bench_pipeline.py s
   return 0;
 }
 namespace curdle_api {
-#define EXP_SKIP(bit) (exp_skip_mask() & (bit) && S.gen > 12 && !latency_mode)
+#define EXP_SKIP(bit) (exp_skip_mask() & (bit) && S.gen > 12 && call.pipelined)
 #else
 #define EXP_SKIP(bit) false
 #endif
 
-// Enqueue every GPU phase of k MSMs on the slot's stream (no host synchronisation).
-// d_points / d_scalars are device pointers holding the pairs of all MSMs back to back
-// and must stay valid until the matching finish_slot(); h_off has k + 1 entries.
-int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scalars, const uint32_t* h_off, size_t k, int c,
-                      int win_begin, int win_end, hipStream_t pre, hipStream_t stream, hipStream_t tail, bool latency_mode,
-                      bool points28_ready, size_t sets, bool many, const ChunkJoin* join, const void* ext_points28,
-                      bool light_host, bool glv, const DaccFront* dfront);
-int enqueue_slot(Ctx& cx, Slot& S, const void* d_points, const void* d_scalars, const uint32_t* h_off, size_t k, int c,
-                 int win_begin, int win_end, hipStream_t pre, hipStream_t stream, hipStream_t tail,
-                 bool latency_mode, bool points28_ready, size_t sets, bool many, const ChunkJoin* join, const void* ext_points28,
-                 bool light_host, bool glv, const DaccFront* dfront) {
-  const int rc = enqueue_slot_impl(cx, S, d_points, d_scalars, h_off, k, c, win_begin, win_end, pre, stream, tail, latency_mode,
-                                   points28_ready, sets, many, join, ext_points28, light_host, glv, dfront);
-  if (rc == CURDLE_OK) {
-    S.coarse_dirty = false;  // every launch of the call is in its queue: k_digits leaves its counters zero
-    S.chain_dirty = false;   // ... and the host's count of the scan chain's tickets is the device's
-  }
-  return rc;
-}
-int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scalars, const uint32_t* h_off, size_t k, int c,
-                      int win_begin, int win_end, hipStream_t pre, hipStream_t stream, hipStream_t tail, bool latency_mode,
-                      bool points28_ready, size_t sets, bool many, const ChunkJoin* join, const void* ext_points28,
-                      bool light_host, bool glv, const DaccFront* dfront) {
-  // ext_points28: the bases are a resident, pre-converted set (curdle_dbases: two records per base in the internal
-  // form, the first h_off[k] of them) -- d_points is not read, nothing is converted or copied
-  if (ext_points28 && (k != 1 || sets != 1)) return fail(CURDLE_EINVAL, "resident bases take one MSM per call");
-  // sets > 1 (curdle_msm_g1_multi): d_points holds `sets` base sets of h_off[k] points each, all
-  // multiplied by the SAME scalars: recoded and sorted once, accumulated per set
-  const size_t n_pairs = h_off[k];
-  size_t n_max = 0;
-  for (size_t j = 0; j < k; j++) {
-    if (h_off[j + 1] < h_off[j]) return fail(CURDLE_EINVAL, "offsets not monotone at %zu", j);
-    if (h_off[j + 1] - h_off[j] > n_max) n_max = h_off[j + 1] - h_off[j];
-  }
-  MsmPlan& p = S.plan;
-  int rc = make_plan(p, n_pairs, k, n_max, c, win_begin, win_end, latency_mode, sets, many, join ? join->seg : 0, light_host, glv);
-  if (rc) return rc;
-  if (dfront && (p.two_level || k != 1 || sets != 1)) return fail(CURDLE_EINVAL, "internal: the fused accumulator front takes one small MSM");
-  // k_scan_one is 16 waves of 121 registers: a block of it needs four SIMDs of one compute unit EMPTY, so beside another
-  // call's accumulation it waits for accumulate waves to end.  Only calls that have the chip to themselves take it.
-  if (p.fuse_scan == 2 && (join || !latency_mode)) p.fuse_scan = 3;  // k_scan_chain: four 60-register waves (L >= 2 holds: make_plan)
-  // a chunk of a host-buffer call sorts (and folds) beside the chunks before it: raised like a pipelined call's sort
-  if (join && knobs::get(knobs::AUX_PRIO) < 0) p.aux_prio = 3;
-  // ... and ONE merge limit for every chunk of an MSM, in both of its enqueue steps, whatever the sizes of the chunks say: the
-  // reduction reads all their fragment lists under the last chunk's plan, and a bucket merged under one limit and read under
-  // another would count twice.  8, what the size rule gives every input large enough to be chunked: a bucket just under the limit
-  // is walked fragment by fragment by the fold and by the reduction (limits of 16 and 32 made 256..1,024 distinct scalar values
-  // from host slices 1.3-1.6x a uniform call: profiles/r06_adversarial_distinct_k.txt).
-  if (join && join->chunked) p.max_small = 8;
-  // the kernels work on the GLV split's terms, two per pair (records and digits 2 i, 2 i + 1)
-  const size_t n = 2 * n_pairs;
-  const size_t kr = k * sets;
-  S.run_stream = tail;
-  S.profiled = false;
+// The launches of enqueue_slot, after its plan and its checks.
+static int enqueue_slot_impl(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, const Streams& st, const ChunkJoin* join) {
+  const MsmPlan& p = S.plan;
+  const size_t k = p.k, sets = p.sets, kr = p.kr, n_pairs = call.off[k];
+  const size_t n = p.n;  // the kernels work on the GLV split's terms, two per pair (records and digits 2 i, 2 i + 1)
   const uint32_t nw = p.win_end - p.win_begin;
-  if (n == 0 || nw == 0) return CURDLE_OK;  // finish_slot writes infinities
+  const hipStream_t pre = st.pre, tail = st.tail;
+  hipStream_t stream = st.main;
+  int rc;
   const size_t nb = k * (size_t)p.NB;
   if (nb > (size_t)1024 * 4096)  // run_passes cuts larger batches; a caller that gets here skipped it
     return fail(CURDLE_EINVAL, "%zu bucket slots exceed the scan capacity of one pass", nb);
-  const size_t nlanes = ((size_t)nw * n + p.L - 1) / p.L;
   if ((rc = ensure(S.offsets, (k + 1) * 4))) return rc;
   if ((rc = ensure(S.counts, nb * 4))) return rc;
   if ((rc = ensure(S.starts, (nb + 1) * 4))) return rc;
@@ -94,17 +46,15 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
     if ((rc = ensure(S.tmp, (size_t)nw * n * 4))) return rc;
     // the bins' cursors, their packed starts + sentinel, and the coarse counts + ticket of k_digits, which must be
     // zero before the call's first launch: the kernel leaves them zero, so they are cleared only when the buffer is
-    // made (or moved), when the window count changes their place, and after a call that failed half-way
+    // made (or moved), when the window count changes their place, and after a call that failed half-way (enqueue_slot)
     const void* before = S.ccur.p;
     if ((rc = ensure(S.ccur, coarse_words(nw) * 4))) return rc;
-    if (S.ccur.p != before || S.coarse_nw != nw || S.coarse_dirty) {
+    if (S.ccur.p != before || S.coarse_nw != nw) {
       HIP_TRY(hipMemsetAsync(S.ccur.p, 0, coarse_words(nw) * 4, pre));
       S.coarse_nw = nw;
     }
-    S.coarse_dirty = true;  // until this call's kernels are all enqueued
   }
-  p.frag_stride = (uint32_t)(nb + nlanes + 1);
-  if (!ext_points28 && (rc = ensure(S.points28, sets * n * kA28Bytes))) return rc;
+  if (!in.points28 && (rc = ensure(S.points28, sets * n * kA28Bytes))) return rc;
   if ((rc = ensure(S.frags, sets * (size_t)p.frag_stride * kX28Bytes))) return rc;
   // what leaves the GPU per window: one sum, or the reduce_bits form's nout bit-positioned points
   const size_t wpts = p.reduce_bits ? p.nout : 1;
@@ -136,7 +86,7 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
   ws.sorted = (uint32_t*)S.sorted.p;
   ws.tmp = p.two_level ? (uint32_t*)S.tmp.p : nullptr;
   ws.ccur = p.two_level ? (uint32_t*)S.ccur.p : nullptr;
-  ws.points28 = ext_points28 ? const_cast<void*>(ext_points28) : S.points28.p;
+  ws.points28 = in.points28 ? const_cast<void*>(in.points28) : S.points28.p;
   ws.frags = S.frags.p;
   ws.partials = S.partials.p;
   ws.winsums28 = S.winsums28.p;
@@ -159,10 +109,7 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
       *S.h_err = 0;
     }
     S.scan_epoch = (S.scan_epoch + 1) & 0x3fffffffu;
-    // (chain_dirty, review of round 5: a call that failed after its k_scan_chain was enqueued -- launch_scan returns
-    // hipGetLastError(), which may be an EARLIER launch's error -- left scan_base behind the device's counter, and every
-    // later launch of the slot would have taken tickets beyond its tile count)
-    if (S.chain.p != before || S.scan_epoch == 0 || S.chain_dirty) {  // a new buffer, or the epochs have gone round: no word may look current
+    if (S.chain.p != before || S.scan_epoch == 0) {  // a new buffer, or the epochs have gone round: no word may look current
       HIP_TRY(hipMemsetAsync(S.chain.p, 0, scan_chain_bytes(), pre));
       S.scan_base = 0;
       if (S.scan_epoch == 0) S.scan_epoch = 1;
@@ -172,7 +119,6 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
     ws.host_err = S.h_err;
     ws.chain_base = S.scan_base;
     ws.chain_epoch = S.scan_epoch;
-    S.chain_dirty = true;  // until this call's kernels are all enqueued (enqueue_slot)
   }
   {
     const void* before = S.mdone.p;
@@ -184,7 +130,7 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
   // the offsets are staged in pinned memory (tail of h_buf) so the copy is truly asynchronous
   uint32_t* h_off_pinned = (uint32_t*)((char*)S.h_buf + host_need - (k + 1) * 4);
   if (k > 1) {  // a single MSM's kernels take [0, n) from the plan
-    for (size_t j = 0; j <= k; j++) h_off_pinned[j] = 2 * h_off[j];  // in terms, like everything the kernels index
+    for (size_t j = 0; j <= k; j++) h_off_pinned[j] = 2 * call.off[j];  // in terms, like everything the kernels index
     HIP_TRY(hipMemcpyAsync(S.offsets.p, h_off_pinned, (k + 1) * 4, hipMemcpyHostToDevice, pre));
   }
   // counts are cleared by k_digits, the large-bucket counter by the scan
@@ -201,22 +147,22 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
   // at 2^17..2^19 -- conversion and sort are both HBM-bound, so side by side they take as long
   // as one after the other, plus two event hops.
   const int phase = join ? join->phase : 0;
-  const bool convert_here = !points28_ready && !ext_points28;  // the device accumulator fills S.points28 itself; a resident base set is converted already
+  const bool convert_here = !in.points28_ready && !in.points28;  // the device accumulator fills S.points28 itself; a resident base set is converted already
   // small calls: conversion and recoding in one launch (the host's launches bound the call until the accumulation
   // starts)
   const size_t front_max = 16384;  // (larger limits measured equal: profiles/r05_small_sort_one_block.txt)
   const bool front = convert_here && phase == 0 && !p.two_level && sets * n_pairs <= front_max;
   if (convert_here && phase == 0 && !front && !EXP_SKIP(1)) {
-    HIP_TRY(launch_convert_points_raw(d_points, (uint32_t)(sets * n_pairs), ws.points28, pre, p.aux_prio));
+    HIP_TRY(launch_convert_points_raw(in.points, (uint32_t)(sets * n_pairs), ws.points28, pre, p.aux_prio));
     prof.mark("convert_points");
   }
   if (phase != 2 && !EXP_SKIP(2)) {
     if (front)
-      HIP_TRY(launch_front(p, ws, d_points, (uint32_t)(sets * n_pairs), d_scalars, pre));
-    else if (dfront)  // the device accumulator's job: loose bases, slot scalars and recoding in one launch
-      HIP_TRY(launch_dacc_front(p, ws, *dfront, pre));
+      HIP_TRY(launch_front(p, ws, in.points, (uint32_t)(sets * n_pairs), in.scalars, pre));
+    else if (in.dfront)  // the device accumulator's job: loose bases, slot scalars and recoding in one launch
+      HIP_TRY(launch_dacc_front(p, ws, *in.dfront, pre));
     else
-      HIP_TRY(launch_digits(p, ws, d_scalars, pre));
+      HIP_TRY(launch_digits(p, ws, in.scalars, pre));
     prof.mark("digits");
     HIP_TRY(launch_hist(p, ws, pre));
     prof.mark("hist");
@@ -234,7 +180,7 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
     if (convert_here) {
       // on the sort stream, beside the accumulation of the chunk before -- on `stream` the four conversions of a 2^20-pair
       // call sat BETWEEN the accumulations, 0.18 ms of the call's critical path (timeline gpurun_out/r5_hosttrace2)
-      HIP_TRY(launch_convert_points_raw(d_points, (uint32_t)(sets * n_pairs), ws.points28, pre, p.aux_prio));
+      HIP_TRY(launch_convert_points_raw(in.points, (uint32_t)(sets * n_pairs), ws.points28, pre, p.aux_prio));
       prof.mark("convert_points");
       HIP_TRY(hipEventRecord(S.pre_done, pre));  // behind the sort's record on the same stream: covers both
     }
@@ -255,12 +201,7 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
     stream = tail;
     prof.st = tail;
   }
-  // The merge launch's grid: a synchronous call has the chip to itself (768 blocks; also the one-chunk host-buffer call, whose join
-  // only splits its own enqueue in two); a chunk of a chunked call runs beside the next chunk's accumulation (256); a pipelined call
-  // pays for every empty block (64: msm_reduce_kernels.hip launch_merge_large).
-  const bool alone = !join || !join->chunked;
-  const uint32_t merge_blocks = latency_mode && alone ? 768u : (join && join->chunked ? 256u : 64u);
-  if (!EXP_SKIP(4)) HIP_TRY(launch_merge_large(p, ws, stream, merge_blocks));
+  if (!EXP_SKIP(4)) HIP_TRY(launch_merge_large(p, ws, stream));
   prof.mark("merge_large");
   if (join && join->accumulate_only) {
     if (join->fold_home) {
@@ -281,11 +222,13 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
   }
   FragSources extra;
   memset(&extra, 0, sizeof(extra));
+  auto shares_plan = [&](const MsmPlan& q) {  // a chunk before this one, of the same MSM
+    return q.c == p.c && q.NB == p.NB && q.seg == p.seg && q.max_small == p.max_small && q.k == 1 && p.k == 1 && sets == 1 &&
+           q.win_begin == p.win_begin && q.win_end == p.win_end;
+  };
   if (join && join->fold_home && join->fold_prev) {
     const Slot& H = *join->fold_home;
-    const MsmPlan& q = join->fold_prev->plan;
-    if (q.c != p.c || q.NB != p.NB || q.seg != p.seg || q.k != 1 || p.k != 1 || sets != 1 || q.win_begin != p.win_begin ||
-        q.win_end != p.win_end || H.fold_sums.cap < (size_t)p.NB * kX28Bytes)
+    if (!shares_plan(join->fold_prev->plan) || H.fold_sums.cap < (size_t)p.NB * kX28Bytes)
       return fail(CURDLE_EINVAL, "chunks of one MSM must share the plan");
     extra.frags[0] = H.fold_sums.p;
     extra.foff[0] = (const uint32_t*)H.fold_meta.p;
@@ -295,10 +238,7 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
   } else if (join) {
     for (Slot* E : join->earlier) {
       if (extra.n >= (uint32_t)kMaxFragSources - 1) return fail(CURDLE_EINVAL, "too many chunks for one reduction");
-      const MsmPlan& q = E->plan;
-      if (q.c != p.c || q.NB != p.NB || q.seg != p.seg || q.k != 1 || p.k != 1 || sets != 1 || q.win_begin != p.win_begin ||
-          q.win_end != p.win_end)
-        return fail(CURDLE_EINVAL, "chunks of one MSM must share the plan");
+      if (!shares_plan(E->plan)) return fail(CURDLE_EINVAL, "chunks of one MSM must share the plan");
       extra.frags[extra.n] = E->frags.p;
       extra.foff[extra.n] = (const uint32_t*)E->foff.p;
       extra.fragcnt[extra.n] = (const uint32_t*)E->fragcnt.p;
@@ -325,6 +265,34 @@ int enqueue_slot_impl(Ctx& cx, Slot& S, const void* d_points, const void* d_scal
     HIP_TRY(hipMemcpyAsync(S.h_buf, ws.winsums, win_bytes, hipMemcpyDeviceToHost, stream));
   }
   return CURDLE_OK;
+}
+
+// Enqueue every GPU phase of call.k MSMs on the slot's streams (no host synchronisation), under the plan make_plan gives
+// the call.  The inputs must stay valid until the matching finish_slot().
+int enqueue_slot(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, const Streams& st, const ChunkJoin* join) {
+  if (!join != !call.joined) return fail(CURDLE_EINVAL, "internal: a joined call takes a ChunkJoin, and no other call does");
+  if (in.points28 && (call.k != 1 || call.sets != 1)) return fail(CURDLE_EINVAL, "resident bases take one MSM per call");
+  int rc = make_plan(S.plan, call);
+  if (rc) return rc;
+  const MsmPlan& p = S.plan;
+  if (in.dfront && (p.two_level || p.k != 1 || p.sets != 1))
+    return fail(CURDLE_EINVAL, "internal: the fused accumulator front takes one small MSM");
+  S.run_stream = st.tail;
+  S.profiled = false;
+  if (p.n == 0 || p.win_end == p.win_begin) return CURDLE_OK;  // finish_slot writes infinities
+  // The kernels leave k_digits' coarse counters, the scan chain and k_merge_large's chunk counters zero, and the host counts
+  // the chain's tickets.  A call that stopped half-way may have left any of them behind (review of round 5: a call that failed
+  // after its k_scan_chain was enqueued -- launch_scan returns hipGetLastError(), which may be an EARLIER launch's error -- left
+  // scan_base behind the device's counter, and every later launch of the slot would have taken tickets beyond its tile count).
+  if (S.suspect) {
+    for (Buf* b : {&S.ccur, &S.chain, &S.mdone})
+      if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->cap, st.pre));
+    S.scan_base = 0;
+  }
+  S.suspect = true;  // until every launch of this call is queued
+  rc = enqueue_slot_impl(cx, S, call, in, st, join);
+  if (rc == CURDLE_OK) S.suspect = false;
+  return rc;
 }
 
 // Wait for the slot's GPU work and produce the k results (host combine unless the
@@ -409,7 +377,9 @@ int finish_slot(Ctx& cx, Slot& S, uint64_t* out) {
   return CURDLE_OK;
 }
 
+// After a failed call: the streams it may have used are idle, and the slot's next call starts clean (enqueue_slot).
 void drain_slot(Ctx& cx, Slot& S) {
+  S.suspect = true;
   (void)hipStreamSynchronize(cx.h2d_stream);
   (void)hipStreamSynchronize(cx.pre_stream);
   (void)hipStreamSynchronize(cx.pre_stream2);
@@ -424,7 +394,7 @@ void drain_slot(Ctx& cx, Slot& S) {
 // ~10 us with 16 hardware queues: 0.58 -> 0.50 ms for a 1,268-pair MSM), and concurrent callers
 // still overlap, each on its slot's stream.  (The three-stream layout of the pipelined entry points was
 // measured slower for synchronous calls in round 2; its knob is gone.)
-SyncStreams sync_streams(Ctx&, Slot& S) { return {S.stream, S.stream, S.stream}; }
+Streams sync_streams(Ctx&, Slot& S) { return {S.stream, S.stream, S.stream}; }
 
 // The scans of the bucket slots hold 1,024 blocks of 4,096 slots: a batch with more slots than
 // that (1,024 MSMs of 2,548 pairs; 2,100 of 628) runs in passes of as many whole MSMs as fit,
@@ -432,45 +402,40 @@ SyncStreams sync_streams(Ctx&, Slot& S) { return {S.stream, S.stream, S.stream};
 // gap between two passes is noise, and the workspaces stay bounded.
 
 // enqueue + finish of k MSMs on slot S, in passes if the batch is too large for one.
-int run_passes(Ctx& cx, Slot& S, const void* d_points, const void* d_scalars, const uint32_t* h_off, size_t k, int c,
-               int win_begin, int win_end, hipStream_t pre, hipStream_t main, hipStream_t tail, uint64_t* out,
-               const void* ext_points28, bool glv) {
+int run_passes(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, const Streams& st, uint64_t* out) {
+  const size_t k = call.k;
   if (k > 1) {
-    size_t n_max = 0;
-    for (size_t j = 0; j < k; j++) {
-      if (h_off[j + 1] < h_off[j]) return fail(CURDLE_EINVAL, "offsets not monotone at %zu", j);
-      if (h_off[j + 1] - h_off[j] > n_max) n_max = h_off[j + 1] - h_off[j];
-    }
     MsmPlan probe;
-    int rc = make_plan(probe, h_off[k] - h_off[0], k, n_max, c, win_begin, win_end, true);
+    int rc = make_plan(probe, call);
     if (rc) return rc;
     size_t per_pass = probe.NB ? kMaxSlotsPerPass / probe.NB : k;
     if (knobs::get(knobs::MAX_MSMS_PER_PASS) > 0) per_pass = (size_t)knobs::get(knobs::MAX_MSMS_PER_PASS);
     if (k > per_pass) {
       std::vector<uint32_t> off;
+      MsmCall pass = call;
+      pass.c = probe.c;  // the whole batch's window width for every pass (a pass's own n_max must not change it)
+      pass.many = true;  // ... and the batch's rules
       for (size_t j0 = 0; j0 < k; j0 += per_pass) {
         const size_t kg = k - j0 < per_pass ? k - j0 : per_pass;
         off.resize(kg + 1);
-        for (size_t j = 0; j <= kg; j++) off[j] = h_off[j0 + j] - h_off[j0];
-        // the whole batch's window width for every pass (a pass's own n_max must not change it)
-        rc = enqueue_slot(cx, S, (const char*)d_points + (size_t)h_off[j0] * 96, (const char*)d_scalars + (size_t)h_off[j0] * 32,
-                          off.data(), kg, probe.c, win_begin, win_end, pre, main, tail, true, false, 1,
-                          /*many=*/true);
+        for (size_t j = 0; j <= kg; j++) off[j] = call.off[j0 + j] - call.off[j0];
+        pass.off = off.data();
+        pass.k = kg;
+        const size_t lo = call.off[j0];
+        rc = enqueue_slot(cx, S, pass, {(const char*)in.points + lo * 96, (const char*)in.scalars + lo * 32}, st);
         if (!rc) rc = finish_slot(cx, S, out + 18 * j0);
         if (rc) return rc;
       }
       return CURDLE_OK;
     }
   }
-  int rc = enqueue_slot(cx, S, d_points, d_scalars, h_off, k, c, win_begin, win_end, pre, main, tail, true, false, 1, false,
-                        nullptr, ext_points28, false, glv);
+  int rc = enqueue_slot(cx, S, call, in, st);
   if (!rc) rc = finish_slot(cx, S, out);
   return rc;
 }
 
-// Synchronous run of k MSMs with inputs on the device.
-int run_device(const void* d_points, const void* d_scalars, const uint32_t* h_off, size_t k, int c, int win_begin,
-               int win_end, uint64_t* out, void* user_stream, const void* ext_points28, bool glv, hipEvent_t wait_for) {
+// Synchronous run of call.k MSMs with inputs on the device.
+int run_device(const MsmCall& call, const MsmInputs& in, uint64_t* out, void* user_stream, hipEvent_t wait_for) {
   Ctx& cx = cur();
   int idx;
   int rc = acquire_slot(cx, true, &idx);
@@ -481,61 +446,52 @@ int run_device(const void* d_points, const void* d_scalars, const uint32_t* h_of
     release_slot(cx, idx);
     return fail(CURDLE_EHIP, "hipSetDevice: %s", hipGetErrorString(he));
   }
-  if (user_stream) {
-    if (wait_for) he = hipStreamWaitEvent((hipStream_t)user_stream, wait_for, 0);
-    rc = he != hipSuccess ? fail(CURDLE_EHIP, "hipStreamWaitEvent: %s", hipGetErrorString(he))
-                          : run_passes(cx, S, d_points, d_scalars, h_off, k, c, win_begin, win_end, (hipStream_t)user_stream,
-                                       (hipStream_t)user_stream, (hipStream_t)user_stream, out, ext_points28, glv);
-  } else {
-    const SyncStreams st = sync_streams(cx, S);
-    if (wait_for) he = hipStreamWaitEvent(st.pre, wait_for, 0);
-    rc = he != hipSuccess ? fail(CURDLE_EHIP, "hipStreamWaitEvent: %s", hipGetErrorString(he))
-                          : run_passes(cx, S, d_points, d_scalars, h_off, k, c, win_begin, win_end, st.pre, st.main, st.tail, out,
-                                       ext_points28, glv);
-  }
+  const hipStream_t us = (hipStream_t)user_stream;
+  const Streams st = user_stream ? Streams{us, us, us} : sync_streams(cx, S);
+  if (wait_for) he = hipStreamWaitEvent(st.pre, wait_for, 0);
+  rc = he != hipSuccess ? fail(CURDLE_EHIP, "hipStreamWaitEvent: %s", hipGetErrorString(he))
+                        : run_passes(cx, S, call, in, st, out);
   if (rc) drain_slot(cx, S);
   release_slot(cx, idx);
   return rc;
 }
 
 // Synchronous run with inputs in host memory: staged through the slot's own buffers.
-int run_host(const uint64_t* points, const uint64_t* scalars, const uint32_t* h_off, size_t k, uint64_t* out, bool glv) {
+int run_host(const MsmCall& call, const uint64_t* points, const uint64_t* scalars, uint64_t* out) {
   Ctx& cx = cur();
   int idx;
   int rc = acquire_slot(cx, true, &idx);
   if (rc) return rc;
   Slot& S = cx.slots[idx];
-  const size_t n = h_off[k];
+  const size_t n = call.off[call.k];
   auto body = [&]() -> int {
     HIP_TRY(hipSetDevice(cx.device));
     int r;
     if ((r = ensure(S.points, n * 96))) return r;
     if ((r = ensure(S.scalars, n * 32))) return r;
-    const SyncStreams st = sync_streams(cx, S);
+    const Streams st = sync_streams(cx, S);
+    const MsmInputs in{S.points.p, S.scalars.p};
     // One mid-size MSM: the scalars cross first and the recoding + sort run while the points are still crossing (on the
     // context's copy stream; a pageable copy occupies this thread, not the GPU) -- the sort, 0.07-0.15 ms of such a call,
     // is off the call's critical path for one event hop.  From 16,384 pairs.
     const size_t overlap_min = 16384;
-    if (k == 1 && n >= overlap_min) {
-      const uint32_t off[2] = {0, (uint32_t)n};
+    if (call.k == 1 && n >= overlap_min) {
+      MsmCall two_step = call;
+      two_step.joined = true;
       ChunkJoin join;
       HIP_TRY(hipMemcpyAsync(S.scalars.p, scalars, n * 32, hipMemcpyHostToDevice, st.pre));
       join.phase = 1;
-      if ((r = enqueue_slot(cx, S, S.points.p, S.scalars.p, off, 1, 0, 0, -1, st.pre, st.main, st.tail, /*latency_mode=*/true, false, 1,
-                            false, &join, nullptr, false, glv)))
-        return r;
+      if ((r = enqueue_slot(cx, S, two_step, in, st, &join))) return r;
       HIP_TRY(hipMemcpyAsync(S.points.p, points, n * 96, hipMemcpyHostToDevice, cx.h2d_stream));
       HIP_TRY(hipEventRecord(S.acc_done, cx.h2d_stream));  // (a scratch event until the accumulation re-records it)
       HIP_TRY(hipStreamWaitEvent(st.pre, S.acc_done, 0));
       join.phase = 2;
-      if ((r = enqueue_slot(cx, S, S.points.p, S.scalars.p, off, 1, 0, 0, -1, st.pre, st.main, st.tail, /*latency_mode=*/true, false, 1,
-                            false, &join, nullptr, false, glv)))
-        return r;
+      if ((r = enqueue_slot(cx, S, two_step, in, st, &join))) return r;
       return finish_slot(cx, S, out);
     }
     HIP_TRY(hipMemcpyAsync(S.points.p, points, n * 96, hipMemcpyHostToDevice, st.pre));
     HIP_TRY(hipMemcpyAsync(S.scalars.p, scalars, n * 32, hipMemcpyHostToDevice, st.pre));
-    return run_passes(cx, S, S.points.p, S.scalars.p, h_off, k, 0, 0, -1, st.pre, st.main, st.tail, out, nullptr, glv);
+    return run_passes(cx, S, call, in, st, out);
   };
   rc = body();
   if (rc) drain_slot(cx, S);

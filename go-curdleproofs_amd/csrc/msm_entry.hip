@@ -12,7 +12,9 @@ int msm_host_one_device(const uint64_t* points, const uint64_t* scalars, size_t 
   }
   if (n >= kHostChunkMin && knobs::get(knobs::HOST_CHUNKS) != 1) return run_host_chunked(points, scalars, n, out_jac, glv);
   const uint32_t off[2] = {0, (uint32_t)n};
-  return run_host(points, scalars, off, 1, out_jac, glv);
+  MsmCall call{off};
+  call.glv = glv;
+  return run_host(call, points, scalars, out_jac);
 }
 
 // share(d, out18) runs on the host thread of context d (whose current context is d) for every
@@ -142,10 +144,9 @@ extern "C" int curdle_msm_g1_replicated(const void* const* d_points, const void*
   if (!d_points || !d_scalars) return fail(CURDLE_EINVAL, "points/scalars null with n = %zu", n);
   for (int d = 0; d < D; d++)
     if (!d_points[d] || !d_scalars[d]) return fail(CURDLE_EINVAL, "device %d: null input pointer", d);
-  if (D == 1) {
-    const uint32_t off[2] = {0, (uint32_t)n};
-    return run_device(d_points[0], d_scalars[0], off, 1, 0, 0, -1, out_jac, nullptr);
-  }
+  const uint32_t off[2] = {0, (uint32_t)n};
+  MsmCall call{off};
+  if (D == 1) return run_device(call, {d_points[0], d_scalars[0]}, out_jac);
   // which partition pays at which size: DESIGN.md section 5 (per-rank step times on one MI355X)
   if (split == 0) split = n >= ((size_t)1 << 22) ? 2 : 1;
   const int c = choose_window_bits(n);
@@ -155,14 +156,16 @@ extern "C" int curdle_msm_g1_replicated(const void* const* d_points, const void*
     if (split == 1) {  // windows [wb, we) of the plan for all n pairs; a device beyond the last window adds infinity
       size_t wb, we;
       even_range((size_t)W, D, d, &wb, &we);
-      const uint32_t off[2] = {0, (uint32_t)n};
-      return run_device(d_points[d], d_scalars[d], off, 1, c, (int)wb, (int)we, part, nullptr);
+      MsmCall range = call;
+      range.c = c;
+      range.win_begin = (int)wb;
+      range.win_end = (int)we;
+      return run_device(range, {d_points[d], d_scalars[d]}, part);
     }
     size_t lo, hi;
     even_range(n, D, d, &lo, &hi);
-    const uint32_t off[2] = {0, (uint32_t)(hi - lo)};
-    return run_device((const char*)d_points[d] + lo * 96, (const char*)d_scalars[d] + lo * 32, off, 1, 0, 0, -1, part,
-                      nullptr);
+    const uint32_t off_d[2] = {0, (uint32_t)(hi - lo)};
+    return run_device(MsmCall{off_d}, {(const char*)d_points[d] + lo * 96, (const char*)d_scalars[d] + lo * 32}, part);
   }, out_jac);
 }
 
@@ -233,15 +236,18 @@ extern "C" int curdle_msm_g1_device_windows_ex(const void* d_points, const void*
   if (rc) return rc;
   if (n && (!d_points || !d_scalars)) return fail(CURDLE_EINVAL, "points/scalars null with n = %zu", n);
   if (n > ((size_t)1 << 27)) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^27 pairs", n);
-  const bool glv = !(flags & CURDLE_MSM_ANY_CURVE_POINT);
   const uint32_t off[2] = {0, (uint32_t)n};
+  MsmCall call{off};
+  call.c = window_bits;
+  call.win_begin = win_begin;
+  call.win_end = win_end;
+  call.glv = !(flags & CURDLE_MSM_ANY_CURVE_POINT);
   Ctx& cx = cur();
   int entry = -1;
   const void* d28 = nullptr;
   hipEvent_t ready = nullptr;
   if ((flags & CURDLE_MSM_BASES_UNCHANGED) && n && (rc = bases_cache_acquire(cx, d_points, n, &entry, &d28, &ready))) return rc;
-  rc = run_device(d_points, d_scalars, off, 1, window_bits, win_begin, win_end, out_jac, stream, entry >= 0 ? d28 : nullptr, glv,
-                  entry >= 0 ? ready : nullptr);
+  rc = run_device(call, {d_points, d_scalars, entry >= 0 ? d28 : nullptr}, out_jac, stream, entry >= 0 ? ready : nullptr);
   bases_cache_release(cx, entry);
   return rc;
 }
@@ -292,6 +298,12 @@ extern "C" int curdle_msm_g1_device_submit_ex(const void* d_points, const void* 
     return rc;
   }
   const uint32_t off[2] = {0, (uint32_t)n};
+  MsmCall call{off};
+  call.c = window_bits;
+  call.win_begin = win_begin;
+  call.win_end = win_end;
+  call.pipelined = true;
+  call.glv = glv;
   const unsigned seq = cx.submit_count.fetch_add(1, std::memory_order_relaxed);
   const unsigned turn = seq % (unsigned)cx.main_streams;
   hipStream_t main = turn == 0 ? cx.main_stream : cx.main_extra[turn - 1];
@@ -302,8 +314,7 @@ extern "C" int curdle_msm_g1_device_submit_ex(const void* d_points, const void* 
   if (entry >= 0 && (he = hipStreamWaitEvent(main, ready, 0)) != hipSuccess)  // the accumulation is what reads the copy
     rc = fail(CURDLE_EHIP, "hipStreamWaitEvent: %s", hipGetErrorString(he));
   if (!rc)
-    rc = enqueue_slot(cx, S, d_points, d_scalars, off, 1, window_bits, win_begin, win_end, pre, main, S.stream,
-                      /*latency_mode=*/false, false, 1, false, nullptr, entry >= 0 ? d28 : nullptr, false, glv);
+    rc = enqueue_slot(cx, S, call, {d_points, d_scalars, entry >= 0 ? d28 : nullptr}, {pre, main, S.stream});
   if (rc) {
     drain_slot(cx, S);
     release_slot(cx, idx);
@@ -371,9 +382,8 @@ extern "C" int curdle_msm_g1_batch_device(const void* d_points, const void* d_sc
     if (j && offsets[j] < offsets[j - 1]) return fail(CURDLE_EINVAL, "offsets not monotone at %zu", j - 1);
     off[j] = (uint32_t)(offsets[j] - offsets[0]);
   }
-  const char* dp = (const char*)d_points + offsets[0] * 96;
-  const char* ds = (const char*)d_scalars + offsets[0] * 32;
-  return run_device(dp, ds, off.data(), k, 0, 0, -1, out_jac, stream);
+  MsmCall call{off.data(), k};
+  return run_device(call, {(const char*)d_points + offsets[0] * 96, (const char*)d_scalars + offsets[0] * 32}, out_jac, stream);
 }
 
 extern "C" int curdle_g1_sum(const uint64_t* jac_points, size_t k, uint64_t out_jac[18]) {
@@ -406,7 +416,8 @@ extern "C" int curdle_msm_g1_batch(const uint64_t* points, const uint64_t* scala
   if (n > ((size_t)1 << 27)) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^27 pairs", n);
   std::vector<uint32_t> off(k + 1);
   for (size_t j = 0; j <= k; j++) off[j] = (uint32_t)(offsets[j] - lo);
-  return run_host(points + 12 * lo, scalars + 4 * lo, off.data(), k, out_jac);
+  MsmCall call{off.data(), k};
+  return run_host(call, points + 12 * lo, scalars + 4 * lo, out_jac);
 }
 
 // k base sets against ONE scalar vector (samemultiscalarargument.go:64-70: the same r against
@@ -435,14 +446,14 @@ extern "C" int curdle_msm_g1_multi(const uint64_t* const* points_sets, size_t k,
     int r;
     if ((r = ensure(S.points, k * n * 96))) return r;
     if ((r = ensure(S.scalars, n * 32))) return r;
-    const SyncStreams st = sync_streams(cx, S);
+    const Streams st = sync_streams(cx, S);
     for (size_t j = 0; j < k; j++)
       HIP_TRY(hipMemcpyAsync((char*)S.points.p + j * n * 96, points_sets[j], n * 96, hipMemcpyHostToDevice, st.pre));
     HIP_TRY(hipMemcpyAsync(S.scalars.p, scalars, n * 32, hipMemcpyHostToDevice, st.pre));
     const uint32_t off[2] = {0, (uint32_t)n};
-    if ((r = enqueue_slot(cx, S, S.points.p, S.scalars.p, off, 1, 0, 0, -1, st.pre, st.main, st.tail,
-                          /*latency_mode=*/true, /*points28_ready=*/false, /*sets=*/k)))
-      return r;
+    MsmCall call{off};
+    call.sets = k;
+    if ((r = enqueue_slot(cx, S, call, {S.points.p, S.scalars.p}, st))) return r;
     return finish_slot(cx, S, out_jac);
   };
   rc = body();

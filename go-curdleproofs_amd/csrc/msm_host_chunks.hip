@@ -52,7 +52,15 @@ int run_host_chunked(const uint64_t* points, const uint64_t* scalars, size_t n, 
     }
     nchunks = slots.size();
   }
-  const int c = choose_window_bits(n);
+  // Every chunk's plan: the whole call's window width, the synchronous rules (the reduction walks all of them with one plan),
+  // and the rules of a chunk (make_plan).
+  MsmCall chunk;
+  chunk.c = choose_window_bits(n);
+  chunk.glv = glv;
+  chunk.joined = chunk.chunked = true;
+  // with three or four fragment lists per bucket the reduction's chain is fragments, not
+  // running sums: half as many buckets per quad (N = 2^20, four chunks: 5.30 -> 5.02 ms)
+  chunk.seg = nchunks >= 3 ? 8 : 0;
   // chunk sizes: (three chunks and more) the first two one unit and the others two units each; otherwise equal
   std::vector<size_t> bounds(nchunks + 1, n);
   bounds[0] = 0;
@@ -87,10 +95,6 @@ int run_host_chunked(const uint64_t* points, const uint64_t* scalars, size_t n, 
       const unsigned seq = cx.submit_count.fetch_add(1, std::memory_order_relaxed);
       const unsigned turn = seq % (unsigned)cx.main_streams;
       pt.main = turn == 0 ? cx.main_stream : cx.main_extra[turn - 1];
-      // with three or four fragment lists per bucket the reduction's chain is fragments, not
-      // running sums: half as many buckets per quad (N = 2^20, four chunks: 5.30 -> 5.02 ms)
-      pt.join.seg = nchunks >= 3 ? 8 : 0;
-      pt.join.chunked = true;
       parts.push_back(pt);
     }
     int r;
@@ -158,20 +162,21 @@ int run_host_chunked(const uint64_t* points, const uint64_t* scalars, size_t n, 
     // every chunk's sort on its slot's own stream, not all of them one after the other on the context's sort stream: three
     // sorts in a row beside the accumulations are late
     auto sort_stream = [&](Part& pt) { return &pt != &parts[0] ? pt.S->stream : cx.pre_stream; };
-    auto enqueue_sort = [&](Part& pt) -> int {  // behind the chunk's scalars
-      hipStream_t ps = sort_stream(pt);
-      HIP_TRY(hipStreamWaitEvent(ps, pt.S->pre_done, 0));
+    auto enqueue = [&](Part& pt) {  // the chunk's step pt.join.phase
       const uint32_t off[2] = {0, (uint32_t)pt.m};
+      MsmCall call = chunk;
+      call.off = off;
+      return enqueue_slot(cx, *pt.S, call, {pt.S->points.p, pt.S->scalars.p}, {sort_stream(pt), pt.main, pt.S->stream}, &pt.join);
+    };
+    auto enqueue_sort = [&](Part& pt) -> int {  // behind the chunk's scalars
+      HIP_TRY(hipStreamWaitEvent(sort_stream(pt), pt.S->pre_done, 0));
       pt.join.phase = 1;
-      // every chunk takes the synchronous rule for its segments (the reduction walks all of them with one plan)
-      return enqueue_slot(cx, *pt.S, pt.S->points.p, pt.S->scalars.p, off, 1, c, 0, -1, ps, pt.main, pt.S->stream,
-                          /*latency_mode=*/true, false, 1, false, &pt.join, nullptr, false, glv);
+      return enqueue(pt);
     };
     auto enqueue_accumulate = [&](size_t i) -> int {  // behind the chunk's points
       Part& pt = parts[i];
       HIP_TRY(hipStreamWaitEvent(pt.main, pt.S->acc_done, 0));
       HIP_TRY(hipStreamWaitEvent(sort_stream(pt), pt.S->acc_done, 0));  // the conversion runs there
-      const uint32_t off[2] = {0, (uint32_t)pt.m};
       const bool is_last = i + 1 == parts.size();
       pt.join.phase = 2;
       pt.join.accumulate_only = !is_last;
@@ -180,8 +185,7 @@ int run_host_chunked(const uint64_t* points, const uint64_t* scalars, size_t n, 
         pt.join.fold_prev = i ? parts[i - 1].S : nullptr;
       }
       if (is_last) pt.join.earlier = last.earlier;
-      int rr = enqueue_slot(cx, *pt.S, pt.S->points.p, pt.S->scalars.p, off, 1, c, 0, -1, sort_stream(pt), pt.main, pt.S->stream,
-                            /*latency_mode=*/true, false, 1, false, &pt.join, nullptr, false, glv);
+      const int rr = enqueue(pt);
       last.earlier.push_back(pt.S);
       return rr;
     };

@@ -96,14 +96,15 @@ struct Slot {
   hipStream_t run_stream = nullptr;
   MsmPlan plan;
   bool profiled = false;
-  Buf chain;                  // k_scan_chain's words and ticket counter (zero when made, never cleared again)
-  bool chain_dirty = false;   // a call failed between taking the chain and its last launch: the host's ticket count may lag the device's -- clear both
+  Buf chain;                  // k_scan_chain's words and ticket counter (zero when made; cleared again only after a failed call)
   Buf mdone;                  // k_merge_large's chunk counters, one per queue entry and base set (zero when made; the kernel leaves them zero)
   uint32_t* h_err = nullptr;  // pinned word a kernel raises when a wait inside it gave up (finish_slot reads it)
   uint32_t scan_epoch = 0;    // epoch of the slot's last k_scan_chain launch (30 bits, never 0)
   uint32_t scan_base = 0;     // tickets the slot's launches have taken so far
   uint32_t coarse_nw = 0;     // window count the zeroed tail of `ccur` was laid out for
-  bool coarse_dirty = false;  // a call was abandoned between its ensure and its last launch: clear `ccur` again
+  // A call failed on this slot, or was abandoned between its first and its last launch: the state the kernels leave
+  // clean (`ccur`, the scan chain's words and the host's ticket count, `mdone`) may not be.  The next call clears it.
+  bool suspect = false;
   int prof_n = 0;
   const char* prof_name[CURDLE_PROF_MAX_KERNELS];
 
@@ -284,9 +285,22 @@ constexpr int kScalarBits = 127;
 constexpr int kScalarBitsNoGlv = 255;
 int choose_window_bits(size_t n, bool many = false);
 int window_widths(int c, uint8_t bits[kMaxWindows], int scalar_bits = kScalarBits);
-int make_plan(MsmPlan& p, size_t n_total, size_t k, size_t n_max, int c, int win_begin, int win_end,
-              bool latency_mode, size_t sets = 1, bool many = false, uint32_t seg_override = 0, bool light_host = false,
-              bool glv = true);
+// Everything that shapes the plan of one call: make_plan decides the whole plan from this alone.
+struct MsmCall {
+  const uint32_t* off = nullptr;  // k + 1 pair offsets of the MSMs, back to back from 0
+  size_t k = 1;                   // scalar vectors (MSMs)
+  size_t sets = 1;                // base sets multiplied by every scalar vector (curdle_msm_g1_multi)
+  int c = 0;                      // maximum window width; 0: the library's choice
+  int win_begin = 0, win_end = -1;  // windows computed by this call; -1: up to the last
+  bool pipelined = false;  // submit / wait: the call shares the chip with other MSMs; false: the caller waits for it alone
+  bool many = false;       // a pass of a larger batch: the batch's rules
+  bool light_host = false;  // a queued MSM of a host-bound batch verifier
+  bool glv = true;          // scalars split with the endomorphism (CURDLE_MSM_ANY_CURVE_POINT: false)
+  bool joined = false;      // a host-buffer call enqueued in two steps or in chunks (a ChunkJoin goes with every enqueue)
+  bool chunked = false;     // ... one of SEVERAL chunks of one MSM, which share the plan's rules in both of their steps
+  uint32_t seg = 0;         // buckets per reduce segment, the same for every chunk (0: the plan's rule)
+};
+int make_plan(MsmPlan& p, const MsmCall& call);
 int checked_window_bits(size_t n, int window_bits, int* c);
 
 // --- msm_enqueue.hip ---------------------------------------------------------
@@ -323,12 +337,10 @@ struct Prof {
 // stops after its accumulation (its fragments stay in its slot; `frags_done` on its tail stream
 // says when), the last one waits for the earlier chunks' events and folds their fragment lists
 // into its own bucket reduction (FragSources, msm_kernels.h).
+// The plan rules of a joined call are MsmCall::joined / chunked / seg; this is only the wiring between the slots.
 struct ChunkJoin {
-  bool chunked = false;               // one of SEVERAL chunks of a host-buffer MSM (set for every chunk, in both of its enqueue steps): the plan rules that differ
-                                      // for chunks -- bucket-merge limit, merge grid -- must be the same in the sort step and in the accumulate step
   bool accumulate_only = false;       // an earlier chunk: no reduce, no window sums, no D2H
   std::vector<Slot*> earlier;         // the last chunk: the slots of the chunks before it
-  uint32_t seg = 0;                   // buckets per reduce segment, the same for every chunk (0: the plan's rule)
   // A chunk is enqueued in two steps: its sort needs only its scalars, which cross PCIe first; the
   // conversion and everything behind it wait for its points.  0: all at once.
   int phase = 0;                      // 1: recoding + sort only; 2: conversion, accumulation, tail (same slot, same plan)
@@ -338,27 +350,25 @@ struct ChunkJoin {
   Slot* fold_prev = nullptr;          // the chunk before this one: its acc_done then means "accumulated AND folded"
 };
 
-
-
-int enqueue_slot(Ctx& cx, Slot& S, const void* d_points, const void* d_scalars, const uint32_t* h_off, size_t k, int c,
-                 int win_begin, int win_end, hipStream_t pre, hipStream_t stream, hipStream_t tail,
-                 bool latency_mode = true, bool points28_ready = false, size_t sets = 1, bool many = false,
-                 const ChunkJoin* join = nullptr, const void* ext_points28 = nullptr, bool light_host = false,
-                 bool glv = true, const DaccFront* dfront = nullptr);
-int finish_slot(Ctx& cx, Slot& S, uint64_t* out);
-void drain_slot(Ctx& cx, Slot& S);
-struct SyncStreams {
+// What one call reads and where: launch-only inputs, which do not shape the plan.
+struct MsmInputs {
+  const void* points = nullptr;       // device: the pairs' points of every base set, back to back (not read with points28)
+  const void* scalars = nullptr;      // device: the scalars of all MSMs, back to back
+  const void* points28 = nullptr;     // resident converted bases (curdle_dbases, kept copies): one MSM, `points` not read
+  bool points28_ready = false;        // the device accumulator has filled the slot's own converted points
+  const DaccFront* dfront = nullptr;  // the device accumulator's fused front (one small MSM)
+};
+struct Streams {
   hipStream_t pre, main, tail;
 };
-SyncStreams sync_streams(Ctx&, Slot& S);
+int enqueue_slot(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, const Streams& st, const ChunkJoin* join = nullptr);
+int finish_slot(Ctx& cx, Slot& S, uint64_t* out);
+void drain_slot(Ctx& cx, Slot& S);
+Streams sync_streams(Ctx&, Slot& S);
 constexpr size_t kMaxSlotsPerPass = (size_t)1024 * 4096;
-int run_passes(Ctx& cx, Slot& S, const void* d_points, const void* d_scalars, const uint32_t* h_off, size_t k, int c,
-               int win_begin, int win_end, hipStream_t pre, hipStream_t main, hipStream_t tail, uint64_t* out,
-               const void* ext_points28 = nullptr, bool glv = true);
-int run_device(const void* d_points, const void* d_scalars, const uint32_t* h_off, size_t k, int c, int win_begin,
-               int win_end, uint64_t* out, void* user_stream, const void* ext_points28 = nullptr, bool glv = true,
-               hipEvent_t wait_for = nullptr);
-int run_host(const uint64_t* points, const uint64_t* scalars, const uint32_t* h_off, size_t k, uint64_t* out, bool glv = true);
+int run_passes(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, const Streams& st, uint64_t* out);
+int run_device(const MsmCall& call, const MsmInputs& in, uint64_t* out, void* user_stream = nullptr, hipEvent_t wait_for = nullptr);
+int run_host(const MsmCall& call, const uint64_t* points, const uint64_t* scalars, uint64_t* out);
 
 // --- msm_host_chunks.hip -----------------------------------------------------
 constexpr size_t kHostChunkMin = (size_t)1 << 19;  // below this a call is one chunk

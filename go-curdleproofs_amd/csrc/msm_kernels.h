@@ -57,6 +57,7 @@ struct MsmPlan {
   uint16_t shift[kMaxWindows];  // bit offset of window w
   uint32_t nbkt[kMaxWindows];   // bucket slots of window w
   uint32_t base[kMaxWindows];   // first slot of window w inside an MSM's NB slots
+  uint32_t merge_blocks;        // (host only, last so that no field the kernels read moves) k_merge_large's grid at most
 };
 
 // Sizes of the internal (fp28.h) point formats, for workspace allocation.
@@ -139,7 +140,7 @@ hipError_t launch_hist(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t str
 hipError_t launch_scan(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream);
 hipError_t launch_scatter(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream);
 hipError_t launch_accumulate(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream);
-hipError_t launch_merge_large(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream, uint32_t max_blocks);
+hipError_t launch_merge_large(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream);
 // extra: fragment lists of earlier chunks (same plan) to fold in besides ws's own; may be null
 hipError_t launch_bucket_reduce(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream, const FragSources* extra = nullptr);
 hipError_t launch_window_sum(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream);

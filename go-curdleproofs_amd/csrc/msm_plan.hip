@@ -50,11 +50,18 @@ int window_widths(int c, uint8_t bits[kMaxWindows], int scalar_bits) {
   return W;
 }
 
-// Plan for k MSMs of n_total pairs in all, the largest having n_max pairs.
-int make_plan(MsmPlan& p, size_t n_total, size_t k, size_t n_max, int c, int win_begin, int win_end,
-              bool latency_mode, size_t sets, bool many, uint32_t seg_override, bool light_host, bool glv) {
+// The whole plan of one call: k MSMs of call.off[k] pairs in all.  No caller changes it afterwards.
+int make_plan(MsmPlan& p, const MsmCall& call) {
+  const size_t k = call.k, sets = call.sets;
+  const bool latency_mode = !call.pipelined, light_host = call.light_host, glv = call.glv;
+  size_t n_total = call.off[k], n_max = 0;
+  for (size_t j = 0; j < k; j++) {
+    if (call.off[j + 1] < call.off[j]) return fail(CURDLE_EINVAL, "offsets not monotone at %zu", j);
+    if (call.off[j + 1] - call.off[j] > n_max) n_max = call.off[j + 1] - call.off[j];
+  }
+  int c = call.c, win_begin = call.win_begin, win_end = call.win_end;
   if (n_total > ((size_t)1 << 27)) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^27 pairs", n_total);
-  many = many || k * sets >= gpu_combine_min();  // a pass of a larger batch keeps the batch's rules
+  const bool many = call.many || k * sets >= gpu_combine_min();  // a pass of a larger batch keeps the batch's rules
   if (c == 0) c = choose_window_bits(n_max, many);
   if (c < 4 || c > 16) return fail(CURDLE_EINVAL, "window_bits %d outside [4, 16]", c);
   memset(&p, 0, sizeof(p));
@@ -127,7 +134,7 @@ int make_plan(MsmPlan& p, size_t n_total, size_t k, size_t n_max, int c, int win
     while (nbk / seg * 4 > lanes && seg < 64) seg *= 2;
     p.seg = seg;
   }
-  if (seg_override) p.seg = seg_override;
+  if (call.seg) p.seg = call.seg;
   if (knobs::get(knobs::REDUCE_SEG) > 0) p.seg = (uint32_t)knobs::get(knobs::REDUCE_SEG);
   if (p.seg < 1) p.seg = 1;
   while (p.seg > min_nbkt || (p.seg & (p.seg - 1))) p.seg >>= 1;
@@ -210,8 +217,9 @@ int make_plan(MsmPlan& p, size_t n_total, size_t k, size_t n_max, int c, int win
     // (two A/B rounds on one box, gpurun_out/r5r; round 4 had measured the raised sort TOGETHER with the raised
     // reduction slower than the reduction alone -- with the lighter sort of this round it is the other way round).
     // Synchronous calls have the chip to themselves; chunked host-buffer calls do not move (4.45-4.57 ms either way).
+    // A joined call (the chunks of a host-buffer call, a two-step one) sorts and folds beside its own earlier chunks: raised too.
     const long long v = knobs::get(knobs::AUX_PRIO);
-    p.aux_prio = v >= 0 ? (uint32_t)(v > 3 ? 3 : v) : (!latency_mode ? 3u : 0u);
+    p.aux_prio = v >= 0 ? (uint32_t)(v > 3 ? 3 : v) : (!latency_mode || call.joined ? 3u : 0u);
   }
   {
     const long long v = knobs::get(knobs::ACC_PRIO);
@@ -229,8 +237,13 @@ int make_plan(MsmPlan& p, size_t n_total, size_t k, size_t n_max, int c, int win
   // which the reduction walks fragment by fragment on its chain, is shorter.  Eight such buckets in one segment made the reduction
   // of a synchronous 2^20 call 0.74 ms where it takes 0.25 (600 distinct scalar values: 13-16 fragments in every occupied bucket;
   // profiles/r06_adversarial_distinct_k.txt).
-  p.max_small = 16;
-  if (k * sets == 1) {
+  // ONE limit for every chunk of a host-buffer call, in both of its enqueue steps, whatever the sizes of the chunks say: the
+  // reduction reads all their fragment lists under the last chunk's plan, and a bucket merged under one limit and read under
+  // another would count twice.  8, what the size rule gives a chunk of up to about 2^24 pairs (and max_large below follows it):
+  // a bucket just under the limit is walked fragment by fragment by the fold and by the reduction (limits of 16 and 32 made
+  // 256..1,024 distinct scalar values from host slices 1.3-1.6x a uniform call: profiles/r06_adversarial_distinct_k.txt).
+  p.max_small = call.chunked ? 8 : 16;
+  if (k * sets == 1 && !call.chunked) {
     if (n_total <= 8192) {
       p.max_small = 8;
     } else if (min_nbkt) {
@@ -241,10 +254,12 @@ int make_plan(MsmPlan& p, size_t n_total, size_t k, size_t n_max, int c, int win
       p.max_small = (uint32_t)(lim < 8 ? 8 : lim > 16 ? 16 : lim);
     }
   }
-  // a bucket with more than max_small fragments holds more than (max_small - 1) * L entries
+  // a bucket with more than max_small (the final limit) fragments holds more than (max_small - 1) * L entries
   uint64_t ml = entries / ((uint64_t)(p.max_small - 1) * p.L) + 1;
   p.max_large = (uint32_t)(ml < nbk ? ml : nbk);
   if (p.max_large == 0) p.max_large = 1;
+  // fragments reserved per base set: one per bucket slot and accumulate lane at most, + 1 (MsmWorkspace::frags)
+  p.frag_stride = (uint32_t)((uint64_t)k * p.NB + (entries + p.L - 1) / p.L + 1);
   // Pairs per sort block: about 512 blocks over all windows, at least 4096 pairs each
   // (an MSM of a batch is never split below that).
   uint64_t ch = (entries + 511) / 512;
@@ -264,16 +279,20 @@ int make_plan(MsmPlan& p, size_t n_total, size_t k, size_t n_max, int c, int win
   }
   // The bucket-slot scans.  k_scan_one -- one block, the slots read once, coalesced, the block scans by wave shuffles --
   // up to 32,768 slots; k_scan_chain (round 5) -- one launch at ANY size, tile sums handed down a chain -- beyond that
-  // and (enqueue_slot) for every pipelined or chunked call, beside whose neighbours k_scan_one's 16 x 121-register block
+  // and for every pipelined or joined call, beside whose neighbours k_scan_one's 16 x 121-register block (four SIMDs EMPTY)
   // cannot start: a rank of the 8-way window split 0.428 -> 0.396 ms per step, synchronous 2^16 / 2^17 / 2^18 pairs 0.610 /
   // 0.808 / 1.149 -> 0.589 / 0.788 / 1.130 ms (profiles/r05_scan_chain.txt).  The six-launch multi-block form is left for
   // ONE case: L = 1 (knob SEG_LEN), since both one-launch forms divide by L with a multiply that needs L >= 2.
   // (Round 6: the knob SCAN and k_scan_fused, the round-2 single-block form, are gone: every comparison is under profiles/.)
   {
     const uint64_t nbs = (uint64_t)k * p.NB;
-    p.fuse_scan = nbs <= 32768 ? 2u : 3u;
+    p.fuse_scan = nbs <= 32768 && latency_mode && !call.joined ? 2u : 3u;
     if (p.L < 2) p.fuse_scan = 0;
   }
+  // The merge launch's grid at most: a synchronous call has the chip to itself (768 blocks; also the one-chunk host-buffer call,
+  // whose join only splits its own enqueue in two); a chunk of a chunked call runs beside the next chunk's accumulation (256); a
+  // pipelined call pays for every empty block (64: msm_reduce_kernels.hip launch_merge_large).
+  p.merge_blocks = call.chunked ? 256u : latency_mode ? 768u : 64u;
   return CURDLE_OK;
 }
 

@@ -709,7 +709,7 @@ __global__ void __launch_bounds__(kBlock, 2)
 // ---------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------
-hipError_t launch_merge_large(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream, uint32_t max_blocks) {
+hipError_t launch_merge_large(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream) {
   // One wave per chunk of 32 to 256 fragments; more chunks than waves go round.  The launch is almost always empty
   // (uniform scalars queue nothing) and every block of it has to find room beside the next accumulation before it can
   // read the empty queue and leave: a synchronous call, which has the chip to itself, takes up to 768 blocks = three
@@ -719,7 +719,7 @@ hipError_t launch_merge_large(const MsmPlan& p, const MsmWorkspace& ws, hipStrea
   const u32 nw = p.win_end - p.win_begin;
   const u64 nlanes = ((u64)nw * p.n + p.L - 1) / p.L;  // fragments <= bucket slots + lanes
   const u64 chunks = (u64)p.max_large + ((u64)p.k * p.NB + nlanes) / 32u;
-  const u32 cap = max_blocks < 1u ? 1u : max_blocks > 768u ? 768u : max_blocks;
+  const u32 cap = p.merge_blocks < 1u ? 1u : p.merge_blocks > 768u ? 768u : p.merge_blocks;  // (make_plan)
   const u32 blocks = (u32)(chunks / 4u + 1u < cap ? chunks / 4u + 1u : cap);
   hipLaunchKernelGGL(k_merge_large, dim3(blocks, p.sets), dim3(kBlock), 0, stream, ws.large, ws.nlarge, ws.foff, ws.fragcnt,
                      reinterpret_cast<X28*>(ws.frags), ws.mdone, p.max_large, p.frag_stride, p.reduce_prio);

@@ -556,8 +556,8 @@ def test_merge_of_large_buckets_in_every_form(gpu, oracle, coracle):
         assert (gpu.msm_wait(t) == exp).all()
         m = 1 << 14
         assert (gpu.msm_g1_device(d_pts.data_ptr(), d_sc.data_ptr(), m) == _walk_expected(oracle, coracle, k, q, sc[:m])).all()
-        # (b') a few hundred distinct values: every occupied bucket holds 9..16 fragments -- over the plan's merge limit at this
-        # size (8), under the chunks' (16: a chunk of a host-buffer call keeps its mid-size buckets for the fold).  The limit
+        # (b') a few hundred distinct values: every occupied bucket holds 9..16 fragments -- over the merge limit (8) of the
+        # plan at this size and of every chunk of a host-buffer call, so they are merged whole or chunk by chunk.  The limit
         # must be the same in a chunk's sort step and in its accumulate step, with two chunks as with four: a bucket merged
         # under one limit and read under the other would count twice.
         table = rand_scalars(rng, 700, oracle)
