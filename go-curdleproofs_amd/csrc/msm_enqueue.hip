@@ -99,15 +99,17 @@ static int enqueue_slot_impl(Ctx& cx, Slot& S, const MsmCall& call, const MsmInp
   ws.results = (G1XYZZ*)S.results.p;
   ws.chain = nullptr;
   ws.chain_ticket = nullptr;
-  ws.host_err = nullptr;
   ws.chain_base = ws.chain_epoch = 0;
+  // the slot's error word goes with every call: k_merge_large raises it when the large-bucket queue overflowed, k_scan_chain
+  // when a wait inside it gave up
+  if (!S.h_err) {
+    HIP_TRY(hipHostMalloc((void**)&S.h_err, 64, hipHostMallocDefault));
+    *S.h_err = 0;
+  }
+  ws.host_err = S.h_err;
   if (p.fuse_scan == 3) {
     const void* before = S.chain.p;
     if ((rc = ensure(S.chain, scan_chain_bytes()))) return rc;
-    if (!S.h_err) {
-      HIP_TRY(hipHostMalloc((void**)&S.h_err, 64, hipHostMallocDefault));
-      *S.h_err = 0;
-    }
     S.scan_epoch = (S.scan_epoch + 1) & 0x3fffffffu;
     if (S.chain.p != before || S.scan_epoch == 0) {  // a new buffer, or the epochs have gone round: no word may look current
       HIP_TRY(hipMemsetAsync(S.chain.p, 0, scan_chain_bytes(), pre));
@@ -116,7 +118,6 @@ static int enqueue_slot_impl(Ctx& cx, Slot& S, const MsmCall& call, const MsmInp
     }
     ws.chain = (unsigned long long*)S.chain.p;
     ws.chain_ticket = (uint32_t*)((char*)S.chain.p + scan_chain_bytes() - 64);
-    ws.host_err = S.h_err;
     ws.chain_base = S.scan_base;
     ws.chain_epoch = S.scan_epoch;
   }
@@ -288,11 +289,23 @@ int enqueue_slot(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, con
     for (Buf* b : {&S.ccur, &S.chain, &S.mdone})
       if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->cap, st.pre));
     S.scan_base = 0;
+    if (S.h_err) *S.h_err = 0;  // (drain_slot waited for the failed call's kernels: none of them stores any more)
   }
   S.suspect = true;  // until every launch of this call is queued
   rc = enqueue_slot_impl(cx, S, call, in, st, join);
   if (rc == CURDLE_OK) S.suspect = false;
   return rc;
+}
+
+// The error word a kernel of the slot's last call raised, cleared, as text for the call's error; nullptr: none.  Read only
+// after that call's kernels are done.
+const char* take_slot_error(Slot& S) {
+  if (!S.h_err || !*S.h_err) return nullptr;
+  const uint32_t e = *S.h_err;
+  *S.h_err = 0;
+  if (e == kErrQueueOverflow)
+    return "the large-bucket queue overflowed (k_merge_large): more buckets over the merge limit than the plan allowed for";
+  return "a wait inside the bucket-slot scan gave up (k_scan_chain)";
 }
 
 // Wait for the slot's GPU work and produce the k results (host combine unless the
@@ -306,10 +319,7 @@ int finish_slot(Ctx& cx, Slot& S, uint64_t* out) {
     return CURDLE_OK;
   }
   HIP_TRY(hipStreamSynchronize(S.run_stream));
-  if (S.h_err && *S.h_err) {
-    *S.h_err = 0;
-    return fail(CURDLE_EHIP, "internal: a wait inside the bucket-slot scan gave up");
-  }
+  if (const char* why = take_slot_error(S)) return fail(CURDLE_EHIP, "internal: %s", why);
   if (S.profiled) {
     std::lock_guard<std::mutex> g(cx.mu);
     curdle_profile& L = cx.last;
@@ -320,14 +330,16 @@ int finish_slot(Ctx& cx, Slot& S, uint64_t* out) {
     }
     L.window_bits = p.c;
     L.num_windows = p.W;
-    L.entries = L.fragments = 0;
-    if (cx.profile == 1) {  // two 4-byte reads after the call has drained: diagnostics only
+    L.entries = L.fragments = L.large_buckets = 0;
+    if (cx.profile == 1) {  // three 4-byte reads after the call has drained: diagnostics only
       const size_t nb = (size_t)p.k * p.NB;
-      uint32_t v[2] = {0, 0};
+      uint32_t v[3] = {0, 0, 0};
       (void)hipMemcpy(&v[0], (const char*)S.starts.p + nb * 4, 4, hipMemcpyDeviceToHost);
       (void)hipMemcpy(&v[1], (const char*)S.foff.p + nb * 4, 4, hipMemcpyDeviceToHost);
+      (void)hipMemcpy(&v[2], (const char*)S.small.p + 1024 * 4, 4, hipMemcpyDeviceToHost);  // MsmWorkspace::nlarge
       L.entries = v[0];
       L.fragments = v[1];
+      L.large_buckets = v[2];
     }
   }
   if (p.gpu_combine) {

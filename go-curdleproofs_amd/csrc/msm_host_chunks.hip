@@ -202,17 +202,13 @@ int run_host_chunked(const uint64_t* points, const uint64_t* scalars, size_t n, 
         }
       }
     r = finish_slot(cx, *parts.back().S, out);  // the last chunk's slot holds the window sums
-    // every chunk ran a bucket-slot scan of its own on its own slot: a scan that gave up in an EARLIER chunk raised that
-    // slot's word, which finish_slot above does not look at (review of round 5: the call returned a wrong sum with
-    // CURDLE_OK and the stale flag failed the next, unrelated call on that slot).  The last chunk's reduction is behind
-    // all of them, so every word is final here.
-    for (size_t i = 0; i + 1 < K; i++) {
-      Slot& Sp = *parts[i].S;
-      if (Sp.h_err && *Sp.h_err) {
-        *Sp.h_err = 0;
-        if (!r) r = fail(CURDLE_EHIP, "internal: a wait inside the bucket-slot scan of chunk %zu gave up", i);
-      }
-    }
+    // every chunk ran a bucket-slot scan and a merge of its own on its own slot: a scan that gave up or a large-bucket queue
+    // that overflowed in an EARLIER chunk raised that slot's word, which finish_slot above does not look at (review of round 5:
+    // the call returned a wrong sum with CURDLE_OK and the stale flag failed the next, unrelated call on that slot).  The last
+    // chunk's reduction is behind all of them, so every word is final here.
+    for (size_t i = 0; i + 1 < K; i++)
+      if (const char* why = take_slot_error(*parts[i].S))
+        if (!r) r = fail(CURDLE_EHIP, "internal: chunk %zu: %s", i, why);
     return r;
   };
   int rc = body();

@@ -98,7 +98,7 @@ struct Slot {
   bool profiled = false;
   Buf chain;                  // k_scan_chain's words and ticket counter (zero when made; cleared again only after a failed call)
   Buf mdone;                  // k_merge_large's chunk counters, one per queue entry and base set (zero when made; the kernel leaves them zero)
-  uint32_t* h_err = nullptr;  // pinned word a kernel raises when a wait inside it gave up (finish_slot reads it)
+  uint32_t* h_err = nullptr;  // pinned word a kernel raises when it cannot finish the call correctly (kErr*; finish_slot reads it)
   uint32_t scan_epoch = 0;    // epoch of the slot's last k_scan_chain launch (30 bits, never 0)
   uint32_t scan_base = 0;     // tickets the slot's launches have taken so far
   uint32_t coarse_nw = 0;     // window count the zeroed tail of `ccur` was laid out for
@@ -363,6 +363,7 @@ struct Streams {
 };
 int enqueue_slot(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, const Streams& st, const ChunkJoin* join = nullptr);
 int finish_slot(Ctx& cx, Slot& S, uint64_t* out);
+const char* take_slot_error(Slot& S);
 void drain_slot(Ctx& cx, Slot& S);
 Streams sync_streams(Ctx&, Slot& S);
 constexpr size_t kMaxSlotsPerPass = (size_t)1024 * 4096;

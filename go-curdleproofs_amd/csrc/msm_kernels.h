@@ -87,13 +87,16 @@ struct MsmWorkspace {
   G1XYZZ* winsums;    // [k][nw]   gnark-form XYZZ, canonical coordinates (host combine)
   G1XYZZ* results;    // [k]       XYZZ results of a batched call, gnark form (normalised by the host)
   // k_scan_chain (MsmPlan::fuse_scan == 3): the chain words [2][1024] (zero when allocated, never cleared again), the
-  // ticket counter behind them, the count it stood at before this launch, this launch's epoch (never 0), and a word
-  // of pinned host memory the kernel raises if a wait inside it gave up
+  // ticket counter behind them, the count it stood at before this launch and this launch's epoch (never 0)
   unsigned long long* chain;
   uint32_t* chain_ticket;
+  // a word of pinned host memory, set on every call: a kernel that cannot finish the call correctly raises it (a plain
+  // store of one of the kErr codes below) and finish_slot fails the call
   uint32_t* host_err;
   uint32_t chain_base, chain_epoch;
 };
+static constexpr uint32_t kErrScanGaveUp = 1;     // k_scan_chain: a wait for an earlier tile gave up
+static constexpr uint32_t kErrQueueOverflow = 2;  // k_merge_large: more buckets over max_small than the large-bucket queue holds
 uint32_t scan_chain_tiles(uint32_t nb);  // blocks (= tickets) one k_scan_chain launch over nb slots takes
 size_t scan_chain_bytes();               // bytes behind MsmWorkspace::chain (the ticket counter at the end)
 

@@ -257,6 +257,9 @@ int make_plan(MsmPlan& p, const MsmCall& call) {
   // a bucket with more than max_small (the final limit) fragments holds more than (max_small - 1) * L entries
   uint64_t ml = entries / ((uint64_t)(p.max_small - 1) * p.L) + 1;
   p.max_large = (uint32_t)(ml < nbk ? ml : nbk);
+  // (test hook, knob MAX_LARGE: a smaller queue, so that the tests can make it overflow and see the call fail)
+  if (knobs::get(knobs::MAX_LARGE) >= 0 && (uint64_t)knobs::get(knobs::MAX_LARGE) < p.max_large)
+    p.max_large = (uint32_t)knobs::get(knobs::MAX_LARGE);
   if (p.max_large == 0) p.max_large = 1;
   // fragments reserved per base set: one per bucket slot and accumulate lane at most, + 1 (MsmWorkspace::frags)
   p.frag_stride = (uint32_t)((uint64_t)k * p.NB + (entries + p.L - 1) / p.L + 1);

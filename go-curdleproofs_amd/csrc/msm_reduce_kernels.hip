@@ -66,10 +66,14 @@ __host__ __device__ inline u32 merge_chunk_shift(u32 m) {  // log2 of the chunk 
 __global__ void __launch_bounds__(kBlock, 2)
     k_merge_large(const u32* __restrict__ large, const u32* __restrict__ nlarge, const u32* __restrict__ foff,
                   const u32* __restrict__ fragcnt, X28* __restrict__ frags, u32* __restrict__ done, u32 max_large,
-                  u32 frag_stride, u32 prio) {
+                  u32 frag_stride, u32 prio, u32* __restrict__ host_err) {
   __shared__ u32 pre[kMergeTile], spre[kMergeTile], gq[kMergeTile], mq[kMergeTile];
   __shared__ u32 sh_scan[kBlock / 64];
-  const u32 nl = min(*nlarge, max_large);
+  const u32 queued = *nlarge;
+  // More buckets went over max_small than the queue holds: the scan dropped the rest, and the reduction would read each
+  // of them as ONE pre-merged fragment.  The call must fail, not return a wrong sum: raise the slot's word (finish_slot).
+  if (queued > max_large && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *host_err = kErrQueueOverflow;
+  const u32 nl = min(queued, max_large);
   if (nl == 0) return;  // the usual case
   set_wave_prio(prio);
   const u32 tid = threadIdx.x;
@@ -721,8 +725,9 @@ hipError_t launch_merge_large(const MsmPlan& p, const MsmWorkspace& ws, hipStrea
   const u64 chunks = (u64)p.max_large + ((u64)p.k * p.NB + nlanes) / 32u;
   const u32 cap = p.merge_blocks < 1u ? 1u : p.merge_blocks > 768u ? 768u : p.merge_blocks;  // (make_plan)
   const u32 blocks = (u32)(chunks / 4u + 1u < cap ? chunks / 4u + 1u : cap);
+  if (!ws.host_err) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_merge_large, dim3(blocks, p.sets), dim3(kBlock), 0, stream, ws.large, ws.nlarge, ws.foff, ws.fragcnt,
-                     reinterpret_cast<X28*>(ws.frags), ws.mdone, p.max_large, p.frag_stride, p.reduce_prio);
+                     reinterpret_cast<X28*>(ws.frags), ws.mdone, p.max_large, p.frag_stride, p.reduce_prio, ws.host_err);
   return hipGetLastError();
 }
 

@@ -802,7 +802,7 @@ __device__ __forceinline__ u32 chain_lookback(u64* __restrict__ words, u32 my, u
     j -= (int)usable;
     if (usable == 0u) {
       if (++spins > kChainSpinLimit) {
-        if (lane == 0) *host_err = 1u;
+        if (lane == 0) *host_err = kErrScanGaveUp;
         prefix = 0;
         break;
       }
@@ -830,7 +830,7 @@ __global__ void __launch_bounds__(kChainThreads)
   __syncthreads();
   const u32 my = sh_my;
   if (my >= ch.ntiles) {  // block-uniform; a launch has exactly ntiles blocks, so this is a host count that lags the device's:
-    if (tid == 0) *ch.host_err = 1u;  // the call must fail, not return sums over unwritten starts (review of round 5)
+    if (tid == 0) *ch.host_err = kErrScanGaveUp;  // the call must fail, not return sums over unwritten starts (review of round 5)
     return;
   }
   u64* words0 = reinterpret_cast<u64*>(ch.words);

@@ -78,7 +78,7 @@ _vp = C.c_void_p
 class _Profile(C.Structure):
     _fields_ = [("n_kernels", C.c_int), ("name", C.c_char_p * 16), ("ms", C.c_float * 16),
                 ("window_bits", C.c_int), ("num_windows", C.c_int), ("entries", C.c_ulonglong),
-                ("fragments", C.c_ulonglong)]
+                ("fragments", C.c_ulonglong), ("large_buckets", C.c_ulonglong)]
 
 
 def _sig(name, restype, *argtypes):
@@ -547,6 +547,7 @@ def profile_last() -> dict:
         "num_windows": p.num_windows,
         "entries": int(p.entries),
         "fragments": int(p.fragments),
+        "large_buckets": int(p.large_buckets),
     }
 
 

@@ -561,6 +561,9 @@ typedef struct {
    * the launch did entries - fragments real mixed additions */
   unsigned long long entries;
   unsigned long long fragments;
+  /* mode 1 only: buckets of the last call with more fragments than its merge limit -- what the
+   * scan counted for the large-bucket queue, beyond its capacity too (the call then fails) */
+  unsigned long long large_buckets;
 } curdle_profile;
 /* on = 1: every MSM call brackets each kernel with hipEvents on the stream it launches on
  * and keeps the durations of the last call.  on = 2: only the dominant kernel (the bucket

@@ -1,6 +1,9 @@
 // Host-only probe of the library's MSM plan (tests/test_plan.py): calls make_plan over a grid of calls and prints, per
 // call, the inputs and the plan fields the plan invariants are about.  No device is touched.
+//   plan_probe n glv pipelined chunked c: the plan of ONE single-MSM call instead (tests/test_msm_large_gpu.py), with
+//   the window widths and the bucket counts per window.
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <vector>
 
@@ -15,12 +18,31 @@ static void probe(const char* shape, const std::vector<uint32_t>& off, MsmCall c
          off.back(), call.k, call.sets, call.c, call.win_begin, call.win_end, call.pipelined, call.joined, call.chunked, call.many,
          call.light_host, call.glv, call.seg, rc);
   if (rc == CURDLE_OK)
-    printf(" terms=%u nw=%d pk=%u psets=%u NB=%u L=%u max_small=%u max_large=%u fuse_scan=%u", p.n, p.win_end - p.win_begin, p.k,
-           p.sets, p.NB, p.L, p.max_small, p.max_large, p.fuse_scan);
+    printf(" terms=%u nw=%d pk=%u psets=%u NB=%u L=%u max_small=%u max_large=%u fuse_scan=%u two_level=%u c=%d", p.n,
+           p.win_end - p.win_begin, p.k, p.sets, p.NB, p.L, p.max_small, p.max_large, p.fuse_scan, p.two_level, p.c);
   printf("\n");
 }
 
-int main() {
+static int one(char** argv) {
+  const uint32_t n = (uint32_t)strtoul(argv[1], nullptr, 0);
+  const std::vector<uint32_t> off = {0, n};
+  MsmCall call;
+  call.off = off.data();
+  call.glv = atoi(argv[2]) != 0;
+  call.pipelined = atoi(argv[3]) != 0;
+  call.joined = call.chunked = atoi(argv[4]) != 0;
+  call.c = atoi(argv[5]);
+  probe("one", off, call);
+  MsmPlan p;
+  if (make_plan(p, call) != CURDLE_OK) return 1;
+  printf("windows");
+  for (int w = 0; w < p.W; w++) printf(" %u:%u", p.bits[w], p.nbkt[w]);
+  printf("\n");
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 6) return one(argv);
   // single MSMs and batches, every mode flag, several window ranges and widths
   const uint32_t sizes[] = {1, 300, 1268, 8192, 16384, 65536, 131072, 1u << 18, 1u << 20, 1u << 22, 1u << 24, 22369622,
                             1u << 25, 1u << 26, 1u << 27};
