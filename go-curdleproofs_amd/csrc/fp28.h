@@ -6,7 +6,8 @@
 // product needs its carry captured (v_addc_co_u32), and the pair issues every
 // 9.25-10.4 cycles per SIMD; the multiply alone issues every 4.9
 // (profiles/r01_ubench_valu.txt).  With 28-bit limbs a 64-bit column accumulator
-// holds all <= 29 products of a column without overflow, so a field product is
+// holds every column without overflow (28 products in mul / sqr, 42 in mul2_inl, at
+// the operand bounds below: tests/test_fp28_model.py), so a field product is
 // 406 bare multiply-adds (315 for a square) plus a shift and a mask per column:
 // measured 1.33x the throughput of the 32-bit form.  R' = 2^392 leaves 11 spare
 // bits over p (381 bits), which buys lazy reduction: products come out below 2p
@@ -38,7 +39,8 @@ struct F28 {
   u32 l[N];
 };
 // XYZZ point, x = X/ZZ, y = Y/ZZZ; infinity <=> ZZ == 0 (all limbs zero).
-// Invariant for stored points: X, Y < 10p; ZZ, ZZZ < 2p; limbs normalised.
+// Invariant for stored points: X, Y < 10p; ZZ, ZZZ < 2p; limbs normalised.  Every formula
+// below accepts Y up to 10p and gives Y3 < 6p back (madd even < 2p), the bound quad28.h states.
 struct X28 {
   F28 x, y, zz, zzz;
 };

@@ -61,6 +61,16 @@ extern "C" int curdle_selftest_op(int op, const uint64_t* in64, size_t n, uint64
   // the widths of every operation live in ONE table (msm_kernels.h), which the launcher and the kernel index too
   const size_t in_w = kSelftestTable[op].in_words, out_w = kSelftestTable[op].out_words;
   if (n > ((size_t)1 << 26)) return fail(CURDLE_EINVAL, "selftest of %zu elements", n);
+  if (op >= 13) {  // raw-limb operations: fp28.h / quad28.h are device headers, there is no host build
+    if (!on_device) return fail(CURDLE_EINVAL, "selftest op %d runs on the device only (fp28.h is a device header)", op);
+    const uint32_t nsel = op == 13 ? kSelftestFieldSels : (op == 14 ? kSelftestPointSels : kSelftestQuadSels);
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t* s = in + i * in_w;
+      if (s[0] >= nsel) return fail(CURDLE_EINVAL, "selftest op %d: element %zu has selector %u (of %u)", op, i, s[0], nsel);
+      if (op == 15 && s[0] == 3 && (s[2] > 31 || (s[2] < 31 && (s[1] >> (s[2] + 1)) != 0)))
+        return fail(CURDLE_EINVAL, "selftest op 15: element %zu has k = %u above bit top = %u", i, s[1], s[2]);
+    }
+  }
   if (!on_device) {
     for (size_t i = 0; i < n; i++) {
       const uint32_t* s = in + i * in_w;

@@ -170,7 +170,7 @@ struct SelftestOp {
   uint32_t out_words;  // ... written per element
   uint32_t lanes;      // lanes per element: 4 for the lane-distributed (quad) operations
 };
-static constexpr int kSelftestOps = 13;
+static constexpr int kSelftestOps = 16;
 static constexpr SelftestOp kSelftestTable[kSelftestOps] = {
     {24, 12, 1}, {24, 12, 1}, {24, 12, 1}, {24, 12, 1},  // 0..3  Fp mul / add / sub / sqr
     {16, 8, 1},                                           // 4     Fr Montgomery -> canonical
@@ -178,7 +178,16 @@ static constexpr SelftestOp kSelftestTable[kSelftestOps] = {
     {96, 48, 4}, {96, 48, 4}, {96, 48, 4},                // 8..10 add / dbl / small multiple on quads
     {8, 10, 1},                                           // 11    the GLV split
     {24, 26, 1},                                          // 12    a base into the MSM's curve and back (+ the two bound flags)
+    {60, 16, 1},                                          // 13    fp28.h field operations on raw limbs
+    {116, 56, 1},                                         // 14    fp28.h point operations on raw limbs, one lane
+    {116, 56, 4},                                         // 15    quad28.h point operations on raw limbs
 };
+// Operations 13..15 read and write the internal 14 x 28-bit limbs directly (no from_gnark / to_gnark on
+// either side).  Word 0 of an element selects the primitive; a selector outside these counts is refused
+// by the host before anything is copied or launched.
+static constexpr uint32_t kSelftestFieldSels = 26;  // op 13
+static constexpr uint32_t kSelftestPointSels = 6;   // op 14
+static constexpr uint32_t kSelftestQuadSels = 4;    // op 15
 // hipErrorInvalidValue for an op outside the table (nothing is launched).
 hipError_t launch_selftest(int op, const uint32_t* d_in, size_t n, uint32_t* d_out, hipStream_t stream);
 

@@ -68,11 +68,115 @@ hipError_t launch_synth_walk(const G1Affine* d_table, const G1Affine& p0, uint32
 // ---------------------------------------------------------------------------
 // All operands and results cross this kernel in gnark form; the operation itself
 // runs in the internal radix-2^28 form the MSM kernels use.
+// Operations 13..15 take the limbs as they are: the words a test writes are the words the primitive sees,
+// so the lazily reduced representations the MSM kernels carry (values up to 18p, limbs up to 2^30) can
+// be driven at the bounds each function states.
+//   op 13: in sel | pad 3 | a | b | c | d (14 words each), out r (14) | flag | pad
+//   op 14 / 15: in sel | k | top | pad | A (X28, 56 words) | B (X28), out X28
+__device__ __forceinline__ void selftest_field(const u32* src, u32* dst) {
+  F28 a, b, c, d, r;
+  for (int k = 0; k < d28::N; k++) {
+    a.l[k] = src[4 + k];
+    b.l[k] = src[18 + k];
+    c.l[k] = src[32 + k];
+    d.l[k] = src[46 + k];
+    r.l[k] = 0;
+  }
+  u32 flag = 0;
+  u32 w[12];
+  switch (src[0]) {
+    case 0: d28::mul_inl(r, a, b); break;
+    case 1: d28::sqr_inl(r, a); break;
+    case 2: d28::mul(r, a, b); break;
+    case 3: d28::sqr(r, a); break;
+    case 4: d28::mul2_inl(r, a, b, c, d); break;
+    case 5: d28::add(r, a, b); break;
+    case 6: d28::sub<4>(r, a, b); break;
+    case 7: d28::sub<8>(r, a, b); break;
+    case 8: d28::sub<16>(r, a, b); break;
+    case 9: d28::sub_raw<4>(r, a, b); break;
+    case 10: d28::sub_raw<8>(r, a, b); break;
+    case 11: d28::sub_raw<16>(r, a, b); break;
+    case 12: d28::dbl_raw(r, a); break;
+    case 13: d28::triple_raw(r, a); break;
+    case 14: d28::x3_fused(r, a, b, c); break;
+    case 15: r = a; d28::norm(r); break;
+    case 16: r = a; d28::canonical_lt2p(r); break;
+    case 17: flag = d28::is_zero_lt2p(a); break;
+    case 18: r = a; d28::cond_sub_pshl<1>(r); break;
+    case 19: r = a; d28::cond_sub_pshl<2>(r); break;
+    case 20: r = a; d28::cond_sub_pshl<3>(r); break;
+    case 21:
+    case 22:
+    case 23:
+    case 24:
+    case 25:
+      if (src[0] == 21) d28::to_gnark(w, a);
+      else d28::to_gnark_msm(w, a, src[0] - 22);
+      for (int k = 0; k < 12; k++) r.l[k] = w[k];
+      break;
+    default: return;  // refused by the host
+  }
+  for (int k = 0; k < d28::N; k++) dst[k] = r.l[k];
+  dst[14] = flag;
+  dst[15] = 0;
+}
+
+__device__ __forceinline__ void selftest_point(const u32* src, u32* dst) {
+  X28 a, b;
+  u32* a32 = reinterpret_cast<u32*>(&a);
+  u32* b32 = reinterpret_cast<u32*>(&b);
+  for (int k = 0; k < 56; k++) {
+    a32[k] = src[4 + k];
+    b32[k] = src[60 + k];
+  }
+  switch (src[0]) {
+    case 0: d28::madd<false>(a, b.x, b.y); break;
+    case 1: d28::madd<true>(a, b.x, b.y); break;
+    case 2: d28::add(a, b); break;
+    case 3: d28::dbl(a); break;
+    case 4: {
+      const F28 x1 = a.x, y1 = a.y;
+      d28::dbl_affine(a, x1, y1);
+      break;
+    }
+    case 5: d28::mul_small(a, b, src[1]); break;
+    default: return;  // refused by the host
+  }
+  for (int k = 0; k < 56; k++) dst[k] = a32[k];
+}
+
 // The widths come from kSelftestTable (msm_kernels.h) as arguments; a branch whose own layout does
 // not match them returns without touching memory, and so does an unknown op.
 __global__ void __launch_bounds__(kBlock, 2)
     k_selftest(int op, const u32* __restrict__ in, size_t n, u32* __restrict__ out, u32 in_w, u32 out_w) {
   size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (op == 15) {  // quad28.h on raw limbs: every branch below is uniform over a quad (one element)
+    if (in_w != 116 || out_w != 56) return;
+    i >>= 2;
+    if (i >= n) return;  // whole quads leave together
+    const u32* src = in + i * in_w;
+    const u32 sel = src[0];
+    if (sel >= kSelftestQuadSels) return;  // refused by the host
+    X28 pa, pb;
+    u32* a32 = reinterpret_cast<u32*>(&pa);
+    u32* b32 = reinterpret_cast<u32*>(&pb);
+    for (int k = 0; k < 56; k++) {
+      a32[k] = src[4 + k];
+      b32[k] = src[60 + k];
+    }
+    F28 ca, cb;
+    q28::from_x28(ca, pa);
+    q28::from_x28(cb, pb);
+    if (sel == 0) q28::add(ca, cb);
+    else if (sel == 1) q28::dbl(ca);
+    else if (sel == 2) q28::dbl_outofline(ca);
+    else q28::mul_small(ca, cb, src[1], (int)min(src[2], 31u));
+    q28::to_x28(pa, ca);
+    if (threadIdx.x & 3u) return;
+    for (int k = 0; k < 56; k++) out[i * out_w + k] = a32[k];
+    return;
+  }
   if (op >= 8 && op <= 10) {  // lane-distributed point operations (quad28.h): four lanes per element
     if (in_w != 96 || out_w != 48) return;
     i >>= 2;
@@ -103,7 +207,13 @@ __global__ void __launch_bounds__(kBlock, 2)
     return;
   }
   if (i >= n) return;
-  if (op == 11) {  // the GLV split exactly as k_digits runs it
+  if (op == 13) {
+    if (in_w != 60 || out_w != 16) return;
+    selftest_field(in + i * in_w, out + i * out_w);
+  } else if (op == 14) {
+    if (in_w != 116 || out_w != 56) return;
+    selftest_point(in + i * in_w, out + i * out_w);
+  } else if (op == 11) {  // the GLV split exactly as k_digits runs it
     if (in_w != 8 || out_w != 10) return;
     Fr k;
     for (int j = 0; j < 8; j++) k.l[j] = in[i * in_w + j];

@@ -19,7 +19,8 @@
 // instruction cache made its product step 3.7x slower than the single-lane one
 // (profiles/r02_quad_experiment.txt).
 //
-// Value bounds are those of fp28.h: stored X < 10p, Y < 6p, ZZ, ZZZ < 2p, limbs normalised;
+// Value bounds are those of fp28.h: stored X < 10p, Y < 10p (the formulas give Y < 6p), ZZ, ZZZ < 2p,
+// limbs normalised;
 // infinity <=> ZZ == 0 (all limbs; lane 2).
 //
 // Formulas: EFD "xyzz" add-2008-s and dbl-2008-s-1 (a = 0), as in fp28.h add() / dbl().

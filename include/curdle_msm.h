@@ -599,8 +599,24 @@ int curdle_synth_points_walk_device(const uint64_t k[4], const uint64_t q[4], si
  *          leaves through 2^388 / 2^390) on plain field elements: in: n x (Fp | Fp), out: n x
  *          (Fp | Fp | 1 if the x image is normalised and below 2p | the same for y); the round trip
  *          is the identity (the host build copies)
- * (limbs are passed as uint32 little-endian; 24/16/96/8/24 in and 12/8/48/10/26 out per item)
- * on_device = 0 runs the same header code on the host CPU. */
+ *   op 13..15: the device-internal arithmetic (csrc/fp28.h, csrc/quad28.h) on RAW internal limbs
+ *          (14 x 28-bit limbs per field element, Montgomery radix 2^392, not reduced; no conversion
+ *          on either side), so tests can drive every bound those functions state.  Word 0 of an item
+ *          is a selector; an item with an unknown selector makes the call fail with CURDLE_EINVAL
+ *          before anything is copied or launched.  Device only: on_device = 0 is CURDLE_EINVAL.
+ *   op 13: in: sel | 3 pad | a | b | c | d (14 words each), out: r (14 words) | flag | pad.
+ *          sel 0 mul_inl(a,b)  1 sqr_inl(a)  2 mul(a,b)  3 sqr(a) (the out-of-line calls)
+ *          4 mul2_inl(a,b,c,d)  5 add(a,b)  6/7/8 sub<4/8/16>(a,b)  9/10/11 sub_raw<4/8/16>(a,b)
+ *          12 dbl_raw(a)  13 triple_raw(a)  14 x3_fused(a,b,c)  15 norm(a)  16 canonical_lt2p(a)
+ *          17 is_zero_lt2p(a) -> flag  18/19/20 cond_sub_pshl<1/2/3>(a)  21 to_gnark(a) and
+ *          22..25 to_gnark_msm(a, role 0..3) -> 12 gnark words in r
+ *   op 14: one-lane points: in: sel | k | top | pad | A (X28: X, Y, ZZ, ZZZ, 56 words) | B (X28),
+ *          out: X28.  sel 0 madd<false>(A, B.x, B.y)  1 madd<true>(A, B.x, B.y)  2 add(A, B)
+ *          3 dbl(A)  4 dbl_affine(A.x, A.y)  5 mul_small(B, k)
+ *   op 15: the same layout through the quads: sel 0 q28::add(A, B)  1 q28::dbl(A)
+ *          2 q28::dbl_outofline(A)  3 q28::mul_small(B, k, top) (top <= 31, k < 2^(top+1))
+ * (limbs are passed as uint32 little-endian; 24/16/96/8/24/60/116 in and 12/8/48/10/26/16/56 out per item)
+ * on_device = 0 runs the same header code on the host CPU (ops 0..12). */
 int curdle_selftest_op(int op, const uint64_t* in, size_t n, uint64_t* out, int on_device);
 /* Words per item operation `op` reads and writes: the ONE table the entry point above, its launcher
  * and its kernel index (a binding sizes its arrays from this instead of keeping a copy).

@@ -126,24 +126,40 @@ def test_knobs_are_read_once_and_changed_only_through_the_hook(cm):
     assert out.stdout.strip() == "11", (out.stdout, out.stderr[-500:])   # at process start the environment does count
 
 
-def test_selftest_operations_share_one_table(cm):
+def test_selftest_operations_and_raw_limb_operations_share_one_table(cm):
     """curdle_selftest_op's buffer sizes, its launcher's grid and its kernel's indexing come from ONE
     table, which the binding asks for too: an unknown operation is refused before anything is
-    allocated or launched (round 3's r3a abort was an operation known to one of them only)."""
-    shapes = [cm.selftest_shape(op) for op in range(13)]
+    allocated or launched (round 3's r3a abort was an operation known to one of them only).  The table
+    has 16 operations; 13..15 (raw internal limbs) are device only and check their selectors first."""
+    shapes = [cm.selftest_shape(op) for op in range(16)]
     assert shapes[:5] == [(24, 12)] * 4 + [(16, 8)]
     assert shapes[5:11] == [(96, 48)] * 6 and shapes[11] == (8, 10) and shapes[12] == (24, 26)
-    for bad in (-1, 13, 99):
+    assert shapes[13] == (60, 16) and shapes[14] == shapes[15] == (116, 56)   # the raw-limb operations
+    for bad in (-1, 16, 99):
         with pytest.raises(RuntimeError):
             cm.selftest_shape(bad)
     inp = np.zeros((3, 8), dtype=np.uint32)
     out = np.zeros((3, 10), dtype=np.uint32)
     for on_device in (0, 1):
-        assert cm._selftest_op(13, cm._ptr(inp), 3, cm._ptr(out), on_device) == cm.EINVAL
+        assert cm._selftest_op(16, cm._ptr(inp), 3, cm._ptr(out), on_device) == cm.EINVAL
+    # the raw-limb operations run fp28.h / quad28.h, device headers: the host build refuses them, and an
+    # unknown selector (word 0) is refused before anything is copied or launched, with or without a device
+    for op, nsel in ((13, 26), (14, 6), (15, 4)):
+        iw, ow = shapes[op]
+        with pytest.raises(RuntimeError, match="device only"):
+            cm.selftest_op(op, np.zeros((2, iw), dtype=np.uint32), False)
+        bad_sel = np.zeros((3, iw), dtype=np.uint32)
+        bad_sel[2, 0] = nsel
+        with pytest.raises(RuntimeError, match="selector"):
+            cm.selftest_op(op, bad_sel, True)
+    bad_top = np.zeros((1, 116), dtype=np.uint32)
+    bad_top[0, :3] = (3, 5, 1)                       # q28::mul_small with k above bit `top`
+    with pytest.raises(RuntimeError, match="above bit top"):
+        cm.selftest_op(15, bad_top, True)
     # the host build of every operation runs on exactly the table's widths
     for op, (iw, ow) in enumerate(shapes):
-        if op in (8, 9, 10):
-            continue            # need valid points: covered on the GPU
+        if op in (8, 9, 10) or op >= 13:
+            continue            # need valid points / a device: covered on the GPU
         assert cm.selftest_op(op, np.zeros((2, iw), dtype=np.uint32), False).shape == (2, ow)
 
 
