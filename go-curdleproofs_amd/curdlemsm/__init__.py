@@ -884,6 +884,26 @@ def g1_decompress_begin(data: bytes):
     return out, st, t.value
 
 
+_decompress_start = _sig("curdle_g1_decompress_start", C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int))
+_decompress_points = _sig("curdle_g1_decompress_points", C.c_int, C.c_int, _vp, _vp)
+
+
+def g1_decompress_start(data: bytes) -> int:
+    """Three-step decode, step one: launches the decoding and returns a ticket at once."""
+    b = np.frombuffer(bytes(data), dtype=np.uint8).copy()
+    t = C.c_int(-1)
+    _check(_decompress_start(_ptr(b), len(b) // 48, C.byref(t)))
+    return t.value
+
+
+def g1_decompress_points(ticket: int, n: int):
+    """Step two: (points, preliminary status) of the ticket's n records; g1_decompress_finish is step three."""
+    out = np.zeros((n, 12), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    _check(_decompress_points(ticket, _ptr(out), _ptr(st)))
+    return out, st
+
+
 def g1_decompress_finish(ticket: int, n: int) -> np.ndarray:
     st = np.zeros(n, dtype=np.uint8)
     _check(_decompress_finish(ticket, _ptr(st)))

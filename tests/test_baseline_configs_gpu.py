@@ -166,6 +166,14 @@ def test_config5_1024_whisk_shuffle_proofs_in_one_batch(gpu, oracle):
     plant(774, proof=bytes(flipped))
     plant(1023, proof=b"\x00" * 4576)
     plant(1022, proof=rogue + sets[6][2][48:])                        # M outside the subgroup
+    # the small-order points of tests/golden/decode_edge_records.npz: (0, 2) of order 3 as a post-shuffle tracker's
+    # second point, and M = T + Q (T of order 10177, Q in G1)
+    from test_decode_edges_gpu import attack_records
+    attack = attack_records(oracle)
+    order3 = list(sets[387 % 8][1])
+    order3[11] = order3[11][:48] + attack["order 3"]
+    plant(387, post=order3)
+    plant(901, proof=attack["T+Q"] + sets[901 % 8][2][48:])
     for nthreads in (16, 3):
         assert gpu.whisk_is_valid_shuffle_proof_batch(crs, pres, posts, proofs, gpu.Rand(2), nthreads=nthreads) == expect
 

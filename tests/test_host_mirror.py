@@ -234,6 +234,27 @@ def test_subgroup_check_of_the_decoder(cm, oracle):
             cm.g1_decompress(oracle.compress(small), True)
 
 
+def test_host_decoder_on_the_edge_records(cm, oracle):
+    """cm.g1_decompress on EVERY record of tests/golden/decode_edge_records.npz (answers from the definitions:
+    tests/golden/gen_decode_edge_records.py), with and without the subgroup test: the oracle's point for OK and
+    INFINITY, CurdleError otherwise.  Where this and a device route disagree on a record, the device is wrong."""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "decode_edge_records.npz"))
+    assert len(z["records"]) >= 439
+    wrong = []
+    for i, (rec, ptb) in enumerate(zip(z["records"], z["points"])):
+        b = ptb.tobytes()
+        pt = (int.from_bytes(b[:48], "big"), int.from_bytes(b[48:], "big"))
+        for check, want in ((True, int(z["status_subgroup"][i])), (False, int(z["status_no_subgroup"][i]))):
+            try:
+                got = oracle.jac_from_mont_limbs([int(v) for v in cm.g1_decompress(rec.tobytes(), check)])
+                ok = (want == 0 and got == pt) or (want == 1 and got is None)
+            except cm.CurdleError as e:
+                ok = want >= 2 and e.code == cm.EINVAL
+            if not ok:
+                wrong.append((i, z["family"][i].decode(), check, want))
+    assert not wrong, wrong
+
+
 def test_inner_product_known_answer_of_the_reference(cm, oracle):
     """The one hard-coded expected value the reference's tests hold on this path:
     common/util_test.go:10-27, IPA([1,2,3,4], [2,3,4,5]) == 40; plus the length-mismatch

@@ -99,6 +99,17 @@ def test_soundness_and_encoding(gpu, oracle, check_mode):
             pass
     with pytest.raises(gpu.CurdleError):
         gpu.verify(crs, proof[:-3], Rs, Ss, Ts, Us, M, gpu.Rand(0))
+    # the proof's first point replaced by a point of order 11, and by T + Q with T of small order and Q in G1
+    # (tests/golden/decode_edge_records.npz): the decoder refuses both, whichever way the checks are evaluated
+    from test_decode_edges_gpu import attack_records
+    attack = attack_records(oracle)
+    for name in ("order 11", "T+Q"):
+        assert gpu.g1_decompress_batch(attack[name], True)[1][0] == gpu.DECODE_NOT_IN_SUBGROUP
+        with pytest.raises(gpu.CurdleError) as e:
+            gpu.verify(crs, attack[name] + proof[48:], Rs, Ss, Ts, Us, M, gpu.Rand(0))
+        assert "decoding" in e.value.msg, name
+        with pytest.raises(gpu.CurdleError):
+            gpu.Proof(attack[name] + proof[48:])
 
 
 def test_prover_is_deterministic_in_its_seed(gpu):

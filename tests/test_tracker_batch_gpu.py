@@ -130,6 +130,15 @@ def pool(gpu, oracle):
     cases["rogue kG"] = ((t, rogue, p), E)
     cases["rogue A"] = ((t, kc, rogue + p[48:]), E)
     cases["rogue B"] = ((t, kc, p[:48] + rogue + p[96:]), E)
+    # ... and the points an attacker would send (tests/golden/decode_edge_records.npz): small order, and small
+    # order hidden behind a G1 point, in the same five positions
+    from test_decode_edges_gpu import attack_records
+    for name, bad in attack_records(oracle).items():
+        cases[name + " rG"] = ((bad + t[48:], kc, p), E)
+        cases[name + " krG"] = ((t[:48] + bad, kc, p), E)
+        cases[name + " kG"] = ((t, bad, p), E)
+        cases[name + " A"] = ((t, kc, bad + p[48:]), E)
+        cases[name + " B"] = ((t, kc, p[:48] + bad + p[96:]), E)
     return hon, cases
 
 
