@@ -36,6 +36,9 @@ __global__ void __launch_bounds__(dacc::kBlock)
   dacc::store_fr(out, slot, acc);
 }
 
+static std::atomic<unsigned long long> g_dacc_builds[4];
+void dacc_count_build(int which) { g_dacc_builds[which & 3].fetch_add(1, std::memory_order_relaxed); }
+
 static hipError_t dacc_lds_optin() {
   static std::atomic<uint32_t> done{0};
   int dev = 0;
@@ -57,9 +60,11 @@ hipError_t launch_dacc_scalars(const void* d_checks, uint32_t n_checks, const vo
   if (need) {
     hipError_t e = dacc_lds_optin();
     if (e != hipSuccess) return e;
+    dacc_count_build(2);
     hipLaunchKernelGGL(k_dacc_scalars<true>, grid, block, need, stream, reinterpret_cast<const curdle_dacc_check*>(d_checks), n_checks,
                        reinterpret_cast<const uint4*>(d_pool), pool_len, n_crs, n_inst, reinterpret_cast<uint4*>(d_out));
   } else {
+    dacc_count_build(3);
     hipLaunchKernelGGL(k_dacc_scalars<false>, grid, block, 0, stream, reinterpret_cast<const curdle_dacc_check*>(d_checks), n_checks,
                        reinterpret_cast<const uint4*>(d_pool), pool_len, n_crs, n_inst, reinterpret_cast<uint4*>(d_out));
   }
@@ -67,3 +72,9 @@ hipError_t launch_dacc_scalars(const void* d_checks, uint32_t n_checks, const vo
 }
 
 }  // namespace curdle
+
+extern "C" int curdle_stat_dacc_builds(unsigned long long out[4]) {
+  if (!out) return CURDLE_EINVAL;
+  for (int i = 0; i < 4; i++) out[i] = curdle::g_dacc_builds[i].load(std::memory_order_relaxed);
+  return CURDLE_OK;
+}

@@ -389,6 +389,11 @@ int dacc_submit_impl(curdle_dacc* acc, const curdle_dacc_check* checks, size_t n
       const curdle_dacc_check& k = checks[c];
       if (k.kind > CURDLE_VEC_FOLD_POW || k.nseg > CURDLE_DACC_MAX_SEGS || k.m > 31)
         return fail(CURDLE_EINVAL, "check %zu: malformed description", c);
+      if (k.kind == CURDLE_VEC_EXPLICIT && k.n_struct) return fail(CURDLE_EINVAL, "check %zu: explicit vectors have no structured part", c);
+      // element indices are 32-bit in the kernel (i = vec_first + offset must not wrap): the vector stays below 2^32
+      // elements; the structured part is held to the 2^31 that 2^m allows the folded kinds, for every kind alike
+      if (k.n_struct > ((uint32_t)1 << 31) || (uint64_t)k.n_struct + k.n_tail > 0xFFFFFFFFull)
+        return fail(CURDLE_EINVAL, "check %zu: vector too long", c);
       if (k.weight_off >= pool_len || k.alpha_off >= pool_len || (size_t)k.tail_off + k.n_tail > pool_len ||
           (k.kind >= CURDLE_VEC_FOLD && (size_t)k.gammas_off + k.m > pool_len) ||
           (k.kind == CURDLE_VEC_FOLD_POW && k.q_off >= pool_len))

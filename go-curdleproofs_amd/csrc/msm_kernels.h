@@ -138,6 +138,7 @@ hipError_t launch_digits(const MsmPlan& p, const MsmWorkspace& ws, const void* d
 hipError_t launch_front(const MsmPlan& p, const MsmWorkspace& ws, const void* d_points, uint32_t npts, const void* d_scalars,
                         hipStream_t stream);
 // loose-base conversion + slot scalars + recoding in ONE launch (small device-accumulator calls; not two-level plans)
+void dacc_count_build(int which);  // dacc_kernels.hip: 0 / 1 the fused front staged / not, 2 / 3 k_dacc_scalars<true> / <false>
 hipError_t launch_dacc_front(const MsmPlan& p, const MsmWorkspace& ws, const DaccFront& f, hipStream_t stream);
 hipError_t launch_hist(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream);
 hipError_t launch_scan(const MsmPlan& p, const MsmWorkspace& ws, hipStream_t stream);

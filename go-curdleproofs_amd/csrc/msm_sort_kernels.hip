@@ -1258,6 +1258,7 @@ hipError_t launch_dacc_front(const MsmPlan& p, const MsmWorkspace& ws, const Dac
   a.nconv = cdiv(f.n_extra, kCvtBlock);
   const size_t need = dacc::lds_bytes(f.pool_len, f.n_checks, kDaccFrontLds - 36 * 1024);  // beside convert_body's 32 KiB stage
   a.staged = need ? 1u : 0u;
+  dacc_count_build(a.staged ? 0 : 1);
   const u32 ndig = cdiv(p.n / 2, kBlock);
   if (p.glv)
     hipLaunchKernelGGL(k_dacc_front<true>, dim3(a.nconv + ndig), dim3(kBlock), need, stream, a, p, ws.digits, ws.counts, p.k * p.NB);

@@ -67,7 +67,7 @@ SYMBOLS = [
     "curdle_g1_compress", "curdle_g1_decompress", "curdle_set_last_error", "curdle_fr_inner_product",
     "curdle_dbases_create", "curdle_dbases_free", "curdle_dbases_size", "curdle_dbases_valid",
     "curdle_msm_g1_dbases", "curdle_msm_g1_dbases_host", "curdle_msm_g1_dbases_windows", "curdle_msm_g1_dbases_submit",
-    "curdle_dacc_begin", "curdle_dacc_run", "curdle_dacc_submit", "curdle_dacc_poll", "curdle_dacc_wait", "curdle_dacc_abort",
+    "curdle_dacc_begin", "curdle_dacc_run", "curdle_dacc_submit", "curdle_dacc_poll", "curdle_dacc_wait", "curdle_dacc_abort", "curdle_stat_dacc_builds",
     "curdle_verify_set_device_acc", "curdle_verify_export_accumulator",
 ]
 
@@ -145,6 +145,13 @@ _dbases_free = _sig("curdle_dbases_free", None, _vp)
 _msm_dbases_windows = _sig("curdle_msm_g1_dbases_windows", C.c_int, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp)
 _msm_dbases_host = _sig("curdle_msm_g1_dbases_host", C.c_int, _vp, _vp, C.c_size_t, _vp)
 _msm_dbases_submit = _sig("curdle_msm_g1_dbases_submit", C.c_int, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int))
+_dacc_begin = _sig("curdle_dacc_begin", C.c_int, _vp, _vp, C.c_size_t, C.POINTER(C.c_void_p))
+_dacc_run = _sig("curdle_dacc_run", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp)
+_dacc_submit = _sig("curdle_dacc_submit", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp)
+_dacc_poll = _sig("curdle_dacc_poll", C.c_int, _vp, C.POINTER(C.c_int))
+_dacc_wait = _sig("curdle_dacc_wait", C.c_int, _vp, _vp)
+_dacc_abort = _sig("curdle_dacc_abort", None, _vp)
+_stat_dacc_builds = _sig("curdle_stat_dacc_builds", C.c_int, C.POINTER(C.c_ulonglong))
 _selftest_op = _sig("curdle_selftest_op", C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_int)
 _selftest_shape = _sig("curdle_selftest_shape", C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 
@@ -376,6 +383,77 @@ class DBases:
         t = C.c_int(-1)
         _check(_msm_dbases_submit(self._h, d_scalars, self.n if n is None else n, window_bits, win_begin, win_end, C.byref(t)))
         return t.value
+
+
+def _dacc_args(bases, inst, checks_u32, pool, xp, xs):
+    inst, pool, xp, xs = _as_u64(inst, 12), _as_u64(pool, 4), _as_u64(xp, 12), _as_u64(xs, 4)
+    checks = np.ascontiguousarray(checks_u32, dtype=np.uint32).reshape(-1, 35)
+    if len(xp) != len(xs):
+        raise ValueError("as many loose scalars as loose points")
+    acc = C.c_void_p()
+    _check(_dacc_begin(bases._h, _ptr(inst) if len(inst) else None, len(inst), C.byref(acc)))
+    n_res = bases.n + len(inst)
+    args = (_ptr(checks) if len(checks) else None, len(checks), _ptr(pool) if len(pool) else None, len(pool),
+            _ptr(xp) if len(xp) else None, _ptr(xs) if len(xs) else None, len(xp))
+    return acc, args, (checks, pool, xp, xs, inst), n_res
+
+
+def dacc_run(bases: "DBases", inst, checks_u32, pool, xp, xs, export: bool = True):
+    """curdle_dacc_begin + curdle_dacc_run over resident `bases` and the instance points `inst`: checks_u32 is
+    (n_checks, 35) uint32 (curdle_dacc_check records), pool / xs Montgomery fr.Elements, xp the loose points.
+    Returns (out_jac, slot scalars (n_res, 4)) -- the scalars are None without export."""
+    acc, args, _keep, n_res = _dacc_args(bases, inst, checks_u32, pool, xp, xs)
+    out = np.zeros(18, dtype=np.uint64)
+    scalars = np.full((n_res, 4), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if export else None
+    _check(_dacc_run(acc, *args, _ptr(out), _ptr(scalars) if export and n_res else None))  # a failed run ends the accumulation
+    return out, scalars
+
+
+class DaccJob:
+    """A submitted accumulation (curdle_dacc_submit): poll() / wait(), or abort()."""
+
+    def __init__(self, acc, keep, scalars):
+        self._acc, self._keep, self.scalars = acc, keep, scalars
+
+    def __del__(self):          # dropped without wait / abort: the workspace slot goes back
+        try:
+            dacc_abort(self)
+        except Exception:       # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+def dacc_submit(bases: "DBases", inst, checks_u32, pool, xp, xs, export: bool = True) -> DaccJob:
+    acc, args, keep, n_res = _dacc_args(bases, inst, checks_u32, pool, xp, xs)
+    scalars = np.full((n_res, 4), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if export else None
+    _check(_dacc_submit(acc, *args, _ptr(scalars) if export and n_res else None))  # a failed submission ends the accumulation
+    return DaccJob(acc, keep, scalars)
+
+
+def dacc_poll(job: DaccJob) -> bool:
+    done = C.c_int(0)
+    _check(_dacc_poll(job._acc, C.byref(done)))
+    return bool(done.value)
+
+
+def dacc_wait(job: DaccJob):
+    """(out_jac, slot scalars or None); ends the accumulation."""
+    out = np.zeros(18, dtype=np.uint64)
+    acc, job._acc = job._acc, None
+    _check(_dacc_wait(acc, _ptr(out)))
+    return out, job.scalars
+
+
+def stat_dacc_builds() -> dict:
+    """Launches of each build of the slot-scalar evaluation so far (curdle_stat_dacc_builds)."""
+    out = (C.c_ulonglong * 4)()
+    _check(_stat_dacc_builds(out))
+    return dict(zip(("front_lds", "front_global", "split_lds", "split_global"), (int(v) for v in out)))
+
+
+def dacc_abort(job: DaccJob) -> None:
+    if job._acc:
+        acc, job._acc = job._acc, None
+        _dacc_abort(acc)
 
 
 def msm_wait(ticket: int) -> np.ndarray:

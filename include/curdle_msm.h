@@ -438,7 +438,7 @@ int curdle_msm_g1_dbases_windows(const curdle_dbases* bases, const void* d_scala
 int curdle_msm_g1_dbases_submit(const curdle_dbases* bases, const void* d_scalars, size_t n, int window_bits,
                                 int win_begin, int win_end, int* ticket);
 
-#define CURDLE_VEC_EXPLICIT 0 /* x_i = tail[i]                                                        */
+#define CURDLE_VEC_EXPLICIT 0 /* x_i = tail[i]: no structured part, n_struct must be 0                */
 #define CURDLE_VEC_CONST 1    /* x_i = scale                                                          */
 #define CURDLE_VEC_FOLD 2     /* x_i = scale * prod_{j : bit j of i set} gammas[m-1-j]                */
 #define CURDLE_VEC_FOLD_POW 3 /* ... * q^(min(i, q_cap) + 1)                                          */
@@ -450,7 +450,17 @@ int curdle_msm_g1_dbases_submit(const curdle_dbases* bases, const void* d_scalar
  * terms).  Offsets index `pool`, an array of Montgomery fr.Elements; the first n_struct
  * elements of x follow the rule of `kind` with weight = alpha * scale folded in by the caller,
  * the n_tail elements after them are explicit and are multiplied by alpha on the device.
- * Segment s says: slots [first, first + len) of resident set `set` take x[vec_first + j]. */
+ * Segment s says: slots [first, first + len) of resident set `set` take x[vec_first + j];
+ * segments may overlap, within a check and between checks: a slot takes the sum.
+ * Refused with CURDLE_EINVAL before anything is launched: an unknown kind, nseg > 6, m > 31
+ * (any kind), n_struct > 0 for EXPLICIT, n_struct > 2^m for the folded kinds, n_struct > 2^31 or
+ * n_struct + n_tail >= 2^32 (element indices and exponents are 32-bit), weight_off or alpha_off
+ * outside the pool (any kind, also where the rule does not read them), [tail_off, tail_off +
+ * n_tail) outside it, [gammas_off, gammas_off + m) outside it for the folded kinds, q_off
+ * outside it for FOLD_POW, a segment past its set or past n_struct + n_tail.  Fields a kind
+ * does not use are ignored, not checked, and have no effect on the result: m (up to 31) and
+ * gammas_off of EXPLICIT / CONST, q_off and q_cap of every kind but FOLD_POW.  m may exceed
+ * log2(n_struct): the leading gammas are then inside the pool and never used. */
 typedef struct {
   uint32_t kind, n_struct, m, q_cap;
   uint32_t weight_off, alpha_off, gammas_off, q_off, tail_off, n_tail;
@@ -484,6 +494,11 @@ int curdle_dacc_submit(curdle_dacc* acc, const curdle_dacc_check* checks, size_t
 int curdle_dacc_poll(curdle_dacc* acc, int* done);
 int curdle_dacc_wait(curdle_dacc* acc, uint64_t out_jac[CURDLE_G1_JAC_U64]);
 void curdle_dacc_abort(curdle_dacc* acc); /* ends an accumulation without its result (submitted or not) */
+/* Diagnostics: launches of each build of the slot-scalar evaluation since the library was loaded --
+ * out[0] the fused front with pool and checks staged in LDS, out[1] the fused front reading global
+ * memory, out[2] / out[3] the separate kernel staged / not (accumulations beyond 16,384 bases).
+ * The builds compute the same scalars; which one ran is visible here only. */
+int curdle_stat_dacc_builds(unsigned long long out[4]);
 
 /* curdleproof.Verify keeps its accumulator on the device by default (the section above);
  * 0 moves it back to the host mirror of msmaccumulator (same accept bit).  Returns the

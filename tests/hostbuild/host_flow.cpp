@@ -12,6 +12,8 @@
 //                                 truncations, random slice prefixes, random blobs
 //   host_flow time <ell> <reps>   host share of Verify (everything but the final MSM), for gprof
 //   host_flow emit <ell> <file>   the serialised proof + instance as a fixture file
+//   host_flow dacc <casefile>     curdle_dacc_begin / _run with export_scalars over packed descriptions
+//                                 (tests/test_dacc_model.py writes them): the slot scalars and the sum in hex
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -591,9 +593,63 @@ static int Emit(size_t ell, const char* path) {
   return 0;
 }
 
+// The device accumulator's C entry points over packed cases.  File: u64 count, then per case u64 n_crs, n_inst,
+// n_checks, pool_len, n_extra, two_step | checks | pool | crs points | instance points | loose points | loose scalars.
+// Prints, per case, "case <k> rc <rc>", then for rc = 0 one "s <hex>" per resident slot (the exported Montgomery element
+// as one 256-bit number) and "sum <18 words>"; two_step = 1 takes submit / poll / wait instead of run.
+static int Dacc(const char* path) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return 1;
+  auto rd = [&](void* dst, size_t bytes) { CHECK(bytes == 0 || fread(dst, 1, bytes, f) == bytes); };
+  uint64_t count = 0;
+  rd(&count, 8);
+  for (uint64_t k = 0; k < count; k++) {
+    uint64_t h[6];
+    rd(h, sizeof(h));
+    const size_t n_crs = h[0], n_inst = h[1], n_checks = h[2], pool_len = h[3], n_extra = h[4], n_res = n_crs + n_inst;
+    CHECK(n_checks < (1u << 20) && pool_len < (1u << 24) && n_res < (1u << 24) && n_extra < (1u << 20));
+    std::vector<curdle_dacc_check> checks(n_checks + 1);
+    std::vector<uint64_t> pool(4 * pool_len + 4), crs(12 * n_crs + 12), inst(12 * n_inst + 12), xp(12 * n_extra + 12),
+        xs(4 * n_extra + 4), exported(4 * n_res + 4, ~0ull);
+    rd(checks.data(), n_checks * sizeof(curdle_dacc_check));
+    rd(pool.data(), pool_len * 32);
+    rd(crs.data(), n_crs * 96);
+    rd(inst.data(), n_inst * 96);
+    rd(xp.data(), n_extra * 96);
+    rd(xs.data(), n_extra * 32);
+    curdle_dbases* bases = nullptr;
+    CHECK(curdle_dbases_create(crs.data(), n_crs, &bases) == CURDLE_OK);
+    curdle_dacc* acc = nullptr;
+    CHECK(curdle_dacc_begin(bases, inst.data(), n_inst, &acc) == CURDLE_OK);
+    uint64_t sum[18];
+    int rc;
+    if (h[5]) {
+      rc = curdle_dacc_submit(acc, checks.data(), n_checks, pool.data(), pool_len, xp.data(), xs.data(), n_extra, exported.data());
+      int done = 0;
+      if (rc == CURDLE_OK) CHECK(curdle_dacc_poll(acc, &done) == CURDLE_OK && done == 1);
+      if (rc == CURDLE_OK) rc = curdle_dacc_wait(acc, sum);
+    } else {
+      rc = curdle_dacc_run(acc, checks.data(), n_checks, pool.data(), pool_len, xp.data(), xs.data(), n_extra, sum, exported.data());
+    }
+    printf("case %llu rc %d\n", (unsigned long long)k, rc);
+    if (rc == CURDLE_OK) {
+      for (size_t i = 0; i < n_res; i++)
+        printf("s %016llx%016llx%016llx%016llx\n", (unsigned long long)exported[4 * i + 3], (unsigned long long)exported[4 * i + 2],
+               (unsigned long long)exported[4 * i + 1], (unsigned long long)exported[4 * i]);
+      printf("sum");
+      for (int w = 0; w < 18; w++) printf(" %016llx", (unsigned long long)sum[w]);
+      printf("\n");
+    }
+    curdle_dbases_free(bases);
+  }
+  fclose(f);
+  printf("dacc: %llu cases\n", (unsigned long long)count);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) {
-    fprintf(stderr, "usage: host_flow flow|fuzz|time|emit <ell> [arg]\n");
+    fprintf(stderr, "usage: host_flow flow|fuzz|time|emit <ell> [arg] | dacc <casefile>\n");
     return 2;
   }
   const std::string mode = argv[1];
@@ -607,6 +663,7 @@ int main(int argc, char** argv) {
     if (mode == "fuzz") return Fuzz(ell, argc > 3 ? atoi(argv[3]) : 200);
     if (mode == "time") return Time(ell, argc > 3 ? atoi(argv[3]) : 20);
     if (mode == "timedev") return TimeDevicePath(ell, argc > 3 ? atoi(argv[3]) : 20);
+    if (mode == "dacc") return Dacc(argv[2]);
     if (mode == "emit") return Emit(ell, argc > 3 ? argv[3] : "proof.bin");
   } catch (const std::exception& e) {
     fprintf(stderr, "host_flow: unexpected exception: %s\n", e.what());

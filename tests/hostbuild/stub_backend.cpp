@@ -117,6 +117,9 @@ static void msm_naive(const uint64_t* points, const uint64_t* scalars, size_t n,
     Fr m, k;
     memcpy(&m, scalars + 4 * i, 32);
     f_from_mont<FrParams>(k, m);
+    bool zero = true;
+    for (int w = 0; w < 8; w++) zero = zero && k.l[w] == 0;
+    if (zero) continue;  // an accumulator slot no check covers
     G1XYZZ px, t;
     g1_from_affine(px, p);
     g1_scalar_mul(t, px, k.l, 8);
@@ -294,8 +297,11 @@ extern "C" int curdle_dacc_submit(curdle_dacc* acc, const curdle_dacc_check* che
   };
   std::vector<alg::Scalar> slots(n_res, alg::Scalar::Zero());
   int rc = CURDLE_OK;
+  for (size_t c = 0; c < n_checks && rc == CURDLE_OK; c++)  // the header: x_i = tail[i], nothing else
+    if (checks[c].kind == CURDLE_VEC_EXPLICIT && checks[c].n_struct)
+      rc = curdle_set_last_error(CURDLE_EINVAL, "explicit vectors have no structured part");
   try {
-    for (size_t slot = 0; slot < n_res; slot++) {
+    for (size_t slot = 0; slot < n_res && rc == CURDLE_OK; slot++) {
       const uint32_t set = slot < n_crs ? CURDLE_SET_CRS : CURDLE_SET_INST;
       const uint32_t idx = (uint32_t)(slot < n_crs ? slot : slot - n_crs);
       for (size_t c = 0; c < n_checks; c++) {

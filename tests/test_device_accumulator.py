@@ -5,21 +5,10 @@ elements) for the same proof, instance and verifier randomness, and decide ident
 import numpy as np
 import pytest
 
+from dacc_model import as_map
 from test_protocol_gpu import setup
 
 pytestmark = pytest.mark.gpu
-
-
-def as_map(oracle, pts, sc):
-    """{base bytes: canonical scalar} with repeated bases merged; zero scalars and the point at
-    infinity dropped (the reference's map keeps (0,0) as a key, the device never stores it)."""
-    out = {}
-    for p, s in zip(pts, sc):
-        if not p.any():
-            continue
-        k = p.tobytes()
-        out[k] = (out.get(k, 0) + oracle.fr_from_mont_limbs([int(v) for v in s])) % oracle.R
-    return {k: v for k, v in out.items() if v}
 
 
 @pytest.mark.parametrize("n", [64, 256])
@@ -145,6 +134,30 @@ def test_device_accumulator_abi_rejects_malformed_descriptions(gpu):
     assert run([1, 4, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # segment past the vector
     assert run([2, 8, 2, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # 8 structured elements, 2^2 folds
     assert run([7, 8, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # unknown kind
+    assert run([0, 8, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # EXPLICIT has no structured part (header)
+    assert run([0, 0, 0, 0, 1, 0, 0, 0, 0, 4, 1, 0, 0, 4, 0]) == 0                # ... its tail alone is fine
+    # 0xFFFFFFFF in every field whose sums must not wrap: refused on the host, nothing launched
+    F = 0xFFFFFFFF
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, F, 8, 0]) == gpu.EINVAL       # first
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 1, F, 0]) == gpu.EINVAL       # len (first + len wraps in 32 bits)
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, F]) == gpu.EINVAL       # vec_first
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 1, F]) == gpu.EINVAL       # vec_first + len wraps to 0
+    assert run([1, F, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # n_struct: beyond 2^31 for any kind
+    assert run([3, F, 31, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL      # ... and beyond 2^m
+    assert run([1, 1 << 31, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == 0          # 2^31 itself is the largest vector
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, 0, F, 1, 0, 0, 8, 0]) == gpu.EINVAL       # n_tail
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, 1, F, 1, 0, 0, 8, 0]) == gpu.EINVAL       # tail_off + n_tail wraps to 0
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, F, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # tail_off
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, F, 2, 1, 0, 0, 8, 0]) == gpu.EINVAL       # tail_off + n_tail wraps to 1
+    assert run([1, 8, 0, 0, 1, F, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # alpha_off, read or not
+    assert run([2, 8, 3, 0, 1, 0, F, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # gammas_off + m wraps
+    assert run([3, 8, 3, 0, 1, 0, 0, F, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL       # q_off of a FOLD_POW check
+    assert run([1, 8, 32, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 0]) == gpu.EINVAL      # m > 31, for a kind that ignores m too
+    assert run([1, 8, 0, 0, 1, 0, 0, 0, 0, 0, 7, 0, 0, 8, 0]) == gpu.EINVAL       # nseg > CURDLE_DACC_MAX_SEGS
+    # fields a kind ignores are not checked and change nothing (the header says so): m, gammas_off, q_off, q_cap of CONST
+    assert run(good) == 0
+    plain = out.copy()
+    assert run([1, 8, 31, F, 1, 0, F, F, 0, 0, 1, 0, 0, 8, 0]) == 0 and (out == plain).all()
 
     # the two-step form: submit, poll until done, wait -- the same sum; misuse is refused
     lib.curdle_dacc_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
