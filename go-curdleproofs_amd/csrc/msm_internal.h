@@ -1,5 +1,5 @@
 // Internals shared by the translation units of the C ABI (msm_context.hip, msm_plan.hip, msm_enqueue.hip,
-// msm_host_chunks.hip, msm_entry.hip, dbases_api.hip, decode_api.hip, misc_api.hip -- ONE file, msm_api.hip, of 3,200 lines
+// msm_host_chunks.hip, msm_entry.hip, dbases_api.hip, decode_api.hip, check_api.hip, misc_api.hip -- ONE file, msm_api.hip, of 3,200 lines
 // until round 6): the context and its workspace slots, the error text, tickets, the phase profiler, and the prototypes
 // of what one unit calls in another.  Everything here is in namespace curdle_api; nothing is exported.
 #pragma once
@@ -374,6 +374,23 @@ int run_host(const MsmCall& call, const uint64_t* points, const uint64_t* scalar
 // --- msm_host_chunks.hip -----------------------------------------------------
 constexpr size_t kHostChunkMin = (size_t)1 << 19;  // below this a call is one chunk
 int run_host_chunked(const uint64_t* points, const uint64_t* scalars, size_t n, uint64_t* out, bool glv = true);
+
+// --- decode_api.hip ----------------------------------------------------------
+int ensure_dslot_streams(Ctx& cx);  // the decode contexts' streams, made on their first use
+
+// --- check_api.hip -----------------------------------------------------------
+// The membership check of points in memory (check_kernels.hip) in two steps, for a caller with work of its own in
+// between (curdle_verify_checked verifies): start copies the `nvec` vectors, back to back, to a decode context and
+// leaves the kernel running on its stream; collect waits and hands out one status byte per point.  With every decode
+// context taken, start runs the check to completion through an MSM slot and RELEASES it before it returns: the
+// caller goes on to call MSM entry points, and must hold no MSM slot while it does (the DSlot comment above).
+struct CheckJob {
+  Ctx* cx = nullptr;
+  int dslot = -1;  // the decode context the check runs on; -1: start has finished it already
+  std::vector<uint8_t> status;
+};
+int check_start(CheckJob& job, const uint64_t* const* vecs, const size_t* lens, int nvec, int subgroup_check);
+int check_collect(CheckJob& job);
 
 // --- dbases_api.hip ----------------------------------------------------------
 void dbases_release_handle(struct ::curdle_dbases* b);

@@ -69,6 +69,8 @@ SYMBOLS = [
     "curdle_msm_g1_dbases", "curdle_msm_g1_dbases_host", "curdle_msm_g1_dbases_windows", "curdle_msm_g1_dbases_submit",
     "curdle_dacc_begin", "curdle_dacc_run", "curdle_dacc_submit", "curdle_dacc_poll", "curdle_dacc_wait", "curdle_dacc_abort", "curdle_stat_dacc_builds",
     "curdle_verify_set_device_acc", "curdle_verify_export_accumulator",
+    "curdle_g1_check_batch", "curdle_g1_check_batch_device", "curdle_verify_checked", "curdle_verify_proof_checked",
+    "curdle_stat_check_paths",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -713,6 +715,32 @@ def verify(crs: CRS, proof: bytes, Rs, Ss, Ts, Us, M, rand: Rand) -> bool:
     return bool(ok.value)
 
 
+_verify_checked = _sig("curdle_verify_checked", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
+                       C.POINTER(C.c_int))
+_verify_proof_checked = _sig("curdle_verify_proof_checked", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
+                             C.POINTER(C.c_int))
+_stat_check_paths = _sig("curdle_stat_check_paths", C.c_int, C.POINTER(C.c_ulonglong))
+
+
+def verify_checked(crs: CRS, proof: bytes, Rs, Ss, Ts, Us, M, rand: Rand) -> bool:
+    """verify() with the instance points checked (range, curve, subgroup; g1_check_batch) on the GPU beside the
+    verification and M on the host: CurdleError(EINVAL, "Ss[17]: not in the prime-order subgroup") for a bad one."""
+    Rs, Ss, Ts, Us = (_as_u64(a, 12) for a in (Rs, Ss, Ts, Us))
+    M = _as_u64(M)
+    pb = np.frombuffer(proof, dtype=np.uint8).copy()
+    ok = C.c_int(0)
+    _check(_verify_checked(crs._h, _ptr(pb), len(pb), _ptr(Rs), _ptr(Ss), _ptr(Ts), _ptr(Us), crs.ell, _ptr(M), rand._h,
+                           C.byref(ok)))
+    return bool(ok.value)
+
+
+def stat_check_paths() -> dict:
+    """Checked verifications so far whose point check ran beside the verification / ran to its end first."""
+    out = (C.c_ulonglong * 2)()
+    _check(_stat_check_paths(out))
+    return {"beside": int(out[0]), "first": int(out[1])}
+
+
 class Proof:
     """A decoded curdleproof.Proof (Proof.FromReader, curdleproof.go:320: every point curve- and
     subgroup-checked).  verify_proof() is the reference's Verify(proof Proof, ...) on it."""
@@ -734,6 +762,16 @@ def verify_proof(crs: CRS, proof: Proof, Rs, Ss, Ts, Us, M, rand: Rand) -> bool:
     M = _as_u64(M)
     ok = C.c_int(0)
     _check(_verify_proof(crs._h, proof._h, _ptr(Rs), _ptr(Ss), _ptr(Ts), _ptr(Us), crs.ell, _ptr(M), rand._h, C.byref(ok)))
+    return bool(ok.value)
+
+
+def verify_proof_checked(crs: CRS, proof: Proof, Rs, Ss, Ts, Us, M, rand: Rand) -> bool:
+    """verify_proof() with the instance points checked, as verify_checked()."""
+    Rs, Ss, Ts, Us = (_as_u64(a, 12) for a in (Rs, Ss, Ts, Us))
+    M = _as_u64(M)
+    ok = C.c_int(0)
+    _check(_verify_proof_checked(crs._h, proof._h, _ptr(Rs), _ptr(Ss), _ptr(Ts), _ptr(Us), crs.ell, _ptr(M), rand._h,
+                                 C.byref(ok)))
     return bool(ok.value)
 
 
@@ -998,6 +1036,27 @@ def g1_decompress_batch(data: bytes, subgroup_check: bool = True):
     st = np.zeros(n, dtype=np.uint8)
     _check(_decompress_batch(_ptr(b), n, 1 if subgroup_check else 0, _ptr(out), _ptr(st)))
     return out, st
+
+
+_check_batch = _sig("curdle_g1_check_batch", C.c_int, _vp, C.c_size_t, C.c_int, _vp)
+_check_batch_device = _sig("curdle_g1_check_batch_device", C.c_int, _vp, C.c_size_t, C.c_int, _vp, _vp)
+
+
+def g1_check_batch(points, subgroup_check: bool = True) -> np.ndarray:
+    """(n, 12) gnark affine points in memory -> (n,) DECODE_* status bytes, on the GPU: infinity, a coordinate >= p,
+    off the curve y^2 = x^3 + 4, and with subgroup_check outside the prime-order subgroup."""
+    points = _as_u64(points, 12)
+    n = points.shape[0] if points.size else 0
+    st = np.zeros(n, dtype=np.uint8)
+    _check(_check_batch(_ptr(points), n, 1 if subgroup_check else 0, _ptr(st)))
+    return st
+
+
+def g1_check_batch_device(ptr: int, n: int, subgroup_check: bool = True, stream=None) -> np.ndarray:
+    """The same for n points resident in device memory at `ptr`; the status bytes come back to host memory."""
+    st = np.zeros(n, dtype=np.uint8)
+    _check(_check_batch_device(ptr, n, 1 if subgroup_check else 0, _ptr(st), stream or None))
+    return st
 
 
 _scalar_mul_batch = _sig("curdle_g1_scalar_mul_batch", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp)

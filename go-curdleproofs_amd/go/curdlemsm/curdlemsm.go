@@ -406,3 +406,60 @@ func DecompressBatch(out []bls12381.G1Affine, status []byte, in []byte, subgroup
 			(*C.uint64_t)(unsafe.Pointer(&out[0])), (*C.uint8_t)(unsafe.Pointer(&status[0])))
 	})
 }
+
+// CheckG1Affine checks points that arrive IN MEMORY -- and so went through no Decoder / SetBytes -- on the GPU
+// (curdle_g1_check_batch): one status per point, DecodeInfinity for (0, 0), DecodeBadEncoding for a coordinate
+// that is not below p, DecodeNotOnCurve, DecodeNotInSubgroup, else DecodeOK.  MultiExp and every other fast
+// path of the library need their bases in G1 (curdle_msm.h, "PRECONDITION"); curdleproof.Verify takes Rs, Ss,
+// Ts, Us and M from its caller unchecked (curdleproof.go:199-207).  The points are only read, and no pointer
+// is kept after the call returns.  UNVERIFIED like the rest of this file: never compiled.
+func CheckG1Affine(points []bls12381.G1Affine) ([]uint8, error) {
+	status := make([]uint8, len(points))
+	if len(points) == 0 {
+		return status, nil
+	}
+	err := locked(func() C.int {
+		return C.curdle_g1_check_batch((*C.uint64_t)(unsafe.Pointer(&points[0])), C.size_t(len(points)), 1,
+			(*C.uint8_t)(unsafe.Pointer(&status[0])))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return status, nil
+}
+
+// VerifyChecked is curdleproof.Verify behind the check of its instance: the 4 ell points of Rs, Ss, Ts, Us in
+// one CheckG1Affine call, M with gnark's own IsOnCurve / IsInSubGroup, then `verify` -- the caller's closure over
+// curdleproof.Verify, whose result is returned untouched if every point passes.  A point at infinity passes, as
+// it does in gnark and in the MSM.  The first failure in the order Rs, Ss, Ts, Us, M is reported, as
+// curdle_verify_checked reports it ("Ss[17]: status 4"); verify is not called for such an instance.
+// The Go package keeps its own protocol code and CRS, so this is the check and the call, not a binding of
+// curdle_verify_checked (which verifies with the library's restatement of the protocol).  UNVERIFIED: never compiled.
+func VerifyChecked(Rs, Ss, Ts, Us []bls12381.G1Affine, M *bls12381.G1Jac, verify func() (bool, error)) (bool, error) {
+	names := [4]string{"Rs", "Ss", "Ts", "Us"}
+	vecs := [4][]bls12381.G1Affine{Rs, Ss, Ts, Us}
+	all := make([]bls12381.G1Affine, 0, len(Rs)+len(Ss)+len(Ts)+len(Us))
+	for _, v := range vecs {
+		all = append(all, v...)
+	}
+	status, err := CheckG1Affine(all)
+	if err != nil {
+		return false, err
+	}
+	at := 0
+	for k, v := range vecs {
+		for i := range v {
+			if st := status[at+i]; st != DecodeOK && st != DecodeInfinity {
+				return false, fmt.Errorf("curdlemsm: %s[%d]: status %d", names[k], i, st)
+			}
+		}
+		at += len(v)
+	}
+	if M == nil {
+		return false, errors.New("curdlemsm: VerifyChecked: M is nil")
+	}
+	if !M.Z.IsZero() && (!M.IsOnCurve() || !M.IsInSubGroup()) {
+		return false, errors.New("curdlemsm: M: not a point of the prime-order subgroup")
+	}
+	return verify()
+}

@@ -131,7 +131,9 @@ int curdle_device_available(void);
  * the begin / points decoding steps before the subgroup verdict -- the result is the well-defined
  * but different point k1 P + k2 (beta x, y)
  * (tests/test_msm_gpu.py::test_bases_outside_the_prime_order_subgroup_...).  The same holds for
- * curdle_g1_scalar_mul_batch and the device accumulator.
+ * curdle_g1_scalar_mul_batch and the device accumulator.  Bases that come from outside and went through no
+ * decoder can be checked first: curdle_g1_check_batch / curdle_g1_check_batch_device (range, curve equation,
+ * subgroup), or curdle_verify_checked for the verifier's instance points.
  * ------------------------------------------------------------------------- */
 int curdle_msm_g1(const uint64_t* points, const uint64_t* scalars, size_t n,
                   uint64_t out_jac[CURDLE_G1_JAC_U64]);
@@ -558,6 +560,37 @@ int curdle_g1_decompress_begin(const uint8_t* in, size_t n, uint64_t* out_affine
 int curdle_g1_decompress_start(const uint8_t* in, size_t n, int* ticket);
 int curdle_g1_decompress_points(int ticket, uint64_t* out_affine, uint8_t* status);
 int curdle_g1_decompress_finish(int ticket, uint8_t* status);
+/* Membership check ON THE GPU for G1 points that arrive IN MEMORY (gnark G1Affine, n x 12 limbs) and so went through
+ * no decoder: the instance vectors of curdleproof.Verify (curdleproof.go:199-207 takes []G1Affine from its caller and
+ * checks nothing) and any base array handed to the MSM entry points, whose precondition (see curdle_msm_g1) is that
+ * every base lies in G1.  One CURDLE_DECODE_* status byte per point, decided in this order: all 24 words zero ->
+ * INFINITY (gnark's IsInfinity); X or Y, as a 384-bit integer, >= p -> BAD_ENCODING (not a field element); y^2 != x^3 + 4
+ * -> NOT_ON_CURVE (the group law never uses b: a point of another curve y^2 = x^3 + b' would run through every kernel
+ * unnoticed, and the subgroup test cannot see it either); with subgroup_check != 0, [z^2] phi(P) + P != inf ->
+ * NOT_IN_SUBGROUP; else OK.  Invalid points do not fail the call.  n = 0: CURDLE_OK, no device needed; n > 2^27 or a
+ * null pointer with n > 0: CURDLE_EINVAL.  No host fallback: without a device the call fails with CURDLE_ENODEV.
+ *   curdle_g1_check_batch          points in host memory
+ *   curdle_g1_check_batch_device   points resident in device memory (check a base array once, before a run of
+ *                                  CURDLE_MSM_BASES_UNCHANGED calls or before curdle_dbases_create); `stream` as in
+ *                                  curdle_msm_g1_device; the status bytes are in HOST memory when it returns. */
+int curdle_g1_check_batch(const uint64_t* points, size_t n, int subgroup_check, uint8_t* status);
+int curdle_g1_check_batch_device(const void* d_points, size_t n, int subgroup_check, uint8_t* status, void* stream);
+/* curdle_verify / curdle_verify_proof with that check on the 4 ell instance points (on the GPU, beside the
+ * verification) and on M (on the host).  An instance point at infinity is acceptable, as it is to gnark and the MSM.
+ * Any other failed point: CURDLE_EINVAL, *ok = 0, and curdle_last_error names vector, index and reason --
+ * "Ss[17]: not in the prime-order subgroup" -- for the first failure in the order Rs, Ss, Ts, Us, M; the verifier's
+ * own result is never reported for such an instance.  If every point passes, return code, *ok and error text are
+ * those of the unchecked call.  A batch (curdle_verify_batch) is checked by its caller: one curdle_g1_check_batch
+ * over all k * 4 ell instance points first. */
+int curdle_verify_checked(const curdle_crs* crs, const uint8_t* proof, size_t proof_len, const uint64_t* Rs,
+                          const uint64_t* Ss, const uint64_t* Ts, const uint64_t* Us, size_t ell,
+                          const uint64_t M[CURDLE_G1_JAC_U64], curdle_rand* rand, int* ok);
+int curdle_verify_proof_checked(const curdle_crs* crs, const curdle_proof* proof, const uint64_t* Rs,
+                                const uint64_t* Ss, const uint64_t* Ts, const uint64_t* Us, size_t ell,
+                                const uint64_t M[CURDLE_G1_JAC_U64], curdle_rand* rand, int* ok);
+/* Diagnostics: checked verifications since the library was loaded whose point check out[0] ran on a decode
+ * context beside the verification, out[1] found every decode context taken and ran to its end first. */
+int curdle_stat_check_paths(unsigned long long out[2]);
 int curdle_set_last_error(int code, const char* msg);  /* internal: shared by the library's translation units */
 
 /* ------------------------------------------------------------------------- *
