@@ -1,7 +1,8 @@
 // Evaluation of the device accumulator's scalar slots (include/curdle_msm.h "Accumulator on the device";
 // msmaccumulator/msmaccumulator.go:38-43 with the x vectors of innerproductargument.go:223-234 and
-// samemultiscalarargument.go:267-277 described instead of computed on the host).  Shared by k_dacc_scalars
-// (dacc_kernels.hip) and k_dacc_front (msm_sort_kernels.hip: the same evaluation feeding the digit recoding directly).
+// samemultiscalarargument.go:267-277 described instead of computed on the host).  Shared by k_dacc_scalars and
+// k_dacc_scalars_members (dacc_kernels.hip: one row of slots, or one row per member of a batch group) and k_dacc_front
+// (msm_sort_kernels.hip: the same evaluation feeding the digit recoding directly).
 //
 // Round 5: a block first stages the pool (the checks' Fr constants) and the check descriptions in LDS when they fit; every
 // lane used to read them from global memory inside its loops -- a dozen dependent loads per check and slot, the same
@@ -65,13 +66,14 @@ __device__ __forceinline__ View setup(uint4* lds, const curdle_dacc_check* check
   return v;
 }
 
-// The scalar of resident slot `slot` (CRS slots first, then the instance's): sum over the checks that cover it.
-__device__ __forceinline__ Fr eval_slot(const View& vw, u32 slot, u32 n_crs) {
+// The scalar of resident slot `slot` (CRS slots first, then the instance's): sum over the checks [c0, c1) that cover it.
+// The member build (k_dacc_scalars_members) walks one member's run of checks; every other build walks them all.
+__device__ __forceinline__ Fr eval_slot_range(const View& vw, u32 slot, u32 n_crs, u32 c0, u32 c1) {
   const u32 set = slot < n_crs ? CURDLE_SET_CRS : CURDLE_SET_INST;
   const u32 idx = slot < n_crs ? slot : slot - n_crs;
   Fr acc;
   f_zero(acc);
-  for (u32 c = 0; c < vw.n_checks; c++) {
+  for (u32 c = c0; c < c1; c++) {
     const curdle_dacc_check& ck = vw.checks[c];
     for (u32 s = 0; s < ck.nseg; s++) {
       if (ck.seg[s].set != set || idx < ck.seg[s].first || idx - ck.seg[s].first >= ck.seg[s].len) continue;
@@ -106,6 +108,7 @@ __device__ __forceinline__ Fr eval_slot(const View& vw, u32 slot, u32 n_crs) {
   }
   return acc;
 }
+__device__ __forceinline__ Fr eval_slot(const View& vw, u32 slot, u32 n_crs) { return eval_slot_range(vw, slot, n_crs, 0, vw.n_checks); }
 
 }  // namespace dacc
 }  // namespace curdle

@@ -371,6 +371,32 @@ extern "C" int curdle_dacc_submit(curdle_dacc* acc, const curdle_dacc_check* che
   return dacc_submit_impl(acc, checks, n_checks, pool, pool_len, extra_points, extra_scalars, n_extra, export_scalars, true);
 }
 namespace curdle_api {
+// The descriptions come from the caller: every offset is checked before a kernel reads through it.
+static int dacc_validate_checks(const curdle_dacc_check* checks, size_t n_checks, size_t pool_len, size_t n_crs, size_t n_inst) {
+  for (size_t c = 0; c < n_checks; c++) {
+    const curdle_dacc_check& k = checks[c];
+    if (k.kind > CURDLE_VEC_FOLD_POW || k.nseg > CURDLE_DACC_MAX_SEGS || k.m > 31)
+      return fail(CURDLE_EINVAL, "check %zu: malformed description", c);
+    if (k.kind == CURDLE_VEC_EXPLICIT && k.n_struct) return fail(CURDLE_EINVAL, "check %zu: explicit vectors have no structured part", c);
+    // element indices are 32-bit in the kernel (i = vec_first + offset must not wrap): the vector stays below 2^32
+    // elements; the structured part is held to the 2^31 that 2^m allows the folded kinds, for every kind alike
+    if (k.n_struct > ((uint32_t)1 << 31) || (uint64_t)k.n_struct + k.n_tail > 0xFFFFFFFFull)
+      return fail(CURDLE_EINVAL, "check %zu: vector too long", c);
+    if (k.weight_off >= pool_len || k.alpha_off >= pool_len || (size_t)k.tail_off + k.n_tail > pool_len ||
+        (k.kind >= CURDLE_VEC_FOLD && (size_t)k.gammas_off + k.m > pool_len) ||
+        (k.kind == CURDLE_VEC_FOLD_POW && k.q_off >= pool_len))
+      return fail(CURDLE_EINVAL, "check %zu: offset outside the pool", c);
+    if (k.kind >= CURDLE_VEC_FOLD && k.n_struct > ((uint64_t)1 << k.m))
+      return fail(CURDLE_EINVAL, "check %zu: more structured elements than 2^m", c);
+    for (uint32_t s = 0; s < k.nseg; s++) {
+      const size_t set_n = k.seg[s].set == CURDLE_SET_CRS ? n_crs : n_inst;
+      if (k.seg[s].set > CURDLE_SET_INST || (size_t)k.seg[s].first + k.seg[s].len > set_n ||
+          (size_t)k.seg[s].vec_first + k.seg[s].len > (size_t)k.n_struct + k.n_tail)
+        return fail(CURDLE_EINVAL, "check %zu: segment %u out of range", c, s);
+    }
+  }
+  return CURDLE_OK;
+}
 int dacc_submit_impl(curdle_dacc* acc, const curdle_dacc_check* checks, size_t n_checks, const uint64_t* pool, size_t pool_len,
                      const uint64_t* extra_points, const uint64_t* extra_scalars, size_t n_extra, uint64_t* export_scalars,
                      bool queued) {
@@ -384,29 +410,7 @@ int dacc_submit_impl(curdle_dacc* acc, const curdle_dacc_check* checks, size_t n
     if ((n_checks && !checks) || (pool_len && !pool) || (n_extra && (!extra_points || !extra_scalars)))
       return fail(CURDLE_EINVAL, "null argument");
     if (n_extra > CURDLE_DACC_MAX_EXTRA) return fail(CURDLE_EINVAL, "%zu loose bases exceed CURDLE_DACC_MAX_EXTRA", n_extra);
-    // the descriptions come from the caller: every offset is checked before a kernel reads through it
-    for (size_t c = 0; c < n_checks; c++) {
-      const curdle_dacc_check& k = checks[c];
-      if (k.kind > CURDLE_VEC_FOLD_POW || k.nseg > CURDLE_DACC_MAX_SEGS || k.m > 31)
-        return fail(CURDLE_EINVAL, "check %zu: malformed description", c);
-      if (k.kind == CURDLE_VEC_EXPLICIT && k.n_struct) return fail(CURDLE_EINVAL, "check %zu: explicit vectors have no structured part", c);
-      // element indices are 32-bit in the kernel (i = vec_first + offset must not wrap): the vector stays below 2^32
-      // elements; the structured part is held to the 2^31 that 2^m allows the folded kinds, for every kind alike
-      if (k.n_struct > ((uint32_t)1 << 31) || (uint64_t)k.n_struct + k.n_tail > 0xFFFFFFFFull)
-        return fail(CURDLE_EINVAL, "check %zu: vector too long", c);
-      if (k.weight_off >= pool_len || k.alpha_off >= pool_len || (size_t)k.tail_off + k.n_tail > pool_len ||
-          (k.kind >= CURDLE_VEC_FOLD && (size_t)k.gammas_off + k.m > pool_len) ||
-          (k.kind == CURDLE_VEC_FOLD_POW && k.q_off >= pool_len))
-        return fail(CURDLE_EINVAL, "check %zu: offset outside the pool", c);
-      if (k.kind >= CURDLE_VEC_FOLD && k.n_struct > ((uint64_t)1 << k.m))
-        return fail(CURDLE_EINVAL, "check %zu: more structured elements than 2^m", c);
-      for (uint32_t s = 0; s < k.nseg; s++) {
-        const size_t set_n = k.seg[s].set == CURDLE_SET_CRS ? n_crs : n_inst;
-        if (k.seg[s].set > CURDLE_SET_INST || (size_t)k.seg[s].first + k.seg[s].len > set_n ||
-            (size_t)k.seg[s].vec_first + k.seg[s].len > (size_t)k.n_struct + k.n_tail)
-          return fail(CURDLE_EINVAL, "check %zu: segment %u out of range", c, s);
-      }
-    }
+    if (int r = dacc_validate_checks(checks, n_checks, pool_len, n_crs, n_inst)) return r;
     HIP_TRY(hipSetDevice(cx.device));
     acc->export_scalars = export_scalars;
     acc->n_total = n;
@@ -532,4 +536,145 @@ extern "C" int curdle_dacc_run(curdle_dacc* acc, const curdle_dacc_check* checks
   int rc = dacc_submit_impl(acc, checks, n_checks, pool, pool_len, extra_points, extra_scalars, n_extra, export_scalars, false);
   if (rc) return rc;  // the submission already ended the accumulation
   return curdle_dacc_wait(acc, out_jac);
+}
+
+// ---------------------------------------------------------------------------
+// The member form: one sum per member of a batch group from ONE pass (include/curdle_msm.h).  A row of slot scalars per
+// member (k_dacc_scalars_members) and one batched MSM whose n_members scalar vectors share the accumulation's converted
+// bases -- CRS | instance | loose, nothing copied or converted per member (MsmCall::shared_bases).  Rows are dense and mostly
+// zero (a member's checks name the CRS and its own instance slots); a zero scalar recodes to zero digits, which the sort
+// drops, so the bucket lists hold what a sparse form would.
+// ---------------------------------------------------------------------------
+extern "C" int curdle_dacc_run_members(curdle_dacc* acc, const curdle_dacc_check* checks, const uint32_t* check_member,
+                                       size_t n_checks, size_t n_members, const uint64_t* pool, size_t pool_len,
+                                       const uint64_t* extra_points, const uint64_t* extra_scalars,
+                                       const uint32_t* extra_member, size_t n_extra, uint64_t* out_jac, uint64_t* export_scalars) {
+  if (!acc) return fail(CURDLE_EINVAL, "null accumulator");
+  if (acc->submitted) return fail(CURDLE_EINVAL, "accumulation already submitted");
+  Ctx& cx = *acc->ctx;
+  Slot& S = cx.slots[acc->slot];
+  const size_t n_crs = acc->n_crs, n_inst = acc->n_inst, n_res = n_crs + n_inst, n_tot = n_res + n_extra;
+  // everything that is refused is refused here, before anything is launched
+  auto refuse = [&]() -> int {
+    if ((n_members && !out_jac) || (n_checks && (!checks || !check_member)) || (pool_len && !pool) ||
+        (n_extra && (!extra_points || !extra_scalars || !extra_member)))
+      return fail(CURDLE_EINVAL, "null argument");
+    if (n_extra > CURDLE_DACC_MAX_EXTRA) return fail(CURDLE_EINVAL, "%zu loose bases exceed CURDLE_DACC_MAX_EXTRA", n_extra);
+    if (n_members == 0 && (n_checks || n_extra)) return fail(CURDLE_EINVAL, "checks or loose pairs without a member");
+    for (size_t c = 0; c < n_checks; c++)
+      if (check_member[c] >= n_members) return fail(CURDLE_EINVAL, "check %zu: member %u of %zu", c, check_member[c], n_members);
+    for (size_t e = 0; e < n_extra; e++)
+      if (extra_member[e] >= n_members) return fail(CURDLE_EINVAL, "loose pair %zu: member %u of %zu", e, extra_member[e], n_members);
+    if (int r = dacc_validate_checks(checks, n_checks, pool_len, n_crs, n_inst)) return r;
+    if (n_members > CURDLE_DACC_MAX_MEMBERS) return fail(CURDLE_EINVAL, "%zu members exceed CURDLE_DACC_MAX_MEMBERS", n_members);
+    if (n_members * n_res > CURDLE_DACC_MAX_MEMBER_SLOTS)
+      return fail(CURDLE_EINVAL, "%zu members x %zu resident slots exceed CURDLE_DACC_MAX_MEMBER_SLOTS", n_members, n_res);
+    return CURDLE_OK;
+  };
+  int rc = refuse();
+  if (rc) {
+    curdle_dacc_abort(acc);
+    return rc;
+  }
+  if (n_members == 0) {
+    curdle_dacc_abort(acc);
+    return CURDLE_OK;
+  }
+  if (n_members == 1) {  // one member is the whole accumulation: curdle_dacc_run's own plan and result
+    rc = curdle_dacc_run(acc, checks, n_checks, pool, pool_len, extra_points, extra_scalars, n_extra, out_jac, export_scalars);
+    if (rc == CURDLE_OK) {
+      dacc_count_members(0, 1);
+      dacc_count_members(1, 1);
+    }
+    return rc;
+  }
+  const size_t k = n_members;
+  std::vector<uint32_t> off(k + 1);
+  for (size_t j = 0; j <= k; j++) off[j] = (uint32_t)(j * n_tot);
+  MsmCall call{off.data()};
+  call.k = k;
+  call.shared_bases = true;
+  {  // the scans of the bucket slots take one pass's worth; a batch of members is not cut into passes (they share the bases)
+    MsmPlan probe;
+    rc = make_plan(probe, call);
+    if (!rc && (size_t)probe.NB * k > kMaxSlotsPerPass)
+      rc = fail(CURDLE_EINVAL, "%zu members x %u bucket slots exceed one pass of the batch path", k, probe.NB);
+    if (rc) {
+      curdle_dacc_abort(acc);
+      return rc;
+    }
+  }
+  bool exported = false;
+  size_t o_export = 0;
+  auto body = [&]() -> int {
+    HIP_TRY(hipSetDevice(cx.device));
+    if (n_tot == 0) {
+      for (size_t j = 0; j < k; j++) set_out_infinity(out_jac + 18 * j);
+      return CURDLE_OK;
+    }
+    // one pinned block: checks, grouped by member | pool | loose points | loose scalars | first check of each member | member of each loose pair
+    const size_t o_pool = (n_checks * sizeof(curdle_dacc_check) + 31) & ~(size_t)31;
+    const size_t o_xp = o_pool + pool_len * 32;
+    const size_t o_xs = o_xp + n_extra * 96;
+    const size_t o_first = o_xs + n_extra * 32;
+    const size_t o_xm = o_first + ((k + 1) * 4 + 31) / 32 * 32;
+    const size_t bytes = (o_xm + n_extra * 4 + 31) & ~(size_t)31;
+    exported = export_scalars && n_res;
+    o_export = bytes;
+    int r;
+    if ((r = ensure_pinned(S, 1, bytes + (exported ? k * n_res * 32 : 0)))) return r;
+    if ((r = ensure(S.job, bytes))) return r;
+    if ((r = ensure(S.scalars, k * n_tot * 32))) return r;
+    char* h = (char*)S.h_stage[1];
+    uint32_t* first = (uint32_t*)(h + o_first);
+    memset(first, 0, (k + 1) * 4);
+    for (size_t c = 0; c < n_checks; c++) first[check_member[c] + 1]++;
+    for (size_t j = 0; j < k; j++) first[j + 1] += first[j];
+    {
+      std::vector<uint32_t> at(first, first + k);
+      curdle_dacc_check* hc = (curdle_dacc_check*)h;
+      for (size_t c = 0; c < n_checks; c++) hc[at[check_member[c]]++] = checks[c];
+    }
+    if (pool_len) memcpy(h + o_pool, pool, pool_len * 32);
+    if (n_extra) {
+      memcpy(h + o_xp, extra_points, n_extra * 96);
+      memcpy(h + o_xs, extra_scalars, n_extra * 32);
+      memcpy(h + o_xm, extra_member, n_extra * 4);
+    }
+    hipStream_t st = S.stream;
+    HIP_TRY(hipMemcpyAsync(S.job.p, h, bytes, hipMemcpyHostToDevice, st));
+    char* dj = (char*)S.job.p;
+    if (n_extra) HIP_TRY(launch_convert_points_raw(dj + o_xp, (uint32_t)n_extra, (char*)S.points28.p + 2 * n_res * kA28Bytes, st));
+    DaccMembers dm;
+    dm.d_checks = dj;
+    dm.d_member_first = dj + o_first;
+    dm.d_pool = dj + o_pool;
+    dm.d_extra_scalars = dj + o_xs;
+    dm.d_extra_member = dj + o_xm;
+    dm.n_checks = (uint32_t)n_checks;
+    dm.pool_len = (uint32_t)pool_len;
+    dm.n_crs = (uint32_t)n_crs;
+    dm.n_inst = (uint32_t)n_inst;
+    dm.n_extra = (uint32_t)n_extra;
+    dm.n_members = (uint32_t)k;
+    HIP_TRY(launch_dacc_scalars_members(dm, S.scalars.p, st));
+    if (exported)  // (tests) the resident part of every row
+      HIP_TRY(hipMemcpy2DAsync(h + o_export, n_res * 32, S.scalars.p, n_tot * 32, n_res * 32, k, hipMemcpyDeviceToHost, st));
+    MsmInputs in;
+    in.scalars = S.scalars.p;
+    in.points28_ready = true;
+    if ((r = enqueue_slot(cx, S, call, in, {st, st, st}))) return r;
+    if ((r = finish_slot(cx, S, out_jac))) return r;
+    if (exported) memcpy(export_scalars, h + o_export, k * n_res * 32);
+    return CURDLE_OK;
+  };
+  rc = body();
+  if (rc) {
+    drain_slot(cx, S);
+  } else {
+    dacc_count_members(0, 1);
+    dacc_count_members(1, k);
+  }
+  dacc_end(acc);
+  return rc;
 }

@@ -54,7 +54,8 @@ static int enqueue_slot_impl(Ctx& cx, Slot& S, const MsmCall& call, const MsmInp
       S.coarse_nw = nw;
     }
   }
-  if (!in.points28 && (rc = ensure(S.points28, sets * n * kA28Bytes))) return rc;
+  // (members that share their bases gather from ONE MSM's worth of records, which the device accumulator has filled)
+  if (!in.points28 && (rc = ensure(S.points28, sets * (p.shared_bases ? n / k : n) * kA28Bytes))) return rc;
   if ((rc = ensure(S.frags, sets * (size_t)p.frag_stride * kX28Bytes))) return rc;
   // what leaves the GPU per window: one sum, or the reduce_bits form's nout bit-positioned points
   const size_t wpts = p.reduce_bits ? p.nout : 1;
@@ -276,6 +277,7 @@ int enqueue_slot(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, con
   int rc = make_plan(S.plan, call);
   if (rc) return rc;
   const MsmPlan& p = S.plan;
+  if (p.shared_bases && !in.points28_ready) return fail(CURDLE_EINVAL, "internal: shared bases are the device accumulator's converted points");
   if (in.dfront && (p.two_level || p.k != 1 || p.sets != 1))
     return fail(CURDLE_EINVAL, "internal: the fused accumulator front takes one small MSM");
   S.run_stream = st.tail;

@@ -299,6 +299,9 @@ struct MsmCall {
   bool joined = false;      // a host-buffer call enqueued in two steps or in chunks (a ChunkJoin goes with every enqueue)
   bool chunked = false;     // ... one of SEVERAL chunks of one MSM, which share the plan's rules in both of their steps
   uint32_t seg = 0;         // buckets per reduce segment, the same for every chunk (0: the plan's rule)
+  // The k MSMs have the same pair count and share ONE converted base array of that many points (the device accumulator's
+  // member form, curdle_dacc_run_members): a sorted entry names the base inside its own MSM.
+  bool shared_bases = false;
 };
 int make_plan(MsmPlan& p, const MsmCall& call);
 int checked_window_bits(size_t n, int window_bits, int* c);

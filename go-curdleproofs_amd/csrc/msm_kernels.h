@@ -45,6 +45,9 @@ struct MsmPlan {
   uint32_t fuse_scan;    // the bucket-slot scans: 0 six launches (multi-block; L = 1 only), 2 k_scan_one (one block, up to 32,768 slots), 3 k_scan_chain (one launch, any size)
   uint32_t glv;          // 1: scalars split with the endomorphism (bases must be in G1); 0: 255-bit scalars whole, any curve point
   uint32_t two_level;    // 1: the scatter runs in two passes (coarse bins, then buckets): single large MSMs
+  // 1: the k MSMs of the call have n / k terms each and share ONE base array of that many records (the device accumulator's
+  // member form): the scatter writes a term's index inside its own MSM, which is the record every member gathers
+  uint32_t shared_bases;
   // The bucket reduction without a scalar multiple (single MSMs; k_reduce_segments / k_reduce_groups):
   // a window's sum_b (b + 1) B_b leaves the GPU as `nout` points with bit positions, which the host's
   // Horner pass over the windows takes in like window sums.  Then G <= 16 (one wave's quads).
@@ -125,6 +128,18 @@ struct DaccFront {
   const void* d_extra_scalars;
   void* d_scalars_out;  // [n_crs + n_inst + n_extra] fr.Elements, or null
   uint32_t n_checks, pool_len, n_crs, n_inst, n_extra;
+};
+
+// The member form of the device accumulator's job (launch_dacc_scalars_members): device pointers into the uploaded job
+// (checks grouped by member | pool | loose points | loose scalars | first check of each member, n_members + 1 words |
+// member of each loose pair) and the counts.
+struct DaccMembers {
+  const void* d_checks;
+  const void* d_member_first;
+  const void* d_pool;
+  const void* d_extra_scalars;
+  const void* d_extra_member;
+  uint32_t n_checks, pool_len, n_crs, n_inst, n_extra, n_members;
 };
 
 // Every launcher enqueues on `stream` and returns the launch status.
@@ -212,6 +227,10 @@ hipError_t launch_g1_subgroup_from_bytes(const uint8_t* in, uint32_t n, uint8_t*
 // dacc_kernels.hip: the slot scalars of the device accumulator (checks: curdle_dacc_check[], pool: fr.Elements).
 hipError_t launch_dacc_scalars(const void* d_checks, uint32_t n_checks, const void* d_pool, uint32_t pool_len, uint32_t n_crs,
                                uint32_t n_inst, void* d_out, hipStream_t stream);
+
+// ... one row of n_crs + n_inst + n_extra scalars per member (d_out: n_members rows back to back), loose pairs included.
+hipError_t launch_dacc_scalars_members(const DaccMembers& m, void* d_out, hipStream_t stream);
+void dacc_count_members(int which, unsigned long long by);  // curdle_stat_dacc_members' three counters
 
 hipError_t launch_scalar_mul_batch(const void* points, const void* scalars, int shared_scalar, const void* addends,
                                    uint32_t n, void* out_xyzz, hipStream_t stream);

@@ -75,6 +75,12 @@ int make_plan(MsmPlan& p, const MsmCall& call) {
   p.n_max = (uint32_t)n_max;
   p.c = c;
   p.glv = glv ? 1u : 0u;
+  if (call.shared_bases) {  // equal-sized MSMs over one base array, sorted by the one-pass scatter (which rebases the entries)
+    for (size_t j = 0; j < k; j++)
+      if (call.off[j + 1] - call.off[j] != call.off[1] - call.off[0]) return fail(CURDLE_EINVAL, "internal: shared bases take MSMs of one size");
+    if (sets != 1 || call.joined) return fail(CURDLE_EINVAL, "internal: shared bases take one base set and one enqueue");
+    p.shared_bases = 1u;
+  }
   // (without the split the terms keep their numbering -- 2 i is k P_i, 2 i + 1 never contributes -- so every
   // kernel behind k_digits is the same code; the opt-out pays for it with a digit array twice the needed size)
   p.W = window_widths(c, p.bits, glv ? kScalarBits : kScalarBitsNoGlv);

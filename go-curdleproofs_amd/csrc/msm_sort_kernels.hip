@@ -300,6 +300,8 @@ __global__ void __launch_bounds__(kSortThreads) k_scatter(const u32* __restrict_
   const u32 nb = p.nbkt[p.win_begin + lw];
   for (u32 b = threadIdx.x; b < nb; b += kSortThreads) lds_cnt[b] = 0;
   __syncthreads();
+  // members that share one base array (MsmPlan::shared_bases): an entry names the term inside its own MSM
+  const u32 rebase = p.shared_bases && p.k != 1 ? offsets[j] : 0u;
   const u32* dw = digits + (size_t)lw * p.n;
   for (u32 i = i0 + threadIdx.x; i < i1; i += kSortThreads) {
     u32 mag = dw[i] & 0x7fffffffu;
@@ -317,7 +319,7 @@ __global__ void __launch_bounds__(kSortThreads) k_scatter(const u32* __restrict_
     u32 mag = d & 0x7fffffffu;
     if (mag) {
       u32 pos = atomicAdd(&lds_cnt[mag - 1], 1u);
-      sorted[pos] = i | (d & 0x80000000u);
+      sorted[pos] = (i - rebase) | (d & 0x80000000u);
     }
   }
 }

@@ -68,6 +68,7 @@ SYMBOLS = [
     "curdle_dbases_create", "curdle_dbases_free", "curdle_dbases_size", "curdle_dbases_valid",
     "curdle_msm_g1_dbases", "curdle_msm_g1_dbases_host", "curdle_msm_g1_dbases_windows", "curdle_msm_g1_dbases_submit",
     "curdle_dacc_begin", "curdle_dacc_run", "curdle_dacc_submit", "curdle_dacc_poll", "curdle_dacc_wait", "curdle_dacc_abort", "curdle_stat_dacc_builds",
+    "curdle_dacc_run_members", "curdle_stat_dacc_members",
     "curdle_verify_set_device_acc", "curdle_verify_export_accumulator",
     "curdle_g1_check_batch", "curdle_g1_check_batch_device", "curdle_verify_checked", "curdle_verify_proof_checked",
     "curdle_stat_check_paths",
@@ -154,6 +155,10 @@ _dacc_poll = _sig("curdle_dacc_poll", C.c_int, _vp, C.POINTER(C.c_int))
 _dacc_wait = _sig("curdle_dacc_wait", C.c_int, _vp, _vp)
 _dacc_abort = _sig("curdle_dacc_abort", None, _vp)
 _stat_dacc_builds = _sig("curdle_stat_dacc_builds", C.c_int, C.POINTER(C.c_ulonglong))
+_dacc_run_members = _sig("curdle_dacc_run_members", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp,
+                         C.c_size_t, _vp, _vp)
+_msm_free_slots = _sig("curdle_msm_free_slots", C.c_int)
+_stat_dacc_members = _sig("curdle_stat_dacc_members", C.c_int, C.POINTER(C.c_ulonglong))
 _selftest_op = _sig("curdle_selftest_op", C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_int)
 _selftest_shape = _sig("curdle_selftest_shape", C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 
@@ -409,6 +414,48 @@ def dacc_run(bases: "DBases", inst, checks_u32, pool, xp, xs, export: bool = Tru
     scalars = np.full((n_res, 4), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if export else None
     _check(_dacc_run(acc, *args, _ptr(out), _ptr(scalars) if export and n_res else None))  # a failed run ends the accumulation
     return out, scalars
+
+
+def dacc_run_members(bases: "DBases", inst, checks_u32, check_member, n_members: int, pool, xp, xs, extra_member,
+                     export: bool = True, check_members: bool = True):
+    """curdle_dacc_begin + curdle_dacc_run_members: the arguments of dacc_run plus the member (below n_members) of every
+    check and of every loose pair.  Returns (sums (n_members, 18), slot scalars (n_members, n_res, 4) or None).  Array
+    lengths that do not match and member indices outside [0, n_members) raise ValueError before anything is begun
+    (check_members=False leaves the indices to the library, which refuses them with EINVAL)."""
+    n_members = int(n_members)
+    if n_members < 0:
+        raise ValueError("n_members is negative")
+    members = []
+    for name, m, n in (("check_member", check_member, len(np.asarray(checks_u32).reshape(-1, 35))),
+                       ("extra_member", extra_member, len(_as_u64(xp, 12)))):
+        m = np.asarray(m if m is not None else [], dtype=np.int64).reshape(-1)
+        if len(m) != n:
+            raise ValueError(f"{name} has {len(m)} entries for {n}")
+        if len(m) and (m.min() < 0 or m.max() >= (n_members if check_members else 1 << 32)):
+            raise ValueError(f"{name} names a member outside [0, {n_members})")
+        members.append(np.ascontiguousarray(m, dtype=np.uint32))
+    cm_, xm_ = members
+    acc, args, _keep, n_res = _dacc_args(bases, inst, checks_u32, pool, xp, xs)
+    out = np.zeros((n_members, 18), dtype=np.uint64)
+    scalars = np.full((n_members, n_res, 4), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if export else None
+    checks_p, n_checks, pool_p, pool_len, xp_p, xs_p, n_extra = args
+    _check(_dacc_run_members(acc, checks_p, _ptr(cm_) if n_checks else None, n_checks, n_members, pool_p, pool_len, xp_p, xs_p,
+                             _ptr(xm_) if n_extra else None, n_extra, _ptr(out) if n_members else None,
+                             _ptr(scalars) if export and n_res and n_members else None))  # ends the accumulation either way
+    return out, scalars
+
+
+def msm_free_slots() -> int:
+    """Workspace slots of the calling thread's context that no call holds right now (curdle_msm_free_slots)."""
+    return int(_msm_free_slots())
+
+
+def stat_dacc_members() -> dict:
+    """curdle_stat_dacc_members: member-form accumulations run, members summed by them, members of failed batch groups
+    that were still verified one by one."""
+    out = (C.c_ulonglong * 3)()
+    _check(_stat_dacc_members(out))
+    return dict(zip(("runs", "members", "one_by_one"), (int(v) for v in out)))
 
 
 class DaccJob:
@@ -823,7 +870,7 @@ class PreparedVerifyBatch:
 def verify_batch(crs: CRS, proofs, Rs, Ss, Ts, Us, Ms, rand: Rand, nthreads: int = 8):
     """Cross-proof batch verification: k proofs over one CRS, one shared accumulator, one MSM.
     proofs: list of bytes; Rs/Ss/Ts/Us: lists of (ell, 12) arrays; Ms: list of 18-limb points.
-    Returns the list of accept bits (exact: a failing batch is settled proof by proof)."""
+    Returns the list of accept bits (exact: a failing group is settled by one sum per member, curdle_dacc_run_members)."""
     return PreparedVerifyBatch(proofs, Rs, Ss, Ts, Us, Ms).run(crs, rand, nthreads)
 
 

@@ -150,9 +150,8 @@ void CheckRecorder::Resolve(const PointDecoder& dec) {
   }
 }
 
-void CheckRecorder::AppendTo(size_t inst_base, std::vector<curdle_dacc_check>* group_checks, std::vector<Scalar>* group_pool,
-                             std::vector<G1Affine>* group_extra_points, std::vector<Scalar>* group_extra_scalars) const {
-  const uint32_t pb = (uint32_t)group_pool->size();
+void CheckRecorder::AppendTo(RecordedGroup* g) const {
+  const uint32_t pb = (uint32_t)g->pool.size(), inst_base = (uint32_t)g->inst.size(), member = g->n_members++;
   for (curdle_dacc_check ck : checks) {
     ck.weight_off += pb;
     ck.alpha_off += pb;
@@ -160,12 +159,14 @@ void CheckRecorder::AppendTo(size_t inst_base, std::vector<curdle_dacc_check>* g
     ck.q_off += pb;
     ck.tail_off += pb;
     for (uint32_t s = 0; s < ck.nseg; s++)
-      if (ck.seg[s].set == kSetInst) ck.seg[s].first += (uint32_t)inst_base;
-    group_checks->push_back(ck);
+      if (ck.seg[s].set == kSetInst) ck.seg[s].first += inst_base;
+    g->checks.push_back(ck);
   }
-  group_pool->insert(group_pool->end(), pool.begin(), pool.end());
-  group_extra_points->insert(group_extra_points->end(), extra_points.begin(), extra_points.end());
-  group_extra_scalars->insert(group_extra_scalars->end(), extra_scalars.begin(), extra_scalars.end());
+  g->check_member.insert(g->check_member.end(), checks.size(), member);
+  g->pool.insert(g->pool.end(), pool.begin(), pool.end());
+  g->extra_points.insert(g->extra_points.end(), extra_points.begin(), extra_points.end());
+  g->extra_scalars.insert(g->extra_scalars.end(), extra_scalars.begin(), extra_scalars.end());
+  g->extra_member.insert(g->extra_member.end(), extra_points.size(), member);
 }
 
 bool RunRecordedChecks(const CRS& crs, const std::vector<G1Affine>& inst, const std::vector<curdle_dacc_check>& checks,
@@ -184,24 +185,82 @@ bool RunRecordedChecks(const CRS& crs, const std::vector<G1Affine>& inst, const 
   return Point::FromJac(out).IsInfinity();
 }
 
+}  // namespace proto
+// The member form and its counters live in the GPU backend (csrc/dbases_api.hip, csrc/dacc_kernels.hip).  Weak here: a
+// backend without them -- the host layer linked over a plain CPU backend, as the sanitizer builds are -- still links,
+// and SettleMembers takes the members' sums from one plain accumulation per member instead.
+void dacc_count_members(int which, unsigned long long by) __attribute__((weak));
+}  // namespace curdle
+extern "C" int curdle_dacc_run_members(curdle_dacc* acc, const curdle_dacc_check* checks, const uint32_t* check_member, size_t n_checks,
+                                       size_t n_members, const uint64_t* pool, size_t pool_len, const uint64_t* extra_points,
+                                       const uint64_t* extra_scalars, const uint32_t* extra_member, size_t n_extra, uint64_t* out_jac,
+                                       uint64_t* export_scalars) __attribute__((weak));
+namespace curdle {
+namespace proto {
+void CountMembersOneByOne(size_t members) {
+  if (dacc_count_members) dacc_count_members(2, members);
+}
+
 RecordedChecksRun::~RecordedChecksRun() {
   if (acc_) curdle_dacc_abort(acc_);
 }
 
-void RecordedChecksRun::Start(const CRS& crs, const std::vector<G1Affine>& inst, const std::vector<curdle_dacc_check>& checks,
-                              const std::vector<Scalar>& pool, const std::vector<G1Affine>& extra_points,
-                              const std::vector<Scalar>& extra_scalars) {
+void RecordedChecksRun::Start(const CRS& crs, RecordedGroup* g) {
   if (acc_) throw std::logic_error("a recorded-checks run is already in flight");
   if (!crs.device) throw std::runtime_error("CRS without a device holder");
   const curdle_dbases* bases = crs.device->Get(crs);
   curdle_dacc* acc = nullptr;
-  int rc = curdle_dacc_begin(bases, reinterpret_cast<const uint64_t*>(inst.data()), inst.size(), &acc);
+  int rc = curdle_dacc_begin(bases, reinterpret_cast<const uint64_t*>(g->inst.data()), g->inst.size(), &acc);
   if (rc != CURDLE_OK) throw device_error("starting the device accumulator", rc);
-  rc = curdle_dacc_submit(acc, checks.data(), checks.size(), reinterpret_cast<const uint64_t*>(pool.data()), pool.size(),
-                          reinterpret_cast<const uint64_t*>(extra_points.data()),
-                          reinterpret_cast<const uint64_t*>(extra_scalars.data()), extra_points.size(), nullptr);
+  rc = curdle_dacc_submit(acc, g->checks.data(), g->checks.size(), reinterpret_cast<const uint64_t*>(g->pool.data()), g->pool.size(),
+                          reinterpret_cast<const uint64_t*>(g->extra_points.data()),
+                          reinterpret_cast<const uint64_t*>(g->extra_scalars.data()), g->extra_points.size(), nullptr);
   if (rc != CURDLE_OK) throw device_error("verifying msm accumulator: computing msm", rc);  // the submission ended it
   acc_ = acc;
+  crs_ = &crs;
+  kept_.Clear();
+  std::swap(kept_, *g);  // no copy: the caller's vectors come back empty, with last group's capacity
+}
+
+bool RecordedChecksRun::SettleMembers(std::vector<char>* ok) {
+  if (acc_ || !crs_) throw std::logic_error("member sums are taken after a group's verdict");
+  const RecordedGroup& g = kept_;
+  const size_t n_res = curdle_dbases_size(crs_->device->Get(*crs_)) + g.inst.size();
+  if (g.n_members > CURDLE_DACC_MAX_MEMBERS || (size_t)g.n_members * n_res > CURDLE_DACC_MAX_MEMBER_SLOTS) return false;
+  curdle_dacc* acc = nullptr;
+  std::vector<uint64_t> sums((size_t)g.n_members * 18);
+  if (!curdle_dacc_run_members) {  // a backend without the member form: member j's checks and loose pairs alone, member by member
+    for (uint32_t j = 0; j < g.n_members; j++) {
+      std::vector<curdle_dacc_check> checks;
+      std::vector<G1Affine> xp;
+      std::vector<Scalar> xs;
+      for (size_t c = 0; c < g.checks.size(); c++)
+        if (g.check_member[c] == j) checks.push_back(g.checks[c]);
+      for (size_t e = 0; e < g.extra_points.size(); e++)
+        if (g.extra_member[e] == j) xp.push_back(g.extra_points[e]), xs.push_back(g.extra_scalars[e]);
+      int rc = curdle_dacc_begin(crs_->device->Get(*crs_), reinterpret_cast<const uint64_t*>(g.inst.data()), g.inst.size(), &acc);
+      if (rc != CURDLE_OK) throw device_error("starting the device accumulator", rc);
+      rc = curdle_dacc_run(acc, checks.data(), checks.size(), reinterpret_cast<const uint64_t*>(g.pool.data()), g.pool.size(),
+                           reinterpret_cast<const uint64_t*>(xp.data()), reinterpret_cast<const uint64_t*>(xs.data()), xp.size(),
+                           sums.data() + 18 * j, nullptr);
+      if (rc != CURDLE_OK) throw device_error("verifying msm accumulator: computing a member's msm", rc);
+    }
+    ok->assign(g.n_members, 0);
+    for (uint32_t j = 0; j < g.n_members; j++) (*ok)[j] = Point::FromJac(sums.data() + 18 * j).IsInfinity() ? 1 : 0;
+    return true;
+  }
+  int rc = curdle_dacc_begin(crs_->device->Get(*crs_), reinterpret_cast<const uint64_t*>(g.inst.data()), g.inst.size(), &acc);
+  if (rc != CURDLE_OK) throw device_error("starting the device accumulator", rc);
+  rc = curdle_dacc_run_members(acc, g.checks.data(), g.check_member.data(), g.checks.size(), g.n_members,
+                               reinterpret_cast<const uint64_t*>(g.pool.data()), g.pool.size(),
+                               reinterpret_cast<const uint64_t*>(g.extra_points.data()),
+                               reinterpret_cast<const uint64_t*>(g.extra_scalars.data()), g.extra_member.data(), g.extra_points.size(),
+                               sums.data(), nullptr);
+  if (rc == CURDLE_EINVAL) return false;  // the descriptions ran once already: what is refused now is the form's shape
+  if (rc != CURDLE_OK) throw device_error("verifying msm accumulator: computing the members' msm", rc);
+  ok->assign(g.n_members, 0);
+  for (uint32_t j = 0; j < g.n_members; j++) (*ok)[j] = Point::FromJac(sums.data() + 18 * j).IsInfinity() ? 1 : 0;
+  return true;
 }
 
 bool RecordedChecksRun::Done() {

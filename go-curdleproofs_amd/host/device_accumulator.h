@@ -50,10 +50,9 @@ class CheckRecorder : public CheckSink {
  public:
   void Check(const Terms& C, const VecExpr& x, const std::vector<BaseSeg>& segs, const std::vector<LooseBase>& loose,
              common::Rand& rand, const char* what) override;
-  // Appends this recording to a group whose instance set already holds `inst_base` slots and
-  // whose pool holds group_pool->size() elements: offsets are rebased.
-  void AppendTo(size_t inst_base, std::vector<curdle_dacc_check>* group_checks, std::vector<Scalar>* group_pool,
-                std::vector<G1Affine>* group_extra_points, std::vector<Scalar>* group_extra_scalars) const;
+  // Appends this recording to a group as its next member: the group's instance set already holds g->inst.size() slots
+  // and its pool g->pool.size() elements (offsets are rebased); every check and loose pair is tagged with the member.
+  void AppendTo(struct RecordedGroup* g) const;
   std::vector<curdle_dacc_check> checks;
   std::vector<Scalar> pool;
   std::vector<G1Affine> extra_points;
@@ -67,6 +66,21 @@ class CheckRecorder : public CheckSink {
 
  private:
   uint32_t Put(const Scalar& s);
+};
+
+// The recorded checks of a group of proofs: what one device accumulation takes, and -- kept until the group's verdict --
+// what the member form takes to say WHICH member failed (curdle_dacc_run_members).
+struct RecordedGroup {
+  std::vector<G1Affine> inst;  // the members' instance points, back to back (the caller appends them after AppendTo)
+  std::vector<curdle_dacc_check> checks;
+  std::vector<Scalar> pool, extra_scalars;
+  std::vector<G1Affine> extra_points;
+  std::vector<uint32_t> check_member, extra_member;  // the member (in order of AppendTo) of every check and loose pair
+  uint32_t n_members = 0;
+  void Clear() {
+    inst.clear(), checks.clear(), pool.clear(), extra_scalars.clear(), extra_points.clear(), check_member.clear(), extra_member.clear();
+    n_members = 0;
+  }
 };
 
 // One MSM over a resident CRS, `inst` (the members' instance points, back to back) and the
@@ -86,16 +100,26 @@ class RecordedChecksRun {
   ~RecordedChecksRun();
   RecordedChecksRun(const RecordedChecksRun&) = delete;
   RecordedChecksRun& operator=(const RecordedChecksRun&) = delete;
-  void Start(const CRS& crs, const std::vector<G1Affine>& inst, const std::vector<curdle_dacc_check>& checks,
-             const std::vector<Scalar>& pool, const std::vector<G1Affine>& extra_points,
-             const std::vector<Scalar>& extra_scalars);  // every argument is copied before it returns
+  // Queues the group's MSM (the library copies every argument before this returns) and TAKES the group: *g is left
+  // empty, its vectors stay here until the next Start for SettleMembers.
+  void Start(const CRS& crs, RecordedGroup* g);
   bool Active() const { return acc_ != nullptr; }
   bool Done();
   bool Finish();
+  // After a Finish() that said false: one more accumulation over the group's instance points, in member form --
+  // ok[j] = 1 iff member j's own sum is the point at infinity, which is what a single Verify of that proof under its own
+  // Rand compares.  false (ok untouched) if the member form refuses the group's shape: the caller verifies one by one.
+  // Throws alg::MsmError on a device failure.
+  bool SettleMembers(std::vector<char>* ok);
 
  private:
   curdle_dacc* acc_ = nullptr;
+  const CRS* crs_ = nullptr;
+  RecordedGroup kept_;
 };
+
+// Members of failed batch groups that were verified one by one after all (curdle_stat_dacc_members, out[2]).
+void CountMembersOneByOne(size_t members);
 
 class DeviceSink : public CheckSink {
  public:

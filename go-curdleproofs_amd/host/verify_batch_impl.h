@@ -180,15 +180,15 @@ std::vector<int> VerifyBatchCore(const CRS& crs, size_t k, Source& src, common::
     const int wid = worker_ids.fetch_add(1);
     size_t threshold = flush * (size_t)(wid + 1) / (size_t)nthreads;
     if (threshold < 4) threshold = flush < 4 ? flush : 4;
-    std::vector<G1Affine> inst;
-    std::vector<curdle_dacc_check> checks;
-    std::vector<Scalar> pool, extra_scalars;
-    std::vector<G1Affine> extra_points;
+    RecordedGroup group;  // the group being recorded
     std::vector<size_t> members;
     // A group's MSM runs while this worker verifies the proofs of its NEXT group: settle() only
-    // queues it (RecordedChecksRun::Start copies every argument), collect() takes the verdict --
-    // polled after every proof, because the group holds a workspace slot until then -- and only a
-    // group that failed is gone through member by member.
+    // queues it (RecordedChecksRun::Start hands the library's copies over and keeps the recording), collect()
+    // takes the verdict -- polled after every proof, because the group holds a workspace slot until then.  A
+    // group that failed is settled by ONE more accumulation in member form (curdle_dacc_run_members): a sum per
+    // member, each exactly the point a single Verify of that proof compares with infinity -- no proof is decoded
+    // again, no transcript re-run.  Only a group whose shape the member form refuses (a very large BATCH_GROUP)
+    // is gone through member by member, and counted (curdle_stat_dacc_members, out[2]).
     RecordedChecksRun run;
     std::vector<size_t> in_flight;  // the members of the group `run` is computing
     std::chrono::steady_clock::time_point run_t0;
@@ -198,12 +198,21 @@ std::vector<int> VerifyBatchCore(const CRS& crs, size_t k, Source& src, common::
       if (BatchTrace())
         fprintf(stderr, "[batch] group of %zu proofs: verdict %.2f ms after its submission\n", in_flight.size(),
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run_t0).count());
-      for (size_t i : in_flight) {
-        if (all) {
-          oks[i] = 1;
+      std::vector<char> member_ok;
+      const auto members_t0 = std::chrono::steady_clock::now();
+      const bool by_member = !all && run.SettleMembers(&member_ok);  // a device failure throws: never read as a verdict
+      if (!all && BatchTrace())
+        fprintf(stderr, "[batch] failed group of %zu proofs: member sums %s, %.2f ms\n", in_flight.size(), by_member ? "taken" : "refused",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - members_t0).count());
+      if (by_member && member_ok.size() != in_flight.size()) throw std::logic_error("member sums do not match the group");
+      if (!all && !by_member) CountMembersOneByOne(in_flight.size());
+      for (size_t m = 0; m < in_flight.size(); m++) {
+        const size_t i = in_flight[m];
+        if (all || by_member) {
+          oks[i] = all || member_ok[m] ? 1 : 0;
           continue;
         }
-        try {  // some check of the group failed: find out whose
+        try {  // the member form refused the group's shape: find out whose check failed one by one
           Proof p = src.DecodeProof(i);
           common::Rand r(seeds[i]);
           std::vector<G1Affine> Rs, Ss, Ts, Us;
@@ -222,13 +231,8 @@ std::vector<int> VerifyBatchCore(const CRS& crs, size_t k, Source& src, common::
       if (members.empty()) return;
       collect();  // at most one group in flight per worker
       run_t0 = std::chrono::steady_clock::now();
-      run.Start(crs, inst, checks, pool, extra_points, extra_scalars);
+      run.Start(crs, &group);  // (takes the recording: `group` comes back empty)
       in_flight.swap(members);
-      inst.clear();
-      checks.clear();
-      pool.clear();
-      extra_points.clear();
-      extra_scalars.clear();
       members.clear();
     };
     try {
@@ -256,13 +260,14 @@ std::vector<int> VerifyBatchCore(const CRS& crs, size_t k, Source& src, common::
           pre = false;  // malformed proof / zero randomizer: rejected in a batch
         }
         if (!pre) continue;
-        rec.AppendTo(inst.size(), &checks, &pool, &extra_points, &extra_scalars);
+        rec.AppendTo(&group);  // member members.size() of the group
+        std::vector<G1Affine>& inst = group.inst;
         inst.insert(inst.end(), Rs.begin(), Rs.end());  // InstIndex: Rs | Ss | Ts | Us
         inst.insert(inst.end(), Ss.begin(), Ss.end());
         inst.insert(inst.end(), Ts.begin(), Ts.end());
         inst.insert(inst.end(), Us.begin(), Us.end());
         members.push_back(i);
-        if (members.size() >= threshold || extra_points.size() + 512 > CURDLE_DACC_MAX_EXTRA) {
+        if (members.size() >= threshold || group.extra_points.size() + 512 > CURDLE_DACC_MAX_EXTRA) {
           settle();
           threshold = flush;
         } else if (run.Active() && run.Done()) {

@@ -341,8 +341,10 @@ int curdle_verify_proof(const curdle_crs* crs, const curdle_proof* proof, const 
  * at a time): k proofs over the same CRS and the same ell.  The host part of each proof runs
  * on `nthreads` worker threads; all proofs' checks are folded into ONE accumulator (per-proof
  * randomness derived from `rand`; the CRS bases merge) and ONE MSM of ~k * (4 ell + 100) pairs
- * decides.  oks[i] receives each proof's accept bit: if the batch MSM fails, the proofs are
- * settled one by one, so the bits are exact either way.  A malformed proof or a zero
+ * decides.  oks[i] receives each proof's accept bit: if a group's MSM fails, the group's
+ * recorded checks are summed once more per member (curdle_dacc_run_members: one GPU pass, no
+ * proof decoded or hashed again; with the host-mirror accumulator, or a group beyond that form's
+ * limits, the members are verified one by one), so the bits are exact either way.  A malformed proof or a zero
  * randomizer counts as rejected here (curdle_verify reports those as errors).
  * proofs / Rs / Ss / Ts / Us: arrays of k pointers; Ms: k x 18 limbs. */
 int curdle_verify_batch(const curdle_crs* crs, size_t k, const uint8_t* const* proofs, const size_t* proof_lens,
@@ -484,6 +486,24 @@ int curdle_dacc_begin(const curdle_dbases* crs, const uint64_t* inst_points, siz
 int curdle_dacc_run(curdle_dacc* acc, const curdle_dacc_check* checks, size_t n_checks, const uint64_t* pool,
                     size_t pool_len, const uint64_t* extra_points, const uint64_t* extra_scalars, size_t n_extra,
                     uint64_t out_jac[CURDLE_G1_JAC_U64], uint64_t* export_scalars);
+/* The member form: one sum per member of a group from ONE pass over the accumulation's bases.  check_member[c] and
+ * extra_member[e] name the member (below n_members) a check or a loose pair belongs to; out_jac[j] is what
+ * curdle_dacc_run would return given only member j's checks and loose pairs, over the same pool and the same resident
+ * CRS and instance points.  Segments of different members may name the same slots: every member has a row of slot
+ * scalars of its own, and the sums come from one batched MSM whose members share the converted bases.  A member
+ * without checks and loose pairs gives infinity; n_members = 1 gives curdle_dacc_run's result bit for bit.
+ * export_scalars (optional, n_members x (n_crs + n_inst) x 4) receives the rows.  Ends the accumulation, whatever it
+ * returns.  Refused like curdle_dacc_run, and with CURDLE_EINVAL before anything is launched: a member index
+ * >= n_members; n_members == 0 with checks or loose pairs; n_members > CURDLE_DACC_MAX_MEMBERS; n_members x
+ * (n_crs + n_inst) > CURDLE_DACC_MAX_MEMBER_SLOTS; a batched MSM of more than 4,194,304 bucket slots (n_members x the
+ * slots of one member's windows: 64 members reach it beyond about 2^15 bases each, fewer members later). */
+#define CURDLE_DACC_MAX_MEMBERS 64
+#define CURDLE_DACC_MAX_MEMBER_SLOTS ((size_t)1 << 22)
+int curdle_dacc_run_members(curdle_dacc* acc, const curdle_dacc_check* checks, const uint32_t* check_member, size_t n_checks,
+                            size_t n_members, const uint64_t* pool, size_t pool_len, const uint64_t* extra_points,
+                            const uint64_t* extra_scalars, const uint32_t* extra_member, size_t n_extra,
+                            uint64_t* out_jac /* n_members x 18, canonical Jacobian */,
+                            uint64_t* export_scalars /* optional: n_members x (n_crs + n_inst) x 4 */);
 /* The same in two steps, for a caller with work to do while the MSM runs (batch verification:
  * a worker submits its group of proofs and goes on verifying the next ones): submit copies
  * every argument and queues the kernels, poll says without blocking whether they are done
@@ -501,6 +521,10 @@ void curdle_dacc_abort(curdle_dacc* acc); /* ends an accumulation without its re
  * memory, out[2] / out[3] the separate kernel staged / not (accumulations beyond 16,384 bases).
  * The builds compute the same scalars; which one ran is visible here only. */
 int curdle_stat_dacc_builds(unsigned long long out[4]);
+/* Diagnostics of the member form since the library was loaded: out[0] member-form accumulations run, out[1] members
+ * summed by them, out[2] members of failed batch groups that were still verified one by one (the batch verifiers'
+ * fall-back when the member form refuses a group's shape). */
+int curdle_stat_dacc_members(unsigned long long out[3]);
 
 /* curdleproof.Verify keeps its accumulator on the device by default (the section above);
  * 0 moves it back to the host mirror of msmaccumulator (same accept bit).  Returns the
