@@ -2,6 +2,8 @@
 // call, the inputs and the plan fields the plan invariants are about.  No device is touched.
 //   plan_probe n glv pipelined chunked c: the plan of ONE single-MSM call instead (tests/test_msm_large_gpu.py), with
 //   the window widths and the bucket counts per window.
+//   plan_probe members n_tot k: the plan of the device accumulator's member form (curdle_dacc_run_members) instead: ONE
+//   call of k MSMs of n_tot pairs each over shared bases (tests/test_dacc_members_model.py, tests/test_dacc_members_mid_gpu.py).
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -41,8 +43,34 @@ static int one(char** argv) {
   return 0;
 }
 
+// k equal offsets, shared_bases: what curdle_dacc_run_members hands make_plan.  `slots` is k * NB, what the scans walk and what
+// the form's limit (kMaxSlotsPerPass) is about; `sort_blocks` is ceil(2 n_tot / chunk), the k_hist / k_scatter blocks per member.
+static int members(char** argv) {
+  const uint32_t n_tot = (uint32_t)strtoul(argv[2], nullptr, 0);
+  const size_t k = (size_t)strtoul(argv[3], nullptr, 0);
+  std::vector<uint32_t> off(k + 1);
+  for (size_t j = 0; j <= k; j++) off[j] = (uint32_t)(j * n_tot);
+  MsmCall call;
+  call.off = off.data();
+  call.k = k;
+  call.shared_bases = true;
+  MsmPlan p;
+  const int rc = make_plan(p, call);
+  printf("members n_tot=%u k=%zu rc=%d", n_tot, k, rc);
+  if (rc == CURDLE_OK) {
+    const uint64_t slots = (uint64_t)k * p.NB;
+    printf(" c=%d NB=%u L=%u chunk=%u max_small=%u max_large=%u fuse_scan=%u gpu_combine=%u slots=%llu sort_blocks=%u fits=%d\nwindows",
+           p.c, p.NB, p.L, p.chunk, p.max_small, p.max_large, p.fuse_scan, p.gpu_combine, (unsigned long long)slots,
+           p.chunk ? (2 * n_tot + p.chunk - 1) / p.chunk : 0, slots <= kMaxSlotsPerPass ? 1 : 0);
+    for (int w = 0; w < p.W; w++) printf(" %u:%u", p.bits[w], p.nbkt[w]);
+  }
+  printf("\n");
+  return rc == CURDLE_OK ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
   if (argc == 6) return one(argv);
+  if (argc == 4 && !strcmp(argv[1], "members")) return members(argv);
   // single MSMs and batches, every mode flag, several window ranges and widths
   const uint32_t sizes[] = {1, 300, 1268, 8192, 16384, 65536, 131072, 1u << 18, 1u << 20, 1u << 22, 1u << 24, 22369622,
                             1u << 25, 1u << 26, 1u << 27};

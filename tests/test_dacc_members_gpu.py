@@ -35,8 +35,9 @@ def resident(gpu, base_pts):
         b.free()
 
 
-def run_case(gpu, oracle, coracle, base_pts, bases, c, cmem, xmem, n_members):
-    crs, inst, loose = M.case_points(c, base_pts)
+def run_case(gpu, oracle, coracle, base_pts, bases, c, cmem, xmem, n_members, points=None):
+    """`points`: the case's (crs, inst, loose) where they are not case_points' tiling (tests/test_dacc_members_mid_gpu.py)."""
+    crs, inst, loose = points or M.case_points(c, base_pts)
     args = (inst, M.pack_checks(c.checks), M.pack_fr(c.pool, oracle), loose, M.pack_fr(c.extra_scalars, oracle))
     before = gpu.stat_dacc_members()
     out, rows = gpu.dacc_run_members(bases, args[0], args[1], cmem, n_members, args[2], args[3], args[4], xmem)
