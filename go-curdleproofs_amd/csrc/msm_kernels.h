@@ -215,6 +215,7 @@ hipError_t launch_g1_decompress(const uint8_t* in, uint32_t n, int subgroup_chec
 // check_kernels.hip: n gnark affine points IN MEMORY (24 u32 each) -> one CURDLE_DECODE_* status byte per point:
 // infinity (all words zero), a coordinate >= p, off the curve, and with subgroup_check outside the prime-order subgroup.
 hipError_t launch_g1_check_affine(const uint32_t* pts, uint32_t n, int subgroup_check, uint8_t* status, hipStream_t stream);
+hipError_t launch_g1_check_jac(const uint32_t* pts, uint32_t n, int subgroup_check, uint8_t* status, hipStream_t stream);
 
 // The subgroup test straight from the n compressed records, without their square roots (so it
 // can run beside launch_g1_decompress(..., subgroup_check = 0, ...)): sub[i] = 0 iff record i,

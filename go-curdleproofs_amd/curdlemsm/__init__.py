@@ -72,6 +72,7 @@ SYMBOLS = [
     "curdle_verify_set_device_acc", "curdle_verify_export_accumulator",
     "curdle_g1_check_batch", "curdle_g1_check_batch_device", "curdle_verify_checked", "curdle_verify_proof_checked",
     "curdle_stat_check_paths",
+    "curdle_g1_check_jac_batch", "curdle_g1_check_jac_batch_device", "curdle_verify_batch_checked", "curdle_stat_batch_checked",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -866,12 +867,44 @@ class PreparedVerifyBatch:
                              int(nthreads), oks))
         return [bool(v) for v in oks]
 
+    def run_checked(self, crs: CRS, rand: Rand, nthreads: int = 8):
+        """curdle_verify_batch_checked on the same arguments: (accept bits, the curdle_point_fault records)."""
+        oks = (C.c_int * self.k)()
+        faults = np.zeros(self.k, dtype=POINT_FAULT)
+        _check(_verify_batch_checked(crs._h, self.k, self._pp, self._lens, *self._inst, crs.ell, _ptr(self._ms), rand._h,
+                                     int(nthreads), oks, _ptr(faults)))
+        return [bool(v) for v in oks], faults
+
 
 def verify_batch(crs: CRS, proofs, Rs, Ss, Ts, Us, Ms, rand: Rand, nthreads: int = 8):
     """Cross-proof batch verification: k proofs over one CRS, one shared accumulator, one MSM.
     proofs: list of bytes; Rs/Ss/Ts/Us: lists of (ell, 12) arrays; Ms: list of 18-limb points.
     Returns the list of accept bits (exact: a failing group is settled by one sum per member, curdle_dacc_run_members)."""
     return PreparedVerifyBatch(proofs, Rs, Ss, Ts, Us, Ms).run(crs, rand, nthreads)
+
+
+_verify_batch_checked = _sig("curdle_verify_batch_checked", C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp,
+                             _vp, C.c_int, _vp, _vp)
+_stat_batch_checked = _sig("curdle_stat_batch_checked", C.c_int, C.POINTER(C.c_ulonglong))
+POINT_FAULT = np.dtype([("code", np.uint8), ("vector", np.uint8), ("pad", np.uint16), ("index", np.uint32)])  # curdle_point_fault
+FAULT_VECTORS = ("Rs", "Ss", "Ts", "Us", "M")
+
+
+def verify_batch_checked(crs: CRS, proofs, Rs, Ss, Ts, Us, Ms, rand: Rand, nthreads: int = 8):
+    """verify_batch() with every member's 4 ell instance points and its M checked (range, curve, subgroup) on the GPU,
+    in chunks beside the verification.  Returns (oks, faults): faults[i] is None, or (vector name, index, DECODE_*
+    code) of member i's first failed point in the order Rs, Ss, Ts, Us, M -- such a member is never verified and has
+    oks[i] False; every other member has the bit verify_batch() gives it from the same rand state."""
+    oks, faults = PreparedVerifyBatch(proofs, Rs, Ss, Ts, Us, Ms).run_checked(crs, rand, nthreads)
+    return (oks, [None if f["code"] <= DECODE_INFINITY else (FAULT_VECTORS[f["vector"]], int(f["index"]), int(f["code"]))
+                  for f in faults])
+
+
+def stat_batch_checked() -> dict:
+    """Checked batches since the library was loaded, members their point check rejected, chunks checked."""
+    out = (C.c_ulonglong * 3)()
+    _check(_stat_batch_checked(out))
+    return {"batches": out[0], "rejected": out[1], "chunks": out[2]}
 
 
 # ---- whisk package (whisk/whisk.go, whisk/types.go): trackers are 96-byte strings rG || krG ----
@@ -1103,6 +1136,27 @@ def g1_check_batch_device(ptr: int, n: int, subgroup_check: bool = True, stream=
     """The same for n points resident in device memory at `ptr`; the status bytes come back to host memory."""
     st = np.zeros(n, dtype=np.uint8)
     _check(_check_batch_device(ptr, n, 1 if subgroup_check else 0, _ptr(st), stream or None))
+    return st
+
+
+_check_jac_batch = _sig("curdle_g1_check_jac_batch", C.c_int, _vp, C.c_size_t, C.c_int, _vp)
+_check_jac_batch_device = _sig("curdle_g1_check_jac_batch_device", C.c_int, _vp, C.c_size_t, C.c_int, _vp, _vp)
+
+
+def g1_check_jac_batch(jac_points, subgroup_check: bool = True) -> np.ndarray:
+    """(n, 18) gnark G1Jac points in memory -> (n,) DECODE_* status bytes, on the GPU: Z = 0 is infinity, then a
+    coordinate >= p, off the curve Y^2 = X^3 + 4 Z^6, and with subgroup_check outside the prime-order subgroup."""
+    jac_points = _as_u64(jac_points, 18)
+    n = jac_points.shape[0] if jac_points.size else 0
+    st = np.zeros(n, dtype=np.uint8)
+    _check(_check_jac_batch(_ptr(jac_points), n, 1 if subgroup_check else 0, _ptr(st)))
+    return st
+
+
+def g1_check_jac_batch_device(ptr: int, n: int, subgroup_check: bool = True, stream=None) -> np.ndarray:
+    """The same for n points resident in device memory at `ptr`; the status bytes come back to host memory."""
+    st = np.zeros(n, dtype=np.uint8)
+    _check(_check_jac_batch_device(ptr, n, 1 if subgroup_check else 0, _ptr(st), stream or None))
     return st
 
 

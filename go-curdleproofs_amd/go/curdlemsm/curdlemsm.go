@@ -463,3 +463,105 @@ func VerifyChecked(Rs, Ss, Ts, Us []bls12381.G1Affine, M *bls12381.G1Jac, verify
 	}
 	return verify()
 }
+
+// CheckG1Jac is CheckG1Affine for points held as G1Jac (curdle_g1_check_jac_batch): a caller's M, crs.H, crs.Gt,
+// crs.Gu, any []G1Jac.  Nothing is normalised on the host: Z = 0 is DecodeInfinity (X and Y are not looked at), a
+// coordinate that is not below p DecodeBadEncoding, Y^2 != X^3 + 4 Z^6 DecodeNotOnCurve, and the subgroup test runs
+// from the projective coordinates.  The points are only read.  UNVERIFIED like the rest of this file: never compiled.
+func CheckG1Jac(points []bls12381.G1Jac) ([]uint8, error) {
+	status := make([]uint8, len(points))
+	if len(points) == 0 {
+		return status, nil
+	}
+	err := locked(func() C.int {
+		return C.curdle_g1_check_jac_batch((*C.uint64_t)(unsafe.Pointer(&points[0])), C.size_t(len(points)), 1,
+			(*C.uint8_t)(unsafe.Pointer(&status[0])))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return status, nil
+}
+
+// PointFault names the first failed point of a batch member, as curdle_point_fault does: Vector 0 Rs, 1 Ss, 2 Ts,
+// 3 Us, 4 M; Code is a Decode* status, DecodeOK for a member with nothing wrong.
+type PointFault struct {
+	Code   uint8
+	Vector uint8
+	Index  uint32
+}
+
+// BatchInstance is one member's instance as curdleproof.Verify takes it.
+type BatchInstance struct {
+	Rs, Ss, Ts, Us []bls12381.G1Affine
+	M              *bls12381.G1Jac
+}
+
+// VerifyBatchChecked is the Go side of curdle_verify_batch_checked for a caller that keeps its own protocol code, as
+// VerifyChecked is of curdle_verify_checked: the instance points of every member in chunks of at most 32,768 points
+// (CheckG1Affine: the four-lanes-per-point kernel), the Ms in one CheckG1Jac, then `verify(i)` -- the caller's
+// closure over curdleproof.Verify -- for the members without a fault, and only for them.  faults[i] is the member's
+// first failure in the order Rs, Ss, Ts, Us, M; a point at infinity passes.  UNVERIFIED: never compiled.
+func VerifyBatchChecked(batch []BatchInstance, verify func(i int) (bool, error)) ([]bool, []PointFault, error) {
+	oks := make([]bool, len(batch))
+	faults := make([]PointFault, len(batch))
+	bad := func(st uint8) bool { return st != DecodeOK && st != DecodeInfinity }
+	for lo := 0; lo < len(batch); {
+		hi, n := lo, 0
+		var chunk []bls12381.G1Affine
+		for hi < len(batch) {
+			b := &batch[hi]
+			m := len(b.Rs) + len(b.Ss) + len(b.Ts) + len(b.Us)
+			if hi > lo && n+m > 32768 {
+				break
+			}
+			for _, v := range [4][]bls12381.G1Affine{b.Rs, b.Ss, b.Ts, b.Us} {
+				chunk = append(chunk, v...)
+			}
+			n += m
+			hi++
+		}
+		status, err := CheckG1Affine(chunk)
+		if err != nil {
+			return nil, nil, err
+		}
+		at := 0
+		for i := lo; i < hi; i++ {
+			b := &batch[i]
+			for k, v := range [4][]bls12381.G1Affine{b.Rs, b.Ss, b.Ts, b.Us} {
+				for j := range v {
+					if st := status[at+j]; bad(st) && faults[i].Code == DecodeOK {
+						faults[i] = PointFault{Code: st, Vector: uint8(k), Index: uint32(j)}
+					}
+				}
+				at += len(v)
+			}
+		}
+		lo = hi
+	}
+	ms := make([]bls12381.G1Jac, len(batch))
+	for i := range batch {
+		if batch[i].M == nil {
+			return nil, nil, errors.New("curdlemsm: VerifyBatchChecked: M is nil")
+		}
+		ms[i] = *batch[i].M
+	}
+	status, err := CheckG1Jac(ms)
+	if err != nil {
+		return nil, nil, err
+	}
+	for i := range batch {
+		if bad(status[i]) && faults[i].Code == DecodeOK {
+			faults[i] = PointFault{Code: status[i], Vector: 4}
+		}
+		if faults[i].Code != DecodeOK {
+			continue
+		}
+		ok, err := verify(i)
+		if err != nil {
+			return nil, nil, err
+		}
+		oks[i] = ok
+	}
+	return oks, faults, nil
+}

@@ -1457,55 +1457,90 @@ bool VerifyStarted(VerifyPrelude& pre, const Proof& proof, const CRS& crs, const
 // `rand`.  If a group's MSM fails, its proofs are verified one by one, so oks[] is exact
 // either way; a proof that does not decode or fails a direct check is rejected without
 // joining a group.
+namespace {
+// pass 1 (DecodeAhead's producers, chunk by chunk, ahead of the workers) walks each proof's
+// wire format and registers its records -- a proof that does not parse is rejected here --,
+// one GPU decoding per chunk; pass 2 (workers) builds the values
+struct BytesSource {
+  const std::vector<BatchItem>& items;
+  std::vector<size_t> first_point;
+  std::vector<char> parses;
+  std::unique_ptr<DecodeAhead> ahead;
+  explicit BytesSource(const std::vector<BatchItem>& it) : items(it), first_point(it.size(), 0), parses(it.size(), 0) {}
+  void Start() {
+    const size_t k = items.size();
+    ahead = std::make_unique<DecodeAhead>(k, DecodeAheadChunk(k, k ? items[0].proof_len / 48 : 0), DecodeAheadProducers(),
+                                          [this](size_t i, PointDecoder& dec) { Scan(i, dec); });
+  }
+  void Scan(size_t i, PointDecoder& dec) {
+    first_point[i] = dec.size();
+    try {
+      Reader scan(items[i].proof, items[i].proof_len, true);
+      scan.collect = &dec;
+      Proof::FromReader(scan);
+      parses[i] = 1;
+    } catch (const std::runtime_error&) {
+    }
+  }
+  bool Ready(size_t i) { return ahead->Ready(i); }
+  bool Usable(size_t i) {
+    ahead->Wait(i);
+    return parses[i] != 0;
+  }
+  Proof DecodeProof(size_t i) {
+    Reader r(items[i].proof, items[i].proof_len, true);
+    r.decoded = &ahead->Wait(i);
+    r.decoded_pos = first_point[i];
+    r.keep_wire = true;  // the proof value lives inside this call, like the caller's bytes
+    return Proof::FromReader(r);
+  }
+  bool Prelude(size_t, VerifyPrelude&) const { return false; }  // the instance arrives decoded
+  void Instance(size_t i, std::vector<G1Affine>& Rs, std::vector<G1Affine>& Ss, std::vector<G1Affine>& Ts,
+                std::vector<G1Affine>& Us, Point& M) const {
+    const BatchItem& it = items[i];
+    Rs.assign(it.Rs, it.Rs + it.ell);
+    Ss.assign(it.Ss, it.Ss + it.ell);
+    Ts.assign(it.Ts, it.Ts + it.ell);
+    Us.assign(it.Us, it.Us + it.ell);
+    M = Point::FromJac(it.M);
+  }
+};
+// ... and the same with the members' points checked ahead of the workers (CheckAhead): a member is usable once both
+// its chunks are there, and not at all if one of its points failed -- no transcript, no recording, no group.
+struct CheckedBytesSource : BytesSource {
+  std::unique_ptr<CheckAhead> checked;
+  using BytesSource::BytesSource;
+  bool Ready(size_t i) { return checked->Ready(i) && BytesSource::Ready(i); }
+  bool Usable(size_t i) { return checked->Wait(i) && BytesSource::Usable(i); }
+};
+}  // namespace
+
 std::vector<int> VerifyBatch(const CRS& crs, const std::vector<BatchItem>& items, common::Rand& rand, int nthreads) {
-  const size_t k = items.size();
-  // pass 1 (DecodeAhead's producers, chunk by chunk, ahead of the workers) walks each proof's
-  // wire format and registers its records -- a proof that does not parse is rejected here --,
-  // one GPU decoding per chunk; pass 2 (workers) builds the values
-  struct BytesSource {
-    const std::vector<BatchItem>& items;
-    std::vector<size_t> first_point;
-    std::vector<char> parses;
-    std::unique_ptr<DecodeAhead> ahead;
-    explicit BytesSource(const std::vector<BatchItem>& it) : items(it), first_point(it.size(), 0), parses(it.size(), 0) {}
-    void Scan(size_t i, PointDecoder& dec) {
-      first_point[i] = dec.size();
-      try {
-        Reader scan(items[i].proof, items[i].proof_len, true);
-        scan.collect = &dec;
-        Proof::FromReader(scan);
-        parses[i] = 1;
-      } catch (const std::runtime_error&) {
-      }
-    }
-    bool Ready(size_t i) { return ahead->Ready(i); }
-    bool Usable(size_t i) {
-      ahead->Wait(i);
-      return parses[i] != 0;
-    }
-    Proof DecodeProof(size_t i) {
-      Reader r(items[i].proof, items[i].proof_len, true);
-      r.decoded = &ahead->Wait(i);
-      r.decoded_pos = first_point[i];
-      r.keep_wire = true;  // the proof value lives inside this call, like the caller's bytes
-      return Proof::FromReader(r);
-    }
-    bool Prelude(size_t, VerifyPrelude&) const { return false; }  // the instance arrives decoded
-    void Instance(size_t i, std::vector<G1Affine>& Rs, std::vector<G1Affine>& Ss, std::vector<G1Affine>& Ts,
-                  std::vector<G1Affine>& Us, Point& M) const {
-      const BatchItem& it = items[i];
-      Rs.assign(it.Rs, it.Rs + it.ell);
-      Ss.assign(it.Ss, it.Ss + it.ell);
-      Ts.assign(it.Ts, it.Ts + it.ell);
-      Us.assign(it.Us, it.Us + it.ell);
-      M = Point::FromJac(it.M);
-    }
-  } src(items);
-  src.ahead = std::make_unique<DecodeAhead>(k, DecodeAheadChunk(k, k ? items[0].proof_len / 48 : 0), DecodeAheadProducers(),
-                                            [&src](size_t i, PointDecoder& dec) { src.Scan(i, dec); });
+  BytesSource src(items);
+  src.Start();
   try {
-    return VerifyBatchCore(crs, k, src, rand, BatchWorkers(nthreads));
+    return VerifyBatchCore(crs, items.size(), src, rand, BatchWorkers(nthreads));
   } catch (...) {
+    src.ahead->Abandon();
+    throw;
+  }
+}
+
+std::vector<int> VerifyBatchChecked(const CRS& crs, const std::vector<BatchItem>& items, common::Rand& rand, int nthreads,
+                                    const ChunkCheckFn& check, PointFault* faults, size_t* chunks_checked) {
+  const size_t k = items.size();
+  CheckedBytesSource src(items);
+  // the check first: its chunks are what the workers wait for longest (1,008 points a member at ell = 252)
+  src.checked = std::make_unique<CheckAhead>(items, CheckAheadChunk(k, k ? items[0].ell : 0), CheckAheadProducers(nthreads), check,
+                                             faults);
+  src.Start();
+  const int workers = CheckedBatchWorkers(nthreads);  // the check's producers come out of the caller's budget
+  try {
+    std::vector<int> oks = VerifyBatchCore(crs, k, src, rand, workers);
+    if (chunks_checked) *chunks_checked = src.checked->Chunks();
+    return oks;
+  } catch (...) {
+    src.checked->Abandon();
     src.ahead->Abandon();
     throw;
   }

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "batch_check.h"
 #include "algebra.h"
 #include "common_rand.h"
 #include "msmaccumulator.h"
@@ -445,6 +446,18 @@ struct BatchItem {  // borrowed buffers: ell affine points each, M as 18 Jacobia
   const uint64_t* M;
 };
 std::vector<int> VerifyBatch(const CRS& crs, const std::vector<BatchItem>& items, common::Rand& rand, int nthreads);
+
+// VerifyBatch with a membership check (range, curve equation, subgroup) of every member's 4 ell instance points and
+// of its M, in chunks, AHEAD of the workers and beside them, as the point decoding is.  The check is the backend's:
+// `check` gets one chunk's affine vectors (na pointers with their lengths, taken as back to back) and its Jacobian
+// points (nj pointers to 18 words each), runs ONE affine and ONE Jacobian kernel over them and returns one
+// CURDLE_DECODE_* byte per point -- or a code of include/curdle_msm.h, with the text in curdle_last_error: the whole
+// batch then fails with it.  The host layer names no backend symbol for it, so the host-only build links as before.
+// A member with a failed point is never verified: oks[i] = 0, and faults[i] names the first failure in the order Rs,
+// Ss, Ts, Us, M.  Infinity is no failure.  Every other member has faults[i].code = 0 and the bit VerifyBatch gives
+// it from the same `rand`.
+std::vector<int> VerifyBatchChecked(const CRS& crs, const std::vector<BatchItem>& items, common::Rand& rand, int nthreads,
+                                    const ChunkCheckFn& check, PointFault* faults, size_t* chunks_checked = nullptr);
 
 // Deferred (default) or eager evaluation of the verifier's check points; see
 // curdle_verify_set_eager in include/curdle_msm.h.  Returns the previous setting.

@@ -41,6 +41,7 @@ enum Id {
   AUX_PRIO,           // wave priority (0..3) of the sort kernels, the conversion and the chunk fold; unset: 3 for pipelined calls, 0 for synchronous ones
   HOST_FOLD,          // 0: chunked host-buffer MSMs keep every chunk's fragments for the one reduction (no progressive folding)
   MAX_LARGE,          // test hook: caps the plan's large-bucket queue (max_large = min(plan, value), at least 1), so a test can overflow it
+  BATCH_CHECKERS,     // checked batch verification: producer threads of the point check
   COUNT
 };
 // The knob's value, or -1 if it is not set (every knob's valid values are >= 0).

@@ -3,6 +3,7 @@
 // include/curdle_msm.h under "Protocol layers".
 #include <string.h>
 
+#include <atomic>
 #include <exception>
 #include <new>
 #include <stdexcept>
@@ -300,6 +301,52 @@ extern "C" int curdle_verify_batch(const curdle_crs* crs, size_t k, const uint8_
     for (size_t i = 0; i < k; i++) oks[i] = res[i];
     return CURDLE_OK;
   });
+}
+
+// curdle_verify_batch_checked behind its argument checks (csrc/check_api.hip owns the entry point and the check).
+int curdle_verify_batch_checked_with(const curdle_crs* crs, size_t k, const uint8_t* const* proofs, const size_t* proof_lens,
+                                     const uint64_t* const* Rs, const uint64_t* const* Ss, const uint64_t* const* Ts,
+                                     const uint64_t* const* Us, size_t ell, const uint64_t* Ms, curdle_rand* rand, int nthreads,
+                                     int* oks, curdle_point_fault* faults, const proto::ChunkCheckFn& check,
+                                     unsigned long long stats[2]) {
+  const int rc = Guard([&]() {
+    std::vector<curdle_point_fault> found(k);
+    std::vector<proto::BatchItem> items(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!proofs[i] || !Rs[i] || !Ss[i] || !Ts[i] || !Us[i]) throw std::runtime_error("null argument in batch item");
+      items[i] = proto::BatchItem{proofs[i],
+                                  proof_lens[i],
+                                  reinterpret_cast<const G1Affine*>(Rs[i]),
+                                  reinterpret_cast<const G1Affine*>(Ss[i]),
+                                  reinterpret_cast<const G1Affine*>(Ts[i]),
+                                  reinterpret_cast<const G1Affine*>(Us[i]),
+                                  ell,
+                                  Ms + 18 * i};
+    }
+    std::atomic<unsigned long long> chunks(0);
+    std::vector<int> res = ShardOverDevices(k, rand->r, nthreads, [&](size_t lo, size_t hi, common::Rand& r, int threads) {
+      std::vector<proto::BatchItem> shard(items.begin() + lo, items.begin() + hi);
+      size_t done = 0;
+      std::vector<int> bits = proto::VerifyBatchChecked(crs->crs, shard, r, threads, check, found.data() + lo, &done);
+      chunks.fetch_add(done);
+      return bits;
+    });
+    unsigned long long rejected = 0;
+    for (size_t i = 0; i < k; i++) {
+      oks[i] = res[i];
+      if (found[i].code > CURDLE_DECODE_INFINITY) rejected++;
+      if (faults) faults[i] = found[i];
+    }
+    stats[0] += rejected;
+    stats[1] += chunks.load();
+    return CURDLE_OK;
+  });
+  if (rc != CURDLE_OK)
+    for (size_t i = 0; i < k; i++) {
+      oks[i] = 0;
+      if (faults) faults[i] = curdle_point_fault{0xff, 0, 0, 0};
+    }
+  return rc;
 }
 
 // ---- whisk package (whisk/whisk.go) ----

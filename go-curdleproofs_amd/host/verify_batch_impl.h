@@ -139,6 +139,143 @@ inline int DecodeAheadProducers() {
   if (knobs::get(knobs::BATCH_PRODUCERS) > 0) return (int)knobs::get(knobs::BATCH_PRODUCERS);
   return 2;
 }
+// The membership check of a checked batch (VerifyBatchChecked), produced the same way: chunk c's instance points and
+// Ms go to the backend's `check` -- pinned staging, one affine and one Jacobian kernel -- while the workers are busy
+// with the chunks before it, and the first failed point of every member is published with the chunk.  The producers
+// only read the caller's arrays and never touch `rand`.  The chunk (CheckAheadChunk below) is at most 32,768 points,
+// so that the check runs on four lanes per point (32 proofs at ell = 252, 64 at ell = 124), under the same
+// BATCH_CHUNK knob.  A chunk's check is a dependent chain of 1.2 ms on an idle GPU and 3-12 ms beside the groups'
+// MSMs, so several are kept in flight, and every producer is a thread of the caller's budget (CheckedBatchWorkers):
+// with 16 threads in all, k = 1,024, ell = 252 / 124, one lease, medians of 7 (profiles/r11_batch_checked.json):
+// 73 / 51 ms with two producers and 12 workers, 72 / 50 with three and 11, 65 / 45 with four and 10, beside 46.5 /
+// 30.7 unchecked.  Four from 16 threads, two from 8, one below.
+class CheckAhead {
+ public:
+  CheckAhead(const std::vector<BatchItem>& items, size_t chunk, int producers, ChunkCheckFn check, PointFault* faults)
+      : items_(items), chunk_(chunk < 1 ? 1 : chunk), check_(std::move(check)), faults_(faults) {
+    const size_t nchunks = (items_.size() + chunk_ - 1) / chunk_;
+    ready_.assign(nchunks, 0);
+    if (producers < 1) producers = 1;
+    if ((size_t)producers > nchunks) producers = (int)nchunks;
+    const int device = curdle_get_device();  // as DecodeAhead: a shard's threads all select the shard's device
+    for (int t = 0; t < producers; t++)
+      threads_.emplace_back([this, device] {
+        (void)curdle_set_device(device);
+        Produce();
+      });
+  }
+  ~CheckAhead() {
+    stop_.store(true);
+    for (auto& t : threads_) t.join();
+  }
+  CheckAhead(const CheckAhead&) = delete;
+  CheckAhead& operator=(const CheckAhead&) = delete;
+  // Did member i pass, once its chunk is checked?  Rethrows a producer's failure (a device error: the batch fails).
+  bool Wait(size_t i) {
+    const size_t c = i / chunk_;
+    std::unique_lock<std::mutex> g(mu_);
+    cv_.wait(g, [&] { return ready_[c] != 0 || error_ != nullptr; });
+    if (!ready_[c]) std::rethrow_exception(error_);
+    return faults_[i].code <= CURDLE_DECODE_INFINITY;
+  }
+  bool Ready(size_t i) {
+    std::lock_guard<std::mutex> g(mu_);
+    return ready_[i / chunk_] != 0 || error_ != nullptr;
+  }
+  void Abandon() { stop_.store(true); }
+  size_t Chunks() const { return done_.load(); }
+
+ private:
+  void Produce() {
+    try {
+      std::vector<const uint64_t*> vecs, jacs;
+      std::vector<size_t> lens;
+      std::vector<uint8_t> st_a, st_j;
+      for (size_t c = next_.fetch_add(1); c < ready_.size() && !stop_.load(); c = next_.fetch_add(1)) {
+        const size_t lo = c * chunk_, hi = lo + chunk_ < items_.size() ? lo + chunk_ : items_.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        vecs.clear();
+        lens.clear();
+        jacs.clear();
+        size_t na = 0;
+        for (size_t i = lo; i < hi; i++) {
+          const BatchItem& it = items_[i];
+          for (const G1Affine* v : {it.Rs, it.Ss, it.Ts, it.Us}) {
+            vecs.push_back(reinterpret_cast<const uint64_t*>(v));
+            lens.push_back(it.ell);
+          }
+          na += 4 * it.ell;
+          jacs.push_back(it.M);
+        }
+        st_a.assign(na, 0);
+        st_j.assign(hi - lo, 0);
+        const int rc = check_(vecs.data(), lens.data(), vecs.size(), jacs.data(), jacs.size(), st_a.data(), st_j.data());
+        if (rc != CURDLE_OK) {
+          char text[256] = "";
+          (void)curdle_last_error(text, sizeof(text));
+          throw alg::MsmError(std::string("checking the batch's points: ") + text, rc);
+        }
+        const uint8_t* st = st_a.data();
+        for (size_t i = lo; i < hi; i++) {
+          PointFault f{};
+          const size_t ell = items_[i].ell;
+          for (size_t j = 0; j < 4 * ell && f.code == 0; j++)
+            if (st[j] > CURDLE_DECODE_INFINITY) f = PointFault{st[j], (uint8_t)(j / ell), 0, (uint32_t)(j % ell)};
+          if (f.code == 0 && st_j[i - lo] > CURDLE_DECODE_INFINITY) f = PointFault{st_j[i - lo], 4, 0, 0};
+          faults_[i] = f;
+          st += 4 * ell;
+        }
+        if (BatchTrace())
+          fprintf(stderr, "[batch] check of chunk %zu (%zu + %zu points): at %.2f ms, %.2f ms\n", c, na, hi - lo,
+                  std::chrono::duration<double, std::milli>(t0 - start_).count(),
+                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        done_.fetch_add(1);
+        std::lock_guard<std::mutex> g(mu_);
+        ready_[c] = 1;
+        cv_.notify_all();
+      }
+    } catch (...) {
+      std::lock_guard<std::mutex> g(mu_);
+      if (!error_) error_ = std::current_exception();
+      cv_.notify_all();
+    }
+  }
+  const std::vector<BatchItem>& items_;
+  size_t chunk_;
+  ChunkCheckFn check_;
+  PointFault* faults_;
+  std::chrono::steady_clock::time_point start_ = std::chrono::steady_clock::now();
+  std::vector<char> ready_;
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::exception_ptr error_;
+  std::atomic<size_t> next_{0}, done_{0};
+  std::atomic<bool> stop_{false};
+  std::vector<std::thread> threads_;
+};
+// DecodeAheadChunk's rule without its floor of 16 members: beyond ell = 512 sixteen members are more than 32,768
+// points, and the check's chunk shrinks (down to one member) to stay on four lanes per point.  Only a single member
+// of more than 8,192 points an instance vector goes to the one-lane build.
+inline size_t CheckAheadChunk(size_t k, size_t ell) {
+  if (knobs::get(knobs::BATCH_CHUNK) > 0) return (size_t)knobs::get(knobs::BATCH_CHUNK);  // tests, tuning
+  size_t c = k / 4;
+  c = c < 16 ? 16 : c > 64 ? 64 : c;
+  if (ell && c * 4 * ell > 32768) c = 32768 / (4 * ell);
+  return c < 1 ? 1 : c;
+}
+inline int CheckAheadProducers(int nthreads) {
+  if (knobs::get(knobs::BATCH_CHECKERS) > 0) return (int)knobs::get(knobs::BATCH_CHECKERS);
+  return nthreads >= 16 ? 4 : nthreads >= 8 ? 2 : 1;
+}
+// The checked batch's workers: what the caller's budget leaves after BOTH kinds of producers.  A check producer is a
+// whole thread of the budget: it copies ~3 MB a chunk into the staging and then waits in hipStreamSynchronize, which
+// spins by default.  Never under two workers from four threads (as BatchWorkers), so small budgets are overshot by
+// the producers; from 8 threads the total is nthreads.
+inline int CheckedBatchWorkers(int nthreads) {
+  const int w = nthreads - DecodeAheadProducers() - CheckAheadProducers(nthreads);
+  return nthreads >= 4 ? (w < 2 ? 2 : w) : nthreads;
+}
+
 // The caller's thread budget covers the producers: `nthreads` threads in all while they run.
 inline int BatchWorkers(int nthreads) {
   const int w = nthreads - DecodeAheadProducers();

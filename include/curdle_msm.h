@@ -604,14 +604,50 @@ int curdle_g1_check_batch_device(const void* d_points, size_t n, int subgroup_ch
  * Any other failed point: CURDLE_EINVAL, *ok = 0, and curdle_last_error names vector, index and reason --
  * "Ss[17]: not in the prime-order subgroup" -- for the first failure in the order Rs, Ss, Ts, Us, M; the verifier's
  * own result is never reported for such an instance.  If every point passes, return code, *ok and error text are
- * those of the unchecked call.  A batch (curdle_verify_batch) is checked by its caller: one curdle_g1_check_batch
- * over all k * 4 ell instance points first. */
+ * those of the unchecked call.  A batch has a checked form of its own: curdle_verify_batch_checked below. */
 int curdle_verify_checked(const curdle_crs* crs, const uint8_t* proof, size_t proof_len, const uint64_t* Rs,
                           const uint64_t* Ss, const uint64_t* Ts, const uint64_t* Us, size_t ell,
                           const uint64_t M[CURDLE_G1_JAC_U64], curdle_rand* rand, int* ok);
 int curdle_verify_proof_checked(const curdle_crs* crs, const curdle_proof* proof, const uint64_t* Rs,
                                 const uint64_t* Ss, const uint64_t* Ts, const uint64_t* Us, size_t ell,
                                 const uint64_t M[CURDLE_G1_JAC_U64], curdle_rand* rand, int* ok);
+/* The same membership check for gnark G1Jac values (n x 18 limbs: X, Y, Z in Montgomery form), the layout of the
+ * verifier's M, of crs.H / Gt / Gu and of every []G1Jac a Go caller holds.  Nothing is normalised on the host and
+ * nothing is inverted: the subgroup test runs from the projective coordinates.  Decided in this order: Z all zero words
+ * -> INFINITY (gnark's rule for G1Jac: X and Y are not looked at); X, Y or Z >= p -> BAD_ENCODING; Y^2 != X^3 + 4 Z^6
+ * -> NOT_ON_CURVE; with subgroup_check != 0, [z^2] phi(P) + P != inf -> NOT_IN_SUBGROUP; else OK.  Arguments, return
+ * codes and the rule that picks the kernel build are those of curdle_g1_check_batch / _device. */
+int curdle_g1_check_jac_batch(const uint64_t* jac_points, size_t n, int subgroup_check, uint8_t* status);
+int curdle_g1_check_jac_batch_device(const void* d_jac_points, size_t n, int subgroup_check, uint8_t* status, void* stream);
+/* curdle_verify_batch with that check on every member's 4 ell instance points and on its M (range, curve equation,
+ * subgroup), ON THE GPU and BESIDE the verification: producer threads gather the points of a chunk of members (at most
+ * 32,768 points, so that the check runs on four lanes per point; only a single member beyond ell = 8,192 is more) into
+ * pinned staging and run ONE affine and ONE Jacobian kernel per chunk, on a decode context when one is free and through
+ * an MSM slot otherwise, ahead of the workers that verify.  The producers (4 from nthreads = 16, 2 from 8, else 1) are
+ * threads of the `nthreads` budget, as the decoding's two are: from 8 threads the call runs nthreads threads in all,
+ * below that at least two workers beside the producers.  Every instance point crosses the link once more; nothing is normalised or tested on the host.
+ *   - A member with a failed point gets oks[i] = 0 and faults[i] = its first failure in the order Rs, Ss, Ts, Us, M
+ *     (then the lowest index).  It is never verified: no transcript, no recording, no place in a group.
+ *   - A point at infinity is acceptable, as in curdle_verify_checked.
+ *   - Every other member has faults[i].code = 0 and the oks[i] curdle_verify_batch gives it on the same batch from the
+ *     same `rand` state (the k seeds are drawn the same way, before anything else).
+ *   - Return codes are curdle_verify_batch's.  On a negative return nothing reads as a verdict: oks[i] = 0 and
+ *     faults[i].code = 0xff for every i.  k = 0: CURDLE_OK, no device needed.  faults may be NULL.
+ *   - With several contexts the batch is sharded as the unchecked call shards it; each shard's check runs on its
+ *     shard's context. */
+typedef struct {
+  uint8_t code;    /* CURDLE_DECODE_*; 0 or 1 = nothing wrong */
+  uint8_t vector;  /* 0 Rs, 1 Ss, 2 Ts, 3 Us, 4 M */
+  uint16_t pad;
+  uint32_t index;  /* within the vector; 0 for M */
+} curdle_point_fault;
+int curdle_verify_batch_checked(const curdle_crs* crs, size_t k, const uint8_t* const* proofs, const size_t* proof_lens,
+                                const uint64_t* const* Rs, const uint64_t* const* Ss, const uint64_t* const* Ts,
+                                const uint64_t* const* Us, size_t ell, const uint64_t* Ms, curdle_rand* rand,
+                                int nthreads, int* oks, curdle_point_fault* faults);
+/* Diagnostics: out[0] checked batches since the library was loaded, out[1] members their point check rejected,
+ * out[2] chunks checked. */
+int curdle_stat_batch_checked(unsigned long long out[3]);
 /* Diagnostics: checked verifications since the library was loaded whose point check out[0] ran on a decode
  * context beside the verification, out[1] found every decode context taken and ran to its end first. */
 int curdle_stat_check_paths(unsigned long long out[2]);
