@@ -128,6 +128,9 @@ int init_locked(Ctx& cx, int device) {
     HIP_TRY(hipEventCreateWithFlags(&s.pre_done, hipEventDisableTiming));
   }
   for (auto& bc : cx.bcache) HIP_TRY(hipEventCreateWithFlags(&bc.ready, hipEventDisableTiming));
+  // the batched transcripts' stream, after every other one: the streams before it keep their place in the order
+  HIP_TRY(hipStreamCreateWithPriority(&cx.tr.stream, hipStreamNonBlocking, prio_least));
+  for (hipEvent_t& e : cx.tr.ev) HIP_TRY(hipEventCreate(&e));
   cx.prio_greatest = prio_greatest;
   cx.prio_least = prio_least;
   cx.device = device;
@@ -214,6 +217,29 @@ void teardown_locked(Ctx& C) {
     d.copy_stream = nullptr;
     if (d.decoded) (void)hipEventDestroy(d.decoded);
     d.decoded = nullptr;
+  }
+  {
+    TrCtx& T = C.tr;
+    if (T.stream) {
+      (void)hipStreamSynchronize(T.stream);
+      (void)hipStreamDestroy(T.stream);
+    }
+    T.stream = nullptr;
+    for (hipEvent_t& e : T.ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+    for (Buf* b : {&T.d_in, &T.d_out}) {
+      if (b->p) (void)hipFree(b->p);
+      b->p = nullptr;
+      b->cap = 0;
+    }
+    if (T.h_in) (void)hipHostFree(T.h_in);
+    T.h_in = nullptr;
+    T.h_in_cap = 0;
+    if (T.h_out) (void)hipHostFree(T.h_out);
+    T.h_out = nullptr;
+    T.h_out_cap = 0;
   }
   for (Slot& S : C.slots) {
     if (S.stream) (void)hipStreamSynchronize(S.stream);
@@ -382,6 +408,7 @@ extern "C" int curdle_shutdown(void) {
     for (DSlot& d : C.dslots)
       if (d.busy) return fail(CURDLE_EBUSY, "a point decoding is still in flight");
     if (C.pending_uploads > 0) return fail(CURDLE_EBUSY, "a resident base set is still being uploaded");
+    if (C.tr.busy) return fail(CURDLE_EBUSY, "a transcript batch is still in flight");
   }
   for (int i = 0; i < have; i++) {
     Ctx& C = g_ctxs[i];

@@ -137,11 +137,29 @@ struct DSlot {
   uint32_t n = 0;
 };
 
+// What curdle_transcript_batch (transcript_api.hip) runs on: a stream and buffers of its own, so that it takes
+// neither an MSM slot nor a decode context and a holder of those may call it.  The stream and the events are made
+// at init (no stream is created later); the buffers only grow.  One call at a time:
+// `busy` under the context's mutex, waiters on `cv`.
+struct TrCtx {
+  std::condition_variable cv;
+  bool busy = false;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the kernel (curdle_transcript_last_kernel_ms)
+  Buf d_in, d_out;                        // tape | start states | rows;  challenges | states | status
+  void* h_in = nullptr;                   // pinned staging of d_in and of d_out
+  size_t h_in_cap = 0;
+  void* h_out = nullptr;
+  size_t h_out_cap = 0;
+  float last_ms = 0;
+};
+
 struct DevWorker;
 struct Ctx {
   std::mutex mu;
   std::condition_variable cv;
   DSlot dslots[kMaxDeferred];
+  TrCtx tr;
   std::atomic<bool> dstreams_ready{false};  // the decode contexts' streams exist (published with release / acquire)
   bool inited = false;
   int device = 0;   // HIP device id

@@ -217,6 +217,25 @@ hipError_t launch_g1_decompress(const uint8_t* in, uint32_t n, int subgroup_chec
 hipError_t launch_g1_check_affine(const uint32_t* pts, uint32_t n, int subgroup_check, uint8_t* status, hipStream_t stream);
 hipError_t launch_g1_check_jac(const uint32_t* pts, uint32_t n, int subgroup_check, uint8_t* status, hipStream_t stream);
 
+// transcript_kernels.hip: one compiled transcript program (host/transcript_batch.h) over k members, `mpw` members
+// on the first lanes of every wave.  Device pointers; rows, states and challenges are 8-byte aligned.
+namespace transcript {
+struct TapeCtl;
+struct TapeBlock;
+}  // namespace transcript
+struct TranscriptArgs {
+  const transcript::TapeCtl* ctl;
+  const transcript::TapeBlock* pool;
+  const uint64_t* data;   // k rows of row_words u64 (transcript::TapeRowWords)
+  const uint64_t* init;   // member m starts from init + m * init_stride: 25 state lanes
+  uint64_t* challenges;   // k x n_challenges x 4
+  uint64_t* states;       // k x 26, or null
+  uint8_t* status;        // k
+  uint64_t tail;          // pos | pos_begin << 8 | cur_flags << 16 after the program
+  uint32_t n_ctl, row_words, init_stride, k, mpw, n_challenges;
+};
+hipError_t launch_transcript_batch(const TranscriptArgs& args, hipStream_t stream);
+
 // The subgroup test straight from the n compressed records, without their square roots (so it
 // can run beside launch_g1_decompress(..., subgroup_check = 0, ...)): sub[i] = 0 iff record i,
 // if it decodes to a point at all, is not in the prime-order subgroup.

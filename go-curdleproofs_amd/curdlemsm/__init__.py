@@ -73,6 +73,7 @@ SYMBOLS = [
     "curdle_g1_check_batch", "curdle_g1_check_batch_device", "curdle_verify_checked", "curdle_verify_proof_checked",
     "curdle_stat_check_paths",
     "curdle_g1_check_jac_batch", "curdle_g1_check_jac_batch_device", "curdle_verify_batch_checked", "curdle_stat_batch_checked",
+    "curdle_transcript_batch", "curdle_transcript_batch_host", "curdle_stat_transcript", "curdle_transcript_last_kernel_ms",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -905,6 +906,69 @@ def stat_batch_checked() -> dict:
     out = (C.c_ulonglong * 3)()
     _check(_stat_batch_checked(out))
     return {"batches": out[0], "rejected": out[1], "chunks": out[2]}
+
+
+# ---- batched Merlin transcripts (curdle_transcript_batch / _host) ----
+TRANSCRIPT_STATE_SIZE = 208
+TR_APPEND, TR_CHALLENGES = 1, 2
+TRANSCRIPT_MAX_TRIES = 256
+TRANSCRIPT_MAX_MEMBERS, TRANSCRIPT_MAX_BYTES, TRANSCRIPT_MAX_CHALLENGES, TRANSCRIPT_MAX_MESSAGES = 65536, 1 << 20, 4096, 65536
+
+
+class _TranscriptStep(C.Structure):      # curdle_transcript_step
+    _fields_ = [("op", C.c_uint32), ("count", C.c_uint32), ("len", C.c_uint32), ("label_len", C.c_uint32), ("label", C.c_char * 32)]
+
+
+_tr_args = (C.c_char_p, _vp, C.POINTER(_TranscriptStep), C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp)
+_transcript_batch = _sig("curdle_transcript_batch", C.c_int, *_tr_args)
+_transcript_batch_host = _sig("curdle_transcript_batch_host", C.c_int, *_tr_args, C.c_int)
+_stat_transcript = _sig("curdle_stat_transcript", C.c_int, C.POINTER(C.c_ulonglong))
+_transcript_last_kernel_ms = _sig("curdle_transcript_last_kernel_ms", C.c_int, C.POINTER(C.c_double))
+
+
+def transcript_steps(program):
+    """program: [(op, label: bytes, count, len)] -> (curdle_transcript_step array, bytes a member's program reads,
+    challenges per member).  Nothing is checked here: the library refuses what is malformed."""
+    steps = (_TranscriptStep * max(1, len(program)))()
+    consumed = n_ch = 0
+    for s, (op, label, count, ln) in zip(steps, program):
+        s.op, s.count, s.len, s.label_len = op, count, ln, len(label)
+        s.label = bytes(label[:32])
+        consumed += count * ln if op == TR_APPEND else 0
+        n_ch += count if op == TR_CHALLENGES else 0
+    return steps, consumed, n_ch
+
+
+def transcript_batch(program, data, label=None, init_states=None, want_states=True, host=False, nthreads=1, data_stride=None):
+    """curdle_transcript_batch (host=True: curdle_transcript_batch_host on nthreads threads): the program
+    [(TR_APPEND | TR_CHALLENGES, label, count, len)] over the k rows of `data` (k x stride uint8; a fresh transcript
+    `label` for every member, or k exported states in init_states).  Returns (challenges k x n x 32 big-endian bytes,
+    states k x 208 or None, status k)."""
+    steps, _, n_ch = transcript_steps(program)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    k = data.shape[0]
+    stride = data.shape[1] if data_stride is None else data_stride
+    init = None if init_states is None else np.ascontiguousarray(init_states, dtype=np.uint8)
+    ch = np.zeros((k, n_ch, 32), dtype=np.uint8)
+    st = np.zeros((k, TRANSCRIPT_STATE_SIZE), dtype=np.uint8) if want_states else None
+    status = np.zeros(k, dtype=np.uint8)
+    args = (label, None if init is None else _ptr(init), steps, len(program), _ptr(data) if data.size else None, stride, k,
+            _ptr(ch) if ch.size else None, None if st is None else _ptr(st), _ptr(status))
+    _check(_transcript_batch_host(*args, nthreads) if host else _transcript_batch(*args))
+    return ch, st, status
+
+
+def stat_transcript() -> dict:
+    """Members hashed on the device since the library was loaded, and members handed back with a non-zero status."""
+    out = (C.c_ulonglong * 2)()
+    _check(_stat_transcript(out))
+    return {"members": out[0], "handed_back": out[1]}
+
+
+def transcript_last_kernel_ms() -> float:
+    out = C.c_double()
+    _check(_transcript_last_kernel_ms(C.byref(out)))
+    return out.value
 
 
 # ---- whisk package (whisk/whisk.go, whisk/types.go): trackers are 96-byte strings rG || krG ----

@@ -1246,6 +1246,9 @@ Proof Prove(const CRS& crs, const std::vector<G1Affine>& Rs, const std::vector<G
 // false = a direct (non-accumulated) check already failed.  Every AccumulateCheck of the
 // sub-arguments goes to `sink`.
 VerifyPrelude::VerifyPrelude() : tr(kTranscript) {}
+const char* const kPreludeTranscript = "curdleproofs";
+const char* const kPreludeStep1 = "curdleproofs_step1";
+const char* const kPreludeVecA = "curdleproofs_vec_a";
 
 void StartVerify(VerifyPrelude& pre, size_t ell, const uint8_t* Rb, const uint8_t* Sb, const uint8_t* Tb, const uint8_t* Ub,
                  const uint8_t Mb[48]) {

@@ -392,6 +392,10 @@ bool Verify(const Proof& proof, const CRS& crs, const std::vector<G1Affine>& Rs,
 // caller that still waits for the GPU to decode the proof runs them meanwhile
 // (curdle_verify, IsValidWhiskShuffleProof).  The encodings are kept: the same-multiscalar
 // argument absorbs Ts and Us a second time.
+// its transcript and labels (curdleproof.go:19-21), for a caller that hashes preludes in a batch
+extern const char* const kPreludeTranscript;
+extern const char* const kPreludeStep1;
+extern const char* const kPreludeVecA;
 struct VerifyPrelude {
   transcript::Transcript tr;
   std::vector<Scalar> as;

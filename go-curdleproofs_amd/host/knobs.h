@@ -42,6 +42,8 @@ enum Id {
   HOST_FOLD,          // 0: chunked host-buffer MSMs keep every chunk's fragments for the one reduction (no progressive folding)
   MAX_LARGE,          // test hook: caps the plan's large-bucket queue (max_large = min(plan, value), at least 1), so a test can overflow it
   BATCH_CHECKERS,     // checked batch verification: producer threads of the point check
+  TRANSCRIPT_LANES,   // curdle_transcript_batch: members per wave (1..64); unset: by the batch's size
+  GPU_PRELUDE,        // 1: the Whisk batch verifier takes its members' transcript preludes from curdle_transcript_batch, a chunk at a time; unset or 0: on the host
   COUNT
 };
 // The knob's value, or -1 if it is not set (every knob's valid values are >= 0).

@@ -23,6 +23,14 @@ namespace transcript {
 class Strobe128 {
  public:
   explicit Strobe128(const std::string& protocol_label);
+  // Export / import of (state, pos, pos_begin, cur_flags) in CURDLE_TRANSCRIPT_STATE_SIZE = 208 bytes: the 200
+  // state bytes, the three position bytes, five zero bytes.  What makes a batched transcript continuable
+  // (curdle_transcript_batch, transcript_batch.h); the caller has checked pos < 166 and pos_begin <= 166.
+  struct Exported {
+    const uint8_t* bytes;
+  };
+  explicit Strobe128(Exported e);
+  void Export(uint8_t out[208]) const;
   void MetaAd(const uint8_t* data, size_t len, bool more);
   void Ad(const uint8_t* data, size_t len, bool more);
   void Prf(uint8_t* out, size_t len, bool more);
@@ -40,6 +48,8 @@ class Strobe128 {
 class Merlin {
  public:
   explicit Merlin(const std::string& label);
+  explicit Merlin(Strobe128::Exported e) : strobe_(e) {}
+  void Export(uint8_t out[208]) const { strobe_.Export(out); }
   void AppendMessage(const std::string& label, const uint8_t* msg, size_t len);
   void ChallengeBytes(const std::string& label, uint8_t* out, size_t len);
 
@@ -51,6 +61,7 @@ class Merlin {
 class Transcript {
  public:
   explicit Transcript(const std::string& label) : inner_(label) {}               // New, :15
+  explicit Transcript(Strobe128::Exported e) : inner_(e) {}                      // a transcript continued from an exported state
   void AppendPoints(const std::string& label, const std::vector<alg::Point>& points);  // :25
   void AppendPoint(const std::string& label, const alg::Point& p);
   void AppendPointsAffine(const std::string& label, const std::vector<G1Affine>& points);  // :32

@@ -3,6 +3,7 @@
 #include "whisk.h"
 
 #include <chrono>
+#include <future>
 #include <memory>
 
 #include "verify_batch_impl.h"
@@ -11,6 +12,13 @@
 
 #include <stdexcept>
 #include <string>
+
+// The batched transcripts live in the GPU backend (csrc/transcript_api.hip).  Weak here, as device_accumulator.cpp names
+// the member form: a backend without them -- the host layer linked over a plain CPU backend, as the sanitizer builds
+// are -- still links, and the batch keeps the host prelude.
+extern "C" int curdle_transcript_batch(const char* transcript_label, const uint8_t* init_states, const curdle_transcript_step* steps,
+                                       size_t n_steps, const uint8_t* data, size_t data_stride, size_t k, uint8_t* challenges,
+                                       uint8_t* states, uint8_t* status) __attribute__((weak));
 
 namespace curdle {
 namespace whisk {
@@ -196,10 +204,79 @@ std::vector<int> IsValidWhiskShuffleProofBatch(const proto::CRS& crs, const std:
     const std::vector<ShuffleBatchItem>& items;
     std::vector<size_t> first_point, first_tracker;
     std::vector<char> parses;
+    // Knob GPU_PRELUDE: the preludes (curdleproof.go:217-224) of a decode-ahead chunk's members from ONE
+    // curdle_transcript_batch, started on a thread of its own when the chunk's first proof is registered and waited
+    // for by the worker that verifies a member.  rc: CURDLE_EINVAL is a refusal of the call's shape (host prelude
+    // instead), any other failure a device failure (an MsmError, never a verdict).
+    struct PreludeChunk {
+      size_t first = 0, count = 0, n = 0;
+      int rc = CURDLE_OK;
+      std::string error;
+      std::vector<uint8_t> data, challenges, states, status;
+      std::shared_future<void> done;
+    };
+    const bool gpu_prelude = knobs::get(knobs::GPU_PRELUDE) > 0 && curdle_transcript_batch != nullptr;
+    const int device = curdle_get_device();
+    size_t chunk = 0;
+    std::vector<std::unique_ptr<PreludeChunk>> pchunks;  // destroyed after `ahead`, whose producers write it
     std::unique_ptr<proto::DecodeAhead> ahead;
     explicit Source(const std::vector<ShuffleBatchItem>& it)
         : items(it), first_point(it.size(), 0), first_tracker(it.size(), 0), parses(it.size(), 0) {}
+    void StartPrelude(size_t c) {
+      auto pc = std::make_unique<PreludeChunk>();
+      pc->first = c * chunk;
+      pc->count = std::min(chunk, items.size() - pc->first);
+      pc->n = items[pc->first].n;
+      for (size_t j = 0; j < pc->count; j++)
+        if (items[pc->first + j].n != pc->n) return;  // one program serves all members: this chunk stays on the host
+      if (pc->n == 0) return;
+      PreludeChunk* p = pc.get();
+      pc->done = std::async(std::launch::async, [this, p] {
+                   const size_t n = p->n, row = 48 * (4 * n + 1);
+                   try {
+                     (void)curdle_set_device(device);
+                     p->data.resize(p->count * row);
+                     for (size_t j = 0; j < p->count; j++) {  // R | S | T | U, then M: the proof's first record
+                       const ShuffleBatchItem& it = items[p->first + j];
+                       uint8_t* b = &p->data[j * row];
+                       for (size_t t = 0; t < n; t++) {
+                         memcpy(b + 48 * t, it.preST[t].rG, 48);
+                         memcpy(b + 48 * (n + t), it.preST[t].krG, 48);
+                         memcpy(b + 48 * (2 * n + t), it.postST[t].rG, 48);
+                         memcpy(b + 48 * (3 * n + t), it.postST[t].krG, 48);
+                       }
+                       memcpy(b + 192 * n, it.proof, 48);
+                     }
+                     p->challenges.resize(p->count * n * 32);
+                     p->states.resize(p->count * CURDLE_TRANSCRIPT_STATE_SIZE);
+                     p->status.assign(p->count, 0);
+                     curdle_transcript_step steps[2];
+                     memset(steps, 0, sizeof(steps));
+                     steps[0].op = CURDLE_TR_APPEND;
+                     steps[0].count = (uint32_t)(4 * n + 1);
+                     steps[0].len = 48;
+                     steps[0].label_len = (uint32_t)strlen(proto::kPreludeStep1);
+                     memcpy(steps[0].label, proto::kPreludeStep1, steps[0].label_len);
+                     steps[1].op = CURDLE_TR_CHALLENGES;
+                     steps[1].count = (uint32_t)n;
+                     steps[1].label_len = (uint32_t)strlen(proto::kPreludeVecA);
+                     memcpy(steps[1].label, proto::kPreludeVecA, steps[1].label_len);
+                     p->rc = curdle_transcript_batch(proto::kPreludeTranscript, nullptr, steps, 2, p->data.data(), row, p->count,
+                                                     p->challenges.data(), p->states.data(), p->status.data());
+                     if (p->rc != CURDLE_OK) {
+                       char buf[256] = "";
+                       (void)curdle_last_error(buf, sizeof(buf));
+                       p->error = buf;
+                     }
+                   } catch (const std::exception& e) {
+                     p->rc = CURDLE_ENOMEM;
+                     p->error = e.what();
+                   }
+                 }).share();
+      pchunks[c] = std::move(pc);
+    }
     void Scan(size_t i, proto::PointDecoder& dec) {
+      if (gpu_prelude && i % chunk == 0) StartPrelude(i / chunk);
       first_point[i] = dec.size();
       try {
         proto::Reader scan(items[i].proof, WHISK_SHUFFLE_PROOF_SIZE, true);
@@ -231,8 +308,23 @@ std::vector<int> IsValidWhiskShuffleProofBatch(const proto::CRS& crs, const std:
       return proto::Proof::FromReader(r);
     }
     // curdleproof.go:217-224 from the trackers' own bytes (a valid record is its point's encoding)
-    bool Prelude(size_t i, proto::VerifyPrelude& pre) const {
+    bool Prelude(size_t i, proto::VerifyPrelude& pre) {
       const size_t n = items[i].n;
+      if (PreludeChunk* pc = gpu_prelude ? pchunks[i / chunk].get() : nullptr) {
+        pc->done.wait();
+        if (pc->rc != CURDLE_OK && pc->rc != CURDLE_EINVAL) throw alg::MsmError("hashing the batch's preludes: " + pc->error, pc->rc);
+        const size_t j = i - pc->first;
+        if (pc->rc == CURDLE_OK && pc->status[j] == 0) {
+          const uint8_t* b = &pc->data[j * 48 * (4 * n + 1)];
+          pre.tr = transcript::Transcript(transcript::Strobe128::Exported{&pc->states[j * CURDLE_TRANSCRIPT_STATE_SIZE]});
+          pre.as.resize(n);
+          for (size_t t = 0; t < n; t++)
+            if (!Scalar::SetBytesCanonical(&pc->challenges[(j * n + t) * 32], &pre.as[t])) throw err("a batched challenge is not canonical");
+          pre.Tb.assign(b + 96 * n, b + 144 * n);
+          pre.Ub.assign(b + 144 * n, b + 192 * n);
+          return true;
+        }
+      }
       std::vector<uint8_t> b(4 * n * G1POINT_SIZE);
       for (size_t t = 0; t < n; t++) {
         memcpy(&b[48 * t], items[i].preST[t].rG, 48);
@@ -264,6 +356,8 @@ std::vector<int> IsValidWhiskShuffleProofBatch(const proto::CRS& crs, const std:
   const auto t0 = std::chrono::steady_clock::now();
   const size_t points_per_proof = k ? WHISK_SHUFFLE_PROOF_SIZE / 48 + 4 * items[0].n : 0;  // an upper bound
   const size_t chunk = proto::DecodeAheadChunk(k, points_per_proof);
+  src.chunk = chunk;
+  src.pchunks.resize((k + chunk - 1) / chunk);
   src.ahead = std::make_unique<proto::DecodeAhead>(k, chunk, proto::DecodeAheadProducers(),
                                                    [&src](size_t i, proto::PointDecoder& dec) { src.Scan(i, dec); });
   std::vector<int> oks;

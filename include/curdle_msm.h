@@ -651,6 +651,74 @@ int curdle_stat_batch_checked(unsigned long long out[3]);
 /* Diagnostics: checked verifications since the library was loaded whose point check out[0] ran on a decode
  * context beside the verification, out[1] found every decode context taken and ran to its end first. */
 int curdle_stat_check_paths(unsigned long long out[2]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Batched Merlin transcripts.  ONE program of transcript operations runs over k members, each with
+ * its own data: the part of a batch's Fiat-Shamir hashing that depends on input bytes only (the
+ * verifier's prelude, curdleproof.go:217-224: 4 ell + 1 encodings appended, ell challenges drawn) is
+ * the same program for every proof.  On the device (csrc/transcript_kernels.hip) every member's
+ * STROBE-128 state lives in one lane's registers; the positions of the sponge depend on the program
+ * alone, so the host compiles the program once per call into constants per rate word.
+ *
+ * A program is a list of steps:
+ *   CURDLE_TR_APPEND      `count` messages of `len` bytes each under `label`, taken in order from the
+ *                         member's data: Merlin's AppendMessage, which is what the reference's
+ *                         AppendPoints (48-byte encodings) and AppendScalars (32 big-endian bytes)
+ *                         do (transcript.go:32-46).
+ *   CURDLE_TR_CHALLENGES  `count` times GetAndAppendChallenge(label) (transcript.go:48-58): 32
+ *                         challenge bytes read as a big-endian integer, drawn again until it is
+ *                         canonical (< r; equal to r is a rejection), then re-appended under the same
+ *                         label.  Each writes its 32 big-endian bytes to the member's output.
+ * Member i reads its messages back to back from data + i * data_stride and writes challenge j of the
+ * program to challenges + (i * n_challenges + j) * 32.
+ *
+ * Exactly one of transcript_label (a fresh transcript.New(label) for every member, transcript.go:15)
+ * and init_states (k exported states, CURDLE_TRANSCRIPT_STATE_SIZE bytes each) is given.  `states`,
+ * if not NULL, receives every member's state after the program: the 200 STROBE state bytes, pos,
+ * pos_begin, cur_flags and five zero bytes.  A state exported by either entry point continues in
+ * either, so a program run whole equals the same program run as two calls.  The states of one call
+ * must agree in pos, pos_begin and cur_flags (they do when they come from one earlier call).
+ *
+ * status[i] != 0: member i drew CURDLE_TRANSCRIPT_MAX_TRIES non-canonical values for one challenge
+ * (probability 0.547^256); its challenges and state are then unspecified.  Every wait is bounded.
+ *
+ * CURDLE_EINVAL, before anything is copied or launched: an unknown op, label_len > 32, data_stride
+ * below the bytes the program reads, both or neither of transcript_label and init_states, a limit
+ * below exceeded, a null pointer that the call would use, states that are not exported states or
+ * disagree in position.  k = 0 is CURDLE_OK.
+ *
+ * curdle_transcript_batch runs on the calling thread's device, on a stream and buffers of its own
+ * (made at curdle_init; it takes neither an MSM workspace slot nor a decode context, so a caller may
+ * hold those meanwhile), concurrent calls one behind the other.  Without a device it fails with
+ * CURDLE_ENODEV: there is no fallback.  curdle_transcript_batch_host runs the same program through
+ * the host's Transcript on nthreads threads and needs no device: the twin that tests and
+ * measurements compare against. */
+#define CURDLE_TRANSCRIPT_STATE_SIZE 208
+#define CURDLE_TR_APPEND 1
+#define CURDLE_TR_CHALLENGES 2
+#define CURDLE_TRANSCRIPT_MAX_TRIES 256
+#define CURDLE_TRANSCRIPT_MAX_MEMBERS 65536     /* k */
+#define CURDLE_TRANSCRIPT_MAX_BYTES 1048576     /* bytes one member's program reads */
+#define CURDLE_TRANSCRIPT_MAX_CHALLENGES 4096   /* challenges per member */
+#define CURDLE_TRANSCRIPT_MAX_MESSAGES 65536    /* steps, and messages + challenges per member */
+#define CURDLE_TRANSCRIPT_MAX_TOTAL 1073741824  /* device entry point: k x (bytes per member + 16) */
+typedef struct {
+  uint32_t op, count, len, label_len; /* len: CURDLE_TR_APPEND only */
+  char label[32];
+} curdle_transcript_step;
+int curdle_transcript_batch(const char* transcript_label, const uint8_t* init_states, const curdle_transcript_step* steps,
+                            size_t n_steps, const uint8_t* data, size_t data_stride, size_t k, uint8_t* challenges,
+                            uint8_t* states, uint8_t* status);
+int curdle_transcript_batch_host(const char* transcript_label, const uint8_t* init_states,
+                                 const curdle_transcript_step* steps, size_t n_steps, const uint8_t* data,
+                                 size_t data_stride, size_t k, uint8_t* challenges, uint8_t* states, uint8_t* status,
+                                 int nthreads);
+/* Diagnostics: out[0] members hashed on the device since the library was loaded, out[1] members handed back
+ * with a non-zero status. */
+int curdle_stat_transcript(unsigned long long out[2]);
+/* Diagnostics: the kernel of the calling thread's device's last curdle_transcript_batch alone, by HIP events, in ms
+ * (0 before the first call). */
+int curdle_transcript_last_kernel_ms(double* out);
 int curdle_set_last_error(int code, const char* msg);  /* internal: shared by the library's translation units */
 
 /* ------------------------------------------------------------------------- *
