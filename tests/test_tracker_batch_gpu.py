@@ -96,8 +96,11 @@ def pool(gpu, oracle):
     R = oracle.R
     cases = {}
     # exceptional group cases inside the chain: all accepted
-    cases["k=1"] = (honest(gpu, oracle, 1, 5, 201)[0], 1)          # kG = G: the table's sum is a doubling
-    cases["k=r-1"] = (honest(gpu, oracle, R - 1, 7, 202)[0], 1)    # kG = -G: the sum is infinity
+    # kG = +-G: the chain's running sum CAN meet the next addend or its negative, but only where the leading bits and
+    # signs of the halves of s and c line up, which one seed leaves to chance (the tables' own sums P + phi(P) never
+    # degenerate); tests/test_tracker_chain_events_gpu.py has members chosen for those branches
+    cases["k=1"] = (honest(gpu, oracle, 1, 5, 201)[0], 1)          # kG = G, krG = rG
+    cases["k=r-1"] = (honest(gpu, oracle, R - 1, 7, 202)[0], 1)    # kG = -G, krG = -rG
     cases["k=0"] = (honest(gpu, oracle, 0, 9, 203)[0], 1)          # kG, krG at infinity
     cases["r=1"] = (honest(gpu, oracle, 11, 1, 204)[0], 1)         # rG = G
     cases["tracker=inf"] = (honest(gpu, oracle, 13, 0, 205)[0], 1)  # rG = krG = inf: B = B' = inf
