@@ -413,6 +413,9 @@ struct CheckJob {
 int check_start(CheckJob& job, const uint64_t* const* vecs, const size_t* lens, int nvec, int subgroup_check);
 int check_collect(CheckJob& job);
 
+// --- transcript_api.hip ------------------------------------------------------
+uint32_t members_per_wave(size_t k);  // the transcript kernel's launch rule, shared with the tracker batch
+
 // --- dbases_api.hip ----------------------------------------------------------
 void dbases_release_handle(struct ::curdle_dbases* b);
 }  // namespace curdle_api

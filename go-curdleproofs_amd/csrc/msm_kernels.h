@@ -262,5 +262,15 @@ hipError_t launch_scalar_mul_batch(const void* points, const void* scalars, int 
 static constexpr uint8_t kTrackerReject = 0, kTrackerAccept = 1, kTrackerError = 2;  // error: a record did not decode, or skip
 hipError_t launch_tracker_check(const void* points, const uint8_t* status, const void* scalars, const uint8_t* skip,
                                 const G1Affine& gen, uint32_t n, uint8_t* out, hipStream_t stream);
+// The device-hashed form's two small kernels.  Gather: n members of the caller's three arrays (96, 48 and 128 bytes
+// each, any alignment) -> rec: 5 n compressed records (rG, krG, kG, A, B); rows: n transcript rows of
+// TapeRowWords(288) u64 (8 zero bytes | kG g1Gen krG rG A B | 8 zero bytes; gen: the generator's 48-byte encoding,
+// 8-byte aligned); scalars + 16 i: S as eight little-endian words (zero where S >= r) and skip[i] = (S >= r).
+// Challenge: the transcript kernel's 32 big-endian bytes of member i -> scalars + 16 i + 8; a member with a
+// non-zero tr_status gets zero scalars and skip[i] = 1.  rec, rows, scalars and challenges are 16-byte aligned.
+hipError_t launch_tracker_gather(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t* proofs, const void* gen,
+                                 uint32_t n, void* rec, void* rows, void* scalars, uint8_t* skip, hipStream_t stream);
+hipError_t launch_tracker_challenge(const void* challenges, const uint8_t* tr_status, uint32_t n, void* scalars,
+                                    uint8_t* skip, hipStream_t stream);
 
 }  // namespace curdle

@@ -1,7 +1,7 @@
-// C ABI of the batched Whisk tracker-proof check (tracker_kernels.hip): curdle_whisk_is_valid_tracker_proof_batch,
-// k calls of IsValidWhiskTrackerProof (the reference's whisk/whisk.go:116-147) in one.
+// C ABI of the batched Whisk tracker-proof check (tracker_kernels.hip): curdle_whisk_is_valid_tracker_proof_batch
+// (_ex, _device), k calls of IsValidWhiskTrackerProof (the reference's whisk/whisk.go:116-147) in one.
 //
-// Per pass of at most kTrackerPass members, on the calling thread's context:
+// Two forms.  HOST-HASHED (tracker_pass), per pass of at most kTrackerPass members, on the calling thread's context:
 //   1. the 5 k records (rG, krG, kG, A, B per member) go up once; the square roots (launch_g1_decompress) run on
 //      the held slot's stream and the subgroup test from the same bytes (launch_g1_subgroup_from_bytes) beside it
 //      on a second slot's stream when one is free -- the two chains overlap, as in the two-step decoding;
@@ -11,16 +11,25 @@
 //      whatever was hashed);
 //   3. s and c go up, k_tracker_check runs behind the square roots, and k + 10 k bytes come back: the verdicts,
 //      the decoding statuses and the subgroup verdicts.
+// DEVICE-HASHED (tracker_pass_device): from bytes to verdicts with no host arithmetic and no host thread.  The three
+// arrays go up as they are (or are read where the caller keeps them: _device) behind the constant tape of the
+// transcript program; k_tracker_gather writes the records, the transcript rows and S / skip; the transcript kernel
+// (launch_transcript_batch, the tape compiled once per process) and the subgroup test run on the second slot's stream
+// beside the square roots; k_tracker_challenge puts c next to s, k_tracker_check runs as above.  Tape, start state,
+// rows and challenges live in the held slot's buffers: the transcript context (TrCtx) and its lock are not touched.
 // No stream is made here and no device memory is allocated once the slots' buffers have grown to the batch.
 #include "msm_internal.h"
 
 #include <algorithm>
 #include <exception>
+#include <stdexcept>
 
 #include "../host/algebra.h"
 #include "../host/transcript.h"
+#include "../host/transcript_batch.h"
 
 namespace {
+std::atomic<unsigned long long> g_tk_stat[3];  // members hashed on the device | on the host | handed back to the host
 
 constexpr size_t kRec = 48;                  // one compressed G1 record
 constexpr size_t kTrackerPass = (size_t)1 << 16;  // members per pass: 327,680 records, 31 MB of decoded points
@@ -46,13 +55,15 @@ bool member_scalars(const uint8_t* tracker, const uint8_t* k_comm, const uint8_t
   return true;
 }
 
+struct Gen {
+  uint8_t b[kRec];
+  Gen() { curdle::alg::Point::Generator().Compressed(b); }
+};
+
 // scalars / skip of members [0, m) of the pass, on up to kMaxHashThreads host threads
 void hash_members(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t* proofs, size_t m, uint32_t* sc,
                   uint8_t* skip) {
-  static const struct Gen {
-    uint8_t b[kRec];
-    Gen() { curdle::alg::Point::Generator().Compressed(b); }
-  } gen;
+  static const Gen gen;
   auto run = [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; i++) {
       const bool ok = member_scalars(trackers + 96 * i, k_comms + kRec * i, proofs + 128 * i, gen.b, sc + 16 * i);
@@ -145,24 +156,173 @@ int tracker_pass(Ctx& cx, Slot& A, Slot* B, const uint8_t* trackers, const uint8
       return fail(CURDLE_EHIP, "tracker check: member %zu of a pass has no verdict", i);
     }
   }
+  g_tk_stat[1].fetch_add(m, std::memory_order_relaxed);
   return CURDLE_OK;
 }
 
-}  // namespace
+// The constant part of the device-hashed form, compiled once per process: the tape of
+//   Transcript("whisk_opening_proof"); AppendPoints("tracker_opening_proof", kG g1Gen krG rG A B);
+//   GetAndAppendChallenge("tracker_opening_proof_challenge")                                  (whisk.go:15-17, 131-134)
+// as one block of bytes, control list | block pool | start state | the generator's encoding, padded to 16.
+struct TrackerTape {
+  std::vector<uint8_t> bytes;
+  size_t pool_off = 0, init_off = 0, gen_off = 0;
+  uint32_t n_ctl = 0;
+  uint64_t tail = 0;
+  TrackerTape() {
+    using namespace curdle::transcript;
+    auto step = [](uint32_t op, uint32_t count, uint32_t len, const char* label) {
+      curdle_transcript_step s = {};
+      s.op = op, s.count = count, s.len = len, s.label_len = (uint32_t)strlen(label);
+      memcpy(s.label, label, s.label_len);
+      return s;
+    };
+    const curdle_transcript_step steps[2] = {step(CURDLE_TR_APPEND, 6, kRec, "tracker_opening_proof"),
+                                             step(CURDLE_TR_CHALLENGES, 1, 0, "tracker_opening_proof_challenge")};
+    uint8_t init[CURDLE_TRANSCRIPT_STATE_SIZE];
+    Transcript("whisk_opening_proof").inner().Export(init);
+    Tape tape;
+    CompileTape(steps, 2, init + 200, &tape);
+    if (tape.consumed != 6 * kRec || tape.n_challenges != 1) throw std::logic_error("tracker tape");
+    const size_t ctl_bytes = tape.ctl.size() * sizeof(TapeCtl), pool_bytes = tape.pool.size() * sizeof(TapeBlock);
+    pool_off = ctl_bytes;
+    init_off = pool_off + pool_bytes;
+    gen_off = init_off + sizeof(init);
+    bytes.assign((gen_off + kRec + 15) / 16 * 16, 0);
+    memcpy(bytes.data(), tape.ctl.data(), ctl_bytes);
+    memcpy(bytes.data() + pool_off, tape.pool.data(), pool_bytes);
+    memcpy(bytes.data() + init_off, init, sizeof(init));
+    memcpy(bytes.data() + gen_off, Gen().b, kRec);
+    n_ctl = (uint32_t)tape.ctl.size();
+    tail = (uint64_t)tape.pos | ((uint64_t)tape.pos_begin << 8) | ((uint64_t)tape.cur_flags << 16);
+  }
+};
+constexpr size_t kRowBytes = 8 * (2 + 6 * kRec / 8);  // transcript::TapeRowWords(288) words
 
-extern "C" int curdle_whisk_is_valid_tracker_proof_batch(const uint8_t* trackers, const uint8_t* k_commitments,
-                                                         const uint8_t* proofs, size_t k, int* results) {
-  if (k == 0) return CURDLE_OK;
+// One device-hashed pass.  `resident`: the three arrays are device pointers, read where they are.  `sa` is the
+// stream the pass runs on: the held slot's, or the caller's (then B is null and everything runs on that stream).
+int tracker_pass_device(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8_t* trackers, const uint8_t* k_comms,
+                        const uint8_t* proofs, bool resident, size_t m, int* results) {
+  static const TrackerTape T;
+  const size_t nrec = 5 * m, tape_bytes = T.bytes.size(), raw_bytes = resident ? 0 : 272 * m;
+  int r;
+  if ((r = ensure(A.scalars, nrec * kRec))) return r;     // compressed records
+  if ((r = ensure(A.points, nrec * 96))) return r;        // decoded records
+  if ((r = ensure(A.counts, 2 * nrec + 2 * m))) return r;  // statuses | subgroup verdicts | member verdicts | transcript statuses
+  if ((r = ensure(A.digits, 64 * m + m))) return r;       // s, c | skip
+  if ((r = ensure(A.sorted, tape_bytes + raw_bytes + (kRowBytes + 32) * m))) return r;  // tape | the arrays | rows | challenges
+  if ((r = ensure_pinned(A, 0, tape_bytes + raw_bytes))) return r;
+  if ((r = ensure_pinned(A, 1, 2 * nrec + 2 * m))) return r;
+  uint8_t* h_in = static_cast<uint8_t*>(A.h_stage[0]);
+  uint8_t* h_out = static_cast<uint8_t*>(A.h_stage[1]);
+  uint8_t* d_tape = static_cast<uint8_t*>(A.sorted.p);
+  uint8_t* d_raw = d_tape + tape_bytes;
+  uint8_t* d_rows = d_raw + raw_bytes;
+  uint8_t* d_ch = d_rows + kRowBytes * m;
+  uint8_t* d_rec = static_cast<uint8_t*>(A.scalars.p);
+  uint8_t* d_status = static_cast<uint8_t*>(A.counts.p);
+  uint8_t* d_sub = d_status + nrec;
+  uint8_t* d_out = d_sub + nrec;
+  uint8_t* d_trst = d_out + m;
+  uint8_t* d_sc = static_cast<uint8_t*>(A.digits.p);
+  memcpy(h_in, T.bytes.data(), tape_bytes);
+  if (!resident) {  // as the caller laid them out: nothing is repacked
+    memcpy(h_in + tape_bytes, trackers, 96 * m);
+    memcpy(h_in + tape_bytes + 96 * m, k_comms, kRec * m);
+    memcpy(h_in + tape_bytes + 144 * m, proofs, 128 * m);
+    trackers = d_raw, k_comms = d_raw + 96 * m, proofs = d_raw + 144 * m;
+  }
+  HIP_TRY(hipMemcpyAsync(d_tape, h_in, tape_bytes + raw_bytes, hipMemcpyHostToDevice, sa));
+  HIP_TRY(launch_tracker_gather(trackers, k_comms, proofs, d_tape + T.gen_off, (uint32_t)m, d_rec, d_rows, d_sc, d_sc + 64 * m, sa));
+  TranscriptArgs ta = {};
+  ta.ctl = reinterpret_cast<const curdle::transcript::TapeCtl*>(d_tape);
+  ta.pool = reinterpret_cast<const curdle::transcript::TapeBlock*>(d_tape + T.pool_off);
+  ta.data = reinterpret_cast<const uint64_t*>(d_rows);
+  ta.init = reinterpret_cast<const uint64_t*>(d_tape + T.init_off);
+  ta.challenges = reinterpret_cast<uint64_t*>(d_ch);
+  ta.states = nullptr;
+  ta.status = d_trst;
+  ta.tail = T.tail;
+  ta.n_ctl = T.n_ctl;
+  ta.row_words = (uint32_t)(kRowBytes / 8);
+  ta.init_stride = 0;
+  ta.k = (uint32_t)m;
+  ta.mpw = members_per_wave(m);
+  ta.n_challenges = 1;
+  if (B) {  // transcripts, then the subgroup test, beside the square roots
+    HIP_TRY(hipEventRecord(A.pre_done, sa));
+    HIP_TRY(hipStreamWaitEvent(B->stream, A.pre_done, 0));
+    HIP_TRY(launch_transcript_batch(ta, B->stream));
+    HIP_TRY(hipEventRecord(B->pre_done, B->stream));
+    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, B->stream));
+    HIP_TRY(hipEventRecord(B->acc_done, B->stream));
+  }
+  HIP_TRY(launch_g1_decompress(d_rec, (uint32_t)nrec, 0, (uint32_t*)A.points.p, d_status, sa));
+  if (B) {
+    HIP_TRY(hipStreamWaitEvent(sa, B->pre_done, 0));
+  } else {
+    HIP_TRY(launch_transcript_batch(ta, sa));
+    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, sa));
+  }
+  HIP_TRY(launch_tracker_challenge(d_ch, d_trst, (uint32_t)m, d_sc, d_sc + 64 * m, sa));
+  G1Affine gen;
+  g1_generator(gen);
+  HIP_TRY(launch_tracker_check(A.points.p, d_status, d_sc, d_sc + 64 * m, gen, (uint32_t)m, d_out, sa));
+  if (B) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));
+  HIP_TRY(hipMemcpyAsync(h_out, d_status, 2 * nrec + 2 * m, hipMemcpyDeviceToHost, sa));
+  HIP_TRY(hipStreamSynchronize(sa));
+  const uint8_t* st = h_out;
+  const uint8_t* sub = h_out + nrec;
+  const uint8_t* verdict = h_out + 2 * nrec;
+  const uint8_t* trst = verdict + m;
+  unsigned long long handed_back = 0;
+  for (size_t i = 0; i < m; i++) {
+    if (trst[i]) {  // 256 rejected draws (0.547^256): the single call settles the member on the host
+      if (resident) return fail(CURDLE_EHIP, "tracker check: member %zu of a pass drew no canonical challenge", i);
+      int ok = 0;
+      const int rc = curdle_whisk_is_valid_tracker_proof(h_in + tape_bytes + 96 * i, h_in + tape_bytes + 96 * m + kRec * i,
+                                                         h_in + tape_bytes + 144 * m + 128 * i, &ok);
+      results[i] = rc ? rc : ok;
+      handed_back++;
+      continue;
+    }
+    bool err = verdict[i] == kTrackerError;  // S >= r, or a record that does not decode
+    for (size_t j = 5 * i; j < 5 * i + 5; j++) err |= st[j] > CURDLE_DECODE_INFINITY || (st[j] == CURDLE_DECODE_OK && !sub[j]);
+    if (err) {
+      results[i] = CURDLE_EINVAL;
+    } else if (verdict[i] == kTrackerAccept || verdict[i] == kTrackerReject) {
+      results[i] = verdict[i];
+    } else {
+      return fail(CURDLE_EHIP, "tracker check: member %zu of a pass has no verdict", i);
+    }
+  }
+  g_tk_stat[0].fetch_add(m - handed_back, std::memory_order_relaxed);
+  g_tk_stat[2].fetch_add(handed_back, std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+// Smallest batch whose transcripts CURDLE_TRACKER_HASH_DEFAULT hashes on the device (knob TRACKER_DEVICE_HASH unset):
+// the smallest measured k at which, on 16 CPUs, device hashing is not slower than the parent's host hashing by more
+// than the spread of the repetitions -- and it holds at every larger measured size too (DESIGN.md section 0;
+// profiles/r13_tracker_device_hash.json, default_rule_from_k).  Medians of 7, device against parent: k = 64 2.23
+// against 2.23 ms, 1,024 2.60 against 2.29 ms (inside the parent's 19 % spread there, but 0.3 ms behind its median),
+// 8,192 3.30 against 3.39 ms, 65,536 20.9 against 26.7 ms.
+constexpr size_t kDeviceHashFrom = 64;
+
+// The whole call: host arrays (hash_device chooses the form) or resident ones (always device-hashed).
+int tracker_batch(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t* proofs, size_t k, bool hash_device,
+                  bool resident, void* user_stream, int* results) {
   int rc = CURDLE_OK;
-  if (!trackers || !k_commitments || !proofs || !results) {
+  if (!trackers || !k_comms || !proofs || !results) {
     rc = fail(CURDLE_EINVAL, "null argument");
   } else {
     Ctx& cx = cur();
     int ia = -1, ib = -1;
     rc = acquire_slot(cx, true, &ia);
     if (rc == CURDLE_OK) {
-      // a second slot only lends its stream to the subgroup test; without one the test runs behind the square roots
-      {
+      // a second slot only lends its stream (and two events) to the subgroup test and the transcripts; without one
+      // they run behind the square roots.  A caller's stream carries the whole pass.
+      if (!user_stream) {
         std::lock_guard<std::mutex> g(cx.mu);
         for (int i = 0; i < kSlots && ib < 0; i++)
           if (!cx.slots[i].busy) {
@@ -174,23 +334,28 @@ extern "C" int curdle_whisk_is_valid_tracker_proof_batch(const uint8_t* trackers
       }
       Slot& A = cx.slots[ia];
       Slot* B = ib >= 0 ? &cx.slots[ib] : nullptr;
+      const hipStream_t sa = user_stream ? (hipStream_t)user_stream : A.stream;
       auto body = [&]() -> int {
         HIP_TRY(hipSetDevice(cx.device));
         for (size_t lo = 0; lo < k; lo += kTrackerPass) {
           const size_t m = std::min(kTrackerPass, k - lo);
-          const int r = tracker_pass(cx, A, B, trackers + 96 * lo, k_commitments + kRec * lo, proofs + 128 * lo, m,
-                                     results + lo);
+          const int r = hash_device ? tracker_pass_device(cx, A, B, sa, trackers + 96 * lo, k_comms + kRec * lo,
+                                                          proofs + 128 * lo, resident, m, results + lo)
+                                    : tracker_pass(cx, A, B, trackers + 96 * lo, k_comms + kRec * lo, proofs + 128 * lo, m,
+                                                   results + lo);
           if (r) return r;
         }
         return CURDLE_OK;
       };
       try {
         rc = body();
+      } catch (const std::logic_error& e) {  // the constant tape did not compile to the shape the kernels expect
+        rc = fail(CURDLE_EHIP, "tracker check: internal error: %s", e.what());
       } catch (const std::exception& e) {
         rc = fail(CURDLE_ENOMEM, "tracker check: %s", e.what());
       }
       if (rc) {  // nothing queued may outlive the slots' hold
-        (void)hipStreamSynchronize(A.stream);
+        (void)hipStreamSynchronize(sa);
         if (B) (void)hipStreamSynchronize(B->stream);
       }
       if (B) release_slot(cx, ib);
@@ -200,4 +365,41 @@ extern "C" int curdle_whisk_is_valid_tracker_proof_batch(const uint8_t* trackers
   if (rc != CURDLE_OK && results)  // "could not compute" must never read as a verdict
     for (size_t i = 0; i < k; i++) results[i] = rc;
   return rc;
+}
+
+}  // namespace
+
+extern "C" int curdle_whisk_is_valid_tracker_proof_batch_ex(const uint8_t* trackers, const uint8_t* k_commitments,
+                                                            const uint8_t* proofs, size_t k, unsigned flags, int* results) {
+  if (flags > CURDLE_TRACKER_HASH_DEVICE) {
+    const int rc = fail(CURDLE_EINVAL, "unknown flags %u", flags);
+    if (results)
+      for (size_t i = 0; i < k; i++) results[i] = rc;
+    return rc;
+  }
+  if (k == 0) return CURDLE_OK;
+  bool device = flags == CURDLE_TRACKER_HASH_DEVICE;
+  if (flags == CURDLE_TRACKER_HASH_DEFAULT) {
+    const long long knob = knobs::get(knobs::TRACKER_DEVICE_HASH);
+    device = knob < 0 ? k >= kDeviceHashFrom : knob != 0;
+  }
+  return tracker_batch(trackers, k_commitments, proofs, k, device, false, nullptr, results);
+}
+
+extern "C" int curdle_whisk_is_valid_tracker_proof_batch(const uint8_t* trackers, const uint8_t* k_commitments,
+                                                         const uint8_t* proofs, size_t k, int* results) {
+  return curdle_whisk_is_valid_tracker_proof_batch_ex(trackers, k_commitments, proofs, k, CURDLE_TRACKER_HASH_DEFAULT, results);
+}
+
+extern "C" int curdle_whisk_is_valid_tracker_proof_batch_device(const void* d_trackers, const void* d_k_commitments,
+                                                                const void* d_proofs, size_t k, int* results, void* stream) {
+  if (k == 0) return CURDLE_OK;
+  return tracker_batch(static_cast<const uint8_t*>(d_trackers), static_cast<const uint8_t*>(d_k_commitments),
+                       static_cast<const uint8_t*>(d_proofs), k, true, true, stream, results);
+}
+
+extern "C" int curdle_stat_tracker(unsigned long long out[3]) {
+  if (!out) return CURDLE_EINVAL;
+  for (int i = 0; i < 3; i++) out[i] = g_tk_stat[i].load(std::memory_order_relaxed);
+  return CURDLE_OK;
 }

@@ -27,14 +27,15 @@ int ensure_host(void*& p, size_t& cap, size_t bytes) {
 // (profiles/r12_transcript_batch.json): 64 waves of one member 10.5 ms, 1,024 waves of one member 27.3 ms, 16 full
 // waves 23.0 ms; 8,192 members as 2,048 waves of four 39.1 ms, as 128 full waves 21.1 ms.  So: at most 128 waves.
 constexpr size_t kMaxWaves = 128;
-uint32_t members_per_wave(size_t k) {
+}  // namespace
+
+uint32_t curdle_api::members_per_wave(size_t k) {
   const long long forced = knobs::get(knobs::TRANSCRIPT_LANES);
   if (forced >= 1 && forced <= 64) return (uint32_t)forced;
   uint32_t mpw = 1;
   while (mpw < 64 && (k + mpw - 1) / mpw > kMaxWaves) mpw *= 2;
   return mpw;
 }
-}  // namespace
 
 extern "C" int curdle_transcript_batch(const char* transcript_label, const uint8_t* init_states,
                                        const curdle_transcript_step* steps, size_t n_steps, const uint8_t* data,

@@ -74,6 +74,7 @@ SYMBOLS = [
     "curdle_stat_check_paths",
     "curdle_g1_check_jac_batch", "curdle_g1_check_jac_batch_device", "curdle_verify_batch_checked", "curdle_stat_batch_checked",
     "curdle_transcript_batch", "curdle_transcript_batch_host", "curdle_stat_transcript", "curdle_transcript_last_kernel_ms",
+    "curdle_whisk_is_valid_tracker_proof_batch_ex", "curdle_whisk_is_valid_tracker_proof_batch_device", "curdle_stat_tracker",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -185,6 +186,9 @@ _whisk_valid_shuffle_batch = _sig("curdle_whisk_is_valid_shuffle_proof_batch", C
 _whisk_gen_shuffle = _sig("curdle_whisk_generate_shuffle_proof", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, _vp)
 _whisk_valid_tracker = _sig("curdle_whisk_is_valid_tracker_proof", C.c_int, _vp, _vp, _vp, C.POINTER(C.c_int))
 _whisk_valid_tracker_batch = _sig("curdle_whisk_is_valid_tracker_proof_batch", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp)
+_whisk_valid_tracker_batch_ex = _sig("curdle_whisk_is_valid_tracker_proof_batch_ex", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_uint, _vp)
+_whisk_valid_tracker_batch_device = _sig("curdle_whisk_is_valid_tracker_proof_batch_device", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp)
+_stat_tracker = _sig("curdle_stat_tracker", C.c_int, C.POINTER(C.c_ulonglong))
 _whisk_gen_tracker = _sig("curdle_whisk_generate_tracker_proof", C.c_int, _vp, _vp, _vp, _vp)
 _verify_set_eager = _sig("curdle_verify_set_eager", C.c_int, C.c_int)
 _reencode = _sig("curdle_proof_reencode", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t))
@@ -1040,10 +1044,14 @@ def whisk_is_valid_tracker_proof(tracker: bytes, k_commitment: bytes, proof: byt
     return bool(ok.value)
 
 
-def whisk_is_valid_tracker_proof_batch(trackers, k_commitments, proofs) -> np.ndarray:
+TRACKER_HASH_DEFAULT, TRACKER_HASH_HOST, TRACKER_HASH_DEVICE = 0, 1, 2
+
+
+def whisk_is_valid_tracker_proof_batch(trackers, k_commitments, proofs, flags=None) -> np.ndarray:
     """k tracker proofs at once on the GPU (curdle_whisk_is_valid_tracker_proof_batch): lists of
     96-byte trackers, 48-byte k commitments and 128-byte proofs.  Returns int32[k]: 1 accept,
-    0 reject, EINVAL where whisk_is_valid_tracker_proof raises CurdleError with EINVAL."""
+    0 reject, EINVAL where whisk_is_valid_tracker_proof raises CurdleError with EINVAL.
+    flags: TRACKER_HASH_* (curdle_whisk_is_valid_tracker_proof_batch_ex); None is the plain call."""
     k = len(trackers)
     if len(k_commitments) != k or len(proofs) != k:
         raise ValueError("trackers, k commitments and proofs need the same count")
@@ -1054,8 +1062,28 @@ def whisk_is_valid_tracker_proof_batch(trackers, k_commitments, proofs) -> np.nd
     if k == 0:
         return out
     t, kc, pb = _bytes_arr(b"".join(trackers)), _bytes_arr(b"".join(k_commitments)), _bytes_arr(b"".join(proofs))
-    _check(_whisk_valid_tracker_batch(_ptr(t), _ptr(kc), _ptr(pb), k, _ptr(out)))
+    if flags is None:
+        _check(_whisk_valid_tracker_batch(_ptr(t), _ptr(kc), _ptr(pb), k, _ptr(out)))
+    else:
+        _check(_whisk_valid_tracker_batch_ex(_ptr(t), _ptr(kc), _ptr(pb), k, flags, _ptr(out)))
     return out
+
+
+def whisk_is_valid_tracker_proof_batch_device(d_trackers: int, d_k_commitments: int, d_proofs: int, k: int,
+                                              stream: int = 0) -> np.ndarray:
+    """The same over resident arrays (curdle_whisk_is_valid_tracker_proof_batch_device): HIP device pointers to
+    k x 96, k x 48 and k x 128 bytes; stream: a hipStream_t or 0.  Transcripts are hashed on the device."""
+    out = np.zeros(k, dtype=np.int32)
+    _check(_whisk_valid_tracker_batch_device(d_trackers, d_k_commitments, d_proofs, k, _ptr(out) if k else None,
+                                             stream or None))
+    return out
+
+
+def stat_tracker() -> dict:
+    """Members of tracker batches hashed on the device, on the host, and handed back to the host."""
+    out = (C.c_ulonglong * 3)()
+    _check(_stat_tracker(out))
+    return {"device": out[0], "host": out[1], "handed_back": out[2]}
 
 
 def whisk_generate_tracker_proof(tracker: bytes, k, rand: Rand) -> bytes:

@@ -407,6 +407,30 @@ func DecompressBatch(out []bls12381.G1Affine, status []byte, in []byte, subgroup
 	})
 }
 
+// Where TrackerProofBatch hashes its members' transcripts (CURDLE_TRACKER_HASH_* in curdle_msm.h).
+const (
+	TrackerHashDefault = 0 // the library's rule
+	TrackerHashHost    = 1 // on host threads started inside the call
+	TrackerHashDevice  = 2 // on the GPU: no host arithmetic, no host thread -- for a service short of cores
+)
+
+// TrackerProofBatch is len(results) calls of whisk.IsValidWhiskTrackerProof (whisk/whisk.go:116) in one
+// (curdle_whisk_is_valid_tracker_proof_batch_ex): trackers 96, kComms 48 and proofs 128 bytes per member, back
+// to back; results[i] = 1 / 0 / -1 for (true, nil) / (false, nil) / (false, err).  UNVERIFIED: never compiled.
+func TrackerProofBatch(results []int32, trackers, kComms, proofs []byte, flags uint) error {
+	k := len(results)
+	if len(trackers) != 96*k || len(kComms) != 48*k || len(proofs) != 128*k {
+		return errors.New("curdlemsm: TrackerProofBatch: mismatched lengths")
+	}
+	if k == 0 {
+		return nil
+	}
+	return locked(func() C.int {
+		return C.curdle_whisk_is_valid_tracker_proof_batch_ex((*C.uint8_t)(unsafe.Pointer(&trackers[0])), (*C.uint8_t)(unsafe.Pointer(&kComms[0])),
+			(*C.uint8_t)(unsafe.Pointer(&proofs[0])), C.size_t(k), C.uint(flags), (*C.int)(unsafe.Pointer(&results[0])))
+	})
+}
+
 // CheckG1Affine checks points that arrive IN MEMORY -- and so went through no Decoder / SetBytes -- on the GPU
 // (curdle_g1_check_batch): one status per point, DecodeInfinity for (0, 0), DecodeBadEncoding for a coordinate
 // that is not below p, DecodeNotOnCurve, DecodeNotInSubgroup, else DecodeOK.  MultiExp and every other fast

@@ -389,7 +389,8 @@ int curdle_whisk_is_valid_tracker_proof(const uint8_t tracker[CURDLE_WHISK_TRACK
 /* k tracker proofs at once, each answered as curdle_whisk_is_valid_tracker_proof answers it
  * (IsValidWhiskTrackerProof, whisk.go:116).  trackers: k x 96 bytes, k_commitments: k x 48,
  * proofs: k x 128, back to back.  The 5 k points are decoded (curve and subgroup checked) and both
- * equations of every member are checked on the GPU; the transcripts are hashed on the host.
+ * equations of every member are checked on the GPU; the transcripts are hashed where
+ * CURDLE_TRACKER_HASH_DEFAULT says (below): this call is _ex with that flag.
  * results[i] = 1 (accept), 0 (reject: (false, nil)) or CURDLE_EINVAL where the single call
  * returns CURDLE_EINVAL ((false, err): a record that is not a point of the subgroup, S >= r).
  * k = 0: CURDLE_OK, nothing read or written, no device needed.  On a negative return every
@@ -397,6 +398,34 @@ int curdle_whisk_is_valid_tracker_proof(const uint8_t tracker[CURDLE_WHISK_TRACK
  * without a device the call fails with CURDLE_ENODEV. */
 int curdle_whisk_is_valid_tracker_proof_batch(const uint8_t* trackers, const uint8_t* k_commitments,
                                               const uint8_t* proofs, size_t k, int* results);
+/* The same call with the place where the members' Merlin transcripts (whisk.go:131-134) are hashed.
+ *   CURDLE_TRACKER_HASH_HOST    on the host, on up to 16 threads started inside the call, with the S < r checks
+ *                               and the gathering of the 5 k records, while the GPU takes the square roots.
+ *   CURDLE_TRACKER_HASH_DEVICE  on the GPU: the three arrays go up as they are, kernels gather the records, check
+ *                               every S < r and hash the transcripts (the batched Merlin kernel of
+ *                               curdle_transcript_batch, over a tape compiled once per process) beside the square
+ *                               roots.  No host arithmetic and no host thread.  A member whose transcript draws
+ *                               CURDLE_TRANSCRIPT_MAX_TRIES non-canonical challenges (probability 0.547^256) is
+ *                               answered by the single call on the host.
+ *   CURDLE_TRACKER_HASH_DEFAULT the library's rule: knob CURDLE_TRACKER_DEVICE_HASH = 1 device, 0 host, unset by
+ *                               the batch's size: on the device from 64 members (DESIGN.md section 0 has the measurement).
+ * The answers are the same under every flag.  Any other flag value: CURDLE_EINVAL, before anything is copied or
+ * launched. */
+#define CURDLE_TRACKER_HASH_DEFAULT 0u
+#define CURDLE_TRACKER_HASH_HOST 1u
+#define CURDLE_TRACKER_HASH_DEVICE 2u
+int curdle_whisk_is_valid_tracker_proof_batch_ex(const uint8_t* trackers, const uint8_t* k_commitments,
+                                                 const uint8_t* proofs, size_t k, unsigned flags, int* results);
+/* The same check over arrays already resident in device memory (HIP device pointers to k x 96, k x 48 and
+ * k x 128 bytes, any alignment); the transcripts are always hashed on the device.  `stream` is a hipStream_t or
+ * NULL for the library's own stream, as in curdle_msm_g1_device: the arrays are read in that stream's order, so
+ * they may have been written on it immediately before.  `results` is host memory and valid when the call returns.
+ * A member whose transcript draws no canonical challenge fails the call (CURDLE_EHIP in every result). */
+int curdle_whisk_is_valid_tracker_proof_batch_device(const void* d_trackers, const void* d_k_commitments,
+                                                     const void* d_proofs, size_t k, int* results, void* stream);
+/* Diagnostics: members of tracker batches since the library was loaded whose transcripts out[0] were hashed on the
+ * device, out[1] on the host, out[2] handed back to the host after a non-zero transcript status. */
+int curdle_stat_tracker(unsigned long long out[3]);
 /* GenerateWhiskTrackerProof, whisk.go:149 */
 int curdle_whisk_generate_tracker_proof(const uint8_t tracker[CURDLE_WHISK_TRACKER_SIZE], const uint64_t k[4],
                                         curdle_rand* rand, uint8_t proof_out[CURDLE_WHISK_TRACKER_PROOF_SIZE]);
