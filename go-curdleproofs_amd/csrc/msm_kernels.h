@@ -273,4 +273,27 @@ hipError_t launch_tracker_gather(const uint8_t* trackers, const uint8_t* k_comms
 hipError_t launch_tracker_challenge(const void* challenges, const uint8_t* tr_status, uint32_t n, void* scalars,
                                     uint8_t* skip, hipStream_t stream);
 
+// compress_kernels.hip: n points in memory -> n x 48 bytes of gnark's compressed encoding (G1Affine.Bytes), one lane
+// per point.  form kCompressJac: gnark G1Jac, 144 bytes each (Z = 0: infinity); kCompressXyzz: G1XYZZ in gnark limbs,
+// 192 bytes each, as launch_scalar_mul_batch writes it (ZZ = 0: infinity).  `in` and `out` may have any alignment.
+static constexpr int kCompressJac = 0, kCompressXyzz = 1;
+hipError_t launch_g1_compress(const void* in, int form, uint32_t n, uint8_t* out, hipStream_t stream);
+
+// tracker_prove_kernels.hip: the small kernels of the batched tracker-proof generator (tracker_api.hip), n members.
+// Pairs: the 3 n (point, scalar) pairs of one launch_scalar_mul_batch, (G, k_i) | (G, b_i) | (rG_i, b_i): `decoded`
+// holds the 2 n decoded tracker records (rG_i, krG_i; a record that did not decode is all zero, which the chain reads
+// as infinity), scalars + 8 i the Montgomery k_i, scalars + 8 (n + i) the b_i, which are copied to 8 (2 n + i).
+hipError_t launch_tracker_prove_pairs(const void* decoded, const G1Affine& gen, uint32_t n, void* points, void* scalars,
+                                      hipStream_t stream);
+// Rows: member i's transcript row, 8 zero bytes | kG g1Gen krG rG A B | 8 zero bytes (launch_tracker_gather's layout),
+// from its tracker record (96 bytes: rG | krG) and the compressed results, kG_i at comp + 48 i, A_i at 48 (n + i),
+// B_i at 48 (2 n + i).  Every pointer is 8-byte aligned.
+hipError_t launch_tracker_prove_rows(const void* trackers, const void* comp, const void* gen, uint32_t n, void* rows,
+                                     hipStream_t stream);
+// Response: proofs + 128 i = A_i | B_i | s_i with s = b - c k in Fr, 32 big-endian bytes; c: the transcript kernel's
+// 32 big-endian bytes per member.  A member with a record whose status is beyond CURDLE_DECODE_INFINITY, or which
+// decoded outside the subgroup (sub = 0), gets 128 zero bytes.
+hipError_t launch_tracker_response(const void* comp, const void* challenges, const void* scalars, const uint8_t* status,
+                                   const uint8_t* sub, uint32_t n, void* proofs, hipStream_t stream);
+
 }  // namespace curdle

@@ -1,5 +1,7 @@
 // C ABI of the batched Whisk tracker-proof check (tracker_kernels.hip): curdle_whisk_is_valid_tracker_proof_batch
-// (_ex, _device), k calls of IsValidWhiskTrackerProof (the reference's whisk/whisk.go:116-147) in one.
+// (_ex, _device), k calls of IsValidWhiskTrackerProof (the reference's whisk/whisk.go:116-147) in one -- and, in the
+// second half of the file, of the batched generator curdle_whisk_generate_tracker_proof_batch (_blinders), k calls of
+// GenerateWhiskTrackerProof (:149-175) in one, on the same tape and slots (tracker_prove_kernels.hip).
 //
 // Two forms.  HOST-HASHED (tracker_pass), per pass of at most kTrackerPass members, on the calling thread's context:
 //   1. the 5 k records (rG, krG, kG, A, B per member) go up once; the square roots (launch_g1_decompress) run on
@@ -27,6 +29,7 @@
 #include "../host/algebra.h"
 #include "../host/transcript.h"
 #include "../host/transcript_batch.h"
+#include "../host/whisk.h"
 
 namespace {
 std::atomic<unsigned long long> g_tk_stat[3];  // members hashed on the device | on the host | handed back to the host
@@ -367,6 +370,222 @@ int tracker_batch(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t
   return rc;
 }
 
+// --- generation: k calls of GenerateWhiskTrackerProof (whisk.go:149-175) in one ---------------------------------------
+//
+// Per pass of at most kTrackerPass members, on the held slot's stream (B, when a second slot is free, lends its stream
+// to the subgroup test, which then runs beside the square roots and the scalar multiplications):
+//   1. tape | trackers go up as they are, and k (with b, when the caller gives the blinders); the 2 m tracker records
+//      are decoded (launch_g1_decompress + launch_g1_subgroup_from_bytes);
+//   2. with a curdle_rand the 4 m status bytes come back, the host draws ONE GetFr per decodable member in member
+//      order -- the single call decodes before it draws (host/whisk.cpp), so a member that fails to decode draws
+//      nothing -- and b goes up;
+//   3. k_tracker_prove_pairs, ONE launch_scalar_mul_batch over (G, k) | (G, b) | (rG, b), launch_g1_compress over the
+//      3 m results, k_tracker_prove_rows, the verifier's tape on launch_transcript_batch, k_tracker_response;
+//   4. 128 m + 5 m bytes come back; the buffers that held k, b and the XYZZ results are overwritten.
+// A member whose transcript comes back with a status (256 rejected draws) is generated by the single path on the host.
+std::atomic<unsigned long long> g_tp_stat[2];  // members generated on the device | handed to the host single path
+
+struct ProvePass {
+  Slot& A;
+  hipStream_t sa;
+  size_t m;
+  // the places a secret was written to in this pass (null: not yet)
+  void* d_sc = nullptr;
+  void* d_xyzz = nullptr;
+  uint8_t* h_secret = nullptr;
+  // Overwrites them, on the pass's stream and behind everything queued there; called on every way out of a pass.
+  int wipe() {
+    hipError_t e = hipSuccess, e2;
+    if (d_sc && (e2 = hipMemsetAsync(d_sc, 0, 96 * m, sa)) != hipSuccess) e = e2;
+    if (d_xyzz && (e2 = hipMemsetAsync(d_xyzz, 0, 576 * m, sa)) != hipSuccess) e = e2;
+    if ((e2 = hipStreamSynchronize(sa)) != hipSuccess) e = e2;
+    if (h_secret) explicit_bzero(h_secret, 64 * m);
+    if (e != hipSuccess) return fail(CURDLE_EHIP, "tracker proofs: clearing the secrets: %s", hipGetErrorString(e));
+    return CURDLE_OK;
+  }
+};
+
+int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders,
+                   curdle_rand* rand, uint8_t* proofs_out, int* results) {
+  static const TrackerTape T;
+  Slot& A = P.A;
+  const hipStream_t sa = P.sa;
+  const size_t m = P.m, nrec = 2 * m, tape_bytes = T.bytes.size();
+  int r;
+  if ((r = ensure(A.sorted, tape_bytes + 96 * m + (kRowBytes + 32) * m))) return r;  // tape | trackers | rows | challenges
+  if ((r = ensure(A.points, (192 + 288 + 576) * m))) return r;  // decoded records | the pairs' points | XYZZ results
+  if ((r = ensure(A.counts, 2 * nrec + m))) return r;           // statuses | subgroup verdicts | transcript statuses
+  if ((r = ensure(A.digits, 96 * m))) return r;                 // k | b | b, Montgomery
+  if ((r = ensure(A.scalars, (144 + 128) * m))) return r;       // kG | A | B compressed, the proofs
+  if ((r = ensure_pinned(A, 0, tape_bytes + 96 * m + 64 * m))) return r;
+  if ((r = ensure_pinned(A, 1, 128 * m + 2 * nrec + m))) return r;
+  uint8_t* h_in = static_cast<uint8_t*>(A.h_stage[0]);
+  uint8_t* h_k = h_in + tape_bytes + 96 * m;
+  uint8_t* h_b = h_k + 32 * m;
+  uint8_t* h_out = static_cast<uint8_t*>(A.h_stage[1]);
+  uint8_t* h_st = h_out + 128 * m;
+  uint8_t* d_tape = static_cast<uint8_t*>(A.sorted.p);
+  uint8_t* d_trk = d_tape + tape_bytes;
+  uint8_t* d_rows = d_trk + 96 * m;
+  uint8_t* d_ch = d_rows + kRowBytes * m;
+  uint8_t* d_dec = static_cast<uint8_t*>(A.points.p);
+  uint8_t* d_pairs = d_dec + 192 * m;
+  uint8_t* d_xyzz = d_pairs + 288 * m;
+  uint8_t* d_status = static_cast<uint8_t*>(A.counts.p);
+  uint8_t* d_sub = d_status + nrec;
+  uint8_t* d_trst = d_sub + nrec;
+  uint8_t* d_sc = static_cast<uint8_t*>(A.digits.p);
+  uint8_t* d_comp = static_cast<uint8_t*>(A.scalars.p);
+  uint8_t* d_proofs = d_comp + 144 * m;
+
+  memcpy(h_in, T.bytes.data(), tape_bytes);
+  memcpy(h_in + tape_bytes, trackers, 96 * m);
+  P.h_secret = h_k;
+  memcpy(h_k, ks, 32 * m);
+  if (blinders) memcpy(h_b, blinders, 32 * m);
+  HIP_TRY(hipMemcpyAsync(d_tape, h_in, tape_bytes + 96 * m, hipMemcpyHostToDevice, sa));
+  P.d_sc = d_sc;
+  HIP_TRY(hipMemcpyAsync(d_sc, h_k, (blinders ? 64 : 32) * m, hipMemcpyHostToDevice, sa));
+  if (B) {
+    HIP_TRY(hipEventRecord(A.pre_done, sa));
+    HIP_TRY(hipStreamWaitEvent(B->stream, A.pre_done, 0));
+    HIP_TRY(launch_g1_subgroup_from_bytes(d_trk, (uint32_t)nrec, d_sub, B->stream));
+    HIP_TRY(hipEventRecord(B->acc_done, B->stream));
+  }
+  HIP_TRY(launch_g1_decompress(d_trk, (uint32_t)nrec, 0, (uint32_t*)d_dec, d_status, sa));
+  if (!B) HIP_TRY(launch_g1_subgroup_from_bytes(d_trk, (uint32_t)nrec, d_sub, sa));
+  auto bad_member = [&](size_t i) {
+    bool bad = false;
+    for (size_t j = 2 * i; j < 2 * i + 2; j++)
+      bad |= h_st[j] > CURDLE_DECODE_INFINITY || (h_st[j] == CURDLE_DECODE_OK && !h_st[nrec + j]);
+    return bad;
+  };
+  if (!blinders) {
+    if (B) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));
+    HIP_TRY(hipMemcpyAsync(h_st, d_status, 2 * nrec, hipMemcpyDeviceToHost, sa));
+    HIP_TRY(hipStreamSynchronize(sa));
+    for (size_t i = 0; i < m; i++) {
+      uint64_t b[4] = {0, 0, 0, 0};
+      if (!bad_member(i) && (r = curdle_rand_get_fr(rand, b))) return r;
+      memcpy(h_b + 32 * i, b, 32);
+    }
+    HIP_TRY(hipMemcpyAsync(d_sc + 32 * m, h_b, 32 * m, hipMemcpyHostToDevice, sa));
+  }
+  G1Affine gen;
+  g1_generator(gen);
+  HIP_TRY(launch_tracker_prove_pairs(d_dec, gen, (uint32_t)m, d_pairs, d_sc, sa));
+  P.d_xyzz = d_xyzz;
+  HIP_TRY(launch_scalar_mul_batch(d_pairs, d_sc, 0, nullptr, (uint32_t)(3 * m), d_xyzz, sa));
+  HIP_TRY(launch_g1_compress(d_xyzz, kCompressXyzz, (uint32_t)(3 * m), d_comp, sa));
+  HIP_TRY(launch_tracker_prove_rows(d_trk, d_comp, d_tape + T.gen_off, (uint32_t)m, d_rows, sa));
+  TranscriptArgs ta = {};
+  ta.ctl = reinterpret_cast<const curdle::transcript::TapeCtl*>(d_tape);
+  ta.pool = reinterpret_cast<const curdle::transcript::TapeBlock*>(d_tape + T.pool_off);
+  ta.data = reinterpret_cast<const uint64_t*>(d_rows);
+  ta.init = reinterpret_cast<const uint64_t*>(d_tape + T.init_off);
+  ta.challenges = reinterpret_cast<uint64_t*>(d_ch);
+  ta.states = nullptr;
+  ta.status = d_trst;
+  ta.tail = T.tail;
+  ta.n_ctl = T.n_ctl;
+  ta.row_words = (uint32_t)(kRowBytes / 8);
+  ta.init_stride = 0;
+  ta.k = (uint32_t)m;
+  ta.mpw = members_per_wave(m);
+  ta.n_challenges = 1;
+  HIP_TRY(launch_transcript_batch(ta, sa));
+  if (B && blinders) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));
+  HIP_TRY(launch_tracker_response(d_comp, d_ch, d_sc, d_status, d_sub, (uint32_t)m, d_proofs, sa));
+  HIP_TRY(hipMemcpyAsync(h_out, d_proofs, 128 * m, hipMemcpyDeviceToHost, sa));
+  HIP_TRY(hipMemcpyAsync(h_st, d_status, 2 * nrec + m, hipMemcpyDeviceToHost, sa));
+  HIP_TRY(hipStreamSynchronize(sa));
+  const uint8_t* trst = h_st + 2 * nrec;
+  unsigned long long handed = 0;
+  for (size_t i = 0; i < m; i++) {
+    uint8_t* out = proofs_out + 128 * i;
+    if (bad_member(i)) {  // where the single call fails to set rG or krG
+      memset(out, 0, 128);
+      results[i] = CURDLE_EINVAL;
+    } else if (trst[i]) {  // 256 rejected draws (0.547^256): the single path settles the member on the host
+      curdle::whisk::WhiskTracker t;
+      memcpy(&t, trackers + 96 * i, 96);
+      try {
+        curdle::whisk::GenerateWhiskTrackerProofWithBlinder(t, curdle::alg::Scalar::FromMont(ks + 4 * i),
+                                                            curdle::alg::Scalar::FromMont(reinterpret_cast<const uint64_t*>(h_b + 32 * i)), out);
+        results[i] = CURDLE_OK;
+      } catch (const std::runtime_error&) {
+        memset(out, 0, 128);
+        results[i] = CURDLE_EINVAL;
+      }
+      handed++;
+    } else {
+      memcpy(out, h_out + 128 * i, 128);
+      results[i] = CURDLE_OK;
+    }
+  }
+  g_tp_stat[0].fetch_add(m - handed, std::memory_order_relaxed);
+  g_tp_stat[1].fetch_add(handed, std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+// The whole call; exactly one of blinders / rand is given.
+int tracker_prove_batch(const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders, curdle_rand* rand, size_t k,
+                        uint8_t* proofs_out, int* results) {
+  int rc = CURDLE_OK;
+  if (!trackers || !ks || (!blinders && !rand) || !proofs_out || !results) {
+    rc = fail(CURDLE_EINVAL, "null argument");
+  } else {
+    Ctx& cx = cur();
+    int ia = -1, ib = -1;
+    rc = acquire_slot(cx, true, &ia);
+    if (rc == CURDLE_OK) {
+      {  // a second slot only lends its stream and an event to the subgroup test
+        std::lock_guard<std::mutex> g(cx.mu);
+        for (int i = 0; i < kSlots && ib < 0; i++)
+          if (!cx.slots[i].busy) {
+            cx.slots[i].busy = true;
+            cx.slots[i].claimed = false;
+            cx.slots[i].gen++;
+            ib = i;
+          }
+      }
+      Slot& A = cx.slots[ia];
+      Slot* B = ib >= 0 ? &cx.slots[ib] : nullptr;
+      auto body = [&]() -> int {
+        HIP_TRY(hipSetDevice(cx.device));
+        for (size_t lo = 0; lo < k; lo += kTrackerPass) {
+          ProvePass P{A, A.stream, std::min(kTrackerPass, k - lo)};
+          int r = prove_pass_run(cx, P, B, trackers + 96 * lo, ks + 4 * lo, blinders ? blinders + 4 * lo : nullptr, rand,
+                                 proofs_out + 128 * lo, results + lo);
+          if (r && B) (void)hipStreamSynchronize(B->stream);
+          const int w = P.wipe();  // on every way out: nothing of k and b stays behind in the slot
+          if (r || w) return r ? r : w;
+        }
+        return CURDLE_OK;
+      };
+      try {
+        rc = body();
+      } catch (const std::logic_error& e) {  // the constant tape did not compile to the shape the kernels expect
+        rc = fail(CURDLE_EHIP, "tracker proofs: internal error: %s", e.what());
+      } catch (const std::exception& e) {
+        rc = fail(CURDLE_ENOMEM, "tracker proofs: %s", e.what());
+      }
+      if (rc) {  // nothing queued may outlive the slots' hold
+        (void)hipStreamSynchronize(A.stream);
+        if (B) (void)hipStreamSynchronize(B->stream);
+      }
+      if (B) release_slot(cx, ib);
+      release_slot(cx, ia);
+    }
+  }
+  if (rc != CURDLE_OK) {  // "could not compute" must never read as a proof
+    if (results)
+      for (size_t i = 0; i < k; i++) results[i] = rc;
+    if (proofs_out) memset(proofs_out, 0, 128 * k);
+  }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" int curdle_whisk_is_valid_tracker_proof_batch_ex(const uint8_t* trackers, const uint8_t* k_commitments,
@@ -401,5 +620,24 @@ extern "C" int curdle_whisk_is_valid_tracker_proof_batch_device(const void* d_tr
 extern "C" int curdle_stat_tracker(unsigned long long out[3]) {
   if (!out) return CURDLE_EINVAL;
   for (int i = 0; i < 3; i++) out[i] = g_tk_stat[i].load(std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+extern "C" int curdle_whisk_generate_tracker_proof_batch_blinders(const uint8_t* trackers, const uint64_t* ks,
+                                                                  const uint64_t* blinders, size_t k, uint8_t* proofs_out,
+                                                                  int* results) {
+  if (k == 0) return CURDLE_OK;
+  return tracker_prove_batch(trackers, ks, blinders, nullptr, k, proofs_out, results);
+}
+
+extern "C" int curdle_whisk_generate_tracker_proof_batch(const uint8_t* trackers, const uint64_t* ks, curdle_rand* rand,
+                                                         size_t k, uint8_t* proofs_out, int* results) {
+  if (k == 0) return CURDLE_OK;
+  return tracker_prove_batch(trackers, ks, nullptr, rand, k, proofs_out, results);
+}
+
+extern "C" int curdle_stat_tracker_prove(unsigned long long out[2]) {
+  if (!out) return CURDLE_EINVAL;
+  for (int i = 0; i < 2; i++) out[i] = g_tp_stat[i].load(std::memory_order_relaxed);
   return CURDLE_OK;
 }

@@ -75,6 +75,8 @@ SYMBOLS = [
     "curdle_g1_check_jac_batch", "curdle_g1_check_jac_batch_device", "curdle_verify_batch_checked", "curdle_stat_batch_checked",
     "curdle_transcript_batch", "curdle_transcript_batch_host", "curdle_stat_transcript", "curdle_transcript_last_kernel_ms",
     "curdle_whisk_is_valid_tracker_proof_batch_ex", "curdle_whisk_is_valid_tracker_proof_batch_device", "curdle_stat_tracker",
+    "curdle_g1_compress_batch", "curdle_g1_compress_batch_device",
+    "curdle_whisk_generate_tracker_proof_batch_blinders", "curdle_whisk_generate_tracker_proof_batch", "curdle_stat_tracker_prove",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -190,12 +192,18 @@ _whisk_valid_tracker_batch_ex = _sig("curdle_whisk_is_valid_tracker_proof_batch_
 _whisk_valid_tracker_batch_device = _sig("curdle_whisk_is_valid_tracker_proof_batch_device", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp)
 _stat_tracker = _sig("curdle_stat_tracker", C.c_int, C.POINTER(C.c_ulonglong))
 _whisk_gen_tracker = _sig("curdle_whisk_generate_tracker_proof", C.c_int, _vp, _vp, _vp, _vp)
+_whisk_gen_tracker_batch_blinders = _sig("curdle_whisk_generate_tracker_proof_batch_blinders", C.c_int, _vp, _vp, _vp, C.c_size_t,
+                                         _vp, _vp)
+_whisk_gen_tracker_batch = _sig("curdle_whisk_generate_tracker_proof_batch", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp)
+_stat_tracker_prove = _sig("curdle_stat_tracker_prove", C.c_int, C.POINTER(C.c_ulonglong))
 _verify_set_eager = _sig("curdle_verify_set_eager", C.c_int, C.c_int)
 _reencode = _sig("curdle_proof_reencode", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t))
 _merlin_tv = _sig("curdle_merlin_test_vector", C.c_int, C.c_char_p, C.c_char_p, _vp, C.c_size_t, C.c_char_p, _vp,
                   C.c_size_t)
 _g1_compress = _sig("curdle_g1_compress", C.c_int, _vp, _vp)
 _g1_decompress = _sig("curdle_g1_decompress", C.c_int, _vp, C.c_int, _vp)
+_g1_compress_batch = _sig("curdle_g1_compress_batch", C.c_int, _vp, C.c_size_t, _vp)
+_g1_compress_batch_device = _sig("curdle_g1_compress_batch_device", C.c_int, _vp, C.c_size_t, _vp, _vp)
 
 
 class CurdleError(RuntimeError):
@@ -1094,6 +1102,41 @@ def whisk_generate_tracker_proof(tracker: bytes, k, rand: Rand) -> bytes:
     return out.tobytes()
 
 
+def whisk_generate_tracker_proof_batch(trackers, ks, rand: "Rand" = None, blinders=None):
+    """k tracker proofs at once on the GPU (curdle_whisk_generate_tracker_proof_batch / _blinders): a list of 96-byte
+    trackers and ks (k, 4), Montgomery fr limbs.  Exactly one of rand (the blinders are drawn as k single calls on it
+    would draw them) and blinders (k, 4) is given.  Returns (proofs uint8[k, 128], results int32[k]): results[i] is OK,
+    or EINVAL with a zero proof where whisk_generate_tracker_proof raises CurdleError with EINVAL."""
+    if (rand is None) == (blinders is None):
+        raise ValueError("give either rand or blinders")
+    k = len(trackers)
+    if any(len(t) != 96 for t in trackers):
+        raise ValueError("tracker 96 B")
+    kk = _as_u64(ks, 4).reshape(-1, 4)
+    if kk.shape[0] != k:
+        raise ValueError("trackers and ks need the same count")
+    proofs = np.zeros((k, WHISK_TRACKER_PROOF_SIZE), dtype=np.uint8)
+    results = np.zeros(k, dtype=np.int32)
+    if k == 0:
+        return proofs, results
+    t = _bytes_arr(b"".join(trackers))
+    if blinders is not None:
+        bb = _as_u64(blinders, 4).reshape(-1, 4)
+        if bb.shape[0] != k:
+            raise ValueError("trackers and blinders need the same count")
+        _check(_whisk_gen_tracker_batch_blinders(_ptr(t), _ptr(kk), _ptr(bb), k, _ptr(proofs), _ptr(results)))
+    else:
+        _check(_whisk_gen_tracker_batch(_ptr(t), _ptr(kk), rand._h, k, _ptr(proofs), _ptr(results)))
+    return proofs, results
+
+
+def stat_tracker_prove() -> dict:
+    """Members of generated tracker-proof batches: generated on the device, handed to the host single path."""
+    out = (C.c_ulonglong * 2)()
+    _check(_stat_tracker_prove(out))
+    return {"device": out[0], "host": out[1]}
+
+
 _set_dev_acc = _sig("curdle_verify_set_device_acc", C.c_int, C.c_int)
 _export_acc = _sig("curdle_verify_export_accumulator", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_int,
                    _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int))
@@ -1272,6 +1315,22 @@ def g1_compress(jac) -> bytes:
     out = np.zeros(48, dtype=np.uint8)
     _check(_g1_compress(_ptr(jac), _ptr(out)))
     return bytes(out)
+
+
+def g1_compress_batch(jac_points) -> np.ndarray:
+    """(n, 18) gnark G1Jac points -> (n, 48) bytes of gnark's compressed encoding, on the GPU
+    (curdle_g1_compress_batch): row i is g1_compress(jac_points[i])."""
+    jac_points = _as_u64(jac_points, 18)
+    n = jac_points.shape[0] if jac_points.size else 0
+    out = np.zeros((n, 48), dtype=np.uint8)
+    _check(_g1_compress_batch(_ptr(jac_points), n, _ptr(out)))
+    return out
+
+
+def g1_compress_batch_device(ptr: int, n: int, out_ptr: int, stream=None) -> None:
+    """The same for n points resident in device memory at `ptr` (any alignment); the n x 48 bytes are written to
+    device memory at `out_ptr` in the stream's order and are complete when the call returns."""
+    _check(_g1_compress_batch_device(ptr or None, n, out_ptr or None, stream or None))
 
 
 def g1_decompress(data: bytes, subgroup_check: bool = True) -> np.ndarray:

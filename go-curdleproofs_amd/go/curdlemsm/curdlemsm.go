@@ -507,6 +507,56 @@ func CheckG1Jac(points []bls12381.G1Jac) ([]uint8, error) {
 	return status, nil
 }
 
+// CompressG1Jac is G1Affine.Bytes of every point of a []G1Jac on the GPU (curdle_g1_compress_batch): one inversion per
+// point on the device instead of FromJacobian + Bytes per point on the host; Z = 0 is the encoding of infinity.  The
+// points are only read.  UNVERIFIED like the rest of this file: never compiled.
+func CompressG1Jac(points []bls12381.G1Jac) ([][48]byte, error) {
+	out := make([][48]byte, len(points))
+	if len(points) == 0 {
+		return out, nil
+	}
+	err := locked(func() C.int {
+		return C.curdle_g1_compress_batch((*C.uint64_t)(unsafe.Pointer(&points[0])), C.size_t(len(points)),
+			(*C.uint8_t)(unsafe.Pointer(&out[0])))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return out, nil
+}
+
+// GenerateWhiskTrackerProofs is whisk.GenerateWhiskTrackerProof for len(trackers) members in one call on the GPU
+// (curdle_whisk_generate_tracker_proof_batch_blinders): trackers[i] is the 96-byte WhiskTracker (rG | krG), ks[i] its
+// opening and blinders[i] the blinder the single call would draw.  errs[i] is non-nil, and proofs[i] zero, where the
+// single call returns an error (a tracker record that is not a point of the subgroup).  ks and blinders are secrets:
+// the library overwrites its copies before it returns.  UNVERIFIED: never compiled.
+func GenerateWhiskTrackerProofs(trackers [][96]byte, ks, blinders []fr.Element) ([][128]byte, []error, error) {
+	k := len(trackers)
+	if len(ks) != k || len(blinders) != k {
+		return nil, nil, errors.New("curdlemsm: GenerateWhiskTrackerProofs: trackers, ks and blinders differ in length")
+	}
+	proofs := make([][128]byte, k)
+	errs := make([]error, k)
+	if k == 0 {
+		return proofs, errs, nil
+	}
+	results := make([]C.int, k)
+	err := locked(func() C.int {
+		return C.curdle_whisk_generate_tracker_proof_batch_blinders((*C.uint8_t)(unsafe.Pointer(&trackers[0])),
+			(*C.uint64_t)(unsafe.Pointer(&ks[0])), (*C.uint64_t)(unsafe.Pointer(&blinders[0])), C.size_t(k),
+			(*C.uint8_t)(unsafe.Pointer(&proofs[0])), &results[0])
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	for i, rc := range results {
+		if rc != 0 {
+			errs[i] = errors.New("curdlemsm: deserializing rG and krG: not a point of the prime-order subgroup")
+		}
+	}
+	return proofs, errs, nil
+}
+
 // PointFault names the first failed point of a batch member, as curdle_point_fault does: Vector 0 Rs, 1 Ss, 2 Ts,
 // 3 Us, 4 M; Code is a Decode* status, DecodeOK for a member with nothing wrong.
 type PointFault struct {

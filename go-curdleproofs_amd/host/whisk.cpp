@@ -445,18 +445,12 @@ bool IsValidWhiskTrackerProof(const WhiskTracker& tracker, const uint8_t kComm[G
   return A_prime == Point::FromAffine(tp.A) && B_prime == Point::FromAffine(tp.B);
 }
 
-void GenerateWhiskTrackerProof(const WhiskTracker& tracker, const Scalar& k, common::Rand& rand,
-                               uint8_t out[TRACKER_PROOF_SIZE]) {
-  G1Affine rG, krG;
-  try {
-    GetPoints(tracker, &rG, &krG);
-  } catch (const std::runtime_error& e) {
-    throw err(std::string("deserializing rG and krG: ") + e.what());
-  }
+namespace {
+// whisk.go:156-174 behind the decoding and the draw
+void TrackerProofCore(const G1Affine& rG, const G1Affine& krG, const Scalar& k, const Scalar& blinder,
+                      uint8_t out[TRACKER_PROOF_SIZE]) {
   const Point g = Point::Generator();
   const Point kG = g.Mul(k);  // :156
-  Scalar blinder;
-  rand.GetFr(blinder.v);      // :157
   const Point A = g.Mul(blinder);
   const Point B = Point::FromAffine(rG).Mul(blinder);
 
@@ -469,6 +463,31 @@ void GenerateWhiskTrackerProof(const WhiskTracker& tracker, const Scalar& k, com
   tp.B = B.Affine();
   tp.S = blinder - challenge * k;  // :171-172
   tp.Serialize(out);
+}
+}  // namespace
+
+void GenerateWhiskTrackerProof(const WhiskTracker& tracker, const Scalar& k, common::Rand& rand,
+                               uint8_t out[TRACKER_PROOF_SIZE]) {
+  G1Affine rG, krG;
+  try {
+    GetPoints(tracker, &rG, &krG);
+  } catch (const std::runtime_error& e) {
+    throw err(std::string("deserializing rG and krG: ") + e.what());
+  }
+  Scalar blinder;
+  rand.GetFr(blinder.v);      // :157
+  TrackerProofCore(rG, krG, k, blinder, out);
+}
+
+void GenerateWhiskTrackerProofWithBlinder(const WhiskTracker& tracker, const Scalar& k, const Scalar& blinder,
+                                          uint8_t out[TRACKER_PROOF_SIZE]) {
+  G1Affine rG, krG;
+  try {
+    GetPoints(tracker, &rG, &krG);
+  } catch (const std::runtime_error& e) {
+    throw err(std::string("deserializing rG and krG: ") + e.what());
+  }
+  TrackerProofCore(rG, krG, k, blinder, out);
 }
 
 }  // namespace whisk

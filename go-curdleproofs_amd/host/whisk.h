@@ -59,6 +59,10 @@ bool IsValidWhiskTrackerProof(const WhiskTracker& tracker, const uint8_t kComm[G
 // whisk.go:149
 void GenerateWhiskTrackerProof(const WhiskTracker& tracker, const alg::Scalar& k, common::Rand& rand,
                                uint8_t out[TRACKER_PROOF_SIZE]);
+// ... with the blinder given instead of drawn: what the batched generator (csrc/tracker_api.hip) hands a
+// member to whose transcript the device could not finish.  The same bytes as the call above for the same blinder.
+void GenerateWhiskTrackerProofWithBlinder(const WhiskTracker& tracker, const alg::Scalar& k, const alg::Scalar& blinder,
+                                          uint8_t out[TRACKER_PROOF_SIZE]);
 
 }  // namespace whisk
 }  // namespace curdle

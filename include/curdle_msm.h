@@ -429,6 +429,35 @@ int curdle_stat_tracker(unsigned long long out[3]);
 /* GenerateWhiskTrackerProof, whisk.go:149 */
 int curdle_whisk_generate_tracker_proof(const uint8_t tracker[CURDLE_WHISK_TRACKER_SIZE], const uint64_t k[4],
                                         curdle_rand* rand, uint8_t proof_out[CURDLE_WHISK_TRACKER_PROOF_SIZE]);
+/* k tracker proofs generated at once ON THE GPU, member i as curdle_whisk_generate_tracker_proof(trackers + 96 i,
+ * ks + 4 i) generates it with the blinder blinders + 4 i (GenerateWhiskTrackerProof, whisk.go:149-175): proofs_out + 128 i
+ * holds byte for byte what the single call writes for the same tracker, k and blinder, and results[i] = CURDLE_OK.
+ * Where the single call returns CURDLE_EINVAL (a tracker record that is not a point of the subgroup), results[i] =
+ * CURDLE_EINVAL and the member's 128 bytes are zero; its neighbours are unaffected.  trackers: k x 96 bytes; ks,
+ * blinders: k x 4 limbs, Montgomery fr.Elements; proofs_out: k x 128 bytes, back to back.
+ * The 2 k tracker records are decoded, the 3 k scalar multiplications kG = k G, A = b G, B = b rG run in one launch,
+ * their results are normalised and compressed (the kernel of curdle_g1_compress_batch), the transcripts are hashed
+ * by the batched Merlin kernel and s = b - c k is computed in Fr, all on the device, in passes of 65,536 members.  A
+ * member whose transcript draws CURDLE_TRANSCRIPT_MAX_TRIES non-canonical challenges (probability 0.547^256) is
+ * generated by the single path on the host.
+ * k = 0: CURDLE_OK, nothing read or written, no device needed.  Null pointers with k > 0: CURDLE_EINVAL.  On a
+ * negative return every results[i] holds that code and proofs_out is zero.  No host fallback: without a device the
+ * call fails with CURDLE_ENODEV.
+ * SECRETS.  ks and blinders are secrets.  The device buffers and the pinned staging that held them, and the
+ * unnormalised results of the scalar multiplications, are overwritten (on the stream that used them) before the call
+ * returns on every path.  The scalar-multiplication chain BRANCHES ON SCALAR BITS, as the host path and gnark's
+ * ScalarMultiplication do: its running time depends on k and b. */
+int curdle_whisk_generate_tracker_proof_batch_blinders(const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders,
+                                                       size_t k, uint8_t* proofs_out, int* results);
+/* The same, drawing the blinders from rand exactly as k successive single calls on that rand would: the single call
+ * decodes its tracker before it draws, so a member that fails to decode draws nothing.  The call decodes, waits for the
+ * 2 k verdicts, draws one GetFr per decodable member in member order on the host and continues; afterwards rand is in
+ * the state the k single calls would have left it in. */
+int curdle_whisk_generate_tracker_proof_batch(const uint8_t* trackers, const uint64_t* ks, curdle_rand* rand, size_t k,
+                                              uint8_t* proofs_out, int* results);
+/* Diagnostics: members of generated batches since the library was loaded, out[0] generated on the device, out[1]
+ * handed to the host single path after a non-zero transcript status. */
+int curdle_stat_tracker_prove(unsigned long long out[2]);
 /* ------------------------------------------------------------------------- *
  * Accumulator on the device
  *   msmaccumulator.AccumulateCheck / Verify (msmaccumulator/msmaccumulator.go:23-64) with
@@ -648,6 +677,22 @@ int curdle_verify_proof_checked(const curdle_crs* crs, const curdle_proof* proof
  * codes and the rule that picks the kernel build are those of curdle_g1_check_batch / _device. */
 int curdle_g1_check_jac_batch(const uint64_t* jac_points, size_t n, int subgroup_check, uint8_t* status);
 int curdle_g1_check_jac_batch_device(const void* d_jac_points, size_t n, int subgroup_check, uint8_t* status, void* stream);
+/* Batched normalisation and compression ON THE GPU: n gnark G1Jac values (n x 18 limbs: X, Y, Z in Montgomery form) ->
+ * n x 48 bytes of gnark's compressed encoding (G1Affine.Bytes), byte for byte what curdle_g1_compress writes for each
+ * point; the counterpart of curdle_g1_decompress_batch.  Z all zero words is infinity (0xC0 and 47 zero bytes, whatever
+ * X and Y hold); otherwise x = X / Z^2 is written big-endian with the flag 0xA0 if y = Y / Z^3 > (p - 1) / 2 and 0x80
+ * otherwise.  One inversion per point (Fermat, a fixed chain), one lane per point.  Nothing is checked: the points are
+ * taken as curdle_g1_compress takes them (coordinates below p; curdle_g1_check_jac_batch is the check).
+ * n = 0: CURDLE_OK, nothing touched, no device needed; a null pointer with n > 0, or n > 2^27: CURDLE_EINVAL before
+ * anything is copied or launched.  No host fallback: without a device the call fails with CURDLE_ENODEV.
+ *   curdle_g1_compress_batch          points and bytes in host memory
+ *   curdle_g1_compress_batch_device   both resident in device memory (HIP device pointers, ANY alignment); `stream` is
+ *                                     a hipStream_t or NULL for the library's own stream, as in curdle_msm_g1_device:
+ *                                     the points are read and the bytes written in that stream's order, so the points
+ *                                     may have been written on it immediately before.  The bytes stay in device
+ *                                     memory; they are complete when the call returns. */
+int curdle_g1_compress_batch(const uint64_t* jac_points, size_t n, uint8_t* out);
+int curdle_g1_compress_batch_device(const void* d_jac_points, size_t n, void* d_out, void* stream);
 /* curdle_verify_batch with that check on every member's 4 ell instance points and on its M (range, curve equation,
  * subgroup), ON THE GPU and BESIDE the verification: producer threads gather the points of a chunk of members (at most
  * 32,768 points, so that the check runs on four lanes per point; only a single member beyond ell = 8,192 is more) into
