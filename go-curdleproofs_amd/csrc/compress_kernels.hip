@@ -7,9 +7,8 @@
 //   kCompressJac   gnark G1Jac, 18 Montgomery u64 limbs (X, Y, Z): x = X / Z^2, y = Y / Z^3; Z = 0 is infinity;
 //   kCompressXyzz  G1XYZZ in gnark limbs, as k_scalar_mul_batch_quad writes it: x = X / ZZ, y = Y / ZZZ; ZZ = 0 is
 //                  infinity.
-// Per point: infinity -> 0xC0 and 47 zero bytes, whatever X and Y hold.  Otherwise ONE inversion by Fermat,
-// d^(p-2), on the fixed 3-bit windows of the decoder's square root (the exponent is the same for every point, so
-// the digit is wave-uniform and picks one of seven call sites): 381 squarings and 120 products, table included.
+// Per point: infinity -> 0xC0 and 47 zero bytes, whatever X and Y hold.  Otherwise ONE inversion by Fermat
+// (invert28.h): 381 squarings and 120 products, table included.
 // Then x and y leave Montgomery form, x is written big-endian, and the flag is 0xA0 if y > (p-1)/2, else 0x80.
 //
 // ONE LANE per point, not a quad: the chain is a field exponentiation, which quad28.h cannot shorten (its four
@@ -21,6 +20,7 @@
 
 #include "../../include/curdle_msm.h"
 #include "fp28.h"
+#include "invert28.h"
 #include "quad28.h"
 #include "subgroup28.h"
 #include "msm_kernels.h"
@@ -29,19 +29,11 @@ namespace curdle {
 
 namespace {
 
-__device__ __forceinline__ u32 kInvExp(int i) {  // p - 2, 381 bits
-  constexpr u32 t[12] = {0xffffaaa9u, 0xb9feffffu, 0xb153ffffu, 0x1eabfffeu, 0xf6b0f624u, 0x6730d2a0u,
-                         0xf38512bfu, 0x64774b84u, 0x434bacd7u, 0x4b1ba7b6u, 0x397fe69au, 0x1a0111eau};
-  return t[i];
-}
 __device__ __forceinline__ u32 kHalfPm1(int i) {  // (p - 1) / 2
   constexpr u32 t[12] = {0xffffd555u, 0xdcff7fffu, 0x58a9ffffu, 0x0f55ffffu, 0x7b587b12u, 0xb3986950u,
                          0x79c2895fu, 0xb23ba5c2u, 0x21a5d66bu, 0x258dd3dbu, 0x1cbff34du, 0x0d0088f5u};
   return t[i];
 }
-// the top window of p - 2 (bits 380..378) is 6: the chain below starts from d^6
-static_assert(((0x1a0111eau >> 26) & 7u) == 6u, "top window of p - 2");
-
 // One coordinate, 12 words at any address; `al` (the same for the whole launch): the address is a multiple of 16.
 __device__ __forceinline__ void load12(u32 w[12], const uint8_t* __restrict__ p, bool al) {
   if (al) {
@@ -60,36 +52,6 @@ __device__ __forceinline__ bool load_coord(F28& r, const uint8_t* __restrict__ p
   for (int k = 0; k < 12; k++) any |= w[k];
   d28::from_gnark(r, w);
   return any != 0;
-}
-
-// d^(p-2): left to right over 127 windows of 3 bits
-__device__ __forceinline__ void invert(F28& y, const F28& d) {
-  F28 t2, t3, t4, t5, t6, t7;
-  d28::sqr(t2, d);
-  d28::mul(t3, t2, d);
-  d28::sqr(t4, t2);
-  d28::mul(t5, t4, d);
-  d28::sqr(t6, t3);
-  d28::mul(t7, t6, d);
-  y = t6;  // window 126
-  for (int w = 125; w >= 0; w--) {
-    d28::sqr_inl(y, y);
-    d28::sqr_inl(y, y);
-    d28::sqr_inl(y, y);
-    const int bit = 3 * w;
-    u32 e = kInvExp(bit >> 5) >> (bit & 31);
-    if ((bit & 31) > 29) e |= kInvExp((bit >> 5) + 1) << (32 - (bit & 31));
-    switch (e & 7u) {
-      case 1: d28::mul(y, y, d); break;
-      case 2: d28::mul(y, y, t2); break;
-      case 3: d28::mul(y, y, t3); break;
-      case 4: d28::mul(y, y, t4); break;
-      case 5: d28::mul(y, y, t5); break;
-      case 6: d28::mul(y, y, t6); break;
-      case 7: d28::mul(y, y, t7); break;
-      default: break;
-    }
-  }
 }
 
 }  // namespace

@@ -279,6 +279,16 @@ hipError_t launch_tracker_challenge(const void* challenges, const uint8_t* tr_st
 static constexpr int kCompressJac = 0, kCompressXyzz = 1;
 hipError_t launch_g1_compress(const void* in, int form, uint32_t n, uint8_t* out, hipStream_t stream);
 
+// normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion
+// per wave of 64 lanes with 1 or 8 points each (Montgomery's trick over a wave scan).  The forms are those of
+// launch_g1_compress; a denominator (Z, or ZZ ZZZ) that is 0 mod p is infinity.  `in` and `out` are multiples of 16
+// and do not overlap.  *groups (may be null): the inversion groups (waves) of the launch.
+static constexpr int kNormalizeJac = 0, kNormalizeXyzz = 1;
+// Up to this many points every lane takes one (the launch is at most one wave per SIMD of the chip's 1,024 and the
+// chain of ONE group is what the caller waits for); beyond it eight.  Knob NORMALIZE_LANE_POINTS (1 or 8) overrides.
+static constexpr uint32_t kNormalizeWideMin = 65536;
+hipError_t launch_g1_normalize(const void* in, int form, uint32_t n, void* out, hipStream_t stream, uint32_t* groups);
+
 // tracker_prove_kernels.hip: the small kernels of the batched tracker-proof generator (tracker_api.hip), n members.
 // Pairs: the 3 n (point, scalar) pairs of one launch_scalar_mul_batch, (G, k_i) | (G, b_i) | (rG_i, b_i): `decoded`
 // holds the 2 n decoded tracker records (rG_i, krG_i; a record that did not decode is all zero, which the chain reads

@@ -77,6 +77,7 @@ SYMBOLS = [
     "curdle_whisk_is_valid_tracker_proof_batch_ex", "curdle_whisk_is_valid_tracker_proof_batch_device", "curdle_stat_tracker",
     "curdle_g1_compress_batch", "curdle_g1_compress_batch_device",
     "curdle_whisk_generate_tracker_proof_batch_blinders", "curdle_whisk_generate_tracker_proof_batch", "curdle_stat_tracker_prove",
+    "curdle_g1_normalize_batch", "curdle_g1_normalize_batch_device", "curdle_g1_scalar_mul_batch_device", "curdle_stat_normalize",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -204,6 +205,11 @@ _g1_compress = _sig("curdle_g1_compress", C.c_int, _vp, _vp)
 _g1_decompress = _sig("curdle_g1_decompress", C.c_int, _vp, C.c_int, _vp)
 _g1_compress_batch = _sig("curdle_g1_compress_batch", C.c_int, _vp, C.c_size_t, _vp)
 _g1_compress_batch_device = _sig("curdle_g1_compress_batch_device", C.c_int, _vp, C.c_size_t, _vp, _vp)
+_g1_normalize_batch = _sig("curdle_g1_normalize_batch", C.c_int, _vp, C.c_int, C.c_size_t, _vp)
+_g1_normalize_batch_device = _sig("curdle_g1_normalize_batch_device", C.c_int, _vp, C.c_int, C.c_size_t, _vp, _vp)
+_scalar_mul_batch_device = _sig("curdle_g1_scalar_mul_batch_device", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp)
+_stat_normalize = _sig("curdle_stat_normalize", C.c_int, C.POINTER(C.c_ulonglong))
+G1_FORM_JAC, G1_FORM_XYZZ = 0, 1
 
 
 class CurdleError(RuntimeError):
@@ -1331,6 +1337,40 @@ def g1_compress_batch_device(ptr: int, n: int, out_ptr: int, stream=None) -> Non
     """The same for n points resident in device memory at `ptr` (any alignment); the n x 48 bytes are written to
     device memory at `out_ptr` in the stream's order and are complete when the call returns."""
     _check(_g1_compress_batch_device(ptr or None, n, out_ptr or None, stream or None))
+
+
+def g1_normalize_batch(points, form=None) -> np.ndarray:
+    """(n, 18) gnark G1Jac or (n, 24) XYZZ points -> (n, 12) gnark affine points on the GPU with a shared inversion
+    (curdle_g1_normalize_batch; gnark's BatchJacobianToAffineG1).  form: G1_FORM_JAC / G1_FORM_XYZZ, or None to take
+    it from the row length.  A denominator that is 0 mod p gives (0, 0)."""
+    points = np.ascontiguousarray(points, dtype=np.uint64)
+    if form is None:
+        form = {18: G1_FORM_JAC, 24: G1_FORM_XYZZ}[points.shape[-1]]
+    n = points.shape[0] if points.size else 0
+    out = np.zeros((n, 12), dtype=np.uint64)
+    _check(_g1_normalize_batch(_ptr(points), int(form), n, _ptr(out)))
+    return out
+
+
+def g1_normalize_batch_device(ptr: int, form: int, n: int, out_ptr: int, stream=None) -> None:
+    """The same for n points resident in device memory at `ptr`; the n x 96 bytes are written to device memory at
+    `out_ptr` in the stream's order and are complete when the call returns.  Both pointers are multiples of 16."""
+    _check(_g1_normalize_batch_device(ptr or None, int(form), n, out_ptr or None, stream or None))
+
+
+def g1_scalar_mul_batch_device(d_points: int, d_scalars: int, n_scalars: int, d_addends: int, n: int, d_out: int,
+                               stream=None) -> None:
+    """g1_scalar_mul_batch with everything resident (curdle_g1_scalar_mul_batch_device): d_out[i] = d_addends[i] +
+    d_scalars[i or 0] * d_points[i] as gnark affine records; d_addends may be 0, d_out may be d_points or d_addends."""
+    _check(_scalar_mul_batch_device(d_points or None, d_scalars or None, n_scalars, d_addends or None, n, d_out or None,
+                                    stream or None))
+
+
+def stat_normalize() -> dict:
+    """Points normalised on the device and inversion groups run since the library was loaded."""
+    out = (C.c_ulonglong * 2)()
+    _check(_stat_normalize(out))
+    return {"points": int(out[0]), "groups": int(out[1])}
 
 
 def g1_decompress(data: bytes, subgroup_check: bool = True) -> np.ndarray:

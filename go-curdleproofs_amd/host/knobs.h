@@ -45,6 +45,7 @@ enum Id {
   TRANSCRIPT_LANES,   // curdle_transcript_batch: members per wave (1..64); unset: by the batch's size
   GPU_PRELUDE,        // 1: the Whisk batch verifier takes its members' transcript preludes from curdle_transcript_batch, a chunk at a time; unset or 0: on the host
   TRACKER_DEVICE_HASH,  // the tracker batch's transcripts under CURDLE_TRACKER_HASH_DEFAULT: 1 hashed on the device, 0 on the host; unset: by the batch's size (tracker_api.hip)
+  NORMALIZE_LANE_POINTS,  // k_g1_normalize: points per lane, 1 or 8 (any other value: as unset); unset: 8 beyond 65,536 points (normalize_kernels.hip)
   COUNT
 };
 // The knob's value, or -1 if it is not set (every knob's valid values are >= 0).

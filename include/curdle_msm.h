@@ -693,6 +693,45 @@ int curdle_g1_check_jac_batch_device(const void* d_jac_points, size_t n, int sub
  *                                     memory; they are complete when the call returns. */
 int curdle_g1_compress_batch(const uint64_t* jac_points, size_t n, uint8_t* out);
 int curdle_g1_compress_batch_device(const void* d_jac_points, size_t n, void* d_out, void* stream);
+/* Batched normalisation ON THE GPU with a SHARED inversion: gnark's BatchJacobianToAffineG1, which the reference calls
+ * in 25 places (transcript/transcript.go:26, innerproductargument.go:238-280, ...).  n points in one of two forms ->
+ * n gnark G1Affine records (12 limbs: x then y, canonical Montgomery limbs), the layout of every base array of this
+ * library (curdle_msm_g1_device, curdle_dbases_create): a device result can be the next call's device input, where
+ * the reference copies down, normalises on one core and copies back up (common/util.go:55-82, the fold steps and
+ * MultiExps of the inner-product and same-multiscalar arguments).
+ *   CURDLE_G1_FORM_JAC   gnark G1Jac, 18 limbs (X, Y, Z): x = X / Z^2, y = Y / Z^3; the denominator is Z
+ *   CURDLE_G1_FORM_XYZZ  24 limbs (X, Y, ZZ, ZZZ), what the point kernels of this library write: x = X / ZZ,
+ *                        y = Y / ZZZ for any non-zero ZZ and ZZZ; the denominator is ZZ ZZZ
+ * A point whose denominator is 0 mod p (decided on the reduced value: limbs that spell p count, and so does ZZ != 0
+ * with ZZZ = 0) is infinity whatever X and Y hold, and comes out as 12 zero limbs; it takes no part in the inversion
+ * its neighbours share.  One Fermat inversion serves a wave of 64 lanes with one point each (up to 65,536 points) or
+ * eight (beyond).  Nothing is checked: coordinates are taken as below 2^384 and the points as they are.
+ * n = 0: CURDLE_OK, nothing touched, no device needed.  Refused with CURDLE_EINVAL before anything is copied or
+ * launched: a null pointer with n > 0, an unknown form, n > 2^24, a device pointer that is not a multiple of 16 (any
+ * element offset into a hipMalloc'd array is one: 144, 192 and 96 are multiples of 16).  No host fallback: without a
+ * device the call fails with CURDLE_ENODEV.
+ *   curdle_g1_normalize_batch          points and records in host memory, in passes of 2^20 points
+ *   curdle_g1_normalize_batch_device   both resident in device memory and not overlapping; `stream` is a hipStream_t
+ *                                      or NULL for the library's own stream, as in curdle_g1_compress_batch_device:
+ *                                      the points are read and the records written in that stream's order, and the
+ *                                      records are complete when the call returns. */
+#define CURDLE_G1_FORM_JAC 0
+#define CURDLE_G1_FORM_XYZZ 1
+int curdle_g1_normalize_batch(const uint64_t* points, int form, size_t n, uint64_t* out_affine);
+int curdle_g1_normalize_batch_device(const void* d_points, int form, size_t n, void* d_out_affine, void* stream);
+/* curdle_g1_scalar_mul_batch with everything resident: d_out_affine[i] = d_addends[i] + d_scalars[i] * d_points[i],
+ * i < n, gnark affine records in and out ((0, 0) = infinity), Montgomery fr.Elements; n_scalars = n, or 1 for one
+ * shared scalar; d_addends may be NULL.  The multiplications run into the library's workspace and are normalised from
+ * there with the shared inversion above, so d_out_affine may be d_points or d_addends (in place) and may go straight
+ * to curdle_msm_g1_device as bases.  `stream`, completion and the pointer rule (every device pointer a multiple of
+ * 16) are those of curdle_g1_normalize_batch_device; n > 2^24 or n_scalars neither n nor 1: CURDLE_EINVAL before any
+ * device work.  Like curdle_g1_scalar_mul_batch it is NOT constant time in the scalars (the chain branches on their
+ * bits), and the workspace that held the unnormalised results is not wiped. */
+int curdle_g1_scalar_mul_batch_device(const void* d_points, const void* d_scalars, size_t n_scalars,
+                                      const void* d_addends, size_t n, void* d_out_affine, void* stream);
+/* Diagnostics: out[0] points normalised on the device since the library was loaded, out[1] inversion groups run
+ * (one Fermat inversion each; at most one per 64 points of a launch). */
+int curdle_stat_normalize(unsigned long long out[2]);
 /* curdle_verify_batch with that check on every member's 4 ell instance points and on its M (range, curve equation,
  * subgroup), ON THE GPU and BESIDE the verification: producer threads gather the points of a chunk of members (at most
  * 32,768 points, so that the check runs on four lanes per point; only a single member beyond ell = 8,192 is more) into
