@@ -273,6 +273,14 @@ hipError_t launch_tracker_gather(const uint8_t* trackers, const uint8_t* k_comms
 hipError_t launch_tracker_challenge(const void* challenges, const uint8_t* tr_status, uint32_t n, void* scalars,
                                     uint8_t* skip, hipStream_t stream);
 
+// tracker_own_kernels.hip: does key j own tracker t, one (key, tracker) pair per quad and 64 trackers of ONE key per
+// block, so that every tested key bit is wave-uniform.  points: decoded records, rG_t at 2 t and krG_t at 2 t + 1, with
+// their CURDLE_DECODE_* status bytes (subgroup test included); keys: Montgomery fr.Elements, 16-byte aligned.  One
+// launch covers trackers [t0, t0 + cnt) of keys [key0, key0 + nkeys), nkeys <= 65,535 (a grid dimension), and writes
+// out[key * stride + t] = CURDLE_TRACKER_NOT_OWNED / _OWNED / _BAD (a status beyond CURDLE_DECODE_INFINITY: no chain).
+hipError_t launch_tracker_own(const void* points, const uint8_t* status, const void* keys, uint32_t t0, uint32_t cnt,
+                              uint32_t key0, uint32_t nkeys, uint8_t* out, size_t stride, hipStream_t stream);
+
 // compress_kernels.hip: n points in memory -> n x 48 bytes of gnark's compressed encoding (G1Affine.Bytes), one lane
 // per point.  form kCompressJac: gnark G1Jac, 144 bytes each (Z = 0: infinity); kCompressXyzz: G1XYZZ in gnark limbs,
 // 192 bytes each, as launch_scalar_mul_batch writes it (ZZ = 0: infinity).  `in` and `out` may have any alignment.

@@ -1,0 +1,196 @@
+// C ABI of the ownership search over Whisk trackers (tracker_own_kernels.hip): curdle_whisk_find_own_trackers /
+// _device, owned[j * n + i] = does key j own tracker i, for m keys and n trackers in one call.  (The single form,
+// curdle_whisk_is_own_tracker, is host code: host/proto_api.cpp.)
+//
+// The call takes ONE MSM slot for its buffers and its stream, like the tracker batch (tracker_api.hip); no stream is
+// made here and nothing is allocated once the slot's buffers have grown.  Per pass of at most kOwnPass trackers:
+//   1. the pass's 2 x 48-byte records ARE the decoder's input: they go up as they are (or are read where the caller
+//      keeps them: _device) and are decoded ONCE, subgroup test included (launch_g1_decompress), for all keys;
+//   2. k_tracker_own runs over the (key, tracker) grid in launches of at most TRACKER_OWN_PAIRS quads, back to back
+//      on the one stream (own_launches below is the rule);
+//   3. the verdict bytes of the pass come back once (host form), with the 2 x status bytes that count the bad pairs.
+// The keys are secrets: see wipe().
+#include "msm_internal.h"
+
+#include <algorithm>
+
+namespace {
+constexpr size_t kOwnMaxTrackers = (size_t)1 << 20;
+constexpr size_t kOwnMaxKeys = 65535;
+constexpr size_t kOwnMaxPairs = (size_t)1 << 24;
+constexpr size_t kOwnPass = (size_t)1 << 17;  // trackers per pass: 262,144 records, 25 MB of decoded points
+constexpr size_t kOwnWave = 16;               // quads of a wave
+// Quads per launch where the knob says nothing.  A full launch of 2^18 quads was measured at 12.3 ms (DESIGN.md
+// section 0, profiles/r16_tracker_own.json), so no single launch holds a shared GPU for long.
+constexpr size_t kOwnPairsDefault = (size_t)1 << 18;
+
+// pairs answered on the device | launches | those of the pairs answered BAD; completed passes only
+std::atomic<unsigned long long> g_own_stat[3];
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+size_t pairs_per_launch() {
+  const long long knob = knobs::get(knobs::TRACKER_OWN_PAIRS);
+  const size_t v = knob < 0 ? kOwnPairsDefault : (size_t)knob;
+  return std::max(kOwnWave, v / kOwnWave * kOwnWave);  // whole waves, at least one
+}
+
+// The launch rule of one pass of `cnt` trackers and m keys, with at most `pairs` quads a launch.  Every key's trackers
+// are padded to whole waves: w = 16 ceil(cnt / 16) quads.  The tracker dimension is cut into chunks of tc = min(w,
+// pairs) quads, and a launch takes one chunk of min(65,535, pairs / tc) keys (at least one).
+struct OwnRule {
+  size_t tc, keys;
+};
+OwnRule own_rule(size_t cnt, size_t pairs) {
+  const size_t w = (cnt + kOwnWave - 1) / kOwnWave * kOwnWave;
+  OwnRule r;
+  r.tc = std::min(w, pairs);
+  r.keys = std::min<size_t>(kOwnMaxKeys, std::max<size_t>(1, pairs / r.tc));
+  return r;
+}
+
+// The launches of one pass over decoded records; *launches: how many.
+int own_launches(const void* d_points, const uint8_t* d_status, const void* d_keys, size_t cnt, size_t m, uint8_t* d_out,
+                 size_t stride, hipStream_t st, unsigned long long* launches) {
+  const OwnRule rule = own_rule(cnt, pairs_per_launch());
+  *launches = 0;
+  for (size_t t0 = 0; t0 < cnt; t0 += rule.tc)
+    for (size_t k0 = 0; k0 < m; k0 += rule.keys) {
+      HIP_TRY(launch_tracker_own(d_points, d_status, d_keys, (uint32_t)t0, (uint32_t)std::min(rule.tc, cnt - t0),
+                                 (uint32_t)k0, (uint32_t)std::min(rule.keys, m - k0), d_out, stride, st));
+      ++*launches;
+    }
+  return CURDLE_OK;
+}
+
+struct OwnCall {
+  Slot& S;
+  hipStream_t st;
+  size_t m;
+  // the library's copies of the keys (null: none yet); the caller's own d_ks is never one of them
+  void* d_keys = nullptr;
+  void* h_keys = nullptr;
+  // Overwrites them, on the call's stream and behind everything queued there; called on every way out.  The kernel
+  // keeps the keys and their split halves in registers only.
+  int wipe() {
+    hipError_t e = hipSuccess, e2;
+    if (d_keys && (e2 = hipMemsetAsync(d_keys, 0, 32 * m, st)) != hipSuccess) e = e2;
+    if ((e2 = hipStreamSynchronize(st)) != hipSuccess) e = e2;
+    if (h_keys) explicit_bzero(h_keys, 32 * m);
+    if (e != hipSuccess) return fail(CURDLE_EHIP, "own trackers: clearing the keys: %s", hipGetErrorString(e));
+    return CURDLE_OK;
+  }
+};
+
+// trackers / ks: host memory (resident false) or device memory; owned likewise.
+int own_run(OwnCall& C, const uint8_t* trackers, size_t n, const uint64_t* ks, bool resident, uint8_t* owned) {
+  Slot& S = C.S;
+  const hipStream_t st = C.st;
+  const size_t m = C.m, cap = std::min(n, kOwnPass);
+  int r;
+  if ((r = ensure(S.points, 192 * cap))) return r;  // decoded records
+  if ((r = ensure(S.counts, 2 * cap))) return r;    // their statuses
+  if ((r = ensure_pinned(S, 1, 2 * cap + (resident ? 0 : m * cap)))) return r;  // statuses | verdicts
+  uint8_t* h_status = static_cast<uint8_t*>(S.h_stage[1]);
+  uint8_t* h_owned = h_status + 2 * cap;
+  uint8_t* d_status = static_cast<uint8_t*>(S.counts.p);
+  const void* d_keys = ks;
+  uint8_t* h_trk = nullptr;
+  if (!resident) {
+    if ((r = ensure(S.scalars, 96 * cap))) return r;  // compressed records
+    if ((r = ensure(S.digits, 32 * m))) return r;     // keys
+    if ((r = ensure(S.sorted, m * cap))) return r;    // verdicts of a pass, one row of the pass's trackers per key
+    const size_t keys_at = (96 * cap + 255) / 256 * 256;  // trackers | keys
+    if ((r = ensure_pinned(S, 0, keys_at + 32 * m))) return r;
+    h_trk = static_cast<uint8_t*>(S.h_stage[0]);
+    C.h_keys = h_trk + keys_at;
+    memcpy(C.h_keys, ks, 32 * m);
+    C.d_keys = S.digits.p;
+    HIP_TRY(hipMemcpyAsync(C.d_keys, C.h_keys, 32 * m, hipMemcpyHostToDevice, st));
+    d_keys = C.d_keys;
+  }
+  for (size_t lo = 0; lo < n; lo += kOwnPass) {
+    const size_t cnt = std::min(kOwnPass, n - lo);
+    const uint8_t* d_rec = trackers + 96 * lo;
+    if (!resident) {
+      memcpy(h_trk, trackers + 96 * lo, 96 * cnt);
+      HIP_TRY(hipMemcpyAsync(S.scalars.p, h_trk, 96 * cnt, hipMemcpyHostToDevice, st));
+      d_rec = static_cast<const uint8_t*>(S.scalars.p);
+    }
+    HIP_TRY(launch_g1_decompress(d_rec, (uint32_t)(2 * cnt), 1, (uint32_t*)S.points.p, d_status, st));
+    unsigned long long launches = 0;
+    if (resident) {
+      if ((r = own_launches(S.points.p, d_status, d_keys, cnt, m, owned + lo, n, st, &launches))) return r;
+    } else {
+      if ((r = own_launches(S.points.p, d_status, d_keys, cnt, m, static_cast<uint8_t*>(S.sorted.p), cnt, st, &launches))) return r;
+      HIP_TRY(hipMemcpyAsync(h_owned, S.sorted.p, m * cnt, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(h_status, d_status, 2 * cnt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!resident)
+      for (size_t j = 0; j < m; j++) memcpy(owned + j * n + lo, h_owned + j * cnt, cnt);
+    unsigned long long bad = 0;
+    for (size_t i = 0; i < cnt; i++)
+      bad += h_status[2 * i] > CURDLE_DECODE_INFINITY || h_status[2 * i + 1] > CURDLE_DECODE_INFINITY;
+    g_own_stat[0].fetch_add(cnt * m, std::memory_order_relaxed);  // the pass is complete: its three counters move together
+    g_own_stat[1].fetch_add(launches, std::memory_order_relaxed);
+    g_own_stat[2].fetch_add(bad * m, std::memory_order_relaxed);
+  }
+  return CURDLE_OK;
+}
+
+int own_through_slot(const uint8_t* trackers, size_t n, const uint64_t* ks, size_t m, bool resident, uint8_t* owned,
+                     void* user_stream) {
+  Ctx& cx = cur();
+  int idx;
+  int rc = acquire_slot(cx, true, &idx);
+  if (rc) return rc;
+  Slot& S = cx.slots[idx];
+  OwnCall C{S, user_stream ? (hipStream_t)user_stream : S.stream, m};
+  auto body = [&]() -> int {
+    HIP_TRY(hipSetDevice(cx.device));
+    return own_run(C, trackers, n, ks, resident, owned);
+  };
+  rc = body();
+  const int w = C.wipe();  // synchronises the stream: nothing queued outlives the slot's hold, nothing of the keys stays
+  release_slot(cx, idx);
+  return rc ? rc : w;
+}
+
+int check_counts(size_t n, size_t m) {
+  if (n > kOwnMaxTrackers) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^20 trackers", n);
+  if (m > kOwnMaxKeys) return fail(CURDLE_EINVAL, "m = %zu exceeds the supported 65,535 keys", m);
+  if (m * n > kOwnMaxPairs) return fail(CURDLE_EINVAL, "m * n = %zu exceeds the supported 2^24 pairs", m * n);
+  return CURDLE_OK;
+}
+}  // namespace
+
+extern "C" int curdle_whisk_find_own_trackers(const uint8_t* trackers, size_t n, const uint64_t* ks, size_t m,
+                                              uint8_t* owned) {
+  if (n == 0 || m == 0) return CURDLE_OK;
+  int rc;
+  if (!trackers || !ks || !owned)
+    rc = fail(CURDLE_EINVAL, "null argument");
+  else if ((rc = check_counts(n, m)) == CURDLE_OK)
+    rc = own_through_slot(trackers, n, ks, m, false, owned, nullptr);
+  size_t bytes;
+  if (rc != CURDLE_OK && owned && !__builtin_mul_overflow(m, n, &bytes))  // "could not compute" never reads as a verdict
+    memset(owned, CURDLE_TRACKER_UNKNOWN, bytes);
+  return rc;
+}
+
+extern "C" int curdle_whisk_find_own_trackers_device(const void* d_trackers, size_t n, const void* d_ks, size_t m,
+                                                     void* d_owned, void* stream) {
+  if (n == 0 || m == 0) return CURDLE_OK;
+  if (!d_trackers || !d_ks || !d_owned) return fail(CURDLE_EINVAL, "null argument");
+  if (int rc = check_counts(n, m)) return rc;
+  if (!aligned16(d_trackers) || !aligned16(d_ks)) return fail(CURDLE_EINVAL, "d_trackers and d_ks must be multiples of 16");
+  return own_through_slot(static_cast<const uint8_t*>(d_trackers), n, static_cast<const uint64_t*>(d_ks), m, true,
+                          static_cast<uint8_t*>(d_owned), stream);
+}
+
+extern "C" int curdle_stat_tracker_own(unsigned long long out[3]) {
+  if (!out) return CURDLE_EINVAL;
+  for (int i = 0; i < 3; i++) out[i] = g_own_stat[i].load(std::memory_order_relaxed);
+  return CURDLE_OK;
+}

@@ -77,6 +77,7 @@ SYMBOLS = [
     "curdle_whisk_is_valid_tracker_proof_batch_ex", "curdle_whisk_is_valid_tracker_proof_batch_device", "curdle_stat_tracker",
     "curdle_g1_compress_batch", "curdle_g1_compress_batch_device",
     "curdle_whisk_generate_tracker_proof_batch_blinders", "curdle_whisk_generate_tracker_proof_batch", "curdle_stat_tracker_prove",
+    "curdle_whisk_is_own_tracker", "curdle_whisk_find_own_trackers", "curdle_whisk_find_own_trackers_device", "curdle_stat_tracker_own",
     "curdle_g1_normalize_batch", "curdle_g1_normalize_batch_device", "curdle_g1_scalar_mul_batch_device", "curdle_stat_normalize",
 ]
 
@@ -197,6 +198,10 @@ _whisk_gen_tracker_batch_blinders = _sig("curdle_whisk_generate_tracker_proof_ba
                                          _vp, _vp)
 _whisk_gen_tracker_batch = _sig("curdle_whisk_generate_tracker_proof_batch", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp)
 _stat_tracker_prove = _sig("curdle_stat_tracker_prove", C.c_int, C.POINTER(C.c_ulonglong))
+_whisk_is_own_tracker = _sig("curdle_whisk_is_own_tracker", C.c_int, _vp, _vp, C.POINTER(C.c_int))
+_whisk_find_own = _sig("curdle_whisk_find_own_trackers", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp)
+_whisk_find_own_device = _sig("curdle_whisk_find_own_trackers_device", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp)
+_stat_tracker_own = _sig("curdle_stat_tracker_own", C.c_int, C.POINTER(C.c_ulonglong))
 _verify_set_eager = _sig("curdle_verify_set_eager", C.c_int, C.c_int)
 _reencode = _sig("curdle_proof_reencode", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t))
 _merlin_tv = _sig("curdle_merlin_test_vector", C.c_int, C.c_char_p, C.c_char_p, _vp, C.c_size_t, C.c_char_p, _vp,
@@ -1141,6 +1146,53 @@ def stat_tracker_prove() -> dict:
     out = (C.c_ulonglong * 2)()
     _check(_stat_tracker_prove(out))
     return {"device": out[0], "host": out[1]}
+
+
+TRACKER_NOT_OWNED, TRACKER_OWNED, TRACKER_BAD, TRACKER_UNKNOWN = 0, 1, 2, 255
+
+
+def whisk_is_own_tracker(tracker: bytes, k) -> bool:
+    """Does k (Montgomery fr limbs) own the 96-byte tracker rG || krG: k rG == krG, infinity included
+    (curdle_whisk_is_own_tracker; host only).  CurdleError with EINVAL if a record does not decode."""
+    if len(tracker) != 96:
+        raise ValueError("tracker 96 B")
+    t, kk = _bytes_arr(tracker), _as_u64(k, 4)
+    owned = C.c_int(0)
+    _check(_whisk_is_own_tracker(_ptr(t), _ptr(kk), C.byref(owned)))
+    return bool(owned.value)
+
+
+def whisk_find_own_trackers(trackers, ks) -> np.ndarray:
+    """m keys against n trackers on the GPU (curdle_whisk_find_own_trackers): a list of 96-byte trackers (or a uint8
+    array of n x 96 bytes) and ks (m, 4), Montgomery fr limbs.  Returns uint8[m, n]: TRACKER_OWNED, TRACKER_NOT_OWNED,
+    or TRACKER_BAD in the whole column of a tracker with a record that does not decode."""
+    if isinstance(trackers, np.ndarray):
+        t = np.ascontiguousarray(trackers, dtype=np.uint8).reshape(-1)
+        if t.size % 96:
+            raise ValueError("tracker 96 B")
+    else:
+        if any(len(x) != 96 for x in trackers):
+            raise ValueError("tracker 96 B")
+        t = _bytes_arr(b"".join(trackers))
+    kk = _as_u64(ks, 4).reshape(-1, 4)
+    n, m = t.size // 96, len(kk)
+    owned = np.full((m, n), TRACKER_UNKNOWN, dtype=np.uint8)
+    _check(_whisk_find_own(_ptr(t) if n else None, n, _ptr(kk) if m else None, m, _ptr(owned) if m * n else None))
+    return owned
+
+
+def whisk_find_own_trackers_device(d_trackers: int, n: int, d_ks: int, m: int, d_owned: int, stream=None) -> None:
+    """The same over resident arrays (curdle_whisk_find_own_trackers_device): HIP device pointers to n x 96 bytes,
+    m x 32 bytes (both multiples of 16) and m x n bytes; stream: a hipStream_t or None.  d_owned is complete when the
+    call returns."""
+    _check(_whisk_find_own_device(d_trackers or None, n, d_ks or None, m, d_owned or None, stream or None))
+
+
+def stat_tracker_own() -> dict:
+    """(key, tracker) pairs answered on the device, launches of the ownership kernel, pairs answered TRACKER_BAD."""
+    out = (C.c_ulonglong * 3)()
+    _check(_stat_tracker_own(out))
+    return {"pairs": int(out[0]), "launches": int(out[1]), "bad": int(out[2])}
 
 
 _set_dev_acc = _sig("curdle_verify_set_device_acc", C.c_int, C.c_int)

@@ -46,6 +46,7 @@ enum Id {
   GPU_PRELUDE,        // 1: the Whisk batch verifier takes its members' transcript preludes from curdle_transcript_batch, a chunk at a time; unset or 0: on the host
   TRACKER_DEVICE_HASH,  // the tracker batch's transcripts under CURDLE_TRACKER_HASH_DEFAULT: 1 hashed on the device, 0 on the host; unset: by the batch's size (tracker_api.hip)
   NORMALIZE_LANE_POINTS,  // k_g1_normalize: points per lane, 1 or 8 (any other value: as unset); unset: 8 beyond 65,536 points (normalize_kernels.hip)
+  TRACKER_OWN_PAIRS,      // curdle_whisk_find_own_trackers: (key, tracker) quads per launch of k_tracker_own, rounded down to whole waves of 16, at least 16; unset: 2^18 (tracker_own_api.hip)
   COUNT
 };
 // The knob's value, or -1 if it is not set (every knob's valid values are >= 0).

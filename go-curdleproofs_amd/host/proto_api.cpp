@@ -429,6 +429,17 @@ extern "C" int curdle_whisk_generate_tracker_proof(const uint8_t* tracker, const
   });
 }
 
+extern "C" int curdle_whisk_is_own_tracker(const uint8_t* tracker, const uint64_t k[4], int* owned) {
+  if (!tracker || !k || !owned) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  *owned = 0;
+  return Guard([&]() {
+    whisk::WhiskTracker t;
+    memcpy(&t, tracker, 96);
+    *owned = whisk::IsOwnWhiskTracker(t, Scalar::FromMont(k)) ? 1 : 0;
+    return CURDLE_OK;
+  });
+}
+
 extern "C" int curdle_verify_set_eager(int eager) { return proto::SetEagerChecks(eager); }
 
 // Round trip of the wire format: decode, re-encode (curdleproof_test.go "encode/decode").

@@ -490,5 +490,16 @@ void GenerateWhiskTrackerProofWithBlinder(const WhiskTracker& tracker, const Sca
   TrackerProofCore(rG, krG, k, blinder, out);
 }
 
+bool IsOwnWhiskTracker(const WhiskTracker& tracker, const Scalar& k) {
+  Point rG, krG;
+  try {
+    rG = SetBytes(tracker.rG, "rG");
+    krG = SetBytes(tracker.krG, "krG");
+  } catch (const std::runtime_error& e) {
+    throw err(std::string("deserializing rG and krG: ") + e.what());
+  }
+  return rG.Mul(k) == krG;  // one GLV chain; the comparison is projective
+}
+
 }  // namespace whisk
 }  // namespace curdle

@@ -63,6 +63,9 @@ void GenerateWhiskTrackerProof(const WhiskTracker& tracker, const alg::Scalar& k
 // member to whose transcript the device could not finish.  The same bytes as the call above for the same blinder.
 void GenerateWhiskTrackerProofWithBlinder(const WhiskTracker& tracker, const alg::Scalar& k, const alg::Scalar& blinder,
                                           uint8_t out[TRACKER_PROOF_SIZE]);
+// Does k own the tracker: k rG == krG as group elements, infinity included (computeTracker, whisk_test.go:98-104,
+// read backwards).  Throws like GenerateWhiskTrackerProof if rG or krG does not decode (curve and subgroup).
+bool IsOwnWhiskTracker(const WhiskTracker& tracker, const alg::Scalar& k);
 
 }  // namespace whisk
 }  // namespace curdle

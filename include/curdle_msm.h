@@ -458,6 +458,44 @@ int curdle_whisk_generate_tracker_proof_batch(const uint8_t* trackers, const uin
 /* Diagnostics: members of generated batches since the library was loaded, out[0] generated on the device, out[1]
  * handed to the host single path after a non-zero transcript status. */
 int curdle_stat_tracker_prove(unsigned long long out[2]);
+/* Which trackers does a key own?  A tracker is (rG, krG) with krG = k rG (computeTracker, whisk_test.go:98-104); a
+ * client that did not make the tracker learns whether it is its own by evaluating k rG == krG.
+ * The single form, host only, no device needed: *owned = 1 iff k rG and krG are the same group element, infinity a
+ * group element like any other (k = 0 owns exactly the trackers whose krG is infinity; a tracker with rG = infinity
+ * is owned by every key iff its krG is infinity; krG = -(k rG) is not owned), else 0.  Both records are decoded as
+ * gnark's SetBytes does (curve and subgroup, whisk/types.go:85-95): if either does not decode the call returns
+ * CURDLE_EINVAL, as curdle_whisk_generate_tracker_proof does, and *owned is 0.  k: a Montgomery fr.Element. */
+int curdle_whisk_is_own_tracker(const uint8_t tracker[CURDLE_WHISK_TRACKER_SIZE], const uint64_t k[4], int* owned);
+/* m keys against n trackers ON THE GPU: owned[j * n + i], one byte, answers key j (ks + 4 j, Montgomery fr.Element)
+ * and tracker i (trackers + 96 i) as the single form answers them: */
+#define CURDLE_TRACKER_NOT_OWNED 0
+#define CURDLE_TRACKER_OWNED 1
+#define CURDLE_TRACKER_BAD 2       /* rG or krG is not the encoding of a point of the subgroup */
+#define CURDLE_TRACKER_UNKNOWN 255 /* the call failed: never reads as a verdict */
+/* A tracker with a record that does not decode has CURDLE_TRACKER_BAD in its byte for EVERY key; its neighbours are
+ * unaffected.  The 2 n records are decoded once (curve and subgroup) for all keys, in passes of 131,072 trackers;
+ * every (key, tracker) pair is one 255-bit scalar multiplication through the GLV split with an exact equality test
+ * on the device, in launches of at most CURDLE_TRACKER_OWN_PAIRS pairs (knob; 262,144) back to back on one stream.
+ * n = 0 or m = 0: CURDLE_OK, nothing read or written, no device needed.  Null pointers otherwise: CURDLE_EINVAL.
+ * Limits: n <= 2^20, m <= 65,535, m n <= 2^24; beyond them CURDLE_EINVAL with the limit named in curdle_last_error,
+ * before anything is copied or launched.  On a negative return `owned` is filled with CURDLE_TRACKER_UNKNOWN.  No
+ * host fallback: without a device the call fails with CURDLE_ENODEV.  The call takes one MSM slot for its buffers.
+ * SECRETS.  ks are secrets.  The device buffer and the pinned staging that held them are overwritten (on the stream
+ * that used them) before the call returns on every path; the kernel keeps a key and the two halves of its split in
+ * registers only.  The scalar-multiplication chain BRANCHES ON KEY BITS, as the host path and gnark's
+ * ScalarMultiplication do: its running time depends on the keys. */
+int curdle_whisk_find_own_trackers(const uint8_t* trackers, size_t n, const uint64_t* ks, size_t m, uint8_t* owned);
+/* The same over arrays resident in device memory: HIP device pointers to n x 96 bytes, m x 32 bytes and m x n bytes.
+ * d_trackers and d_ks must be multiples of 16 (CURDLE_EINVAL otherwise); d_owned may have any alignment.  `stream` is
+ * a hipStream_t or NULL for the library's own stream, as in curdle_msm_g1_device: the arrays are read and d_owned is
+ * written in that stream's order, and d_owned is complete when the call returns.  The caller's d_ks is read where it
+ * is and not touched: the library makes no copy of the keys in this form. */
+int curdle_whisk_find_own_trackers_device(const void* d_trackers, size_t n, const void* d_ks, size_t m,
+                                          void* d_owned, void* stream);
+/* Diagnostics since the library was loaded: out[0] (key, tracker) pairs answered on the device, out[1] launches of
+ * the ownership kernel, out[2] those of the pairs that were answered CURDLE_TRACKER_BAD without a chain.  The counters
+ * move when a tracker pass has completed: a pass that fails midway leaves its pairs and launches uncounted. */
+int curdle_stat_tracker_own(unsigned long long out[3]);
 /* ------------------------------------------------------------------------- *
  * Accumulator on the device
  *   msmaccumulator.AccumulateCheck / Verify (msmaccumulator/msmaccumulator.go:23-64) with
