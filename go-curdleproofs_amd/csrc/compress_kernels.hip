@@ -3,10 +3,13 @@
 // the device for a group element: until this kernel every result of a point kernel left as XYZZ and the host
 // normalised it; the batched tracker-proof generator (tracker_api.hip) hashes and emits kG, A and B from here.
 //
-// Two input forms, the template parameter:
+// Three input forms, the template parameter:
 //   kCompressJac   gnark G1Jac, 18 Montgomery u64 limbs (X, Y, Z): x = X / Z^2, y = Y / Z^3; Z = 0 is infinity;
 //   kCompressXyzz  G1XYZZ in gnark limbs, as k_scalar_mul_batch_quad writes it: x = X / ZZ, y = Y / ZZZ; ZZ = 0 is
-//                  infinity.
+//                  infinity;
+//   kCompressAffine gnark G1Affine, 96 bytes, as k_g1_normalize writes it: both coordinates zero is infinity.  Internal
+//                  (no CURDLE_G1_FORM_* value): the fixed-base calls (fbase_api.hip) normalise their XYZZ results with
+//                  ONE shared inversion per wave and encode the records here, where NOTHING is inverted.
 // Per point: infinity -> 0xC0 and 47 zero bytes, whatever X and Y hold.  Otherwise ONE inversion by Fermat
 // (invert28.h): 381 squarings and 120 products, table included.
 // Then x and y leave Montgomery form, x is written big-endian, and the flag is 0xA0 if y > (p-1)/2, else 0x80.
@@ -59,7 +62,7 @@ __device__ __forceinline__ bool load_coord(F28& r, const uint8_t* __restrict__ p
 template <int FORM>
 __global__ void __launch_bounds__(kBlock, 2)
     k_g1_compress(const uint8_t* __restrict__ in, u32 n, uint8_t* __restrict__ out) {
-  constexpr size_t kStride = FORM == kCompressJac ? 144 : 192;
+  constexpr size_t kStride = FORM == kCompressJac ? 144 : (FORM == kCompressXyzz ? 192 : 96);
   const u32 i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const uint8_t* src = in + kStride * (size_t)i;
@@ -82,6 +85,20 @@ __global__ void __launch_bounds__(kBlock, 2)
   };
   u32 xw[12], yw[12];
   F28 d, inv, a, c;
+  if constexpr (FORM == kCompressAffine) {
+    const bool any_x = load_coord(a, src, al_in), any_y = load_coord(c, src + 48, al_in);
+    if (!any_x && !any_y) {
+#pragma unroll
+      for (int k = 0; k < 11; k++) xw[k] = 0;
+      xw[11] = 0xc0000000u;
+      return put(xw);
+    }
+    to_canonical(xw, a);
+    to_canonical(yw, c);
+    const bool larger = cmp12([&](int k) { return yw[k]; }, [](int k) { return kHalfPm1(k); }) > 0;
+    xw[11] |= larger ? 0xa0000000u : 0x80000000u;
+    return put(xw);
+  }
   // the denominator: Z, or ZZ ZZZ (then 1 / ZZ = ZZZ / d and 1 / ZZZ = ZZ / d)
   const bool finite = load_coord(d, src + 96, al_in);  // Z | ZZ
   if (!finite) {
@@ -117,12 +134,14 @@ __global__ void __launch_bounds__(kBlock, 2)
 
 hipError_t launch_g1_compress(const void* in, int form, uint32_t n, uint8_t* out, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  if (form != kCompressJac && form != kCompressXyzz) return hipErrorInvalidValue;
+  if (form != kCompressJac && form != kCompressXyzz && form != kCompressAffine) return hipErrorInvalidValue;
   const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
   if (form == kCompressJac)
     hipLaunchKernelGGL(k_g1_compress<kCompressJac>, grid, block, 0, stream, (const uint8_t*)in, n, out);
-  else
+  else if (form == kCompressXyzz)
     hipLaunchKernelGGL(k_g1_compress<kCompressXyzz>, grid, block, 0, stream, (const uint8_t*)in, n, out);
+  else
+    hipLaunchKernelGGL(k_g1_compress<kCompressAffine>, grid, block, 0, stream, (const uint8_t*)in, n, out);
   return hipGetLastError();
 }
 

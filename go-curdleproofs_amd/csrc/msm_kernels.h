@@ -284,8 +284,19 @@ hipError_t launch_tracker_own(const void* points, const uint8_t* status, const v
 // compress_kernels.hip: n points in memory -> n x 48 bytes of gnark's compressed encoding (G1Affine.Bytes), one lane
 // per point.  form kCompressJac: gnark G1Jac, 144 bytes each (Z = 0: infinity); kCompressXyzz: G1XYZZ in gnark limbs,
 // 192 bytes each, as launch_scalar_mul_batch writes it (ZZ = 0: infinity).  `in` and `out` may have any alignment.
-static constexpr int kCompressJac = 0, kCompressXyzz = 1;
+// kCompressAffine (internal: no public CURDLE_G1_FORM_* value): gnark G1Affine records, 96 bytes each, as
+// launch_g1_normalize writes them (both coordinates zero: infinity); nothing is inverted.
+static constexpr int kCompressJac = 0, kCompressXyzz = 1, kCompressAffine = 2;
 hipError_t launch_g1_compress(const void* in, int form, uint32_t n, uint8_t* out, hipStream_t stream);
+
+// fbase_kernels.hip: out[i] = (scalars[i] * multipliers[i] mod r) * P as G1XYZZ in gnark limbs (all zero for
+// infinity), one lane per scalar, at most 32 mixed additions from table28: the 8,160 multiples d * 2^(8 w) * P of
+// curdle_host_fixed_base_table, entry w * 255 + d - 1, as launch_convert_points_raw converts them but kA28Bytes apart
+// (P's records only).  scalars / multipliers: Montgomery fr.Elements, multiples of 16; multipliers may be null.
+// READS TABLE ENTRIES AT ADDRESSES CHOSEN BY SCALAR DIGITS.
+static constexpr uint32_t kFbaseEntries = 32 * 255;
+hipError_t launch_fbase_mul(const void* table28, const void* scalars, const void* multipliers, uint32_t n, void* out_xyzz,
+                            hipStream_t stream);
 
 // normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion
 // per wave of 64 lanes with 1 or 8 points each (Montgomery's trick over a wave scan).  The forms are those of

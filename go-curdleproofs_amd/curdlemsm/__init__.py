@@ -79,6 +79,8 @@ SYMBOLS = [
     "curdle_whisk_generate_tracker_proof_batch_blinders", "curdle_whisk_generate_tracker_proof_batch", "curdle_stat_tracker_prove",
     "curdle_whisk_is_own_tracker", "curdle_whisk_find_own_trackers", "curdle_whisk_find_own_trackers_device", "curdle_stat_tracker_own",
     "curdle_g1_normalize_batch", "curdle_g1_normalize_batch_device", "curdle_g1_scalar_mul_batch_device", "curdle_stat_normalize",
+    "curdle_fbase_create", "curdle_fbase_free", "curdle_g1_fixed_base_mul_batch", "curdle_g1_fixed_base_mul_batch_device",
+    "curdle_stat_fbase", "curdle_whisk_compute_tracker", "curdle_whisk_k_commitment", "curdle_whisk_compute_trackers_batch",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -202,6 +204,14 @@ _whisk_is_own_tracker = _sig("curdle_whisk_is_own_tracker", C.c_int, _vp, _vp, C
 _whisk_find_own = _sig("curdle_whisk_find_own_trackers", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp)
 _whisk_find_own_device = _sig("curdle_whisk_find_own_trackers_device", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp)
 _stat_tracker_own = _sig("curdle_stat_tracker_own", C.c_int, C.POINTER(C.c_ulonglong))
+_fbase_create = _sig("curdle_fbase_create", C.c_int, _vp, C.POINTER(_vp))
+_fbase_free = _sig("curdle_fbase_free", None, _vp)
+_fbase_mul = _sig("curdle_g1_fixed_base_mul_batch", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, _vp)
+_fbase_mul_device = _sig("curdle_g1_fixed_base_mul_batch_device", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, _vp, _vp)
+_stat_fbase = _sig("curdle_stat_fbase", C.c_int, C.POINTER(C.c_ulonglong))
+_whisk_compute_tracker = _sig("curdle_whisk_compute_tracker", C.c_int, _vp, _vp, _vp)
+_whisk_k_commitment = _sig("curdle_whisk_k_commitment", C.c_int, _vp, _vp)
+_whisk_compute_trackers_batch = _sig("curdle_whisk_compute_trackers_batch", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp)
 _verify_set_eager = _sig("curdle_verify_set_eager", C.c_int, C.c_int)
 _reencode = _sig("curdle_proof_reencode", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t))
 _merlin_tv = _sig("curdle_merlin_test_vector", C.c_int, C.c_char_p, C.c_char_p, _vp, C.c_size_t, C.c_char_p, _vp,
@@ -1193,6 +1203,105 @@ def stat_tracker_own() -> dict:
     out = (C.c_ulonglong * 3)()
     _check(_stat_tracker_own(out))
     return {"pairs": int(out[0]), "launches": int(out[1]), "bad": int(out[2])}
+
+
+G1_OUT_AFFINE, G1_OUT_COMPRESSED = 0, 1
+
+
+class FBase:
+    """One G1 point's table of 8,160 multiples on the device (curdle_fbase): point is a gnark G1Affine, 12 Montgomery
+    limbs, on the curve, in the subgroup and not infinity (CurdleError with EINVAL otherwise)."""
+
+    def __init__(self, point):
+        p = _as_u64(point, 12).reshape(12)
+        h = _vp()
+        _check(_fbase_create(_ptr(p), C.byref(h)))
+        self._h = h
+
+    def free(self) -> None:
+        if self._h:
+            _fbase_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def fbase_create(point) -> FBase:
+    return FBase(point)
+
+
+def _fbase_handle(base):
+    if base is None:
+        return None                                   # the generator's table
+    if not base._h:
+        raise ValueError("the FBase was freed")
+    return base._h
+
+
+def g1_fixed_base_mul_batch(scalars, multipliers=None, base=None, out_form=G1_OUT_AFFINE) -> np.ndarray:
+    """out[i] = (scalars[i] * multipliers[i] mod r) * P on the GPU (curdle_g1_fixed_base_mul_batch): scalars and
+    multipliers (n, 4) Montgomery fr limbs, multipliers may be None; base an FBase or None for the generator.  Returns
+    (n, 12) uint64 affine records or (n, 48) uint8 compressed encodings."""
+    sc = _as_u64(scalars, 4).reshape(-1, 4)
+    n = len(sc)
+    mu = _as_u64(multipliers, 4).reshape(-1, 4) if multipliers is not None else None
+    if mu is not None and len(mu) != n:
+        raise ValueError("one multiplier per scalar")
+    out = np.zeros((n, 48), dtype=np.uint8) if out_form == G1_OUT_COMPRESSED else np.zeros((n, 12), dtype=np.uint64)
+    _check(_fbase_mul(_fbase_handle(base), _ptr(sc) if n else None,
+                      _ptr(mu) if mu is not None and n else None, n, int(out_form), _ptr(out) if n else None))
+    return out
+
+
+def g1_fixed_base_mul_batch_device(d_scalars: int, d_multipliers: int, n: int, d_out: int, base=None,
+                                   out_form=G1_OUT_AFFINE, stream=None) -> None:
+    """The same over resident arrays (curdle_g1_fixed_base_mul_batch_device): HIP device pointers, multiples of 16
+    except a compressed d_out; d_multipliers may be 0.  d_out is complete when the call returns and must not overlap
+    the inputs."""
+    _check(_fbase_mul_device(_fbase_handle(base), d_scalars or None, d_multipliers or None, n,
+                             int(out_form), d_out or None, stream or None))
+
+
+def stat_fbase() -> dict:
+    """Scalars multiplied by the fixed-base kernel, its launches, and tables built since the library was loaded."""
+    out = (C.c_ulonglong * 3)()
+    _check(_stat_fbase(out))
+    return {"scalars": int(out[0]), "launches": int(out[1]), "tables": int(out[2])}
+
+
+def whisk_compute_tracker(k, r) -> bytes:
+    """computeTracker (whisk_test.go:98-104) on the host: the 96 bytes r G | k r G for Montgomery fr limbs k, r."""
+    kk, rr = _as_u64(k, 4).reshape(4), _as_u64(r, 4).reshape(4)
+    out = np.zeros(96, dtype=np.uint8)
+    _check(_whisk_compute_tracker(_ptr(kk), _ptr(rr), _ptr(out)))
+    return bytes(out)
+
+
+def whisk_k_commitment(k) -> bytes:
+    """getKComm (whisk_test.go:106-109) on the host: the 48 bytes of k G."""
+    kk = _as_u64(k, 4).reshape(4)
+    out = np.zeros(48, dtype=np.uint8)
+    _check(_whisk_k_commitment(_ptr(kk), _ptr(out)))
+    return bytes(out)
+
+
+def whisk_compute_trackers_batch(ks, rs=None, commitments=True):
+    """n trackers and key commitments on the GPU (curdle_whisk_compute_trackers_batch): ks, rs (n, 4) Montgomery fr
+    limbs; rs None means r = 1.  Returns (trackers uint8[n, 96], commitments uint8[n, 48] or None)."""
+    kk = _as_u64(ks, 4).reshape(-1, 4)
+    n = len(kk)
+    rr = _as_u64(rs, 4).reshape(-1, 4) if rs is not None else None
+    if rr is not None and len(rr) != n:
+        raise ValueError("one r per k")
+    trackers = np.zeros((n, 96), dtype=np.uint8)
+    comms = np.zeros((n, 48), dtype=np.uint8) if commitments else None
+    _check(_whisk_compute_trackers_batch(_ptr(kk) if n else None, _ptr(rr) if rr is not None and n else None, n,
+                                         _ptr(trackers) if n else None, _ptr(comms) if comms is not None and n else None))
+    return trackers, comms
 
 
 _set_dev_acc = _sig("curdle_verify_set_device_acc", C.c_int, C.c_int)

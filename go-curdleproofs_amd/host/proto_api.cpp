@@ -440,6 +440,23 @@ extern "C" int curdle_whisk_is_own_tracker(const uint8_t* tracker, const uint64_
   });
 }
 
+extern "C" int curdle_whisk_compute_tracker(const uint64_t k[4], const uint64_t r[4], uint8_t* tracker_out) {
+  if (!k || !r || !tracker_out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  return Guard([&]() {
+    const whisk::WhiskTracker t = whisk::ComputeWhiskTracker(Scalar::FromMont(k), Scalar::FromMont(r));
+    memcpy(tracker_out, &t, 96);
+    return CURDLE_OK;
+  });
+}
+
+extern "C" int curdle_whisk_k_commitment(const uint64_t k[4], uint8_t* out) {
+  if (!k || !out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  return Guard([&]() {
+    whisk::WhiskKCommitment(Scalar::FromMont(k), out);
+    return CURDLE_OK;
+  });
+}
+
 extern "C" int curdle_verify_set_eager(int eager) { return proto::SetEagerChecks(eager); }
 
 // Round trip of the wire format: decode, re-encode (curdleproof_test.go "encode/decode").

@@ -501,5 +501,21 @@ bool IsOwnWhiskTracker(const WhiskTracker& tracker, const Scalar& k) {
   return rG.Mul(k) == krG;  // one GLV chain; the comparison is projective
 }
 
+namespace {
+const alg::FixedBase& GeneratorTable() {
+  static const alg::FixedBase table(Point::Generator().Affine());
+  return table;
+}
+}  // namespace
+
+WhiskTracker ComputeWhiskTracker(const Scalar& k, const Scalar& r) {
+  WhiskTracker t;
+  GeneratorTable().Mul(r).Compressed(t.rG);
+  GeneratorTable().Mul(k * r).Compressed(t.krG);  // k (r G) = (k r mod r) G
+  return t;
+}
+
+void WhiskKCommitment(const Scalar& k, uint8_t out[G1POINT_SIZE]) { GeneratorTable().Mul(k).Compressed(out); }
+
 }  // namespace whisk
 }  // namespace curdle

@@ -66,6 +66,10 @@ void GenerateWhiskTrackerProofWithBlinder(const WhiskTracker& tracker, const alg
 // Does k own the tracker: k rG == krG as group elements, infinity included (computeTracker, whisk_test.go:98-104,
 // read backwards).  Throws like GenerateWhiskTrackerProof if rG or krG does not decode (curve and subgroup).
 bool IsOwnWhiskTracker(const WhiskTracker& tracker, const alg::Scalar& k);
+// computeTracker, whisk_test.go:98-104: (r G, k r G), each a multiple of the generator from its FixedBase table.
+WhiskTracker ComputeWhiskTracker(const alg::Scalar& k, const alg::Scalar& r);
+// getKComm, whisk_test.go:106-109: k G in gnark's compressed form.
+void WhiskKCommitment(const alg::Scalar& k, uint8_t out[G1POINT_SIZE]);
 
 }  // namespace whisk
 }  // namespace curdle

@@ -497,6 +497,66 @@ int curdle_whisk_find_own_trackers_device(const void* d_trackers, size_t n, cons
  * move when a tracker pass has completed: a pass that fails midway leaves its pairs and launches uncounted. */
 int curdle_stat_tracker_own(unsigned long long out[3]);
 /* ------------------------------------------------------------------------- *
+ * Fixed-base scalar multiplication in G1 ON THE GPU; Whisk trackers in bulk
+ *   The first step of the tracker life cycle: tracker = (r G, k r G), commitment = k G (computeTracker and getKComm,
+ *   whisk/whisk_test.go:98-109), for every validator at once.  Every one of those points is a multiple of ONE point,
+ *   so k P is at most 32 mixed additions from a table d 2^(8 w) P of 32 windows x 255 digits and no doubling
+ *   (csrc/fbase_kernels.hip; the table is the host layer's curdle_host_fixed_base_table, converted once).
+ * ------------------------------------------------------------------------- */
+typedef struct curdle_fbase curdle_fbase; /* one point's table of 8,160 multiples on the device */
+/* point_affine: a gnark G1Affine.  It must be on the curve, in the prime-order subgroup and not infinity (checked on
+ * the host; the kernel's exactness argument needs the subgroup): CURDLE_EINVAL otherwise, the reason in
+ * curdle_last_error, *out null.  The table is built on the host and made resident on the calling thread's context
+ * (CURDLE_ENODEV without a device).  A handle follows curdle_dbases' rules: it keeps its multiples, makes its copy on
+ * another context when a call there first names it, and re-makes it after curdle_shutdown, so it stays usable until it
+ * is freed; curdle_fbase_free while a call reads the table is deferred to that call's end.  Null is a no-op. */
+int curdle_fbase_create(const uint64_t point_affine[12], curdle_fbase** out);
+void curdle_fbase_free(curdle_fbase* b);
+#define CURDLE_G1_OUT_AFFINE 0     /* n x 12 limbs, gnark G1Affine, as curdle_g1_normalize_batch writes them */
+#define CURDLE_G1_OUT_COMPRESSED 1 /* n x 48 bytes, gnark's compressed encoding */
+/* out[i] = (scalars[i] * multipliers[i] mod r) * P, or scalars[i] * P when multipliers is null; P is base's point, the
+ * G1 generator when base is null (its table is built at first use on a context, once however many threads race for
+ * it, and counts in curdle_stat_fbase).  scalars, multipliers: n Montgomery fr.Elements, below r.  Affine output is
+ * bit for bit what curdle_g1_normalize_batch gives for the same point (infinity: all zero), compressed output byte for
+ * byte what curdle_g1_compress gives (G1Affine.Bytes; infinity: 0xc0 and zeros).  The results are normalised with one
+ * shared inversion per wave; the compressed form encodes the records without a further inversion.
+ * The call takes one MSM slot and works in passes of at most CURDLE_FBASE_PASS scalars (knob; 1,048,576; rounded down
+ * to a multiple of 256, at least 256), one kernel launch each.  n = 0: CURDLE_OK, nothing read or written, no device
+ * needed.  A null scalars or out, or an unknown out_form: CURDLE_EINVAL.  Limit: n <= 2^24.  Every refusal comes
+ * before anything is copied or launched.  No host fallback: without a device the call fails with CURDLE_ENODEV.
+ * SECRETS.  scalars and multipliers are secrets.  The device buffers and the pinned staging that held them, and the
+ * unnormalised results, are overwritten (on the stream that used them) before the call returns on every path.  THE
+ * KERNEL READS TABLE ENTRIES AT ADDRESSES CHOSEN BY SCALAR DIGITS and skips zero digits: its memory access pattern
+ * and its running time depend on the scalars. */
+int curdle_g1_fixed_base_mul_batch(const curdle_fbase* base, const uint64_t* scalars, const uint64_t* multipliers,
+                                   size_t n, int out_form, void* out);
+/* The same over arrays resident in device memory: HIP device pointers, multiples of 16 (CURDLE_EINVAL otherwise)
+ * except a compressed d_out, which may have any alignment.  `stream` is a hipStream_t or NULL for the library's own,
+ * as in curdle_msm_g1_device; d_out is complete when the call returns.  The caller's arrays are read where they are:
+ * the library makes no copy of the scalars in this form.  d_out must not overlap d_scalars or d_multipliers: affine
+ * output in place over the scalars is NOT supported. */
+int curdle_g1_fixed_base_mul_batch_device(const curdle_fbase* base, const void* d_scalars, const void* d_multipliers,
+                                          size_t n, int out_form, void* d_out, void* stream);
+/* Diagnostics since the library was loaded: out[0] scalars multiplied on the device, out[1] launches of the
+ * fixed-base kernel, out[2] tables built (uploaded and converted, the generator's included).  The first two move when
+ * a pass has completed: a pass that fails midway leaves its scalars and its launch uncounted. */
+int curdle_stat_fbase(unsigned long long out[3]);
+/* computeTracker (whisk/whisk_test.go:98-104): tracker_out = r G | k r G, both in gnark's compressed encoding.  Host
+ * only, no device needed.  k, r: Montgomery fr.Elements.  k r = 0 gives the encoding of infinity, as Bytes() does. */
+int curdle_whisk_compute_tracker(const uint64_t k[4], const uint64_t r[4], uint8_t tracker_out[CURDLE_WHISK_TRACKER_SIZE]);
+/* getKComm (whisk/whisk_test.go:106-109): out = k G, compressed.  Host only. */
+int curdle_whisk_k_commitment(const uint64_t k[4], uint8_t out[48]);
+/* n of each at once ON THE GPU: trackers_out + 96 i = r_i G | k_i r_i G and k_commitments_out + 48 i = k_i G, byte for
+ * byte what the two single calls write for (ks + 4 i, rs + 4 i).  rs null: r = 1 for every member, the fork's initial
+ * trackers (G, k G).  k_commitments_out null: the commitments are not computed.  Per pass ONE launch of the
+ * fixed-base kernel over the generator's table for the 3 m (2 m) products of m members, one normalisation and one
+ * encoding; a pass is at most CURDLE_FBASE_PASS products.
+ * n = 0: CURDLE_OK, no device needed.  Null ks or trackers_out with n > 0: CURDLE_EINVAL.  Limit: n <= 2^22.  On a
+ * negative return both outputs are zero (a count beyond the limit is refused without touching them).  No host
+ * fallback: CURDLE_ENODEV without a device.  SECRETS: as curdle_g1_fixed_base_mul_batch. */
+int curdle_whisk_compute_trackers_batch(const uint64_t* ks, const uint64_t* rs, size_t n, uint8_t* trackers_out,
+                                        uint8_t* k_commitments_out);
+/* ------------------------------------------------------------------------- *
  * Accumulator on the device
  *   msmaccumulator.AccumulateCheck / Verify (msmaccumulator/msmaccumulator.go:23-64) with
  *   the base -> scalar map kept on the GPU as an array of scalar slots indexed by base, for
