@@ -130,6 +130,48 @@ def test_device_pointers_of_any_alignment(gpu, oracle, pool, off_in, off_out):
     assert (out[:off_out] == 0x5A).all() and (out[off_out + n * 48:] == 0x5A).all()     # nothing beyond the n x 48 bytes
 
 
+def sign_edge_case(oracle):
+    """The records of tests/golden/decode_edge_records.npz that pin the sign flag, each beside the affine point it
+    stands for: every record of the sign_edge and x_on_curve families and the order-3 points (0, +-2) of torsion.  The
+    record IS the expected encoding; nothing of this project computed it.  Every point comes as G1Jac with Z = 1,
+    Z = p - 1 and a seeded random Z.  Returns (limbs (3 k, 18), the 3 k records)."""
+    import os
+    from conftest import ROOT
+    z = np.load(os.path.join(ROOT, "tests", "golden", "decode_edge_records.npz"))
+    P, half = oracle.P, (oracle.P - 1) // 2
+    rng = np.random.default_rng(381)
+    limbs, want, near = [], [], set()
+    for fam, rec, ptb in zip(z["family"], z["records"], z["points"]):
+        b = ptb.tobytes()
+        pt = (int.from_bytes(b[:48], "big"), int.from_bytes(b[48:], "big"))
+        if not (fam in (b"sign_edge", b"x_on_curve") or (fam == b"torsion" and pt[0] == 0)):
+            continue
+        assert oracle.is_on_curve(pt) and pt[1] != half
+        for zc in (1, P - 1, int.from_bytes(rng.bytes(47), "big") + 2):
+            limbs.append(jac_limbs(oracle, pt, zc))
+            want.append(rec.tobytes())
+        if fam == b"sign_edge":
+            # what the family was built to be: y and (p - 1) / 2 differ in the lowest 32-bit word alone
+            assert pt[1] >> 32 == half >> 32
+            assert bool(rec[0] & 0x20) == (pt[1] > half)
+            near.add(int(rec[0]) & 0x20)
+    assert near == {0, 0x20}                                                    # both flags at the threshold
+    assert {w[0] for w in want if w[1:] == bytes(47)} == {0x80, 0xA0}           # ... and at x = 0
+    assert len(want) == 3 * (24 + 14 + 16)                                      # torsion holds (0, 2) and (0, -2) eight times each
+    return np.array(limbs, dtype=np.uint64), want
+
+
+def test_sign_edges_from_the_decode_fixture(gpu, oracle):
+    """y within 15 of (p - 1) / 2 on either side: only here can the low eleven words of the kernel's own copy of
+    (p - 1) / 2 change an output byte (the decoder's copy is pinned by the same records in test_decode_edges_gpu)."""
+    limbs, want = sign_edge_case(oracle)
+    got = gpu.g1_compress_batch(limbs)
+    assert got.shape == (len(want), 48) and got.dtype == np.uint8
+    for i, w in enumerate(want):
+        assert got[i].tobytes() == w, i
+        assert gpu.g1_compress(limbs[i]) == w, i
+
+
 def test_round_trip_through_the_decoder(gpu, oracle, pool):
     """decompress_batch(compress_batch(P)) == P for subgroup points and infinity."""
     pts = pool[:24] + [None]

@@ -258,8 +258,9 @@ def test_whisk_batch_over_both_contexts(two, oracle):
 
 def test_the_suite_above_with_two_logical_devices(gpu, tmp_path):
     """devices = {0, 0} cannot see a missing hipSetDevice: both contexts' streams, events and
-    allocations live on the one device whatever thread made them.  So the tests above run once
-    more, in a child process, under tools/logical_devices_shim.cpp: the one GPU reports TWO devices,
+    allocations live on the one device whatever thread made them.  So the tests above and those of
+    tests/test_multi_device_batches.py run once more, in a child process, under
+    tools/logical_devices_shim.cpp: the one GPU reports TWO devices,
     every stream / event / allocation is tagged with the logical device current at its creation,
     and a launch, event record or copy that mixes logical devices -- or a big-LDS launch whose
     opt-in was made on the other device -- fails the call.  The child must pass with no violation
@@ -272,8 +273,9 @@ def test_the_suite_above_with_two_logical_devices(gpu, tmp_path):
     # in front of whatever the environment already preloads, which stays
     preload = ":".join(p for p in (shim, os.environ.get("LD_PRELOAD", "")) if p)
     env = dict(os.environ, LD_PRELOAD=preload, CURDLE_TEST_DEVICES="0,1", CURDLE_LOGICAL_DEVICES="2")
-    p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_multi_device.py"), "-x", "-q",
-                        "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_multi_device.py"),
+                        os.path.join(ROOT, "tests", "test_multi_device_batches.py"), "-x", "-q", "-p", "no:cacheprovider"],
+                       env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     tail = p.stdout[-2500:] + p.stderr[-2500:]
     assert p.returncode == 0, tail
     assert "VIOLATION" not in p.stderr, tail

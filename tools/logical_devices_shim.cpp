@@ -7,10 +7,15 @@
 // punish it:
 //   * a kernel launch on a stream of another logical device than the calling thread's current one
 //   * an event recorded on a stream of another logical device than the event's
-//   * an asynchronous copy / memset whose device-side pointer belongs to another logical device
-//     than the stream it is queued on (legal in HIP with peer access, never intended here)
+//   * an asynchronous copy (hipMemcpyAsync, hipMemcpy2DAsync) / memset whose device-side pointer belongs to
+//     another logical device than the stream it is queued on (legal in HIP with peer access, never intended here)
+//   * hipEventElapsedTime over events of two logical devices
 //   * a launch with more than 64 KiB of dynamic LDS of a kernel whose hipFuncSetAttribute opt-in was
 //     not made while THIS logical device was current (the attribute is per device)
+// Of the HIP calls libcurdlemsm.so makes, the ones that pass through unchecked are legal from any device on real
+// hardware -- hipStreamSynchronize, hipStreamQuery, hipStreamWaitEvent (waiting for another device's event is what
+// events are for), hipFree, hipHostMalloc / hipHostFree (pinned host memory has no device) -- or name no handle the
+// shim could compare (hipMemcpyFromSymbol, hipGetLastError, hipDeviceGetStreamPriorityRange).
 // A violation is printed ("[logical-devices] VIOLATION ...") and the call fails with
 // hipErrorInvalidResourceHandle, so the library fails loudly; the summary at exit says how many
 // launches were checked on which logical devices.
@@ -277,6 +282,18 @@ hipError_t hipEventRecord(hipEvent_t ev, hipStream_t s) {
   }
   return fn(ev, s);
 }
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
+  REAL(hipEventElapsedTime);
+  int da = -1, db = -1;
+  {
+    std::lock_guard<std::mutex> g(g_mu);
+    auto ia = g_events.find((void*)a), ib = g_events.find((void*)b);
+    if (ia != g_events.end()) da = ia->second;
+    if (ib != g_events.end()) db = ib->second;
+  }
+  if (da >= 0 && db >= 0 && da != db) return violation("hipEventElapsedTime: events of different devices", da, db);
+  return fn(ms, a, b);
+}
 
 // ---- memory ----
 hipError_t hipMalloc(void** p, size_t n) {
@@ -309,6 +326,13 @@ hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind ki
   hipError_t e = check_ptr_on_stream("hipMemcpyAsync: destination of another device than the stream", dst, s);
   if (e == hipSuccess) e = check_ptr_on_stream("hipMemcpyAsync: source of another device than the stream", src, s);
   return e != hipSuccess ? e : fn(dst, src, n, kind, s);
+}
+hipError_t hipMemcpy2DAsync(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind,
+                            hipStream_t s) {
+  REAL(hipMemcpy2DAsync);
+  hipError_t e = check_ptr_on_stream("hipMemcpy2DAsync: destination of another device than the stream", dst, s);
+  if (e == hipSuccess) e = check_ptr_on_stream("hipMemcpy2DAsync: source of another device than the stream", src, s);
+  return e != hipSuccess ? e : fn(dst, dpitch, src, spitch, width, height, kind, s);
 }
 hipError_t hipMemsetAsync(void* dst, int v, size_t n, hipStream_t s) {
   REAL(hipMemsetAsync);
