@@ -4,7 +4,7 @@
 // The checked verifier lives here, with the backend, and calls the exported curdle_verify*: nothing under host/
 // refers to these symbols, so the host-only build (tests/hostbuild) links as before.  The checked BATCH verifier
 // (curdle_verify_batch_checked, at the end) hands the host layer its per-chunk check as a callback (host/batch_check.h).
-#include "msm_internal.h"
+#include "api_helpers.h"
 #include "../host/batch_check.h"
 
 namespace {
@@ -25,13 +25,10 @@ int check_on_stream(const void* d_points, size_t n, bool jac, int subgroup_check
 int check_through_slot(Ctx& cx, const uint64_t* const* vecs, const size_t* lens, int nvec, const void* d_points, size_t n,
                        int subgroup_check, uint8_t* status, void* user_stream, bool jac = false) {
   const size_t size = jac ? 144 : 96;
-  int idx;
-  int rc = acquire_slot(cx, true, &idx);
-  if (rc) return rc;
-  Slot& S = cx.slots[idx];
-  const hipStream_t st = user_stream ? (hipStream_t)user_stream : S.stream;
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cx, true, user_stream);
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
     int r;
     if ((r = ensure(S.counts, n))) return r;
     if ((r = ensure_pinned(S, 1, n))) return r;
@@ -48,11 +45,7 @@ int check_through_slot(Ctx& cx, const uint64_t* const* vecs, const size_t* lens,
     if ((r = check_on_stream(d_points, n, jac, subgroup_check, S.counts.p, S.h_stage[1], st))) return r;
     memcpy(status, S.h_stage[1], n);
     return CURDLE_OK;
-  };
-  rc = body();
-  if (rc) (void)hipStreamSynchronize(st);  // nothing queued may outlive the slot's hold
-  release_slot(cx, idx);
-  return rc;
+  });
 }
 
 // A decode context's pinned staging, grown to `in_bytes` of input and `out_bytes` of what comes back.
@@ -221,11 +214,7 @@ extern "C" int curdle_g1_check_jac_batch_device(const void* d_jac_points, size_t
   return check_through_slot(cur(), nullptr, nullptr, 0, d_jac_points, n, subgroup_check, status, stream, true);
 }
 
-extern "C" int curdle_stat_check_paths(unsigned long long out[2]) {
-  if (!out) return CURDLE_EINVAL;
-  for (int i = 0; i < 2; i++) out[i] = g_check_paths[i].load(std::memory_order_relaxed);
-  return CURDLE_OK;
-}
+extern "C" int curdle_stat_check_paths(unsigned long long out[2]) { return read_stats(out, g_check_paths, 2); }
 
 namespace {
 // verify(&ok) is the unchecked call.  The check of the 4 ell instance points is started before it, on a decode
@@ -347,23 +336,16 @@ int check_chunk(const uint64_t* const* avecs, const size_t* alens, size_t na, co
     D.busy = false;
     return rc;
   }
-  int sidx;
-  int rc = acquire_slot(cx, true, &sidx);
-  if (rc) return rc;
-  Slot& S = cx.slots[sidx];
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cx, true, nullptr);
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
     int r;
     if ((r = ensure(S.counts, n))) return r;
     if ((r = ensure_pinned(S, 1, n))) return r;
     if ((r = ensure(S.points, bytes))) return r;
     if ((r = ensure_pinned(S, 0, bytes))) return r;
     return run(S.points.p, S.counts.p, S.h_stage[0], S.h_stage[1], S.stream);
-  };
-  rc = body();
-  if (rc) (void)hipStreamSynchronize(S.stream);  // nothing queued may outlive the slot's hold
-  release_slot(cx, sidx);
-  return rc;
+  });
 }
 }  // namespace
 
@@ -389,8 +371,4 @@ extern "C" int curdle_verify_batch_checked(const curdle_crs* crs, size_t k, cons
   return rc;
 }
 
-extern "C" int curdle_stat_batch_checked(unsigned long long out[3]) {
-  if (!out) return CURDLE_EINVAL;
-  for (int i = 0; i < 3; i++) out[i] = g_batch_checked[i].load(std::memory_order_relaxed);
-  return CURDLE_OK;
-}
+extern "C" int curdle_stat_batch_checked(unsigned long long out[3]) { return read_stats(out, g_batch_checked, 3); }

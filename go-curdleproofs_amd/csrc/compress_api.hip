@@ -1,9 +1,9 @@
 // C ABI of the batched G1 compression (compress_kernels.hip): curdle_g1_compress_batch / _device, n calls of
 // curdle_g1_compress (gnark's G1Affine.Bytes of a G1Jac) in one -- the counterpart of curdle_g1_decompress_batch.
-// Both run through an MSM slot, like the membership check of check_api.hip: the slot lends its stream, and the host
+// Both run through an MSM slot held by a SlotHold (api_helpers.h): the slot lends its stream, and the host
 // form its buffers and pinned staging, in passes of kCompressPass points so that the staging stays bounded.  No
 // stream is made here and nothing is allocated once the slot's buffers have grown to a pass.
-#include "msm_internal.h"
+#include "api_helpers.h"
 
 #include <algorithm>
 
@@ -14,13 +14,10 @@ constexpr size_t kCompressPass = (size_t)1 << 20;  // 144 MB of points, 48 MB of
 // Host points (d_in null: `jac` is copied up and the bytes come back to `out`) or resident ones (d_in -> d_out, both
 // device memory), on the slot's stream or the caller's.  The stream is synchronised before the slot is released.
 int compress_through_slot(Ctx& cx, const uint64_t* jac, const void* d_in, size_t n, uint8_t* out, void* d_out, void* user_stream) {
-  int idx;
-  int rc = acquire_slot(cx, true, &idx);
-  if (rc) return rc;
-  Slot& S = cx.slots[idx];
-  const hipStream_t st = user_stream ? (hipStream_t)user_stream : S.stream;
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cx, true, user_stream);
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
     if (d_in) {
       HIP_TRY(launch_g1_compress(d_in, kCompressJac, (uint32_t)n, static_cast<uint8_t*>(d_out), st));
       HIP_TRY(hipStreamSynchronize(st));
@@ -43,11 +40,7 @@ int compress_through_slot(Ctx& cx, const uint64_t* jac, const void* d_in, size_t
       memcpy(out + 48 * lo, S.h_stage[1], m * 48);
     }
     return CURDLE_OK;
-  };
-  rc = body();
-  if (rc) (void)hipStreamSynchronize(st);  // nothing queued may outlive the slot's hold
-  release_slot(cx, idx);
-  return rc;
+  });
 }
 }  // namespace
 

@@ -1,6 +1,7 @@
 // Resident, pre-converted base sets (curdle_dbases) and the verifier's accumulator on the device (curdle_dacc): C ABI and
-// the host side of both.  (Part of msm_api.hip until round 6.)
-#include "msm_internal.h"
+// the host side of both.  (Part of msm_api.hip until round 6.)  A set's device copies are a ResidentCopy, the synchronous
+// call over one holds its slot with a SlotHold (api_helpers.h).
+#include "api_helpers.h"
 
 // ---------------------------------------------------------------------------
 // Accumulator on the device
@@ -8,12 +9,7 @@
 struct curdle_dbases {
   size_t n = 0;
   std::vector<uint64_t> host;  // the n gnark points: a context that has not used the set yet converts its own copy from here
-  std::mutex mu;
-  void* d28[kMaxDevices] = {};       // per context: n internal-form points (P and phi(P) each), kA28Bytes apart
-  unsigned epoch[kMaxDevices] = {};  // the context generation each copy belongs to
-  int hipdev[kMaxDevices] = {};      // ... and the HIP device it was allocated on (a copy outlives its context: no device reset)
-  int users = 0;                     // accumulations in flight that copy from this set
-  bool dead = false;                 // curdle_dbases_free came while users > 0: the last user deletes
+  ResidentCopy copy;           // per context: n internal-form points (P and phi(P) each), kA28Bytes apart; null while n = 0
 };
 struct curdle_dacc {
   Ctx* ctx = nullptr;  // the context the accumulation runs on (the beginning thread's current one)
@@ -29,85 +25,28 @@ struct curdle_dacc {
 };
 
 namespace curdle_api {
-void dbases_destroy(curdle_dbases* b) {  // nobody else holds b any more
-  for (int i = 0; i < kMaxDevices; i++) {
-    if (!b->d28[i]) continue;
-    // curdle_shutdown destroys a context's streams and workspaces, not the device: a copy made under a
-    // closed context is still an allocation of its device and is freed here (review of round 3: it leaked)
-    if (hipSetDevice(b->hipdev[i]) == hipSuccess) (void)hipFree(b->d28[i]);
-  }
-  delete b;
-}
-
 // The set's copy on context cx, converted on first use (and again after a shutdown); takes a
 // user reference that dbases_release gives back.
 int dbases_acquire(Ctx& cx, curdle_dbases* b, void** d28) {
-  std::lock_guard<std::mutex> gb(b->mu);
-  if (b->dead) return fail(CURDLE_EINVAL, "resident bases were freed");
-  const int o = cx.ordinal;
-  unsigned epoch;
-  int device;
-  hipStream_t st = nullptr;
-  {  // the context's mutex only to bring it up and read what the copy is tied to: the upload and the
-     // conversion below run under the set's own mutex, so that they do not hold up every slot acquire /
-     // release of the context (review of round 3).  On the context's utility stream: a stream created and
-     // destroyed here cost every later verification 0.25 ms until the next hipFree
-     // (tools/dbg_verify_slowdown.py: 0.85 -> 1.09 ms at ell = 252 after ANY base set had been made).
-    std::lock_guard<std::mutex> g(cx.mu);
-    int rc = init_default_locked(cx);
-    if (rc) return rc;
-    epoch = cx.epoch;
-    device = cx.device;
-    st = cx.util_stream;
-  }
-  if (b->d28[o] && (b->epoch[o] != epoch || b->hipdev[o] != device)) {  // a copy made under a context that was closed since
-    if (hipSetDevice(b->hipdev[o]) == hipSuccess) (void)hipFree(b->d28[o]);
-    b->d28[o] = nullptr;
-  }
-  if (!b->d28[o] && b->n) {
-    // the upload runs outside cx.mu on the context's utility stream: counted as in flight, so that a
-    // concurrent curdle_shutdown answers CURDLE_EBUSY instead of destroying the stream under the copy
-    // (review of round 4), and published only if the context is still the one the copy was made under
-    {
-      std::lock_guard<std::mutex> g(cx.mu);
-      if (!cx.inited || cx.epoch != epoch) return fail(CURDLE_EBUSY, "the context was shut down under a resident-bases upload");
-      cx.pending_uploads++;
-    }
-    struct Pending {
-      Ctx& c;
-      ~Pending() {
-        std::lock_guard<std::mutex> g(c.mu);
-        c.pending_uploads--;
-      }
-    } pending{cx};
-    hipError_t e = hipSetDevice(device);
-    void *dst = nullptr, *tmp = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&dst, 2 * b->n * kA28Bytes);  // P and phi(P) per base (launch_convert_points_raw)
-    if (e == hipSuccess) e = hipMalloc(&tmp, b->n * 96);
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp, b->host.data(), b->n * 96, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_convert_points_raw(tmp, (uint32_t)b->n, dst, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) {
-      if (dst) (void)hipFree(dst);
-      return fail(e == hipErrorOutOfMemory ? CURDLE_ENOMEM : CURDLE_EHIP, "resident bases: %s", hipGetErrorString(e));
-    }
-    b->d28[o] = dst;
-    b->epoch[o] = epoch;
-    b->hipdev[o] = device;
-  }
-  b->users++;
-  *d28 = b->d28[o];
-  return CURDLE_OK;
+  static const ResidentCopy::Text text = {"resident bases were freed", "the context was shut down under a resident-bases upload",
+                                          "resident bases"};
+  ResidentCopy::Upload upload;
+  if (b->n)  // an empty set has nothing to upload: its copy stays null
+    upload = [b](hipStream_t st, void** dst) {
+      void* tmp = nullptr;
+      hipError_t e = hipMalloc(dst, 2 * b->n * kA28Bytes);  // P and phi(P) per base (launch_convert_points_raw)
+      if (e == hipSuccess) e = hipMalloc(&tmp, b->n * 96);
+      if (e == hipSuccess) e = hipMemcpyAsync(tmp, b->host.data(), b->n * 96, hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = launch_convert_points_raw(tmp, (uint32_t)b->n, *dst, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (tmp) (void)hipFree(tmp);
+      return e;
+    };
+  return b->copy.acquire(cx, upload, text, d28);
 }
 
 void dbases_release(curdle_dbases* b) {
-  bool last = false;
-  {
-    std::lock_guard<std::mutex> g(b->mu);
-    last = --b->users == 0 && b->dead;
-  }
-  if (last) dbases_destroy(b);
+  if (b->copy.release()) delete b;
 }
 }  // namespace curdle_api
 
@@ -138,15 +77,7 @@ extern "C" int curdle_dbases_create(const uint64_t* points, size_t n, curdle_dba
 }
 
 extern "C" void curdle_dbases_free(curdle_dbases* b) {
-  if (!b) return;
-  {
-    std::lock_guard<std::mutex> g(b->mu);
-    if (b->users > 0) {  // an accumulation is still copying from the set: its end deletes it
-      b->dead = true;
-      return;
-    }
-  }
-  dbases_destroy(b);
+  if (b && b->copy.free_or_defer()) delete b;
 }
 
 extern "C" size_t curdle_dbases_size(const curdle_dbases* b) { return b ? b->n : 0; }
@@ -213,15 +144,9 @@ extern "C" int curdle_msm_g1_dbases_host(const curdle_dbases* bases, const uint6
   curdle_dbases* set = const_cast<curdle_dbases*>(bases);
   void* d28 = nullptr;
   if ((rc = dbases_acquire(cx, set, &d28))) return rc;
-  int idx;
-  rc = acquire_slot(cx, true, &idx);
-  if (rc) {
-    dbases_release(set);
-    return rc;
-  }
-  Slot& S = cx.slots[idx];
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cx, true, nullptr);
+  rc = H.run([&]() -> int {
+    Slot& S = H.slot();
     int r;
     if ((r = ensure(S.scalars, n * 32))) return r;
     const Streams st = sync_streams(cx, S);
@@ -232,10 +157,7 @@ extern "C" int curdle_msm_g1_dbases_host(const curdle_dbases* bases, const uint6
     in.scalars = S.scalars.p;
     in.points28 = d28;
     return run_passes(cx, S, call, in, st, out_jac);
-  };
-  rc = body();
-  if (rc) drain_slot(cx, S);
-  release_slot(cx, idx);
+  }, SlotHold::kDrainSlot);
   dbases_release(set);
   return rc;
 }

@@ -1,6 +1,6 @@
 // C ABI of the batched point decoding (decode_kernels.hip) and the batched scalar multiplications (group_kernels.hip).
 // (Part of msm_api.hip until round 6.)
-#include "msm_internal.h"
+#include "api_helpers.h"
 
 
 // ---------------------------------------------------------------------------
@@ -29,12 +29,9 @@ extern "C" int curdle_g1_decompress_batch(const uint8_t* in, size_t n, int subgr
     }
     if (rc2 != CURDLE_EBUSY) return rc2;
   }
-  int idx;
-  int rc = acquire_slot(cx, true, &idx);
-  if (rc) return rc;
-  Slot& S = cx.slots[idx];
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cx, true, nullptr);
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
     int r;
     // the slot's generic buffers: compressed input, decoded output, status bytes
     if ((r = ensure(S.scalars, n * 48))) return r;
@@ -57,11 +54,7 @@ extern "C" int curdle_g1_decompress_batch(const uint8_t* in, size_t n, int subgr
     memcpy(out_affine, h_out, n * 96);
     memcpy(status, h_out + n * 96, n);
     return CURDLE_OK;
-  };
-  rc = body();
-  if (rc) (void)hipStreamSynchronize(S.stream);  // nothing queued may outlive the slot's hold
-  release_slot(cx, idx);
-  return rc;
+  });
 }
 
 // Two-step form: begin decodes (square root, curve check, sign) and returns the points, and
@@ -291,12 +284,9 @@ extern "C" int curdle_g1_scalar_mul_batch(const uint64_t* points, const uint64_t
   if (n == 0) return CURDLE_OK;
   if (n_scalars != n && n_scalars != 1) return fail(CURDLE_EINVAL, "n_scalars must be n or 1");
   if (n > ((size_t)1 << 24)) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^24 points", n);
-  int idx;
-  int rc = acquire_slot(cx, true, &idx);
-  if (rc) return rc;
-  Slot& S = cx.slots[idx];
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cx, true, nullptr);
+  return H.run([&]() -> int {  // a failed body is synchronised: `res` is a local, nothing may still be copying into it
+    Slot& S = H.slot();
     int r;
     if ((r = ensure(S.points, n * 96))) return r;
     if ((r = ensure(S.scalars, n_scalars * 32))) return r;
@@ -312,9 +302,5 @@ extern "C" int curdle_g1_scalar_mul_batch(const uint64_t* points, const uint64_t
     HIP_TRY(hipStreamSynchronize(S.stream));
     curdle_host_batch_to_affine(out_affine, res.data(), n);  // one shared inversion
     return CURDLE_OK;
-  };
-  rc = body();
-  if (rc) (void)hipStreamSynchronize(S.stream);  // `res` is a local: nothing may still be copying into it
-  release_slot(cx, idx);
-  return rc;
+  });
 }

@@ -3,31 +3,27 @@
 // as affine records or compressed bytes; and curdle_whisk_compute_trackers_batch, computeTracker and getKComm
 // (whisk/whisk_test.go:98-109) for n validators in one call -- one launch of k_fbase_mul over 3 m scalars per pass.
 //
-// A call takes ONE MSM slot for its buffers and its stream, like the normalisation (normalize_api.hip); no stream is
+// A call takes ONE MSM slot for its buffers and its stream, held by a SlotHold (api_helpers.h); no stream is
 // made here and nothing is allocated once the slot's buffers have grown.  Per pass of at most FBASE_PASS scalars:
 //   1. the scalars (and multipliers) go up through the slot's pinned staging, or are read where the caller keeps them;
 //   2. k_fbase_mul writes G1XYZZ results into the slot's workspace;
 //   3. k_g1_normalize makes affine records of them with ONE inversion per wave, straight into the caller's array
 //      (resident, affine) or into the slot's;
 //   4. compressed output: k_g1_compress<kCompressAffine> encodes the records -- nothing is inverted per point.
-// A table belongs to a handle and has one copy per context, made on first use there, as a resident base set's has
-// (dbases_api.hip); the generator's handle is the library's own and is never freed.
+// A table belongs to a handle and has one copy per context, made on first use there: a ResidentCopy (api_helpers.h),
+// as a resident base set's is; the generator's handle is the library's own and is never freed.
 //
 // THE KERNEL READS TABLE ENTRIES AT ADDRESSES CHOSEN BY SCALAR DIGITS and skips zero digits: memory access pattern and
-// running time depend on the scalars.  What the library itself holds of them is overwritten on every way out: see wipe().
-#include "msm_internal.h"
+// running time depend on the scalars.  What the library itself holds of them is overwritten on every way out: the call's
+// WipeList (api_helpers.h).
+#include "api_helpers.h"
 #include "../host/host_ops.h"
 
 #include <algorithm>
 
 struct curdle_fbase {
   std::vector<uint64_t> host;  // the 8,160 gnark affine multiples: a context that has not used the table yet converts its own copy
-  std::mutex mu;
-  void* d28[kMaxDevices] = {};       // per context: kFbaseEntries records of d28::A28, kA28Bytes apart
-  unsigned epoch[kMaxDevices] = {};  // the context generation each copy belongs to
-  int hipdev[kMaxDevices] = {};      // ... and the HIP device it was allocated on
-  int users = 0;                     // calls in flight that read this table
-  bool dead = false;                 // curdle_fbase_free came while users > 0: the last user deletes
+  ResidentCopy copy;           // per context: kFbaseEntries records of d28::A28, kA28Bytes apart
 };
 
 namespace {
@@ -38,90 +34,37 @@ constexpr size_t kFbPassDefault = (size_t)1 << 20;
 // scalars multiplied on the device | launches of k_fbase_mul | tables built; completed passes only
 std::atomic<unsigned long long> g_fb_stat[3];
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 size_t pass_size() {
   const long long knob = knobs::get(knobs::FBASE_PASS);
   const size_t v = knob < 0 ? kFbPassDefault : (size_t)knob;
   return std::max<size_t>(256, v / 256 * 256);
 }
 
-void fbase_destroy(curdle_fbase* b) {  // nobody else holds b any more
-  for (int i = 0; i < kMaxDevices; i++) {
-    if (!b->d28[i]) continue;
-    if (hipSetDevice(b->hipdev[i]) == hipSuccess) (void)hipFree(b->d28[i]);  // a copy outlives its context (dbases_destroy)
-  }
-  delete b;
-}
-
 // The table's copy on context cx, uploaded and converted on first use (and again after a shutdown); takes a user
-// reference that fbase_release gives back.  dbases_acquire's rules, step by step.
+// reference that fbase_release gives back.
 int fbase_acquire(Ctx& cx, curdle_fbase* b, void** d28) {
-  std::lock_guard<std::mutex> gb(b->mu);
-  if (b->dead) return fail(CURDLE_EINVAL, "the fixed-base table was freed");
-  const int o = cx.ordinal;
-  unsigned epoch;
-  int device;
-  hipStream_t st = nullptr;
-  {
-    std::lock_guard<std::mutex> g(cx.mu);
-    int rc = init_default_locked(cx);
-    if (rc) return rc;
-    epoch = cx.epoch;
-    device = cx.device;
-    st = cx.util_stream;
-  }
-  if (b->d28[o] && (b->epoch[o] != epoch || b->hipdev[o] != device)) {  // a copy made under a context that was closed since
-    if (hipSetDevice(b->hipdev[o]) == hipSuccess) (void)hipFree(b->d28[o]);
-    b->d28[o] = nullptr;
-  }
-  if (!b->d28[o]) {
-    {  // counted as in flight: a concurrent curdle_shutdown answers CURDLE_EBUSY instead of destroying the stream under the copy
-      std::lock_guard<std::mutex> g(cx.mu);
-      if (!cx.inited || cx.epoch != epoch) return fail(CURDLE_EBUSY, "the context was shut down under a fixed-base table upload");
-      cx.pending_uploads++;
-    }
-    struct Pending {
-      Ctx& c;
-      ~Pending() {
-        std::lock_guard<std::mutex> g(c.mu);
-        c.pending_uploads--;
-      }
-    } pending{cx};
+  static const ResidentCopy::Text text = {"the fixed-base table was freed", "the context was shut down under a fixed-base table upload",
+                                          "fixed-base table"};
+  return b->copy.acquire(cx, [b](hipStream_t st, void** dst) {
     const size_t n = kFbaseEntries;
-    hipError_t e = hipSetDevice(device);
-    void *dst = nullptr, *raw = nullptr, *both = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&dst, n * kA28Bytes);
+    void *raw = nullptr, *both = nullptr;
+    hipError_t e = hipMalloc(dst, n * kA28Bytes);
     if (e == hipSuccess) e = hipMalloc(&raw, n * 96);
     if (e == hipSuccess) e = hipMalloc(&both, 2 * n * kA28Bytes);  // P and phi(P) per entry (launch_convert_points_raw)
     if (e == hipSuccess) e = hipMemcpyAsync(raw, b->host.data(), n * 96, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = launch_convert_points_raw(raw, (uint32_t)n, both, st);
     // the kernel gathers P's records only: kept dense, one 128-byte line each, so the table is half the L2 footprint
-    if (e == hipSuccess) e = hipMemcpy2DAsync(dst, kA28Bytes, both, 2 * kA28Bytes, kA28Bytes, n, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(*dst, kA28Bytes, both, 2 * kA28Bytes, kA28Bytes, n, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (raw) (void)hipFree(raw);
     if (both) (void)hipFree(both);
-    if (e != hipSuccess) {
-      if (dst) (void)hipFree(dst);
-      return fail(e == hipErrorOutOfMemory ? CURDLE_ENOMEM : CURDLE_EHIP, "fixed-base table: %s", hipGetErrorString(e));
-    }
-    b->d28[o] = dst;
-    b->epoch[o] = epoch;
-    b->hipdev[o] = device;
-    g_fb_stat[2].fetch_add(1, std::memory_order_relaxed);
-  }
-  b->users++;
-  *d28 = b->d28[o];
-  return CURDLE_OK;
+    if (e == hipSuccess) g_fb_stat[2].fetch_add(1, std::memory_order_relaxed);
+    return e;
+  }, text, d28);
 }
 
 void fbase_release(curdle_fbase* b) {
-  bool last = false;
-  {
-    std::lock_guard<std::mutex> g(b->mu);
-    last = --b->users == 0 && b->dead;
-  }
-  if (last) fbase_destroy(b);
+  if (b->copy.release()) delete b;
 }
 
 curdle_fbase* fbase_new(const G1Affine& p) {
@@ -171,36 +114,23 @@ const char* check_affine_host(const G1Affine& a) {
   return nullptr;
 }
 
-// What a call holds of the secrets, and the one way out.
+// The slot and the stream of a call, and what it holds of the secrets: the library's device copy of scalars and
+// multipliers, the pinned staging they went through and the unnormalised results (S.sorted).  The caller's arrays are
+// never wiped; the kernel keeps the scalar and its digits in registers only.
 struct FbCall {
-  Slot& S;
-  hipStream_t st;
-  void* d_sc = nullptr;    // the library's device copy of scalars and multipliers (null: none; the caller's arrays are never wiped)
-  size_t d_sc_bytes = 0;
-  void* h_sc = nullptr;    // ... and the pinned staging they went through
-  size_t h_sc_bytes = 0;
-  void* d_xyzz = nullptr;  // the unnormalised results
-  size_t d_xyzz_bytes = 0;
-  // Overwrites them, on the call's stream and behind everything queued there; called on every way out.  The kernel keeps
-  // the scalar and its digits in registers only.
-  int wipe() {
-    hipError_t e = hipSuccess, e2;
-    if (d_sc && (e2 = hipMemsetAsync(d_sc, 0, d_sc_bytes, st)) != hipSuccess) e = e2;
-    if (d_xyzz && (e2 = hipMemsetAsync(d_xyzz, 0, d_xyzz_bytes, st)) != hipSuccess) e = e2;
-    if ((e2 = hipStreamSynchronize(st)) != hipSuccess) e = e2;
-    if (h_sc) explicit_bzero(h_sc, h_sc_bytes);
-    if (e != hipSuccess) return fail(CURDLE_EHIP, "fixed-base multiplication: clearing the scalars: %s", hipGetErrorString(e));
-    return CURDLE_OK;
-  }
+  SlotHold& H;
+  WipeList W;
+  Slot& slot() { return H.slot(); }
+  hipStream_t stream() { return H.stream(); }
 };
 
 // The launches of one pass over resident scalars: cnt products -> XYZZ (S.sorted) -> affine records at d_affine (16-byte
 // aligned) -> if d_comp, their encodings there (any alignment).
 int fb_launches(FbCall& C, const void* d_table, const void* d_scalars, const void* d_mults, size_t cnt, void* d_affine,
                 uint8_t* d_comp) {
-  HIP_TRY(launch_fbase_mul(d_table, d_scalars, d_mults, (uint32_t)cnt, C.d_xyzz, C.st));
-  HIP_TRY(launch_g1_normalize(C.d_xyzz, kNormalizeXyzz, (uint32_t)cnt, d_affine, C.st, nullptr));
-  if (d_comp) HIP_TRY(launch_g1_compress(d_affine, kCompressAffine, (uint32_t)cnt, d_comp, C.st));
+  HIP_TRY(launch_fbase_mul(d_table, d_scalars, d_mults, (uint32_t)cnt, C.slot().sorted.p, C.stream()));
+  HIP_TRY(launch_g1_normalize(C.slot().sorted.p, kNormalizeXyzz, (uint32_t)cnt, d_affine, C.stream(), nullptr));
+  if (d_comp) HIP_TRY(launch_g1_compress(d_affine, kCompressAffine, (uint32_t)cnt, d_comp, C.stream()));
   return CURDLE_OK;
 }
 
@@ -212,14 +142,13 @@ void count_pass(size_t cnt) {
 // scalars / multipliers / out: host memory (resident false) or device memory.
 int fb_run(FbCall& C, const void* d_table, const uint8_t* scalars, const uint8_t* mults, size_t n, bool resident, int out_form,
            uint8_t* out) {
-  Slot& S = C.S;
+  Slot& S = C.slot();
   const size_t pass = pass_size(), cap = std::min(n, pass);
   const bool comp = out_form == CURDLE_G1_OUT_COMPRESSED;
   const size_t rec = comp ? 48 : 96;
   int r;
   if ((r = ensure(S.sorted, cap * sizeof(G1XYZZ)))) return r;
-  C.d_xyzz = S.sorted.p;
-  C.d_xyzz_bytes = cap * sizeof(G1XYZZ);
+  C.W.note_device(S.sorted.p, cap * sizeof(G1XYZZ));
   if (comp || !resident)
     if ((r = ensure(S.points, cap * 96))) return r;  // affine records
   if (!resident) {
@@ -227,10 +156,8 @@ int fb_run(FbCall& C, const void* d_table, const uint8_t* scalars, const uint8_t
     if ((r = ensure(S.scalars, cap * 64))) return r;           // scalars | multipliers
     if ((r = ensure_pinned(S, 0, cap * 64))) return r;
     if ((r = ensure_pinned(S, 1, cap * rec))) return r;
-    C.d_sc = S.scalars.p;
-    C.d_sc_bytes = cap * 64;
-    C.h_sc = S.h_stage[0];
-    C.h_sc_bytes = cap * 64;
+    C.W.note_device(S.scalars.p, cap * 64);
+    C.W.note_host(S.h_stage[0], cap * 64);
   }
   for (size_t lo = 0; lo < n; lo += pass) {
     const size_t cnt = std::min(pass, n - lo);
@@ -246,45 +173,34 @@ int fb_run(FbCall& C, const void* d_table, const uint8_t* scalars, const uint8_t
       uint8_t* d = static_cast<uint8_t*>(S.scalars.p);
       memcpy(h, scalars + 32 * lo, 32 * cnt);
       if (mults) memcpy(h + 32 * cnt, mults + 32 * lo, 32 * cnt);
-      HIP_TRY(hipMemcpyAsync(d, h, (mults ? 64 : 32) * cnt, hipMemcpyHostToDevice, C.st));
+      HIP_TRY(hipMemcpyAsync(d, h, (mults ? 64 : 32) * cnt, hipMemcpyHostToDevice, C.stream()));
       if ((r = fb_launches(C, d_table, d, mults ? d + 32 * cnt : nullptr, cnt, S.points.p,
                            comp ? static_cast<uint8_t*>(S.digits.p) : nullptr)))
         return r;
-      HIP_TRY(hipMemcpyAsync(S.h_stage[1], comp ? S.digits.p : S.points.p, rec * cnt, hipMemcpyDeviceToHost, C.st));
+      HIP_TRY(hipMemcpyAsync(S.h_stage[1], comp ? S.digits.p : S.points.p, rec * cnt, hipMemcpyDeviceToHost, C.stream()));
     }
-    HIP_TRY(hipStreamSynchronize(C.st));
+    HIP_TRY(hipStreamSynchronize(C.stream()));
     if (!resident) memcpy(out + rec * lo, S.h_stage[1], rec * cnt);
     count_pass(cnt);
   }
   return CURDLE_OK;
 }
 
-int fb_through_slot(const curdle_fbase* base, const void* scalars, const void* mults, size_t n, bool resident, int out_form,
-                    void* out, void* user_stream) {
+// One call through the table's copy on the calling thread's context and an MSM slot: run(C, d_table) does the passes.
+template <class Run>
+int fb_through_slot(const curdle_fbase* base, void* user_stream, Run run) {
   Ctx& cx = cur();
   curdle_fbase* b = base ? const_cast<curdle_fbase*>(base) : generator_base();
   if (!b) return fail(CURDLE_ENOMEM, "out of memory");
   void* d_table = nullptr;
   int rc = fbase_acquire(cx, b, &d_table);
   if (rc) return rc;
-  int idx;
-  rc = acquire_slot(cx, true, &idx);
-  if (rc) {
-    fbase_release(b);
-    return rc;
-  }
-  Slot& S = cx.slots[idx];
-  FbCall C{S, user_stream ? (hipStream_t)user_stream : S.stream};
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
-    return fb_run(C, d_table, static_cast<const uint8_t*>(scalars), static_cast<const uint8_t*>(mults), n, resident, out_form,
-                  static_cast<uint8_t*>(out));
-  };
-  rc = body();
-  const int w = C.wipe();  // synchronises the stream: nothing queued outlives the slot's hold, nothing of the scalars stays
-  release_slot(cx, idx);
+  SlotHold H(cx, true, user_stream);
+  FbCall C{H, WipeList(H.stream())};
+  H.wipe_on_exit(&C.W, "fixed-base multiplication: clearing the scalars");  // nothing of the scalars stays
+  rc = H.run([&]() -> int { return run(C, d_table); });
   fbase_release(b);
-  return rc ? rc : w;
+  return rc;
 }
 
 int check_args(const void* scalars, size_t n, int out_form, const void* out) {
@@ -300,22 +216,20 @@ int check_args(const void* scalars, size_t n, int out_form, const void* out) {
 // multipliers at its first, so the lanes see (r, 1), (k, r) and (1, k): r G, k r G and k G in ONE launch, no copy between.
 int trackers_run(FbCall& C, const void* d_table, const uint64_t* ks, const uint64_t* rs, size_t n, uint8_t* trackers_out,
                  uint8_t* kcomm_out) {
-  Slot& S = C.S;
+  Slot& S = C.slot();
   const size_t cols = kcomm_out ? 3 : 2;
   const size_t mp = std::max<size_t>(1, pass_size() / cols), cap = std::min(n, mp);
   int r;
   if ((r = ensure(S.sorted, cols * cap * sizeof(G1XYZZ)))) return r;
-  C.d_xyzz = S.sorted.p;
-  C.d_xyzz_bytes = cols * cap * sizeof(G1XYZZ);
+  C.W.note_device(S.sorted.p, cols * cap * sizeof(G1XYZZ));
   if ((r = ensure(S.points, cols * cap * 96))) return r;     // affine records, column by column
   if ((r = ensure(S.digits, cols * cap * 48))) return r;     // their encodings
   if ((r = ensure(S.counts, 96 * cap))) return r;            // the trackers: r G | k r G member by member
   if ((r = ensure(S.scalars, (cols + 1) * cap * 32))) return r;
   if ((r = ensure_pinned(S, 0, (cols + 1) * cap * 32))) return r;
   if ((r = ensure_pinned(S, 1, cols * cap * 48))) return r;
-  C.d_sc = S.scalars.p;
-  C.h_sc = S.h_stage[0];
-  C.d_sc_bytes = C.h_sc_bytes = (cols + 1) * cap * 32;
+  C.W.note_device(S.scalars.p, (cols + 1) * cap * 32);
+  C.W.note_host(S.h_stage[0], (cols + 1) * cap * 32);
   Fr one;
   f_one(one);
   for (size_t lo = 0; lo < n; lo += mp) {
@@ -329,16 +243,16 @@ int trackers_run(FbCall& C, const void* d_table, const uint64_t* ks, const uint6
       memcpy(h + 32 * m, h, 32 * m);  // r = 1: the fork's initial trackers (G, k G)
     memcpy(h + 64 * m, ks + 4 * lo, 32 * m);
     if (kcomm_out) memcpy(h + 96 * m, h, 32 * m);
-    HIP_TRY(hipMemcpyAsync(d, h, (cols + 1) * m * 32, hipMemcpyHostToDevice, C.st));
+    HIP_TRY(hipMemcpyAsync(d, h, (cols + 1) * m * 32, hipMemcpyHostToDevice, C.stream()));
     uint8_t* comp = static_cast<uint8_t*>(S.digits.p);
     if ((r = fb_launches(C, d_table, d + 32 * m, d, cols * m, S.points.p, comp))) return r;
     // the two tracker columns member by member
-    HIP_TRY(hipMemcpy2DAsync(S.counts.p, 96, comp, 48, 48, m, hipMemcpyDeviceToDevice, C.st));
-    HIP_TRY(hipMemcpy2DAsync(static_cast<uint8_t*>(S.counts.p) + 48, 96, comp + 48 * m, 48, 48, m, hipMemcpyDeviceToDevice, C.st));
+    HIP_TRY(hipMemcpy2DAsync(S.counts.p, 96, comp, 48, 48, m, hipMemcpyDeviceToDevice, C.stream()));
+    HIP_TRY(hipMemcpy2DAsync(static_cast<uint8_t*>(S.counts.p) + 48, 96, comp + 48 * m, 48, 48, m, hipMemcpyDeviceToDevice, C.stream()));
     uint8_t* ho = static_cast<uint8_t*>(S.h_stage[1]);
-    HIP_TRY(hipMemcpyAsync(ho, S.counts.p, 96 * m, hipMemcpyDeviceToHost, C.st));
-    if (kcomm_out) HIP_TRY(hipMemcpyAsync(ho + 96 * m, comp + 96 * m, 48 * m, hipMemcpyDeviceToHost, C.st));
-    HIP_TRY(hipStreamSynchronize(C.st));
+    HIP_TRY(hipMemcpyAsync(ho, S.counts.p, 96 * m, hipMemcpyDeviceToHost, C.stream()));
+    if (kcomm_out) HIP_TRY(hipMemcpyAsync(ho + 96 * m, comp + 96 * m, 48 * m, hipMemcpyDeviceToHost, C.stream()));
+    HIP_TRY(hipStreamSynchronize(C.stream()));
     memcpy(trackers_out + 96 * lo, ho, 96 * m);
     if (kcomm_out) memcpy(kcomm_out + 48 * lo, ho + 96 * m, 48 * m);
     count_pass(cols * m);
@@ -369,22 +283,17 @@ extern "C" int curdle_fbase_create(const uint64_t point_affine[12], curdle_fbase
 }
 
 extern "C" void curdle_fbase_free(curdle_fbase* b) {
-  if (!b) return;
-  {
-    std::lock_guard<std::mutex> g(b->mu);
-    if (b->users > 0) {  // a call is still reading the table: its end deletes it
-      b->dead = true;
-      return;
-    }
-  }
-  fbase_destroy(b);
+  if (b && b->copy.free_or_defer()) delete b;
 }
 
 extern "C" int curdle_g1_fixed_base_mul_batch(const curdle_fbase* base, const uint64_t* scalars, const uint64_t* multipliers,
                                               size_t n, int out_form, void* out) {
   if (n == 0) return CURDLE_OK;
   if (int rc = check_args(scalars, n, out_form, out)) return rc;
-  return fb_through_slot(base, scalars, multipliers, n, false, out_form, out, nullptr);
+  return fb_through_slot(base, nullptr, [&](FbCall& C, const void* d_table) {
+    return fb_run(C, d_table, reinterpret_cast<const uint8_t*>(scalars), reinterpret_cast<const uint8_t*>(multipliers), n, false,
+                  out_form, static_cast<uint8_t*>(out));
+  });
 }
 
 extern "C" int curdle_g1_fixed_base_mul_batch_device(const curdle_fbase* base, const void* d_scalars, const void* d_multipliers,
@@ -393,7 +302,10 @@ extern "C" int curdle_g1_fixed_base_mul_batch_device(const curdle_fbase* base, c
   if (int rc = check_args(d_scalars, n, out_form, d_out)) return rc;
   if (!aligned16(d_scalars) || !aligned16(d_multipliers) || (out_form == CURDLE_G1_OUT_AFFINE && !aligned16(d_out)))
     return fail(CURDLE_EINVAL, "device pointers must be multiples of 16 (a compressed d_out may have any alignment)");
-  return fb_through_slot(base, d_scalars, d_multipliers, n, true, out_form, d_out, stream);
+  return fb_through_slot(base, stream, [&](FbCall& C, const void* d_table) {
+    return fb_run(C, d_table, static_cast<const uint8_t*>(d_scalars), static_cast<const uint8_t*>(d_multipliers), n, true,
+                  out_form, static_cast<uint8_t*>(d_out));
+  });
 }
 
 extern "C" int curdle_whisk_compute_trackers_batch(const uint64_t* ks, const uint64_t* rs, size_t n, uint8_t* trackers_out,
@@ -401,29 +313,12 @@ extern "C" int curdle_whisk_compute_trackers_batch(const uint64_t* ks, const uin
   if (n == 0) return CURDLE_OK;
   if (n > kFbMaxMembers) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^22 trackers", n);
   int rc;
-  if (!ks || !trackers_out) {
+  if (!ks || !trackers_out)
     rc = fail(CURDLE_EINVAL, "null argument");
-  } else {
-    Ctx& cx = cur();
-    curdle_fbase* b = generator_base();
-    void* d_table = nullptr;
-    rc = b ? fbase_acquire(cx, b, &d_table) : fail(CURDLE_ENOMEM, "out of memory");
-    int idx = -1;
-    if (!rc && (rc = acquire_slot(cx, true, &idx))) fbase_release(b);
-    if (!rc) {
-      Slot& S = cx.slots[idx];
-      FbCall C{S, S.stream};
-      auto body = [&]() -> int {
-        HIP_TRY(hipSetDevice(cx.device));
-        return trackers_run(C, d_table, ks, rs, n, trackers_out, k_commitments_out);
-      };
-      rc = body();
-      const int w = C.wipe();
-      release_slot(cx, idx);
-      fbase_release(b);
-      if (!rc) rc = w;
-    }
-  }
+  else
+    rc = fb_through_slot(nullptr, nullptr, [&](FbCall& C, const void* d_table) {
+      return trackers_run(C, d_table, ks, rs, n, trackers_out, k_commitments_out);
+    });
   if (rc != CURDLE_OK) {  // a failed call leaves nothing that reads as a tracker
     if (trackers_out) memset(trackers_out, 0, 96 * n);
     if (k_commitments_out) memset(k_commitments_out, 0, 48 * n);
@@ -431,8 +326,4 @@ extern "C" int curdle_whisk_compute_trackers_batch(const uint64_t* ks, const uin
   return rc;
 }
 
-extern "C" int curdle_stat_fbase(unsigned long long out[3]) {
-  if (!out) return CURDLE_EINVAL;
-  for (int i = 0; i < 3; i++) out[i] = g_fb_stat[i].load(std::memory_order_relaxed);
-  return CURDLE_OK;
-}
+extern "C" int curdle_stat_fbase(unsigned long long out[3]) { return read_stats(out, g_fb_stat, 3); }

@@ -8,8 +8,9 @@
 // THIS FILE: the contexts (one per configured device), their workspace slots and buffers, the error text, device
 // selection, initialisation and shutdown.  The plan is msm_plan.hip, the phase sequencing msm_enqueue.hip (+ msm_host_chunks.hip),
 // the MSM entry points msm_entry.hip, resident bases and the device accumulator dbases_api.hip, point decoding
-// decode_api.hip, the rest misc_api.hip.
-#include "msm_internal.h"
+// decode_api.hip, the rest misc_api.hip.  What the batched families share on the host side (api_helpers.h: the scoped
+// slot hold, the wipe list, the per-context resident copy) is defined here too, next to the slots it works on.
+#include "api_helpers.h"
 
 // ---------------------------------------------------------------------------
 // Errors
@@ -150,23 +151,37 @@ void set_out_infinity(uint64_t out[18]) {
 // --- slot management -----------------------------------------------------------
 // A slot belongs to the caller from acquire to release; the context mutex only
 // guards the busy flags, so several threads can run MSMs concurrently.
+// the first free slot, marked as taken by a new call, or -1; the caller holds cx.mu
+static int take_free_slot_locked(Ctx& cx) {
+  for (int i = 0; i < kSlots; i++) {
+    Slot& s = cx.slots[i];
+    if (s.busy) continue;
+    s.busy = true;
+    s.claimed = false;
+    s.gen++;
+    return i;
+  }
+  return -1;
+}
+
 int acquire_slot(Ctx& cx, bool block, int* idx) {
   std::unique_lock<std::mutex> g(cx.mu);
   int rc = init_default_locked(cx);
   if (rc) return rc;
   for (;;) {
-    for (int i = 0; i < kSlots; i++) {
-      if (!cx.slots[i].busy) {
-        cx.slots[i].busy = true;
-        cx.slots[i].claimed = false;
-        cx.slots[i].gen++;
-        *idx = i;
-        return CURDLE_OK;
-      }
+    const int i = take_free_slot_locked(cx);
+    if (i >= 0) {
+      *idx = i;
+      return CURDLE_OK;
     }
     if (!block) return fail(CURDLE_EBUSY, "all %d MSM slots are in flight; call curdle_msm_wait first", kSlots);
     cx.cv.wait(g);
   }
+}
+
+int try_acquire_slot(Ctx& cx) {
+  std::lock_guard<std::mutex> g(cx.mu);
+  return take_free_slot_locked(cx);
 }
 
 void release_slot(Ctx& cx, int idx) {
@@ -175,6 +190,117 @@ void release_slot(Ctx& cx, int idx) {
     cx.slots[idx].busy = false;
   }
   cx.cv.notify_one();
+}
+
+// --- what the entry-point families share (api_helpers.h) -------------------------
+int SlotHold::set_device() {
+  HIP_TRY(hipSetDevice(cx_.device));
+  return CURDLE_OK;
+}
+
+int SlotHold::finish(int rc, OnFailure on_failure) {
+  if (rc && on_failure == kDrainSlot) {
+    drain_slot(cx_, slot());
+  } else if (rc) {  // nothing queued may outlive the slots' hold
+    (void)hipStreamSynchronize(st_);
+    if (b_ >= 0) (void)hipStreamSynchronize(cx_.slots[b_].stream);
+  }
+  const int w = wipe_ ? wipe_->wipe(wipe_what_) : CURDLE_OK;
+  if (b_ >= 0) release_slot(cx_, b_);
+  release_slot(cx_, a_);
+  return rc ? rc : w;
+}
+
+int WipeList::wipe(const char* what) {
+  hipError_t e = hipSuccess, e2;
+  for (int i = 0; i < ndev; i++)
+    if ((e2 = hipMemsetAsync(dev[i].p, 0, dev[i].bytes, st)) != hipSuccess && e == hipSuccess) e = e2;
+  if ((e2 = hipStreamSynchronize(st)) != hipSuccess && e == hipSuccess) e = e2;
+  for (int i = 0; i < nhost; i++) explicit_bzero(host[i].p, host[i].bytes);
+  if (e != hipSuccess) return fail(CURDLE_EHIP, "%s: %s", what, hipGetErrorString(e));
+  if (lost) return fail(CURDLE_EHIP, "%s: more ranges than the list holds", what);
+  return CURDLE_OK;
+}
+
+int read_stats(unsigned long long* out, const std::atomic<unsigned long long>* counters, int n) {
+  if (!out) return CURDLE_EINVAL;
+  for (int i = 0; i < n; i++) out[i] = counters[i].load(std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+ResidentCopy::~ResidentCopy() {  // nobody else holds the handle any more
+  for (int i = 0; i < kMaxDevices; i++) {
+    if (!d28[i]) continue;
+    // curdle_shutdown destroys a context's streams and workspaces, not the device: a copy made under a
+    // closed context is still an allocation of its device and is freed here (review of round 3: it leaked)
+    if (hipSetDevice(hipdev[i]) == hipSuccess) (void)hipFree(d28[i]);
+  }
+}
+
+int ResidentCopy::acquire(Ctx& cx, const Upload& upload, const Text& text, void** out) {
+  std::lock_guard<std::mutex> gb(mu);
+  if (dead) return fail(CURDLE_EINVAL, "%s", text.freed);
+  const int o = cx.ordinal;
+  unsigned ep;
+  int device;
+  hipStream_t st = nullptr;
+  {  // the context's mutex only to bring it up and read what the copy is tied to: the upload and the
+     // conversion below run under the handle's own mutex, so that they do not hold up every slot acquire /
+     // release of the context (review of round 3).  On the context's utility stream: a stream created and
+     // destroyed here cost every later verification 0.25 ms until the next hipFree
+     // (tools/dbg_verify_slowdown.py: 0.85 -> 1.09 ms at ell = 252 after ANY base set had been made).
+    std::lock_guard<std::mutex> g(cx.mu);
+    int rc = init_default_locked(cx);
+    if (rc) return rc;
+    ep = cx.epoch;
+    device = cx.device;
+    st = cx.util_stream;
+  }
+  if (d28[o] && (epoch[o] != ep || hipdev[o] != device)) {  // a copy made under a context that was closed since
+    if (hipSetDevice(hipdev[o]) == hipSuccess) (void)hipFree(d28[o]);
+    d28[o] = nullptr;
+  }
+  if (!d28[o] && upload) {
+    // the upload runs outside cx.mu on the context's utility stream: counted as in flight, so that a
+    // concurrent curdle_shutdown answers CURDLE_EBUSY instead of destroying the stream under the copy
+    // (review of round 4), and published only if the context is still the one the copy was made under
+    {
+      std::lock_guard<std::mutex> g(cx.mu);
+      if (!cx.inited || cx.epoch != ep) return fail(CURDLE_EBUSY, "%s", text.shut_down);
+      cx.pending_uploads++;
+    }
+    struct Pending {
+      Ctx& c;
+      ~Pending() {
+        std::lock_guard<std::mutex> g(c.mu);
+        c.pending_uploads--;
+      }
+    } pending{cx};
+    void* dst = nullptr;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = upload(st, &dst);
+    if (e != hipSuccess) {
+      if (dst) (void)hipFree(dst);
+      return fail(e == hipErrorOutOfMemory ? CURDLE_ENOMEM : CURDLE_EHIP, "%s: %s", text.upload, hipGetErrorString(e));
+    }
+    d28[o] = dst;
+    epoch[o] = ep;
+    hipdev[o] = device;
+  }
+  users++;
+  *out = d28[o];
+  return CURDLE_OK;
+}
+
+bool ResidentCopy::release() {
+  std::lock_guard<std::mutex> g(mu);
+  return --users == 0 && dead;
+}
+
+bool ResidentCopy::free_or_defer() {
+  std::lock_guard<std::mutex> g(mu);
+  if (users > 0) dead = true;  // a call is still reading a copy: its end deletes the handle
+  return !dead;
 }
 
 }  // namespace curdle_api

@@ -1,7 +1,7 @@
 // The MSM entry points of the C ABI (include/curdle_msm.h): host slices, device-resident inputs, window ranges, the
 // submit / wait pair, the kept-bases cache behind CURDLE_MSM_BASES_UNCHANGED, several devices behind one call, batches
 // and shared-scalar calls.  (Part of msm_api.hip until round 6.)
-#include "msm_internal.h"
+#include "api_helpers.h"
 
 namespace curdle_api {
 // One MSM from host buffers on the calling thread's context.
@@ -437,12 +437,9 @@ extern "C" int curdle_msm_g1_multi(const uint64_t* const* points_sets, size_t k,
   if (k * n > ((size_t)1 << 27)) return fail(CURDLE_EINVAL, "k*n = %zu exceeds the supported 2^27 pairs", k * n);
   for (size_t j = 0; j < k; j++)
     if (!points_sets[j]) return fail(CURDLE_EINVAL, "points_sets[%zu] is null", j);
-  int idx;
-  int rc = acquire_slot(cx, true, &idx);
-  if (rc) return rc;
-  Slot& S = cx.slots[idx];
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cx, true, nullptr);
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
     int r;
     if ((r = ensure(S.points, k * n * 96))) return r;
     if ((r = ensure(S.scalars, n * 32))) return r;
@@ -455,9 +452,5 @@ extern "C" int curdle_msm_g1_multi(const uint64_t* const* points_sets, size_t k,
     call.sets = k;
     if ((r = enqueue_slot(cx, S, call, {S.points.p, S.scalars.p}, st))) return r;
     return finish_slot(cx, S, out_jac);
-  };
-  rc = body();
-  if (rc) drain_slot(cx, S);
-  release_slot(cx, idx);
-  return rc;
+  }, SlotHold::kDrainSlot);
 }

@@ -1,11 +1,11 @@
 // C ABI of the batched G1 normalisation (normalize_kernels.hip): curdle_g1_normalize_batch / _device, gnark's
 // BatchJacobianToAffineG1 on the GPU, and curdle_g1_scalar_mul_batch_device, the resident form of
 // curdle_g1_scalar_mul_batch whose results stay on the device as affine points -- the layout every base array of
-// this library has, so a device result can be the next call's device input.  All three run through an MSM slot, like
-// the compression of compress_api.hip: the slot lends its stream, the host form its buffers and pinned staging in
+// this library has, so a device result can be the next call's device input.  All three run through an MSM slot held
+// by a SlotHold (api_helpers.h): the slot lends its stream, the host form its buffers and pinned staging in
 // passes of kNormalizePass points, the scalar multiplications their XYZZ workspace.  No stream is made here and
 // nothing is allocated once the slot's buffers have grown.
-#include "msm_internal.h"
+#include "api_helpers.h"
 
 #include <algorithm>
 
@@ -17,7 +17,6 @@ constexpr size_t kNormalizePass = (size_t)1 << 20;  // up to 192 MB of points, 9
 std::atomic<unsigned long long> g_nz_stat[2];  // points normalised on the device | inversion groups run
 
 size_t record_bytes(int form) { return form == CURDLE_G1_FORM_JAC ? 144 : 192; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // one launch of k_g1_normalize and its two counters
 int normalize_launch(const void* d_in, int form, size_t n, void* d_out, hipStream_t st) {
@@ -32,14 +31,11 @@ int normalize_launch(const void* d_in, int form, size_t n, void* d_out, hipStrea
 // both device memory), on the slot's stream or the caller's.  The stream is synchronised before the slot is released.
 int normalize_through_slot(Ctx& cx, const uint64_t* points, const void* d_in, int form, size_t n, uint64_t* out, void* d_out,
                            void* user_stream) {
-  int idx;
-  int rc = acquire_slot(cx, true, &idx);
-  if (rc) return rc;
-  Slot& S = cx.slots[idx];
-  const hipStream_t st = user_stream ? (hipStream_t)user_stream : S.stream;
   const size_t rec = record_bytes(form);
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cx, true, user_stream);
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
     int r;
     if (d_in) {
       if ((r = normalize_launch(d_in, form, n, d_out, st))) return r;
@@ -62,11 +58,7 @@ int normalize_through_slot(Ctx& cx, const uint64_t* points, const void* d_in, in
       memcpy(out + 12 * lo, S.h_stage[1], m * 96);
     }
     return CURDLE_OK;
-  };
-  rc = body();
-  if (rc) (void)hipStreamSynchronize(st);  // nothing queued may outlive the slot's hold
-  release_slot(cx, idx);
-  return rc;
+  });
 }
 
 int check_form_and_count(int form, size_t n) {
@@ -99,14 +91,10 @@ extern "C" int curdle_g1_scalar_mul_batch_device(const void* d_points, const voi
   if (n > kNormalizeMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^24 points", n);
   if (!aligned16(d_points) || !aligned16(d_scalars) || !aligned16(d_addends) || !aligned16(d_out_affine))
     return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
-  Ctx& cx = cur();
-  int idx;
-  int rc = acquire_slot(cx, true, &idx);
-  if (rc) return rc;
-  Slot& S = cx.slots[idx];
-  const hipStream_t st = stream ? (hipStream_t)stream : S.stream;
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
+  SlotHold H(cur(), true, stream);
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
     int r;
     // every result is in the slot's workspace before the first record is written: the output may be d_points or d_addends
     if ((r = ensure(S.sorted, n * sizeof(G1XYZZ)))) return r;
@@ -114,15 +102,7 @@ extern "C" int curdle_g1_scalar_mul_batch_device(const void* d_points, const voi
     if ((r = normalize_launch(S.sorted.p, CURDLE_G1_FORM_XYZZ, n, d_out_affine, st))) return r;
     HIP_TRY(hipStreamSynchronize(st));
     return CURDLE_OK;
-  };
-  rc = body();
-  if (rc) (void)hipStreamSynchronize(st);
-  release_slot(cx, idx);
-  return rc;
+  });
 }
 
-extern "C" int curdle_stat_normalize(unsigned long long out[2]) {
-  if (!out) return CURDLE_EINVAL;
-  for (int i = 0; i < 2; i++) out[i] = g_nz_stat[i].load(std::memory_order_relaxed);
-  return CURDLE_OK;
-}
+extern "C" int curdle_stat_normalize(unsigned long long out[2]) { return read_stats(out, g_nz_stat, 2); }

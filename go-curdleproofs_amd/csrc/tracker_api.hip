@@ -19,8 +19,9 @@
 // (launch_transcript_batch, the tape compiled once per process) and the subgroup test run on the second slot's stream
 // beside the square roots; k_tracker_challenge puts c next to s, k_tracker_check runs as above.  Tape, start state,
 // rows and challenges live in the held slot's buffers: the transcript context (TrCtx) and its lock are not touched.
-// No stream is made here and no device memory is allocated once the slots' buffers have grown to the batch.
-#include "msm_internal.h"
+// No stream is made here and no device memory is allocated once the slots' buffers have grown to the batch.  Both
+// halves hold their slot, and the second one when one is free, with a SlotHold (api_helpers.h).
+#include "api_helpers.h"
 
 #include <algorithm>
 #include <exception>
@@ -38,6 +39,19 @@ constexpr size_t kRec = 48;                  // one compressed G1 record
 constexpr size_t kTrackerPass = (size_t)1 << 16;  // members per pass: 327,680 records, 31 MB of decoded points
 constexpr size_t kHashPerThread = 128;       // members' transcripts per host thread (one is ~2.7 us)
 constexpr unsigned kMaxHashThreads = 16;
+
+// The body of a batch: the constant tape is compiled on its first use and the host's share allocates, and neither may
+// leave the C ABI as an exception.
+template <class Body>
+int guarded(const char* what, Body body) {
+  try {
+    return body();
+  } catch (const std::logic_error& e) {  // the constant tape did not compile to the shape the kernels expect
+    return fail(CURDLE_EHIP, "%s: internal error: %s", what, e.what());
+  } catch (const std::exception& e) {
+    return fail(CURDLE_ENOMEM, "%s: %s", what, e.what());
+  }
+}
 
 // One member's challenge and response, in the kernel's layout (s then c, canonical, little-endian words);
 // false if S is not canonical (< r), as TrackerProof.FromBytes requires (types.go:105-117).
@@ -320,26 +334,14 @@ int tracker_batch(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t
     rc = fail(CURDLE_EINVAL, "null argument");
   } else {
     Ctx& cx = cur();
-    int ia = -1, ib = -1;
-    rc = acquire_slot(cx, true, &ia);
-    if (rc == CURDLE_OK) {
-      // a second slot only lends its stream (and two events) to the subgroup test and the transcripts; without one
-      // they run behind the square roots.  A caller's stream carries the whole pass.
-      if (!user_stream) {
-        std::lock_guard<std::mutex> g(cx.mu);
-        for (int i = 0; i < kSlots && ib < 0; i++)
-          if (!cx.slots[i].busy) {
-            cx.slots[i].busy = true;
-            cx.slots[i].claimed = false;
-            cx.slots[i].gen++;
-            ib = i;
-          }
-      }
-      Slot& A = cx.slots[ia];
-      Slot* B = ib >= 0 ? &cx.slots[ib] : nullptr;
-      const hipStream_t sa = user_stream ? (hipStream_t)user_stream : A.stream;
-      auto body = [&]() -> int {
-        HIP_TRY(hipSetDevice(cx.device));
+    SlotHold H(cx, true, user_stream);
+    // a second slot only lends its stream (and two events) to the subgroup test and the transcripts; without one
+    // they run behind the square roots.  A caller's stream carries the whole pass.
+    Slot* B = user_stream ? nullptr : H.try_second();
+    rc = H.run([&]() -> int {
+      return guarded("tracker check", [&]() -> int {
+        Slot& A = H.slot();
+        const hipStream_t sa = H.stream();
         for (size_t lo = 0; lo < k; lo += kTrackerPass) {
           const size_t m = std::min(kTrackerPass, k - lo);
           const int r = hash_device ? tracker_pass_device(cx, A, B, sa, trackers + 96 * lo, k_comms + kRec * lo,
@@ -349,21 +351,8 @@ int tracker_batch(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t
           if (r) return r;
         }
         return CURDLE_OK;
-      };
-      try {
-        rc = body();
-      } catch (const std::logic_error& e) {  // the constant tape did not compile to the shape the kernels expect
-        rc = fail(CURDLE_EHIP, "tracker check: internal error: %s", e.what());
-      } catch (const std::exception& e) {
-        rc = fail(CURDLE_ENOMEM, "tracker check: %s", e.what());
-      }
-      if (rc) {  // nothing queued may outlive the slots' hold
-        (void)hipStreamSynchronize(sa);
-        if (B) (void)hipStreamSynchronize(B->stream);
-      }
-      if (B) release_slot(cx, ib);
-      release_slot(cx, ia);
-    }
+      });
+    });
   }
   if (rc != CURDLE_OK && results)  // "could not compute" must never read as a verdict
     for (size_t i = 0; i < k; i++) results[i] = rc;
@@ -389,20 +378,7 @@ struct ProvePass {
   Slot& A;
   hipStream_t sa;
   size_t m;
-  // the places a secret was written to in this pass (null: not yet)
-  void* d_sc = nullptr;
-  void* d_xyzz = nullptr;
-  uint8_t* h_secret = nullptr;
-  // Overwrites them, on the pass's stream and behind everything queued there; called on every way out of a pass.
-  int wipe() {
-    hipError_t e = hipSuccess, e2;
-    if (d_sc && (e2 = hipMemsetAsync(d_sc, 0, 96 * m, sa)) != hipSuccess) e = e2;
-    if (d_xyzz && (e2 = hipMemsetAsync(d_xyzz, 0, 576 * m, sa)) != hipSuccess) e = e2;
-    if ((e2 = hipStreamSynchronize(sa)) != hipSuccess) e = e2;
-    if (h_secret) explicit_bzero(h_secret, 64 * m);
-    if (e != hipSuccess) return fail(CURDLE_EHIP, "tracker proofs: clearing the secrets: %s", hipGetErrorString(e));
-    return CURDLE_OK;
-  }
+  WipeList W;  // the places a secret was written to in this pass; wiped on every way out of the pass
 };
 
 int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders,
@@ -440,11 +416,11 @@ int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, cons
 
   memcpy(h_in, T.bytes.data(), tape_bytes);
   memcpy(h_in + tape_bytes, trackers, 96 * m);
-  P.h_secret = h_k;
+  P.W.note_host(h_k, 64 * m);
   memcpy(h_k, ks, 32 * m);
   if (blinders) memcpy(h_b, blinders, 32 * m);
   HIP_TRY(hipMemcpyAsync(d_tape, h_in, tape_bytes + 96 * m, hipMemcpyHostToDevice, sa));
-  P.d_sc = d_sc;
+  P.W.note_device(d_sc, 96 * m);
   HIP_TRY(hipMemcpyAsync(d_sc, h_k, (blinders ? 64 : 32) * m, hipMemcpyHostToDevice, sa));
   if (B) {
     HIP_TRY(hipEventRecord(A.pre_done, sa));
@@ -474,7 +450,7 @@ int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, cons
   G1Affine gen;
   g1_generator(gen);
   HIP_TRY(launch_tracker_prove_pairs(d_dec, gen, (uint32_t)m, d_pairs, d_sc, sa));
-  P.d_xyzz = d_xyzz;
+  P.W.note_device(d_xyzz, 576 * m);
   HIP_TRY(launch_scalar_mul_batch(d_pairs, d_sc, 0, nullptr, (uint32_t)(3 * m), d_xyzz, sa));
   HIP_TRY(launch_g1_compress(d_xyzz, kCompressXyzz, (uint32_t)(3 * m), d_comp, sa));
   HIP_TRY(launch_tracker_prove_rows(d_trk, d_comp, d_tape + T.gen_off, (uint32_t)m, d_rows, sa));
@@ -536,47 +512,21 @@ int tracker_prove_batch(const uint8_t* trackers, const uint64_t* ks, const uint6
     rc = fail(CURDLE_EINVAL, "null argument");
   } else {
     Ctx& cx = cur();
-    int ia = -1, ib = -1;
-    rc = acquire_slot(cx, true, &ia);
-    if (rc == CURDLE_OK) {
-      {  // a second slot only lends its stream and an event to the subgroup test
-        std::lock_guard<std::mutex> g(cx.mu);
-        for (int i = 0; i < kSlots && ib < 0; i++)
-          if (!cx.slots[i].busy) {
-            cx.slots[i].busy = true;
-            cx.slots[i].claimed = false;
-            cx.slots[i].gen++;
-            ib = i;
-          }
-      }
-      Slot& A = cx.slots[ia];
-      Slot* B = ib >= 0 ? &cx.slots[ib] : nullptr;
-      auto body = [&]() -> int {
-        HIP_TRY(hipSetDevice(cx.device));
+    SlotHold H(cx, true, nullptr);
+    Slot* B = H.try_second();  // a second slot only lends its stream and an event to the subgroup test
+    rc = H.run([&]() -> int {
+      return guarded("tracker proofs", [&]() -> int {
         for (size_t lo = 0; lo < k; lo += kTrackerPass) {
-          ProvePass P{A, A.stream, std::min(kTrackerPass, k - lo)};
+          ProvePass P{H.slot(), H.stream(), std::min(kTrackerPass, k - lo), WipeList(H.stream())};
           int r = prove_pass_run(cx, P, B, trackers + 96 * lo, ks + 4 * lo, blinders ? blinders + 4 * lo : nullptr, rand,
                                  proofs_out + 128 * lo, results + lo);
           if (r && B) (void)hipStreamSynchronize(B->stream);
-          const int w = P.wipe();  // on every way out: nothing of k and b stays behind in the slot
+          const int w = P.W.wipe("tracker proofs: clearing the secrets");  // nothing of k and b stays behind in the slot
           if (r || w) return r ? r : w;
         }
         return CURDLE_OK;
-      };
-      try {
-        rc = body();
-      } catch (const std::logic_error& e) {  // the constant tape did not compile to the shape the kernels expect
-        rc = fail(CURDLE_EHIP, "tracker proofs: internal error: %s", e.what());
-      } catch (const std::exception& e) {
-        rc = fail(CURDLE_ENOMEM, "tracker proofs: %s", e.what());
-      }
-      if (rc) {  // nothing queued may outlive the slots' hold
-        (void)hipStreamSynchronize(A.stream);
-        if (B) (void)hipStreamSynchronize(B->stream);
-      }
-      if (B) release_slot(cx, ib);
-      release_slot(cx, ia);
-    }
+      });
+    });
   }
   if (rc != CURDLE_OK) {  // "could not compute" must never read as a proof
     if (results)
@@ -617,11 +567,7 @@ extern "C" int curdle_whisk_is_valid_tracker_proof_batch_device(const void* d_tr
                        static_cast<const uint8_t*>(d_proofs), k, true, true, stream, results);
 }
 
-extern "C" int curdle_stat_tracker(unsigned long long out[3]) {
-  if (!out) return CURDLE_EINVAL;
-  for (int i = 0; i < 3; i++) out[i] = g_tk_stat[i].load(std::memory_order_relaxed);
-  return CURDLE_OK;
-}
+extern "C" int curdle_stat_tracker(unsigned long long out[3]) { return read_stats(out, g_tk_stat, 3); }
 
 extern "C" int curdle_whisk_generate_tracker_proof_batch_blinders(const uint8_t* trackers, const uint64_t* ks,
                                                                   const uint64_t* blinders, size_t k, uint8_t* proofs_out,
@@ -636,8 +582,4 @@ extern "C" int curdle_whisk_generate_tracker_proof_batch(const uint8_t* trackers
   return tracker_prove_batch(trackers, ks, nullptr, rand, k, proofs_out, results);
 }
 
-extern "C" int curdle_stat_tracker_prove(unsigned long long out[2]) {
-  if (!out) return CURDLE_EINVAL;
-  for (int i = 0; i < 2; i++) out[i] = g_tp_stat[i].load(std::memory_order_relaxed);
-  return CURDLE_OK;
-}
+extern "C" int curdle_stat_tracker_prove(unsigned long long out[2]) { return read_stats(out, g_tp_stat, 2); }

@@ -2,15 +2,16 @@
 // _device, owned[j * n + i] = does key j own tracker i, for m keys and n trackers in one call.  (The single form,
 // curdle_whisk_is_own_tracker, is host code: host/proto_api.cpp.)
 //
-// The call takes ONE MSM slot for its buffers and its stream, like the tracker batch (tracker_api.hip); no stream is
+// The call takes ONE MSM slot for its buffers and its stream, held by a SlotHold (api_helpers.h); no stream is
 // made here and nothing is allocated once the slot's buffers have grown.  Per pass of at most kOwnPass trackers:
 //   1. the pass's 2 x 48-byte records ARE the decoder's input: they go up as they are (or are read where the caller
 //      keeps them: _device) and are decoded ONCE, subgroup test included (launch_g1_decompress), for all keys;
 //   2. k_tracker_own runs over the (key, tracker) grid in launches of at most TRACKER_OWN_PAIRS quads, back to back
 //      on the one stream (own_launches below is the rule);
 //   3. the verdict bytes of the pass come back once (host form), with the 2 x status bytes that count the bad pairs.
-// The keys are secrets: see wipe().
-#include "msm_internal.h"
+// The keys are secrets: the library's copies of them are on the call's WipeList (api_helpers.h) and are overwritten on
+// every way out; the kernel keeps the keys and their split halves in registers only.
+#include "api_helpers.h"
 
 #include <algorithm>
 
@@ -26,8 +27,6 @@ constexpr size_t kOwnPairsDefault = (size_t)1 << 18;
 
 // pairs answered on the device | launches | those of the pairs answered BAD; completed passes only
 std::atomic<unsigned long long> g_own_stat[3];
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 size_t pairs_per_launch() {
   const long long knob = knobs::get(knobs::TRACKER_OWN_PAIRS);
@@ -63,30 +62,11 @@ int own_launches(const void* d_points, const uint8_t* d_status, const void* d_ke
   return CURDLE_OK;
 }
 
-struct OwnCall {
-  Slot& S;
-  hipStream_t st;
-  size_t m;
-  // the library's copies of the keys (null: none yet); the caller's own d_ks is never one of them
-  void* d_keys = nullptr;
-  void* h_keys = nullptr;
-  // Overwrites them, on the call's stream and behind everything queued there; called on every way out.  The kernel
-  // keeps the keys and their split halves in registers only.
-  int wipe() {
-    hipError_t e = hipSuccess, e2;
-    if (d_keys && (e2 = hipMemsetAsync(d_keys, 0, 32 * m, st)) != hipSuccess) e = e2;
-    if ((e2 = hipStreamSynchronize(st)) != hipSuccess) e = e2;
-    if (h_keys) explicit_bzero(h_keys, 32 * m);
-    if (e != hipSuccess) return fail(CURDLE_EHIP, "own trackers: clearing the keys: %s", hipGetErrorString(e));
-    return CURDLE_OK;
-  }
-};
-
-// trackers / ks: host memory (resident false) or device memory; owned likewise.
-int own_run(OwnCall& C, const uint8_t* trackers, size_t n, const uint64_t* ks, bool resident, uint8_t* owned) {
-  Slot& S = C.S;
-  const hipStream_t st = C.st;
-  const size_t m = C.m, cap = std::min(n, kOwnPass);
+// trackers / ks: host memory (resident false) or device memory; owned likewise.  W: the library's copies of the keys
+// (the caller's own d_ks is never one of them).
+int own_run(Slot& S, hipStream_t st, WipeList& W, const uint8_t* trackers, size_t n, const uint64_t* ks, size_t m,
+            bool resident, uint8_t* owned) {
+  const size_t cap = std::min(n, kOwnPass);
   int r;
   if ((r = ensure(S.points, 192 * cap))) return r;  // decoded records
   if ((r = ensure(S.counts, 2 * cap))) return r;    // their statuses
@@ -103,11 +83,12 @@ int own_run(OwnCall& C, const uint8_t* trackers, size_t n, const uint64_t* ks, b
     const size_t keys_at = (96 * cap + 255) / 256 * 256;  // trackers | keys
     if ((r = ensure_pinned(S, 0, keys_at + 32 * m))) return r;
     h_trk = static_cast<uint8_t*>(S.h_stage[0]);
-    C.h_keys = h_trk + keys_at;
-    memcpy(C.h_keys, ks, 32 * m);
-    C.d_keys = S.digits.p;
-    HIP_TRY(hipMemcpyAsync(C.d_keys, C.h_keys, 32 * m, hipMemcpyHostToDevice, st));
-    d_keys = C.d_keys;
+    uint8_t* h_keys = h_trk + keys_at;
+    W.note_host(h_keys, 32 * m);
+    memcpy(h_keys, ks, 32 * m);
+    W.note_device(S.digits.p, 32 * m);
+    HIP_TRY(hipMemcpyAsync(S.digits.p, h_keys, 32 * m, hipMemcpyHostToDevice, st));
+    d_keys = S.digits.p;
   }
   for (size_t lo = 0; lo < n; lo += kOwnPass) {
     const size_t cnt = std::min(kOwnPass, n - lo);
@@ -141,20 +122,10 @@ int own_run(OwnCall& C, const uint8_t* trackers, size_t n, const uint64_t* ks, b
 
 int own_through_slot(const uint8_t* trackers, size_t n, const uint64_t* ks, size_t m, bool resident, uint8_t* owned,
                      void* user_stream) {
-  Ctx& cx = cur();
-  int idx;
-  int rc = acquire_slot(cx, true, &idx);
-  if (rc) return rc;
-  Slot& S = cx.slots[idx];
-  OwnCall C{S, user_stream ? (hipStream_t)user_stream : S.stream, m};
-  auto body = [&]() -> int {
-    HIP_TRY(hipSetDevice(cx.device));
-    return own_run(C, trackers, n, ks, resident, owned);
-  };
-  rc = body();
-  const int w = C.wipe();  // synchronises the stream: nothing queued outlives the slot's hold, nothing of the keys stays
-  release_slot(cx, idx);
-  return rc ? rc : w;
+  SlotHold H(cur(), true, user_stream);
+  WipeList W(H.stream());
+  H.wipe_on_exit(&W, "own trackers: clearing the keys");  // nothing of the keys stays, however the call ends
+  return H.run([&]() -> int { return own_run(H.slot(), H.stream(), W, trackers, n, ks, m, resident, owned); });
 }
 
 int check_counts(size_t n, size_t m) {
@@ -189,8 +160,4 @@ extern "C" int curdle_whisk_find_own_trackers_device(const void* d_trackers, siz
                           static_cast<uint8_t*>(d_owned), stream);
 }
 
-extern "C" int curdle_stat_tracker_own(unsigned long long out[3]) {
-  if (!out) return CURDLE_EINVAL;
-  for (int i = 0; i < 3; i++) out[i] = g_own_stat[i].load(std::memory_order_relaxed);
-  return CURDLE_OK;
-}
+extern "C" int curdle_stat_tracker_own(unsigned long long out[3]) { return read_stats(out, g_own_stat, 3); }

@@ -3,7 +3,7 @@
 // twin curdle_transcript_batch_host in host/transcript.cpp), tape, start states and the members' rows go up in ONE
 // copy, ONE kernel runs (transcript_kernels.hip), challenges, states and status bytes come back in ONE copy -- all on
 // the context's transcript stream and buffers (TrCtx, msm_internal.h), never through an MSM slot or a decode context.
-#include "msm_internal.h"
+#include "api_helpers.h"
 #include "../host/transcript.h"
 #include "../host/transcript_batch.h"
 
@@ -149,11 +149,7 @@ extern "C" int curdle_transcript_batch(const char* transcript_label, const uint8
   return CURDLE_OK;
 }
 
-extern "C" int curdle_stat_transcript(unsigned long long out[2]) {
-  if (!out) return CURDLE_EINVAL;
-  for (int i = 0; i < 2; i++) out[i] = g_tr_stat[i].load(std::memory_order_relaxed);
-  return CURDLE_OK;
-}
+extern "C" int curdle_stat_transcript(unsigned long long out[2]) { return read_stats(out, g_tr_stat, 2); }
 
 extern "C" int curdle_transcript_last_kernel_ms(double* out) {
   if (!out) return fail(CURDLE_EINVAL, "null argument");
