@@ -98,6 +98,7 @@ struct Slot {
   bool profiled = false;
   Buf chain;                  // k_scan_chain's words and ticket counter (zero when made; cleared again only after a failed call)
   Buf mdone;                  // k_merge_large's chunk counters, one per queue entry and base set (zero when made; the kernel leaves them zero)
+  Buf tracker_keep;           // the combined tracker check: what must survive the MSM it runs in this slot (tracker_api.hip)
   uint32_t* h_err = nullptr;  // pinned word a kernel raises when it cannot finish the call correctly (kErr*; finish_slot reads it)
   uint32_t scan_epoch = 0;    // epoch of the slot's last k_scan_chain launch (30 bits, never 0)
   uint32_t scan_base = 0;     // tickets the slot's launches have taken so far
@@ -111,7 +112,7 @@ struct Slot {
   Buf* all_bufs(int i) {
     Buf* b[] = {&points, &scalars, &offsets, &points28, &counts, &starts, &cursor, &fragcnt, &foff, &small,
                 &digits, &sorted,  &frags,   &partials, &winsums, &winsums28, &results, &job,      &tmp,    &ccur,
-                &fold_sums, &fold_meta, &chain,   &mdone};
+                &fold_sums, &fold_meta, &chain,   &mdone,    &tracker_keep};
     return i < (int)(sizeof(b) / sizeof(b[0])) ? b[i] : nullptr;
   }
 };

@@ -273,6 +273,21 @@ hipError_t launch_tracker_gather(const uint8_t* trackers, const uint8_t* k_comms
 hipError_t launch_tracker_challenge(const void* challenges, const uint8_t* tr_status, uint32_t n, void* scalars,
                                     uint8_t* skip, hipStream_t stream);
 
+// tracker_combine_kernels.hip: the scalars of the combined tracker check, one lane per member.  From the records'
+// status bytes and subgroup verdicts, s | c at sc + 16 i (launch_tracker_challenge's layout) and skip, member i's five
+// MSM scalars (Montgomery fr.Elements, for rG krG kG A B: sigma s, sigma c, rho c, -rho, -sigma; all zero for an
+// excluded member) go to scalars + 40 i words, and block b's sum of rho s mod r to pair 5 n + b, whose point (the
+// generator) the kernel writes to points + 96 (5 n + b) bytes.  scalars and points hold 5 n + tracker_combine_blocks(n)
+// pairs, 16-byte aligned.  seed: the first nine words of the SHAKE256 rate block "curdle/tracker-combine/v1" | seed |
+// le64(0) | 0x1f; `first` is the index in the call of the pass's member 0.
+struct TrackerCombineSeed {
+  uint64_t w[9];
+};
+uint32_t tracker_combine_blocks(uint32_t n);
+hipError_t launch_tracker_combine(const uint8_t* status, const uint8_t* sub, const void* sc, const uint8_t* skip,
+                                  const TrackerCombineSeed& seed, uint64_t first, uint32_t n, const G1Affine& gen,
+                                  void* scalars, void* points, hipStream_t stream);
+
 // tracker_own_kernels.hip: does key j own tracker t, one (key, tracker) pair per quad and 64 trackers of ONE key per
 // block, so that every tested key bit is wave-uniform.  points: decoded records, rG_t at 2 t and krG_t at 2 t + 1, with
 // their CURDLE_DECODE_* status bytes (subgroup test included); keys: Montgomery fr.Elements, 16-byte aligned.  One

@@ -19,6 +19,9 @@
 // (launch_transcript_batch, the tape compiled once per process) and the subgroup test run on the second slot's stream
 // beside the square roots; k_tracker_challenge puts c next to s, k_tracker_check runs as above.  Tape, start state,
 // rows and challenges live in the held slot's buffers: the transcript context (TrCtx) and its lock are not touched.
+// COMBINED (tracker_pass_combined, curdle_whisk_is_valid_tracker_proof_batch_combined / _device): the device-hashed
+// pass up to k_tracker_challenge, then ONE randomly weighted MSM over the decoded records settles the pass;
+// k_tracker_check runs only when the sum is not infinity (the section before the generation half has the layout).
 // No stream is made here and no device memory is allocated once the slots' buffers have grown to the batch.  Both
 // halves hold their slot, and the second one when one is free, with a SlotHold (api_helpers.h).
 #include "api_helpers.h"
@@ -359,6 +362,232 @@ int tracker_batch(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t
   return rc;
 }
 
+// --- the combined form: a pass settled by ONE randomly weighted MSM -----------------------------------------------------
+//
+// curdle_whisk_is_valid_tracker_proof_batch_combined (_device).  A pass starts as tracker_pass_device does (upload,
+// gather, transcripts and subgroup test beside the square roots, k_tracker_challenge); then k_tracker_combine
+// (tracker_combine_kernels.hip) writes the 5 m scalars of the weighted sum of the members' 2 m equations and one
+// (G, partial sum) pair per block, and the library's own MSM (enqueue_slot / finish_slot) runs over the decoded records
+// on the pass's stream.  Infinity: every member that was not excluded is accepted.  Anything else: k_tracker_check
+// runs as in the plain form and its verdicts are the answer.
+//
+// The MSM runs in the HELD slot, so the pass keeps nothing it needs afterwards in a buffer enqueue_slot writes
+// (offsets, counts, starts, cursor, fragcnt, foff, small, digits, sorted, tmp, ccur, points28, frags, partials,
+// winsums, winsums28, results, chain, mdone and the pinned h_buf).  enqueue_slot never touches `points` and `scalars`
+// (they are the staging of the host-buffer MSM entry points, which hold their own slot), `tracker_keep` (this
+// pass's alone) or the pinned h_stage pair, and that is where everything read after the MSM lives:
+//   points        the 5 m decoded records | the blocks' generator points        (the MSM's bases; the fallback's input)
+//   scalars       the 5 m compressed records | the 5 m + blocks MSM scalars
+//   tracker_keep  statuses | subgroup verdicts | member verdicts | transcript statuses | skip | s, c
+// `sorted` holds tape, arrays, rows and challenges as in the plain form: all of it is consumed by k_tracker_challenge,
+// in stream order before the MSM's first kernel.  No second slot is waited for: B only lends its stream, as above, and
+// on a caller's stream there is none and the whole pass, MSM included, runs on that stream.
+std::atomic<unsigned long long> g_tc_stat[4];  // passes settled by the sum | fallen back | members accepted by a sum | excluded
+std::atomic<float> g_tc_kernel_ms{0};          // k_tracker_combine in the last curdle_whisk_tracker_combined_scalars, by HIP events
+
+void combine_seed_words(const uint8_t seed[32], TrackerCombineSeed* out) {
+  static const char kDomain[] = "curdle/tracker-combine/v1";  // 25 bytes
+  uint8_t block[72] = {0};
+  memcpy(block, kDomain, 25);
+  memcpy(block + 25, seed, 32);
+  block[65] = 0x1f;  // SHAKE's domain bits and the first padding bit, behind the 65 bytes of input
+  memcpy(out->w, block, 72);
+}
+
+struct CombineDiag {  // curdle_whisk_tracker_combined_scalars: the pass stops behind k_tracker_combine
+  uint64_t* scalars_out;
+  uint64_t* g_out;
+};
+
+int tracker_pass_combined(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8_t* trackers, const uint8_t* k_comms,
+                          const uint8_t* proofs, bool resident, size_t m, size_t first, const TrackerCombineSeed& seed,
+                          int* results, const CombineDiag* diag) {
+  static const TrackerTape T;
+  const size_t nrec = 5 * m, tape_bytes = T.bytes.size(), raw_bytes = resident ? 0 : 272 * m;
+  const size_t nblk = tracker_combine_blocks((uint32_t)m), npairs = nrec + nblk;
+  const size_t bytes_out = 2 * nrec + 3 * m;          // statuses | subgroup verdicts | member verdicts | transcript statuses | skip
+  const size_t sc_off = (bytes_out + 15) / 16 * 16;  // s, c behind them
+  int r;
+  if ((r = ensure(A.scalars, nrec * kRec + npairs * 32))) return r;
+  if ((r = ensure(A.points, npairs * 96))) return r;
+  if ((r = ensure(A.tracker_keep, sc_off + 64 * m))) return r;
+  if ((r = ensure(A.sorted, tape_bytes + raw_bytes + (kRowBytes + 32) * m))) return r;  // tape | the arrays | rows | challenges
+  if ((r = ensure_pinned(A, 0, tape_bytes + raw_bytes))) return r;
+  if ((r = ensure_pinned(A, 1, bytes_out + (diag ? nblk * 32 : 0)))) return r;
+  uint8_t* h_in = static_cast<uint8_t*>(A.h_stage[0]);
+  uint8_t* h_out = static_cast<uint8_t*>(A.h_stage[1]);
+  uint8_t* d_tape = static_cast<uint8_t*>(A.sorted.p);
+  uint8_t* d_raw = d_tape + tape_bytes;
+  uint8_t* d_rows = d_raw + raw_bytes;
+  uint8_t* d_ch = d_rows + kRowBytes * m;
+  uint8_t* d_rec = static_cast<uint8_t*>(A.scalars.p);
+  uint8_t* d_msm_sc = d_rec + nrec * kRec;
+  uint8_t* d_status = static_cast<uint8_t*>(A.tracker_keep.p);
+  uint8_t* d_sub = d_status + nrec;
+  uint8_t* d_out = d_sub + nrec;
+  uint8_t* d_trst = d_out + m;
+  uint8_t* d_skip = d_trst + m;
+  uint8_t* d_sc = d_status + sc_off;
+  memcpy(h_in, T.bytes.data(), tape_bytes);
+  if (!resident) {
+    memcpy(h_in + tape_bytes, trackers, 96 * m);
+    memcpy(h_in + tape_bytes + 96 * m, k_comms, kRec * m);
+    memcpy(h_in + tape_bytes + 144 * m, proofs, 128 * m);
+    trackers = d_raw, k_comms = d_raw + 96 * m, proofs = d_raw + 144 * m;
+  }
+  HIP_TRY(hipMemcpyAsync(d_tape, h_in, tape_bytes + raw_bytes, hipMemcpyHostToDevice, sa));
+  HIP_TRY(launch_tracker_gather(trackers, k_comms, proofs, d_tape + T.gen_off, (uint32_t)m, d_rec, d_rows, d_sc, d_skip, sa));
+  TranscriptArgs ta = {};
+  ta.ctl = reinterpret_cast<const curdle::transcript::TapeCtl*>(d_tape);
+  ta.pool = reinterpret_cast<const curdle::transcript::TapeBlock*>(d_tape + T.pool_off);
+  ta.data = reinterpret_cast<const uint64_t*>(d_rows);
+  ta.init = reinterpret_cast<const uint64_t*>(d_tape + T.init_off);
+  ta.challenges = reinterpret_cast<uint64_t*>(d_ch);
+  ta.states = nullptr;
+  ta.status = d_trst;
+  ta.tail = T.tail;
+  ta.n_ctl = T.n_ctl;
+  ta.row_words = (uint32_t)(kRowBytes / 8);
+  ta.init_stride = 0;
+  ta.k = (uint32_t)m;
+  ta.mpw = members_per_wave(m);
+  ta.n_challenges = 1;
+  if (B) {  // transcripts, then the subgroup test, beside the square roots
+    HIP_TRY(hipEventRecord(A.pre_done, sa));
+    HIP_TRY(hipStreamWaitEvent(B->stream, A.pre_done, 0));
+    HIP_TRY(launch_transcript_batch(ta, B->stream));
+    HIP_TRY(hipEventRecord(B->pre_done, B->stream));
+    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, B->stream));
+    HIP_TRY(hipEventRecord(B->acc_done, B->stream));
+  }
+  HIP_TRY(launch_g1_decompress(d_rec, (uint32_t)nrec, 0, (uint32_t*)A.points.p, d_status, sa));
+  if (B) {
+    HIP_TRY(hipStreamWaitEvent(sa, B->pre_done, 0));
+  } else {
+    HIP_TRY(launch_transcript_batch(ta, sa));
+    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, sa));
+  }
+  HIP_TRY(launch_tracker_challenge(d_ch, d_trst, (uint32_t)m, d_sc, d_skip, sa));
+  // the scalars wait for the subgroup verdicts too: a record outside the subgroup must get a zero scalar
+  if (B) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));
+  G1Affine gen;
+  g1_generator(gen);
+  if (diag) {  // the diagnostic brackets the kernel with the slot's profiling events (made on their first use, like Prof's)
+    if (!A.ev_made) {
+      for (auto& e : A.ev) HIP_TRY(hipEventCreate(&e));
+      A.ev_made = true;
+    }
+    HIP_TRY(hipEventRecord(A.ev[0], sa));
+  }
+  HIP_TRY(launch_tracker_combine(d_status, d_sub, d_sc, d_skip, seed, (uint64_t)first, (uint32_t)m, gen, d_msm_sc, A.points.p, sa));
+  if (diag) {
+    HIP_TRY(hipEventRecord(A.ev[1], sa));
+    HIP_TRY(hipMemcpyAsync(diag->scalars_out, d_msm_sc, nrec * 32, hipMemcpyDeviceToHost, sa));
+    HIP_TRY(hipMemcpyAsync(h_out + bytes_out, d_msm_sc + nrec * 32, nblk * 32, hipMemcpyDeviceToHost, sa));
+    HIP_TRY(hipStreamSynchronize(sa));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, A.ev[0], A.ev[1]));
+    g_tc_kernel_ms.store(ms, std::memory_order_relaxed);
+    Fr g;
+    f_zero(g);
+    for (size_t b = 0; b < nblk; b++) {
+      Fr part;
+      memcpy(part.l, h_out + bytes_out + 32 * b, 32);
+      fr_add(g, g, part);
+    }
+    memcpy(diag->g_out, g.l, 32);
+    return CURDLE_OK;
+  }
+  // everything but the chains' verdicts comes back behind the scalars, ahead of the MSM: finish_slot's wait covers it
+  HIP_TRY(hipMemcpyAsync(h_out, d_status, bytes_out, hipMemcpyDeviceToHost, sa));
+  const uint32_t off[2] = {0, (uint32_t)npairs};
+  MsmCall call{off};
+  MsmInputs in;
+  in.points = A.points.p;
+  in.scalars = d_msm_sc;
+  uint64_t sum[18];
+  if ((r = enqueue_slot(cx, A, call, in, {sa, sa, sa}))) return r;
+  if ((r = finish_slot(cx, A, sum))) return r;
+  bool settled = true;  // Z = 0: the weighted sum is the point at infinity
+  for (int w = 12; w < 18; w++) settled &= sum[w] == 0;
+  const uint8_t* st = h_out;
+  const uint8_t* sub = h_out + nrec;
+  const uint8_t* verdict = h_out + 2 * nrec;
+  const uint8_t* trst = verdict + m;
+  const uint8_t* skip = trst + m;
+  if (!settled) {
+    HIP_TRY(launch_tracker_check(A.points.p, d_status, d_sc, d_skip, gen, (uint32_t)m, d_out, sa));
+    HIP_TRY(hipMemcpyAsync(h_out + 2 * nrec, d_out, m, hipMemcpyDeviceToHost, sa));
+    HIP_TRY(hipStreamSynchronize(sa));
+  }
+  unsigned long long accepted = 0, excluded = 0;
+  for (size_t i = 0; i < m; i++) {
+    if (trst[i]) {  // 256 rejected draws (0.547^256): the single call settles the member on the host
+      if (resident) return fail(CURDLE_EHIP, "tracker check: member %zu of a pass drew no canonical challenge", i);
+      int ok = 0;
+      const int rc = curdle_whisk_is_valid_tracker_proof(h_in + tape_bytes + 96 * i, h_in + tape_bytes + 96 * m + kRec * i,
+                                                         h_in + tape_bytes + 144 * m + 128 * i, &ok);
+      results[i] = rc ? rc : ok;
+      excluded++;
+      continue;
+    }
+    bool err = skip[i] != 0;  // S >= r
+    for (size_t j = 5 * i; j < 5 * i + 5; j++) err |= st[j] > CURDLE_DECODE_INFINITY || (st[j] == CURDLE_DECODE_OK && !sub[j]);
+    if (err) {
+      results[i] = CURDLE_EINVAL;
+      excluded++;
+    } else if (settled) {
+      results[i] = kTrackerAccept;
+      accepted++;
+    } else if (verdict[i] == kTrackerAccept || verdict[i] == kTrackerReject) {
+      results[i] = verdict[i];
+    } else {
+      return fail(CURDLE_EHIP, "tracker check: member %zu of a pass has no verdict", i);
+    }
+  }
+  g_tc_stat[settled ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+  g_tc_stat[2].fetch_add(accepted, std::memory_order_relaxed);
+  g_tc_stat[3].fetch_add(excluded, std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+// The whole combined call: host arrays or resident ones; with `diag`, one pass that stops behind the scalars.
+int tracker_batch_combined(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t* proofs, size_t k,
+                           const uint8_t* seed, bool resident, void* user_stream, int* results, const CombineDiag* diag) {
+  int rc = CURDLE_OK;
+  if (!trackers || !k_comms || !proofs || !seed || (!diag && !results) || (diag && (!diag->scalars_out || !diag->g_out))) {
+    rc = fail(CURDLE_EINVAL, "null argument");
+  } else if (diag && k > kTrackerPass) {
+    rc = fail(CURDLE_EINVAL, "the scalars of at most %zu members (one pass) can be read back", kTrackerPass);
+  } else {
+    TrackerCombineSeed words;
+    combine_seed_words(seed, &words);
+    Ctx& cx = cur();
+    SlotHold H(cx, true, user_stream);
+    Slot* B = user_stream ? nullptr : H.try_second();  // never waited for: it only lends its stream
+    rc = H.run([&]() -> int {
+      return guarded("combined tracker check", [&]() -> int {
+        Slot& A = H.slot();
+        const hipStream_t sa = H.stream();
+        for (size_t lo = 0; lo < k; lo += kTrackerPass) {
+          const size_t m = std::min(kTrackerPass, k - lo);
+          const int r = tracker_pass_combined(cx, A, B, sa, trackers + 96 * lo, k_comms + kRec * lo, proofs + 128 * lo,
+                                              resident, m, lo, words, results ? results + lo : nullptr, diag);
+          if (r) {  // nothing queued may outlive the hold (the drain below knows neither a caller's stream nor B)
+            (void)hipStreamSynchronize(sa);
+            if (B) (void)hipStreamSynchronize(B->stream);
+            return r;
+          }
+        }
+        return CURDLE_OK;
+      });
+    }, SlotHold::kDrainSlot);
+  }
+  if (rc != CURDLE_OK && results)  // "could not compute" must never read as a verdict
+    for (size_t i = 0; i < k; i++) results[i] = rc;
+  return rc;
+}
+
 // --- generation: k calls of GenerateWhiskTrackerProof (whisk.go:149-175) in one ---------------------------------------
 //
 // Per pass of at most kTrackerPass members, on the held slot's stream (B, when a second slot is free, lends its stream
@@ -568,6 +797,37 @@ extern "C" int curdle_whisk_is_valid_tracker_proof_batch_device(const void* d_tr
 }
 
 extern "C" int curdle_stat_tracker(unsigned long long out[3]) { return read_stats(out, g_tk_stat, 3); }
+
+extern "C" int curdle_whisk_is_valid_tracker_proof_batch_combined(const uint8_t* trackers, const uint8_t* k_commitments,
+                                                                  const uint8_t* proofs, size_t k, const uint8_t seed[32],
+                                                                  int* results) {
+  if (k == 0) return CURDLE_OK;
+  return tracker_batch_combined(trackers, k_commitments, proofs, k, seed, false, nullptr, results, nullptr);
+}
+
+extern "C" int curdle_whisk_is_valid_tracker_proof_batch_combined_device(const void* d_trackers, const void* d_k_commitments,
+                                                                         const void* d_proofs, size_t k, const uint8_t seed[32],
+                                                                         int* results, void* stream) {
+  if (k == 0) return CURDLE_OK;
+  return tracker_batch_combined(static_cast<const uint8_t*>(d_trackers), static_cast<const uint8_t*>(d_k_commitments),
+                                static_cast<const uint8_t*>(d_proofs), k, seed, true, stream, results, nullptr);
+}
+
+extern "C" int curdle_stat_tracker_combined(unsigned long long out[4]) { return read_stats(out, g_tc_stat, 4); }
+
+extern "C" int curdle_tracker_combined_last_kernel_ms(double* out) {
+  if (!out) return CURDLE_EINVAL;
+  *out = g_tc_kernel_ms.load(std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+extern "C" int curdle_whisk_tracker_combined_scalars(const uint8_t* trackers, const uint8_t* k_commitments,
+                                                     const uint8_t* proofs, size_t k, const uint8_t seed[32],
+                                                     uint64_t* scalars_out, uint64_t g_out[4]) {
+  if (k == 0) return CURDLE_OK;
+  const CombineDiag diag{scalars_out, g_out};
+  return tracker_batch_combined(trackers, k_commitments, proofs, k, seed, false, nullptr, nullptr, &diag);
+}
 
 extern "C" int curdle_whisk_generate_tracker_proof_batch_blinders(const uint8_t* trackers, const uint64_t* ks,
                                                                   const uint64_t* blinders, size_t k, uint8_t* proofs_out,

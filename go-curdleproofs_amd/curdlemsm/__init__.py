@@ -81,6 +81,8 @@ SYMBOLS = [
     "curdle_g1_normalize_batch", "curdle_g1_normalize_batch_device", "curdle_g1_scalar_mul_batch_device", "curdle_stat_normalize",
     "curdle_fbase_create", "curdle_fbase_free", "curdle_g1_fixed_base_mul_batch", "curdle_g1_fixed_base_mul_batch_device",
     "curdle_stat_fbase", "curdle_whisk_compute_tracker", "curdle_whisk_k_commitment", "curdle_whisk_compute_trackers_batch",
+    "curdle_whisk_is_valid_tracker_proof_batch_combined", "curdle_whisk_is_valid_tracker_proof_batch_combined_device",
+    "curdle_stat_tracker_combined", "curdle_whisk_tracker_combined_scalars", "curdle_tracker_combined_last_kernel_ms",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -195,6 +197,13 @@ _whisk_valid_tracker_batch = _sig("curdle_whisk_is_valid_tracker_proof_batch", C
 _whisk_valid_tracker_batch_ex = _sig("curdle_whisk_is_valid_tracker_proof_batch_ex", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_uint, _vp)
 _whisk_valid_tracker_batch_device = _sig("curdle_whisk_is_valid_tracker_proof_batch_device", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp)
 _stat_tracker = _sig("curdle_stat_tracker", C.c_int, C.POINTER(C.c_ulonglong))
+_whisk_valid_tracker_batch_combined = _sig("curdle_whisk_is_valid_tracker_proof_batch_combined", C.c_int, _vp, _vp, _vp, C.c_size_t,
+                                           _vp, _vp)
+_whisk_valid_tracker_batch_combined_device = _sig("curdle_whisk_is_valid_tracker_proof_batch_combined_device", C.c_int, _vp, _vp,
+                                                  _vp, C.c_size_t, _vp, _vp, _vp)
+_stat_tracker_combined = _sig("curdle_stat_tracker_combined", C.c_int, C.POINTER(C.c_ulonglong))
+_tracker_combined_last_kernel_ms = _sig("curdle_tracker_combined_last_kernel_ms", C.c_int, C.POINTER(C.c_double))
+_whisk_tracker_combined_scalars = _sig("curdle_whisk_tracker_combined_scalars", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp)
 _whisk_gen_tracker = _sig("curdle_whisk_generate_tracker_proof", C.c_int, _vp, _vp, _vp, _vp)
 _whisk_gen_tracker_batch_blinders = _sig("curdle_whisk_generate_tracker_proof_batch_blinders", C.c_int, _vp, _vp, _vp, C.c_size_t,
                                          _vp, _vp)
@@ -1113,6 +1122,74 @@ def stat_tracker() -> dict:
     out = (C.c_ulonglong * 3)()
     _check(_stat_tracker(out))
     return {"device": out[0], "host": out[1], "handed_back": out[2]}
+
+
+def _tracker_members(trackers, k_commitments, proofs, seed):
+    k = len(trackers)
+    if len(k_commitments) != k or len(proofs) != k:
+        raise ValueError("trackers, k commitments and proofs need the same count")
+    if (any(len(t) != 96 for t in trackers) or any(len(c) != 48 for c in k_commitments)
+            or any(len(p) != WHISK_TRACKER_PROOF_SIZE for p in proofs)):
+        raise ValueError("tracker 96 B, k commitment 48 B, tracker proof 128 B")
+    if len(seed) != 32:
+        raise ValueError("the seed is 32 bytes")
+    return k
+
+
+def whisk_is_valid_tracker_proof_batch_combined(trackers, k_commitments, proofs, seed: bytes) -> np.ndarray:
+    """The tracker batch settled per pass by one randomly weighted MSM
+    (curdle_whisk_is_valid_tracker_proof_batch_combined).  seed: 32 bytes, unpredictable to whoever made the proofs
+    and fresh per call (os.urandom(32)).  Returns int32[k] as whisk_is_valid_tracker_proof_batch does."""
+    k = _tracker_members(trackers, k_commitments, proofs, seed)
+    out = np.zeros(k, dtype=np.int32)
+    if k == 0:
+        return out
+    t, kc, pb = _bytes_arr(b"".join(trackers)), _bytes_arr(b"".join(k_commitments)), _bytes_arr(b"".join(proofs))
+    sd = _bytes_arr(seed)
+    _check(_whisk_valid_tracker_batch_combined(_ptr(t), _ptr(kc), _ptr(pb), k, _ptr(sd), _ptr(out)))
+    return out
+
+
+def whisk_is_valid_tracker_proof_batch_combined_device(d_trackers: int, d_k_commitments: int, d_proofs: int, k: int,
+                                                       seed: bytes, stream: int = 0) -> np.ndarray:
+    """The same over resident arrays (curdle_whisk_is_valid_tracker_proof_batch_combined_device); the seed is host
+    memory."""
+    if len(seed) != 32:
+        raise ValueError("the seed is 32 bytes")
+    out = np.zeros(k, dtype=np.int32)
+    sd = _bytes_arr(seed)
+    _check(_whisk_valid_tracker_batch_combined_device(d_trackers or None, d_k_commitments or None, d_proofs or None, k,
+                                                      _ptr(sd), _ptr(out) if k else None, stream or None))
+    return out
+
+
+def stat_tracker_combined() -> dict:
+    """Combined tracker batches: passes settled by the sum, passes that fell back to the chains, members accepted by a
+    sum, members excluded from one."""
+    out = (C.c_ulonglong * 4)()
+    _check(_stat_tracker_combined(out))
+    return {"settled": out[0], "fell_back": out[1], "accepted": out[2], "excluded": out[3]}
+
+
+def tracker_combined_last_kernel_ms() -> float:
+    """k_tracker_combine in the last whisk_tracker_combined_scalars, by HIP events."""
+    out = C.c_double()
+    _check(_tracker_combined_last_kernel_ms(C.byref(out)))
+    return out.value
+
+
+def whisk_tracker_combined_scalars(trackers, k_commitments, proofs, seed: bytes):
+    """Diagnostic (curdle_whisk_tracker_combined_scalars): the MSM scalars of the combined form for at most one pass,
+    (uint64[k, 5, 4], uint64[4]): Montgomery fr limbs per record, and the generator's total."""
+    k = _tracker_members(trackers, k_commitments, proofs, seed)
+    scalars = np.zeros((k, 5, 4), dtype=np.uint64)
+    g = np.zeros(4, dtype=np.uint64)
+    if k == 0:
+        return scalars, g
+    t, kc, pb = _bytes_arr(b"".join(trackers)), _bytes_arr(b"".join(k_commitments)), _bytes_arr(b"".join(proofs))
+    sd = _bytes_arr(seed)
+    _check(_whisk_tracker_combined_scalars(_ptr(t), _ptr(kc), _ptr(pb), k, _ptr(sd), _ptr(scalars), _ptr(g)))
+    return scalars, g
 
 
 def whisk_generate_tracker_proof(tracker: bytes, k, rand: Rand) -> bytes:

@@ -431,6 +431,26 @@ func TrackerProofBatch(results []int32, trackers, kComms, proofs []byte, flags u
 	})
 }
 
+// TrackerProofBatchCombined answers like TrackerProofBatch, but settles every pass of 65,536 members with ONE
+// randomly weighted MSM and runs the per-member chains only for a pass whose sum is not infinity
+// (curdle_whisk_is_valid_tracker_proof_batch_combined): for batches expected to be honest.  seed must come from
+// crypto/rand, unpredictable to whoever made the proofs and fresh for every call; an accept is then wrong with
+// probability at most 2^-128 per call, and 0 / -1 are exact.  UNVERIFIED: never compiled.
+func TrackerProofBatchCombined(results []int32, trackers, kComms, proofs []byte, seed *[32]byte) error {
+	k := len(results)
+	if len(trackers) != 96*k || len(kComms) != 48*k || len(proofs) != 128*k || seed == nil {
+		return errors.New("curdlemsm: TrackerProofBatchCombined: mismatched lengths or no seed")
+	}
+	if k == 0 {
+		return nil
+	}
+	return locked(func() C.int {
+		return C.curdle_whisk_is_valid_tracker_proof_batch_combined((*C.uint8_t)(unsafe.Pointer(&trackers[0])),
+			(*C.uint8_t)(unsafe.Pointer(&kComms[0])), (*C.uint8_t)(unsafe.Pointer(&proofs[0])), C.size_t(k),
+			(*C.uint8_t)(unsafe.Pointer(&seed[0])), (*C.int)(unsafe.Pointer(&results[0])))
+	})
+}
+
 // CheckG1Affine checks points that arrive IN MEMORY -- and so went through no Decoder / SetBytes -- on the GPU
 // (curdle_g1_check_batch): one status per point, DecodeInfinity for (0, 0), DecodeBadEncoding for a coordinate
 // that is not below p, DecodeNotOnCurve, DecodeNotInSubgroup, else DecodeOK.  MultiExp and every other fast

@@ -426,6 +426,56 @@ int curdle_whisk_is_valid_tracker_proof_batch_device(const void* d_trackers, con
 /* Diagnostics: members of tracker batches since the library was loaded whose transcripts out[0] were hashed on the
  * device, out[1] on the host, out[2] handed back to the host after a non-zero transcript status. */
 int curdle_stat_tracker(unsigned long long out[3]);
+/* The COMBINED form of the tracker batch: per pass of at most 65,536 members, ONE randomly weighted multi-scalar
+ * multiplication settles every member at once.  The 2 m equations of the pass's members (whisk.go:136-144) are
+ * weighted by two 128-bit coefficients per member and summed over the 5 m decoded records and G:
+ *     sum_i  rho_i (s_i G + c_i kG_i - A_i)  +  sigma_i (s_i rG_i + c_i krG_i - B_i)
+ * If the sum is the point at infinity, every member of the pass that was not refused is answered 1.  If it is not,
+ * the pass runs the per-member check of curdle_whisk_is_valid_tracker_proof_batch_ex and answers exactly as that call
+ * does.  Refusals are exact in both cases: a member with S >= r, a record that does not decode or a record outside
+ * the subgroup is answered CURDLE_EINVAL, takes no part in the sum (its scalars are zero, so its records reach no
+ * bucket) and does not make a pass fall back.  A 0 is only ever the per-member check's answer.  The transcripts are
+ * always hashed on the device (CURDLE_TRACKER_HASH_DEVICE).
+ *
+ * `seed` (32 bytes, host memory in both forms) is what the coefficients are derived from, on the device:
+ *     SHAKE256("curdle/tracker-combine/v1" | seed | le64(i))[0:32] = rho_i | sigma_i   (two little-endian integers),
+ * i the member's index in the call.  The seed MUST be unpredictable to whoever made the proofs and FRESH for every
+ * call (32 bytes of the operating system's randomness): someone who knows the coefficients in advance can make
+ * invalid proofs whose errors cancel in the sum.
+ *
+ * Error bound: an accept is wrong with probability at most 2^-128 per call.  The sum is a polynomial of degree 1 in
+ * each coefficient over F_r whose coefficient on rho_i (sigma_i) is member i's error in its first (second) equation,
+ * a multiple of G since every record that takes part is in the subgroup.  One invalid member leaves a non-zero
+ * coefficient on its rho or its sigma; with all other coefficients fixed, at most one of that coefficient's 2^128
+ * values makes the sum vanish.  (SHAKE256 is taken as a random function of the unpredictable seed.)
+ *
+ * Cost: a batch in which every member is valid or refused pays the MSM and no chains.  A batch with ONE rejected
+ * member pays the combined pass PLUS the chains of that pass: more than the plain call.  Nothing routes to this
+ * form automatically; the existing entry points never take it.
+ *
+ * Conventions are those of _ex / _device: results[i] = 1, 0 or CURDLE_EINVAL; k = 0: CURDLE_OK, no device needed; a
+ * null pointer (the seed included) with k > 0: CURDLE_EINVAL before any device work; on a negative return every
+ * results[i] holds that code.  _device: HIP device pointers of any alignment, `stream` a hipStream_t or NULL; on a
+ * caller's stream the whole pass, the MSM included, runs on that stream. */
+int curdle_whisk_is_valid_tracker_proof_batch_combined(const uint8_t* trackers, const uint8_t* k_commitments,
+                                                       const uint8_t* proofs, size_t k, const uint8_t seed[32], int* results);
+int curdle_whisk_is_valid_tracker_proof_batch_combined_device(const void* d_trackers, const void* d_k_commitments,
+                                                              const void* d_proofs, size_t k, const uint8_t seed[32],
+                                                              int* results, void* stream);
+/* Diagnostics of the combined form since the library was loaded: out[0] passes settled by the sum, out[1] passes that
+ * fell back to the per-member chains, out[2] members accepted by a sum, out[3] members excluded from a sum (answered
+ * CURDLE_EINVAL or handed back to the host), in either kind of pass. */
+int curdle_stat_tracker_combined(unsigned long long out[4]);
+/* Diagnostic (like curdle_selftest_op): the MSM scalars the combined form computes for k <= 65,536 members (one
+ * pass; more: CURDLE_EINVAL), without the MSM.  scalars_out: k x 5 x 4 limbs, Montgomery fr.Elements, member i's
+ * scalars for rG, krG, kG, A, B: sigma s, sigma c, rho c, -rho, -sigma, all zero for an excluded member.  g_out: the
+ * generator's scalar, sum rho_i s_i mod r (Montgomery), added up on the host from the kernel's per-block sums.  The
+ * fallback hides a broken sum behind correct answers; this call and the counters make the sum testable. */
+int curdle_whisk_tracker_combined_scalars(const uint8_t* trackers, const uint8_t* k_commitments,
+                                          const uint8_t* proofs, size_t k, const uint8_t seed[32], uint64_t* scalars_out, uint64_t g_out[4]);
+/* Milliseconds k_tracker_combine took in the process's last successful curdle_whisk_tracker_combined_scalars, by HIP
+ * events around the kernel alone (like curdle_transcript_last_kernel_ms); 0 before the first. */
+int curdle_tracker_combined_last_kernel_ms(double* out);
 /* GenerateWhiskTrackerProof, whisk.go:149 */
 int curdle_whisk_generate_tracker_proof(const uint8_t tracker[CURDLE_WHISK_TRACKER_SIZE], const uint64_t k[4],
                                         curdle_rand* rand, uint8_t proof_out[CURDLE_WHISK_TRACKER_PROOF_SIZE]);
