@@ -415,7 +415,9 @@ int check_start(CheckJob& job, const uint64_t* const* vecs, const size_t* lens, 
 int check_collect(CheckJob& job);
 
 // --- transcript_api.hip ------------------------------------------------------
-uint32_t members_per_wave(size_t k);  // the transcript kernel's launch rule, shared with the tracker batch
+// The transcript launch's rule, shared with the tracker batch: fills a->sheet (which of the two kernels) and a->mpw
+// (the lane kernel's members per wave) for a batch of k members.
+void choose_transcript_kernel(size_t k, curdle::TranscriptArgs* a);
 
 // --- dbases_api.hip ----------------------------------------------------------
 void dbases_release_handle(struct ::curdle_dbases* b);

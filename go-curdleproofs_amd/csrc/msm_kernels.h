@@ -233,8 +233,16 @@ struct TranscriptArgs {
   uint8_t* status;        // k
   uint64_t tail;          // pos | pos_begin << 8 | cur_flags << 16 after the program
   uint32_t n_ctl, row_words, init_stride, k, mpw, n_challenges;
+  uint32_t sheet;         // 1: k_transcript_sheet (transcript_sheet_kernels.hip), two members per wave; `mpw` is then unused
 };
+// Kernel and geometry (`sheet`, `mpw`) are the caller's, from choose_transcript_kernel (transcript_api.hip); the launch
+// dispatches on `sheet` and counts the members each kernel hashed (transcript_path_counts: lane kernel | sheet kernel).
 hipError_t launch_transcript_batch(const TranscriptArgs& args, hipStream_t stream);
+hipError_t launch_transcript_sheet(const TranscriptArgs& args, hipStream_t stream);
+void transcript_path_counts(unsigned long long out[2]);
+// transcript_sheet_kernels.hip: `reps` dependent Keccak-f[1600] on each of n states of 25 u64 (device pointers), by
+// keccak_f1600_dev with one state per wave (sheet = 0) or by sheet_keccak_f1600 with two (sheet = 1).
+hipError_t launch_keccak_permute(const uint64_t* in, uint64_t* out, uint32_t n, uint32_t reps, int sheet, hipStream_t stream);
 
 // The subgroup test straight from the n compressed records, without their square roots (so it
 // can run beside launch_g1_decompress(..., subgroup_check = 0, ...)): sub[i] = 0 iff record i,

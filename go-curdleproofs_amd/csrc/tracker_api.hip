@@ -267,7 +267,7 @@ int tracker_pass_device(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8_t
   ta.row_words = (uint32_t)(kRowBytes / 8);
   ta.init_stride = 0;
   ta.k = (uint32_t)m;
-  ta.mpw = members_per_wave(m);
+  choose_transcript_kernel(m, &ta);
   ta.n_challenges = 1;
   if (B) {  // transcripts, then the subgroup test, beside the square roots
     HIP_TRY(hipEventRecord(A.pre_done, sa));
@@ -450,7 +450,7 @@ int tracker_pass_combined(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8
   ta.row_words = (uint32_t)(kRowBytes / 8);
   ta.init_stride = 0;
   ta.k = (uint32_t)m;
-  ta.mpw = members_per_wave(m);
+  choose_transcript_kernel(m, &ta);
   ta.n_challenges = 1;
   if (B) {  // transcripts, then the subgroup test, beside the square roots
     HIP_TRY(hipEventRecord(A.pre_done, sa));
@@ -696,7 +696,7 @@ int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, cons
   ta.row_words = (uint32_t)(kRowBytes / 8);
   ta.init_stride = 0;
   ta.k = (uint32_t)m;
-  ta.mpw = members_per_wave(m);
+  choose_transcript_kernel(m, &ta);
   ta.n_challenges = 1;
   HIP_TRY(launch_transcript_batch(ta, sa));
   if (B && blinders) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));

@@ -27,14 +27,40 @@ int ensure_host(void*& p, size_t& cap, size_t bytes) {
 // (profiles/r12_transcript_batch.json): 64 waves of one member 10.5 ms, 1,024 waves of one member 27.3 ms, 16 full
 // waves 23.0 ms; 8,192 members as 2,048 waves of four 39.1 ms, as 128 full waves 21.1 ms.  So: at most 128 waves.
 constexpr size_t kMaxWaves = 128;
-}  // namespace
 
-uint32_t curdle_api::members_per_wave(size_t k) {
+uint32_t members_per_wave(size_t k) {
   const long long forced = knobs::get(knobs::TRANSCRIPT_LANES);
   if (forced >= 1 && forced <= 64) return (uint32_t)forced;
   uint32_t mpw = 1;
   while (mpw < 64 && (k + mpw - 1) / mpw > kMaxWaves) mpw *= 2;
   return mpw;
+}
+
+// Largest k for which an unset TRANSCRIPT_SHEET takes the sheet kernel (a state spread over lanes, two members per
+// wave: transcript_sheet_kernels.hip).  The rule: the largest measured k at which the sheet kernel's wall time is
+// below the lane kernel's by more than the larger of the two spreads of the repetitions; above it the lane kernel,
+// whose 64 states per wave do far less work per member once the chip is full.  Measured on the prelude at ell = 124
+// (profiles/r20_transcript_sheet.json, medians of 7, one lease; lane against sheet, wall ms, the larger spread in
+// brackets): k = 1: 8.53 / 2.62 (1.83); 64: 10.84 / 3.43 (0.37); 256: 13.11 / 3.56 (0.60); 1,024: 19.45 / 5.31 (0.60);
+// 4,096: 31.04 / 14.75 (0.78); 8,192: 37.82 / 27.67 (1.35) -- the kernels alone at 8,192: 21.0 / 11.4 ms.  The sheet
+// kernel is ahead at every measured size, by less and less; 8,192 is the largest measured (65,536 members of that
+// prelude exceed CURDLE_TRANSCRIPT_MAX_TOTAL), so nothing is claimed beyond it.  ell = 252 agrees: 78.97 / 58.85 (3.80)
+// at 8,192.
+constexpr size_t kSheetMaxMembers = 8192;
+}  // namespace
+
+// Which kernel hashes a batch of k members, and its geometry: the one rule for every caller of launch_transcript_batch
+// (curdle_transcript_batch here, the tracker batches and the tracker prover in tracker_api.hip).  Knob
+// TRANSCRIPT_SHEET decides when set; TRANSCRIPT_LANES alone is a statement about the lane kernel and selects it.
+void curdle_api::choose_transcript_kernel(size_t k, TranscriptArgs* a) {
+  const long long forced = knobs::get(knobs::TRANSCRIPT_SHEET);
+  bool sheet;
+  if (forced >= 0)
+    sheet = forced != 0;
+  else
+    sheet = !knobs::is_set(knobs::TRANSCRIPT_LANES) && k <= kSheetMaxMembers;
+  a->sheet = sheet ? 1 : 0;
+  a->mpw = members_per_wave(k);
 }
 
 extern "C" int curdle_transcript_batch(const char* transcript_label, const uint8_t* init_states,
@@ -111,7 +137,7 @@ extern "C" int curdle_transcript_batch(const char* transcript_label, const uint8
     a.row_words = (uint32_t)row_words;
     a.init_stride = init_states ? CURDLE_TRANSCRIPT_STATE_SIZE / 8 : 0;
     a.k = (uint32_t)k;
-    a.mpw = members_per_wave(k);
+    choose_transcript_kernel(k, &a);
     a.n_challenges = (uint32_t)n_ch;
     HIP_TRY(hipMemcpyAsync(d_in, h, in_bytes, hipMemcpyHostToDevice, T.stream));
     HIP_TRY(hipEventRecord(T.ev[0], T.stream));
@@ -150,6 +176,69 @@ extern "C" int curdle_transcript_batch(const char* transcript_label, const uint8
 }
 
 extern "C" int curdle_stat_transcript(unsigned long long out[2]) { return read_stats(out, g_tr_stat, 2); }
+
+extern "C" int curdle_stat_transcript_paths(unsigned long long out[2]) {
+  if (!out) return CURDLE_EINVAL;
+  transcript_path_counts(out);
+  return CURDLE_OK;
+}
+
+// `reps` dependent permutations of n states by one of the two device forms of Keccak-f[1600]: a transcript call's
+// stream, buffers and hold, one copy up, one kernel between the events, one copy back.
+extern "C" int curdle_keccak_permute_batch(const uint64_t* states_in, size_t n, unsigned form, unsigned reps, uint64_t* states_out,
+                                           double* kernel_ms) {
+  if (!states_in || !states_out) return fail(CURDLE_EINVAL, "null argument");
+  if (form > 1) return fail(CURDLE_EINVAL, "form %u: 0 is a state per lane, 1 a state spread over lanes", form);
+  if (reps == 0 || reps > CURDLE_KECCAK_PERMUTE_MAX_REPS) return fail(CURDLE_EINVAL, "reps %u outside 1..%d", reps, CURDLE_KECCAK_PERMUTE_MAX_REPS);
+  if (n > CURDLE_KECCAK_PERMUTE_MAX_STATES) return fail(CURDLE_EINVAL, "%zu states exceed CURDLE_KECCAK_PERMUTE_MAX_STATES", n);
+  if (n == 0) {
+    if (kernel_ms) *kernel_ms = 0;
+    return CURDLE_OK;
+  }
+  const size_t bytes = n * 200;
+  Ctx& cx = cur();
+  TrCtx& T = cx.tr;
+  {
+    std::unique_lock<std::mutex> g(cx.mu);
+    int rc = init_default_locked(cx);
+    if (rc) return rc;
+    T.cv.wait(g, [&] { return !T.busy; });
+    T.busy = true;
+  }
+  float ms = 0;
+  auto body = [&]() -> int {
+    HIP_TRY(hipSetDevice(cx.device));
+    int r;
+    if ((r = ensure_host(T.h_in, T.h_in_cap, bytes))) return r;
+    if ((r = ensure_host(T.h_out, T.h_out_cap, bytes))) return r;
+    if ((r = ensure(T.d_in, bytes))) return r;
+    if ((r = ensure(T.d_out, bytes))) return r;
+    memcpy(T.h_in, states_in, bytes);
+    HIP_TRY(hipMemcpyAsync(T.d_in.p, T.h_in, bytes, hipMemcpyHostToDevice, T.stream));
+    HIP_TRY(hipEventRecord(T.ev[0], T.stream));
+    HIP_TRY(launch_keccak_permute(static_cast<const uint64_t*>(T.d_in.p), static_cast<uint64_t*>(T.d_out.p), (uint32_t)n, reps, (int)form, T.stream));
+    HIP_TRY(hipEventRecord(T.ev[1], T.stream));
+    HIP_TRY(hipMemcpyAsync(T.h_out, T.d_out.p, bytes, hipMemcpyDeviceToHost, T.stream));
+    HIP_TRY(hipStreamSynchronize(T.stream));
+    HIP_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
+    memcpy(states_out, T.h_out, bytes);
+    return CURDLE_OK;
+  };
+  int rc;
+  try {
+    rc = body();
+  } catch (const std::bad_alloc&) {
+    rc = fail(CURDLE_ENOMEM, "out of memory");
+  }
+  if (rc && T.stream) (void)hipStreamSynchronize(T.stream);  // nothing queued may outlive the hold
+  {
+    std::lock_guard<std::mutex> g(cx.mu);
+    T.busy = false;
+  }
+  T.cv.notify_one();
+  if (!rc && kernel_ms) *kernel_ms = ms;
+  return rc;
+}
 
 extern "C" int curdle_transcript_last_kernel_ms(double* out) {
   if (!out) return fail(CURDLE_EINVAL, "null argument");

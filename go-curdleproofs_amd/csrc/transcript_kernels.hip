@@ -13,6 +13,8 @@
 // until ALL its members have an accepted draw.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+
 #include "../host/transcript_batch.h"
 #include "keccak_dev.h"
 #include "msm_kernels.h"
@@ -122,13 +124,26 @@ __global__ __launch_bounds__(64) void k_transcript_batch(TranscriptArgs p) {
   }
   p.status[m] = (uint8_t)status;
 }
+std::atomic<unsigned long long> g_paths[2];  // members launched on k_transcript_batch | on k_transcript_sheet
 }  // namespace
 
 hipError_t launch_transcript_batch(const TranscriptArgs& args, hipStream_t stream) {
   if (args.k == 0) return hipSuccess;
-  const uint32_t blocks = (args.k + args.mpw - 1) / args.mpw;
-  hipLaunchKernelGGL(k_transcript_batch, dim3(blocks), dim3(64), 0, stream, args);
-  return hipGetLastError();
+  hipError_t e;
+  if (args.sheet) {
+    e = launch_transcript_sheet(args, stream);
+  } else {
+    const uint32_t blocks = (args.k + args.mpw - 1) / args.mpw;
+    hipLaunchKernelGGL(k_transcript_batch, dim3(blocks), dim3(64), 0, stream, args);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) g_paths[args.sheet ? 1 : 0].fetch_add(args.k, std::memory_order_relaxed);
+  return e;
+}
+
+void transcript_path_counts(unsigned long long out[2]) {
+  out[0] = g_paths[0].load(std::memory_order_relaxed);
+  out[1] = g_paths[1].load(std::memory_order_relaxed);
 }
 
 }  // namespace curdle

@@ -83,6 +83,7 @@ SYMBOLS = [
     "curdle_stat_fbase", "curdle_whisk_compute_tracker", "curdle_whisk_k_commitment", "curdle_whisk_compute_trackers_batch",
     "curdle_whisk_is_valid_tracker_proof_batch_combined", "curdle_whisk_is_valid_tracker_proof_batch_combined_device",
     "curdle_stat_tracker_combined", "curdle_whisk_tracker_combined_scalars", "curdle_tracker_combined_last_kernel_ms",
+    "curdle_stat_transcript_paths", "curdle_keccak_permute_batch",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -1011,6 +1012,33 @@ def transcript_last_kernel_ms() -> float:
     out = C.c_double()
     _check(_transcript_last_kernel_ms(C.byref(out)))
     return out.value
+
+
+_stat_transcript_paths = _sig("curdle_stat_transcript_paths", C.c_int, C.POINTER(C.c_ulonglong))
+_keccak_permute_batch = _sig("curdle_keccak_permute_batch", C.c_int, _vp, C.c_size_t, C.c_uint, C.c_uint, _vp, C.POINTER(C.c_double))
+KECCAK_PERMUTE_MAX_REPS, KECCAK_PERMUTE_MAX_STATES = 4096, 65536
+KECCAK_LANE, KECCAK_SHEET = 0, 1
+
+
+def stat_transcript_paths() -> dict:
+    """Members since the library was loaded whose transcripts the lane kernel hashed, and the sheet kernel (knob
+    TRANSCRIPT_SHEET), counted at the launch: the tracker batches' device-hashed members are in it."""
+    out = (C.c_ulonglong * 2)()
+    _check(_stat_transcript_paths(out))
+    return {"lane": out[0], "sheet": out[1]}
+
+
+def keccak_permute_batch(states, form: int, reps: int = 1, want_ms: bool = False):
+    """curdle_keccak_permute_batch: `reps` dependent Keccak-f[1600] on each row of `states` (n x 25 uint64) on the
+    device; form KECCAK_LANE (a state per lane, one per wave) or KECCAK_SHEET (a state spread over lanes).  Returns
+    the n x 25 result, with want_ms (result, the kernel's ms by HIP events)."""
+    a = np.ascontiguousarray(states, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[1] != 25:
+        raise ValueError(f"expected n x 25 words, got {a.shape}")
+    out = np.zeros_like(a)
+    ms = C.c_double()
+    _check(_keccak_permute_batch(_ptr(a), a.shape[0], form, reps, _ptr(out), C.byref(ms)))
+    return (out, ms.value) if want_ms else out
 
 
 # ---- whisk package (whisk/whisk.go, whisk/types.go): trackers are 96-byte strings rG || krG ----

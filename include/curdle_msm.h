@@ -953,7 +953,18 @@ int curdle_stat_check_paths(unsigned long long out[2]);
  * hold those meanwhile), concurrent calls one behind the other.  Without a device it fails with
  * CURDLE_ENODEV: there is no fallback.  curdle_transcript_batch_host runs the same program through
  * the host's Transcript on nthreads threads and needs no device: the twin that tests and
- * measurements compare against. */
+ * measurements compare against.
+ *
+ * Two kernels run a tape, with the same bits out.  The lane kernel (csrc/transcript_kernels.hip) keeps a
+ * whole state in one lane, up to 64 members per wave: the most members per second on a full chip, but a
+ * call waits for a chain of about 7,000 dependent instructions per permutation however few members it
+ * has.  The sheet kernel (csrc/transcript_sheet_kernels.hip, csrc/keccak_sheet.h) spreads a state's 25
+ * words over 25 lanes, two members per wave, and exchanges words between lanes: a shorter chain, more
+ * work per member.  Knob TRANSCRIPT_SHEET (CURDLE_TRANSCRIPT_SHEET, curdle_plan_override): 1 always the
+ * sheet kernel, 0 never, unset the library's rule by batch size (choose_transcript_kernel in
+ * csrc/transcript_api.hip, with the measurements it rests on); TRANSCRIPT_LANES set with
+ * TRANSCRIPT_SHEET unset means the lane kernel.  Every caller of the launch follows the same rule: this
+ * entry point, the tracker batches that hash on the device, the tracker prover. */
 #define CURDLE_TRANSCRIPT_STATE_SIZE 208
 #define CURDLE_TR_APPEND 1
 #define CURDLE_TR_CHALLENGES 2
@@ -980,6 +991,20 @@ int curdle_stat_transcript(unsigned long long out[2]);
 /* Diagnostics: the kernel of the calling thread's device's last curdle_transcript_batch alone, by HIP events, in ms
  * (0 before the first call). */
 int curdle_transcript_last_kernel_ms(double* out);
+/* Diagnostics: members since the library was loaded whose transcripts out[0] the lane kernel hashed, out[1] the sheet
+ * kernel -- counted at the launch, so every caller is in it, the tracker batches included. */
+int curdle_stat_transcript_paths(unsigned long long out[2]);
+/* The device's Keccak-f[1600] alone: `reps` dependent permutations of each of n states (25 little-endian u64 each,
+ * host memory; states_out may be states_in).  form 0: a state per lane (what the lane kernel runs), one state per wave;
+ * form 1: a state spread over lanes (what the sheet kernel runs), two states per wave.  *kernel_ms, if not NULL, receives
+ * the kernel's time alone by HIP events.  Runs like a transcript call (its stream, its buffers, one call at a time).
+ * CURDLE_EINVAL before any device work: a null array, form > 1, reps outside 1..CURDLE_KECCAK_PERMUTE_MAX_REPS,
+ * n > CURDLE_KECCAK_PERMUTE_MAX_STATES; n = 0 is CURDLE_OK; CURDLE_ENODEV without a device.  For tests and for
+ * measuring the chain of dependent permutations. */
+#define CURDLE_KECCAK_PERMUTE_MAX_REPS 4096
+#define CURDLE_KECCAK_PERMUTE_MAX_STATES 65536
+int curdle_keccak_permute_batch(const uint64_t* states_in, size_t n, unsigned form, unsigned reps, uint64_t* states_out,
+                                double* kernel_ms);
 int curdle_set_last_error(int code, const char* msg);  /* internal: shared by the library's translation units */
 
 /* ------------------------------------------------------------------------- *
