@@ -127,6 +127,8 @@ int make_plan(MsmPlan& p, const MsmCall& call) {
   // against half a round; the 8 / 4 / 2 windows of a rank of the multi-GPU split -- which the
   // rule before this one left at 4-bucket segments, two rounds of quads for 8 windows --
   // 1.83 -> 1.52, 0.98 -> 0.88 and 0.61 -> 0.59 ms.
+  // (the reduction without a scalar multiple, reduce_bits below: single MSMs of at least 300 pairs; terms are two per pair)
+  const bool bits_form = k * sets == 1 && !many && !light_host && n_total >= 600;
   if (latency_mode) {
     // (round 4: a whole round, 131,072 lanes, since the reduction lost its per-segment scalar multiple: shorter
     // segments now cost a quad almost nothing extra -- 131,072 pairs 0.93 -> 0.89 ms, 2^20 3.45 -> 3.41)
@@ -135,7 +137,15 @@ int make_plan(MsmPlan& p, const MsmCall& call) {
     while (nbk / seg * 4 > lanes && seg < 32) seg *= 2;
     p.seg = nbk / seg * 4 <= lanes ? seg : 16;
   } else {
-    const uint64_t lanes = 32768;  // (16,384 / 65,536 / 131,072 measured equal: profiles/r04_pipeline_phase_costs.txt)
+    // (16,384 / 65,536 / 131,072 measured equal in round 4: profiles/r04_pipeline_phase_costs.txt)
+    // Round 21: no longer equal for the form without a scalar multiple (bits_form: single MSMs).  The slot-time of the
+    // walk is about the same at any length (four times the waves for a quarter of the chain), but the step follows the
+    // CHAIN: ~2.5 dependent additions per bucket of the segment, which everything behind the walk waits for with only
+    // four MSMs in flight.  A shorter segment costs this form a few thousand more additions in the levels above and
+    // nothing else.  A whole round of lanes: N = 2^20, 4 in flight, 32 / 16 / 8 buckets per segment 2.92 / 2.79 / 2.76 ms
+    // per step on one lease, 4 and 2 buckets no better than 8 (profiles/r21_pipelined_segment_length.txt).  Batches
+    // keep the quarter round: every one of their segments pays a scalar multiple.
+    const uint64_t lanes = bits_form ? 131072 : 32768;
     uint32_t seg = p.seg;
     while (nbk / seg * 4 > lanes && seg < 64) seg *= 2;
     p.seg = seg;
@@ -157,8 +167,7 @@ int make_plan(MsmPlan& p, const MsmCall& call) {
     // (light_host: a queued MSM of a batch verifier -- a host-bound caller with dozens in flight, to whom the
     // longer host pass costs throughput and the shorter GPU chain buys nothing: 1,024 Whisk proofs 31-36 ms
     // per batch with k_bucket_reduce_quad, 41-46 with this form)
-    const bool shapes = k * sets == 1 && !many && !light_host;
-    p.reduce_bits = shapes && n_total >= 600 ? 1u : 0u;  // terms: two per pair
+    p.reduce_bits = bits_form ? 1u : 0u;
   }
   const uint32_t gmax = p.reduce_bits ? 16u : 64u;  // quads per group: one wave's, or one block's
   p.G = min_nbkt / p.seg < gmax ? min_nbkt / p.seg : gmax;
@@ -330,6 +339,27 @@ extern "C" int curdle_msm_window_widths_ex(size_t n, int window_bits, unsigned f
   if (widths)
     for (int w = 0; w < W; w++) widths[w] = bits[w];
   return W;
+}
+
+// What make_plan decides about the bucket reduction of ONE device-resident MSM of n pairs (or a window range of it), for
+// a synchronous call or a pipelined one, under the knobs as they stand.  Nothing is launched and no device is needed.
+extern "C" int curdle_msm_reduce_plan(size_t n, int window_bits, int win_begin, int win_end, int pipelined, uint32_t out[8]) {
+  if (!out) return fail(CURDLE_EINVAL, "null argument");
+  if (n > ((size_t)1 << 27)) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^27 pairs", n);
+  int c;
+  if (checked_window_bits(n, window_bits, &c)) return CURDLE_EINVAL;
+  const uint32_t off[2] = {0, (uint32_t)n};
+  MsmCall call{off};
+  call.c = window_bits;
+  call.win_begin = win_begin;
+  call.win_end = win_end;
+  call.pipelined = pipelined != 0;
+  MsmPlan p;
+  const int rc = make_plan(p, call);
+  if (rc) return rc;
+  const uint32_t v[8] = {p.reduce_bits, p.two_level, p.seg, p.G, p.NS, (uint32_t)p.c, p.max_small, p.L};
+  memcpy(out, v, sizeof(v));
+  return CURDLE_OK;
 }
 
 extern "C" int curdle_msm_window_widths(size_t n, int window_bits, int widths[64]) {

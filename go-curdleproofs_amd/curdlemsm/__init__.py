@@ -84,6 +84,7 @@ SYMBOLS = [
     "curdle_whisk_is_valid_tracker_proof_batch_combined", "curdle_whisk_is_valid_tracker_proof_batch_combined_device",
     "curdle_stat_tracker_combined", "curdle_whisk_tracker_combined_scalars", "curdle_tracker_combined_last_kernel_ms",
     "curdle_stat_transcript_paths", "curdle_keccak_permute_batch",
+    "curdle_msm_reduce_plan",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -1026,6 +1027,18 @@ def stat_transcript_paths() -> dict:
     out = (C.c_ulonglong * 2)()
     _check(_stat_transcript_paths(out))
     return {"lane": out[0], "sheet": out[1]}
+
+
+_msm_reduce_plan = _sig("curdle_msm_reduce_plan", C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32))
+
+
+def msm_reduce_plan(n: int, window_bits: int = 0, win_begin: int = 0, win_end: int = -1, pipelined: bool = False) -> dict:
+    """What the plan of one device-resident MSM of n pairs decides about its bucket reduction (curdle_msm_reduce_plan),
+    under the knobs as they stand; no device needed."""
+    out = (C.c_uint32 * 8)()
+    _check(_msm_reduce_plan(n, window_bits, win_begin, win_end, 1 if pipelined else 0, out))
+    names = ("reduce_bits", "two_level", "seg", "G", "NS", "window_bits", "max_small", "L")
+    return {k: int(v) for k, v in zip(names, out)}
 
 
 def keccak_permute_batch(states, form: int, reps: int = 1, want_ms: bool = False):

@@ -1033,6 +1033,15 @@ typedef struct {
  * not notice.  on = 0: off. */
 int curdle_profile_enable(int on);
 int curdle_profile_last(curdle_profile* out);
+/* Diagnostics: what the library's plan decides about the bucket reduction of ONE device-resident MSM of n pairs over
+ * windows [win_begin, win_end) (win_end = -1: up to the last; window_bits = 0: the library's choice), called
+ * synchronously (pipelined = 0) or through submit / wait (1), under the knobs as they stand:
+ *   out[0] 1 if the window leaves the GPU as bit-positioned points (no scalar multiple)
+ *   out[1] 1 if the scatter runs in two passes   out[2] buckets per segment   out[3] segments per group
+ *   out[4] segments of the call   out[5] the window width   out[6] the merge limit (fragments per bucket)
+ *   out[7] sorted positions per accumulate lane
+ * Nothing is launched and no device is needed.  CURDLE_EINVAL for arguments an MSM call would refuse. */
+int curdle_msm_reduce_plan(size_t n, int window_bits, int win_begin, int win_end, int pipelined, uint32_t out[8]);
 
 /* Synthetic MSM bases of SURVEY.md section 8(d), generated on the GPU into
  * device memory: P_i = (k + i*q) * G for i < n, gnark G1Affine layout.  k and
