@@ -187,11 +187,7 @@ extern "C" int curdle_msm_g1_dbases_submit(const curdle_dbases* bases, const voi
     return fail(CURDLE_EHIP, "hipSetDevice: %s", hipGetErrorString(he));
   }
   const uint32_t off[2] = {0, (uint32_t)n};
-  const unsigned seq = cx.submit_count.fetch_add(1, std::memory_order_relaxed);
-  const unsigned turn = seq % (unsigned)cx.main_streams;
-  hipStream_t main = turn == 0 ? cx.main_stream : cx.main_extra[turn - 1];
   const bool partial = win_begin > 0 || (win_end >= 0 && win_end < curdle_msm_num_windows(n, window_bits));
-  hipStream_t pre = partial && cx.pre_streams == 2 && (seq & 1u) ? cx.pre_stream2 : cx.pre_stream;
   MsmCall call{off};
   call.c = window_bits;
   call.win_begin = win_begin;
@@ -200,7 +196,7 @@ extern "C" int curdle_msm_g1_dbases_submit(const curdle_dbases* bases, const voi
   MsmInputs in;
   in.scalars = d_scalars;
   in.points28 = d28;
-  rc = enqueue_slot(cx, S, call, in, {pre, main, S.stream});
+  rc = enqueue_slot(cx, S, call, in, pipelined_streams(cx, S, partial));
   if (rc) {
     drain_slot(cx, S);
     release_slot(cx, idx);

@@ -94,24 +94,49 @@ int init_locked(Ctx& cx, int device) {
     return fail(CURDLE_ENODEV, "no HIP device visible (%s)", e == hipSuccess ? "count is 0" : hipGetErrorString(e));
   if (device < 0 || device >= ndev) return fail(CURDLE_EINVAL, "device %d out of range (%d visible)", device, ndev);
   HIP_TRY(hipSetDevice(device));
+  int prio_least = 0, prio_greatest = 0;
+  HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+  StreamPlan sp;
+  cx.hw_queues = hw_queue_count();
+  int rc = stream_plan(cx.hw_queues, false, &sp);
+  if (rc) return rc;
+  cx.compact = sp.compact;
+  cx.main_streams = sp.main_streams;
+  StreamPlan sp_range;
+  if ((rc = stream_plan(cx.hw_queues, true, &sp_range))) return rc;
+  cx.pre_streams = sp_range.pre_streams;
+  // With more streams than hardware queues (GPU_MAX_HW_QUEUES: 4 unless the host process raises it) streams share queues.
+  // The runtime hands a stream its queue when the stream is first used, a new queue while the process has fewer than the
+  // limit and the least used one afterwards (kernel traces of round 22).  So under the compact plan the four streams of a
+  // pipelined MSM are made first and used once here, before any other stream of the context is: each gets a queue of its
+  // own, and every stream made later shares one of the four, idle while a pipeline runs.
+  if (cx.compact) {
+    HIP_TRY(hipStreamCreateWithPriority(&cx.main_stream, hipStreamNonBlocking, prio_least));
+    cx.device = device;  // the first handle exists (see below)
+    for (int i = 0; i + 1 < cx.main_streams; i++)
+      HIP_TRY(hipStreamCreateWithPriority(&cx.main_extra[i], hipStreamNonBlocking, prio_least));
+    HIP_TRY(hipStreamCreateWithPriority(&cx.pre_stream, hipStreamNonBlocking, prio_least));
+    HIP_TRY(hipStreamCreateWithPriority(&cx.tail_stream, hipStreamNonBlocking, prio_least));
+    hipEvent_t touch = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&touch, hipEventDisableTiming));
+    hipError_t te = hipSuccess;
+    for (hipStream_t st : {cx.main_stream, cx.main_extra[0], cx.pre_stream, cx.tail_stream})
+      if (st && te == hipSuccess && (te = hipEventRecord(touch, st)) == hipSuccess) te = hipStreamSynchronize(st);
+    (void)hipEventDestroy(touch);
+    HIP_TRY(te);
+  }
   HIP_TRY(hipStreamCreateWithFlags(&cx.util_stream, hipStreamNonBlocking));
   // only now: a failure before the first handle exists leaves the context exactly as it was (review of round 4: with
   // the id set first, a failed util_stream left cx.device on the failed id and nothing to tear down by)
   cx.device = device;  // from here on a failure leaves handles behind: curdle_init_devices tears them down
   HIP_TRY(hipStreamCreateWithFlags(&cx.h2d_stream, hipStreamNonBlocking));
-  int prio_least = 0, prio_greatest = 0;
-  HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-  HIP_TRY(hipStreamCreateWithPriority(&cx.main_stream, hipStreamNonBlocking, prio_least));
-  if (knobs::is_set(knobs::MAIN_STREAMS)) {
-    cx.main_streams = (int)knobs::get(knobs::MAIN_STREAMS);
-    if (cx.main_streams < 1 || cx.main_streams > 4) cx.main_streams = 1;
+  if (!cx.compact) {
+    HIP_TRY(hipStreamCreateWithPriority(&cx.main_stream, hipStreamNonBlocking, prio_least));
+    // Only the streams that will be used: a stream nobody launches on must not cost a queue.
+    for (int i = 0; i + 1 < cx.main_streams; i++)
+      HIP_TRY(hipStreamCreateWithPriority(&cx.main_extra[i], hipStreamNonBlocking, prio_least));
+    HIP_TRY(hipStreamCreateWithPriority(&cx.pre_stream, hipStreamNonBlocking, prio_least));
   }
-  // Only the streams that will be used: with more streams than hardware queues
-  // (GPU_MAX_HW_QUEUES: 4 by default, 16 under bench.py) streams share queues, and which ones
-  // do depends on the creation order -- a stream nobody launches on must not cost a queue.
-  for (int i = 0; i + 1 < cx.main_streams; i++)
-    HIP_TRY(hipStreamCreateWithPriority(&cx.main_extra[i], hipStreamNonBlocking, prio_least));
-  HIP_TRY(hipStreamCreateWithPriority(&cx.pre_stream, hipStreamNonBlocking, prio_least));
   HIP_TRY(hipStreamCreateWithPriority(&cx.pre_stream2, hipStreamNonBlocking, prio_least));
   // Tail streams at normal priority: on ROCm 7.2 all high-priority streams of a process appear to
   // share one hardware queue, which serialises the tails of consecutive MSMs (measured in round 2:
@@ -127,6 +152,7 @@ int init_locked(Ctx& cx, int device) {
     HIP_TRY(hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, tail_prio));
     HIP_TRY(hipEventCreateWithFlags(&s.acc_done, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&s.pre_done, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
   }
   for (auto& bc : cx.bcache) HIP_TRY(hipEventCreateWithFlags(&bc.ready, hipEventDisableTiming));
   // the batched transcripts' stream, after every other one: the streams before it keep their place in the order
@@ -394,6 +420,9 @@ void teardown_locked(Ctx& C) {
     S.acc_done = nullptr;
     if (S.pre_done) (void)hipEventDestroy(S.pre_done);
     S.pre_done = nullptr;
+    if (S.done) (void)hipEventDestroy(S.done);
+    S.done = nullptr;
+    S.done_recorded = false;
   }
   for (auto& bc : C.bcache) {
     if (bc.buf.p) (void)hipFree(bc.buf.p);
@@ -416,7 +445,7 @@ void teardown_locked(Ctx& C) {
     (void)hipStreamDestroy(st);
     st = nullptr;
   }
-  for (hipStream_t* st : {&C.pre_stream, &C.pre_stream2}) {
+  for (hipStream_t* st : {&C.pre_stream, &C.pre_stream2, &C.tail_stream}) {
     if (*st) {
       (void)hipStreamSynchronize(*st);
       (void)hipStreamDestroy(*st);
@@ -472,7 +501,7 @@ extern "C" int curdle_init_devices(const int* devices, int n) {
       const bool was = cx.inited;
       rc = init_locked(cx, devices[i]);  // context 0 may be up already (curdle_init): same device or CURDLE_EINVAL
       brought_up[i] = !was && cx.inited;
-      if (rc && !was && !cx.inited) brought_up[i] = cx.util_stream != nullptr;  // failed half-way: its streams exist
+      if (rc && !was && !cx.inited) brought_up[i] = cx.util_stream || cx.main_stream;  // failed half-way: its streams exist (the compact plan makes main_stream first)
     }
     if (rc) {
       char keep[256];

@@ -282,6 +282,7 @@ int enqueue_slot(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, con
     return fail(CURDLE_EINVAL, "internal: the fused accumulator front takes one small MSM");
   S.run_stream = st.tail;
   S.profiled = false;
+  S.done_recorded = false;
   if (p.n == 0 || p.win_end == p.win_begin) return CURDLE_OK;  // finish_slot writes infinities
   // The kernels leave k_digits' coarse counters, the scan chain and k_merge_large's chunk counters zero, and the host counts
   // the chain's tickets.  A call that stopped half-way may have left any of them behind (review of round 5: a call that failed
@@ -295,6 +296,11 @@ int enqueue_slot(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, con
   }
   S.suspect = true;  // until every launch of this call is queued
   rc = enqueue_slot_impl(cx, S, call, in, st, join);
+  if (rc == CURDLE_OK && call.pipelined) {
+    // the call's last operation is on its tail stream: the wait is for this call alone, whatever is queued behind it there
+    HIP_TRY(hipEventRecord(S.done, st.tail));
+    S.done_recorded = true;
+  }
   if (rc == CURDLE_OK) S.suspect = false;
   return rc;
 }
@@ -320,7 +326,10 @@ int finish_slot(Ctx& cx, Slot& S, uint64_t* out) {
     for (size_t j = 0; j < k; j++) set_out_infinity(out + 18 * j);
     return CURDLE_OK;
   }
-  HIP_TRY(hipStreamSynchronize(S.run_stream));
+  if (S.done_recorded)
+    HIP_TRY(hipEventSynchronize(S.done));
+  else
+    HIP_TRY(hipStreamSynchronize(S.run_stream));
   if (const char* why = take_slot_error(S)) return fail(CURDLE_EHIP, "internal: %s", why);
   if (S.profiled) {
     std::lock_guard<std::mutex> g(cx.mu);
@@ -400,6 +409,7 @@ void drain_slot(Ctx& cx, Slot& S) {
   (void)hipStreamSynchronize(cx.main_stream);
   for (auto& st : cx.main_extra)
     if (st) (void)hipStreamSynchronize(st);
+  if (cx.tail_stream) (void)hipStreamSynchronize(cx.tail_stream);
   (void)hipStreamSynchronize(S.stream);
 }
 
@@ -409,6 +419,16 @@ void drain_slot(Ctx& cx, Slot& S) {
 // still overlap, each on its slot's stream.  (The three-stream layout of the pipelined entry points was
 // measured slower for synchronous calls in round 2; its knob is gone.)
 Streams sync_streams(Ctx&, Slot& S) { return {S.stream, S.stream, S.stream}; }
+
+// Streams of a pipelined call (submit / wait) under the context's stream plan: the sort stream (window ranges alternate
+// over two), the accumulate streams in turn, and for the tail the plan's one tail stream or the slot's own.
+Streams pipelined_streams(Ctx& cx, Slot& S, bool window_range) {
+  const unsigned seq = cx.submit_count.fetch_add(1, std::memory_order_relaxed);
+  const unsigned turn = seq % (unsigned)cx.main_streams;
+  const hipStream_t main = turn == 0 ? cx.main_stream : cx.main_extra[turn - 1];
+  const hipStream_t pre = window_range && cx.pre_streams == 2 && (seq & 1u) ? cx.pre_stream2 : cx.pre_stream;
+  return {pre, main, cx.compact ? cx.tail_stream : S.stream};
+}
 
 // The scans of the bucket slots hold 1,024 blocks of 4,096 slots: a batch with more slots than
 // that (1,024 MSMs of 2,548 pairs; 2,100 of 628) runs in passes of as many whole MSMs as fit,

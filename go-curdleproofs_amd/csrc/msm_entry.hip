@@ -304,17 +304,13 @@ extern "C" int curdle_msm_g1_device_submit_ex(const void* d_points, const void* 
   call.win_end = win_end;
   call.pipelined = true;
   call.glv = glv;
-  const unsigned seq = cx.submit_count.fetch_add(1, std::memory_order_relaxed);
-  const unsigned turn = seq % (unsigned)cx.main_streams;
-  hipStream_t main = turn == 0 ? cx.main_stream : cx.main_extra[turn - 1];
   uint8_t wb[kMaxWindows];
   const int W = window_widths(c_checked, wb, glv ? kScalarBits : kScalarBitsNoGlv);
-  const bool partial = win_begin > 0 || (win_end >= 0 && win_end < W);
-  hipStream_t pre = partial && cx.pre_streams == 2 && (seq & 1u) ? cx.pre_stream2 : cx.pre_stream;
-  if (entry >= 0 && (he = hipStreamWaitEvent(main, ready, 0)) != hipSuccess)  // the accumulation is what reads the copy
+  const Streams st = pipelined_streams(cx, S, win_begin > 0 || (win_end >= 0 && win_end < W));
+  if (entry >= 0 && (he = hipStreamWaitEvent(st.main, ready, 0)) != hipSuccess)  // the accumulation is what reads the copy
     rc = fail(CURDLE_EHIP, "hipStreamWaitEvent: %s", hipGetErrorString(he));
   if (!rc)
-    rc = enqueue_slot(cx, S, call, {d_points, d_scalars, entry >= 0 ? d28 : nullptr}, {pre, main, S.stream});
+    rc = enqueue_slot(cx, S, call, {d_points, d_scalars, entry >= 0 ? d28 : nullptr}, st);
   if (rc) {
     drain_slot(cx, S);
     release_slot(cx, idx);

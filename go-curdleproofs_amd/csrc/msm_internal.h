@@ -76,9 +76,13 @@ struct Buf {
 };
 
 struct Slot {
-  hipStream_t stream = nullptr;  // high priority: the tail phases
+  hipStream_t stream = nullptr;  // the slot's own stream: synchronous calls, and the tail phases of a pipelined call under the wide stream plan
   hipEvent_t acc_done = nullptr;
   hipEvent_t pre_done = nullptr;
+  // Behind the last tail operation of a pipelined call: what curdle_msm_wait waits for.  A wait for the tail STREAM would,
+  // on the compact plan's one tail stream, also wait for the tail of every MSM submitted later.
+  hipEvent_t done = nullptr;
+  bool done_recorded = false;  // the call in flight is waited for by `done`, not by its tail stream
   Buf points, scalars, offsets, points28, counts, starts, cursor, fragcnt, foff, small, digits, sorted, frags, partials,
       winsums, winsums28, results, job, tmp, ccur, fold_sums, fold_meta;
   void* h_stage[2] = {nullptr, nullptr};  // pinned staging of the device accumulator (instance points; job)
@@ -190,6 +194,13 @@ struct Ctx {
   // bottleneck of the pipeline (8 ranks: 1.06 -> 0.80 ms per step with 5 in flight).
   hipStream_t pre_stream2 = nullptr;
   int pre_streams = 2;
+  // The stream plan of pipelined calls, chosen when the context is created (stream_plan, msm_plan.hip).  Wide: every slot's
+  // tail on the slot's own stream -- eleven busy streams with eight in flight, which overlap only on as many hardware
+  // queues.  Compact: ONE tail stream for every slot, created with main_stream, main_extra[0] and pre_stream ahead of every
+  // other stream of the context, so that the four streams a whole pipelined MSM uses sit on four hardware queues of their own.
+  bool compact = false;
+  int hw_queues = 4;                  // GPU_MAX_HW_QUEUES as the process has it (the runtime's default: 4)
+  hipStream_t tail_stream = nullptr;  // compact plan only
   Slot slots[kSlots];
   // Converted copies of base arrays whose callers promised they do not change (CURDLE_MSM_BASES_UNCHANGED): keyed
   // by the device pointer and the count, made on first use on util_stream, reused by every later flagged call.
@@ -323,6 +334,14 @@ struct MsmCall {
   bool shared_bases = false;
 };
 int make_plan(MsmPlan& p, const MsmCall& call);
+// Which streams pipelined calls run on, from the hardware queues the process has and the STREAM_PLAN knob.
+constexpr int kWideMinQueues = 16;  // hardware queues from which every slot's tail stream has a queue of its own
+struct StreamPlan {
+  bool compact;
+  int main_streams, pre_streams, tail_streams;  // busy streams of that kind while a pipeline of such calls runs
+};
+int hw_queue_count();  // GPU_MAX_HW_QUEUES as the HIP runtime reads it; 4 when unset
+int stream_plan(int hw_queues, bool window_range, StreamPlan* out);
 int checked_window_bits(size_t n, int window_bits, int* c);
 
 // --- msm_enqueue.hip ---------------------------------------------------------
@@ -388,6 +407,7 @@ int finish_slot(Ctx& cx, Slot& S, uint64_t* out);
 const char* take_slot_error(Slot& S);
 void drain_slot(Ctx& cx, Slot& S);
 Streams sync_streams(Ctx&, Slot& S);
+Streams pipelined_streams(Ctx& cx, Slot& S, bool window_range);
 constexpr size_t kMaxSlotsPerPass = (size_t)1024 * 4096;
 int run_passes(Ctx& cx, Slot& S, const MsmCall& call, const MsmInputs& in, const Streams& st, uint64_t* out);
 int run_device(const MsmCall& call, const MsmInputs& in, uint64_t* out, void* user_stream = nullptr, hipEvent_t wait_for = nullptr);

@@ -362,6 +362,53 @@ extern "C" int curdle_msm_reduce_plan(size_t n, int window_bits, int win_begin, 
   return CURDLE_OK;
 }
 
+namespace curdle_api {
+// The hardware queues the HIP runtime gives the process: GPU_MAX_HW_QUEUES, read the way the runtime reads it (its
+// default is 4).  Only read: the library sets no runtime variable.
+int hw_queue_count() {
+  const char* e = getenv("GPU_MAX_HW_QUEUES");
+  const long v = e && *e ? atol(e) : 0;
+  return v >= 1 ? (int)(v > 1024 ? 1024 : v) : 4;
+}
+
+// The stream plan of pipelined calls (Ctx::compact).  The wide plan keeps a tail stream per slot, which overlap only where
+// each has a hardware queue of its own: from 16 queues.  Below that the slots' tails shared queues with the accumulate and
+// sort streams, and an accumulation waited behind another MSM's whole tail (profiles/r22_stream_plan.txt): the compact
+// plan's busy streams -- two accumulate streams, one sort stream, one tail stream -- fit four queues.
+// Knob STREAM_PLAN: 0 or unset by the queue count, 1 wide, 2 compact.
+int stream_plan(int hw_queues, bool window_range, StreamPlan* out) {
+  if (hw_queues < 1) return fail(CURDLE_EINVAL, "hw_queues = %d: at least one hardware queue expected", hw_queues);
+  const long long forced = knobs::get(knobs::STREAM_PLAN);
+  if (forced > 2) return fail(CURDLE_EINVAL, "CURDLE_STREAM_PLAN = %lld: 0 (auto), 1 (wide) or 2 (compact)", forced);
+  int mains = 2;
+  if (knobs::is_set(knobs::MAIN_STREAMS)) {
+    mains = (int)knobs::get(knobs::MAIN_STREAMS);
+    if (mains < 1 || mains > 4) mains = 1;
+  }
+  out->compact = forced == 2 || (forced <= 0 && hw_queues < kWideMinQueues);
+  out->main_streams = out->compact && mains > 2 ? 2 : mains;
+  // Window ranges alternate their sorts over two streams (Ctx::pre_stream2) under the wide plan.  Under the compact plan a
+  // fifth busy stream shares a queue with one of the four: the 8-way rank's step measured 0.54 ms with two sort streams,
+  // 0.42 with one (the wide plan on 4 queues: 0.45; profiles/r22_stream_plan.txt).
+  out->pre_streams = window_range && !out->compact ? 2 : 1;
+  out->tail_streams = out->compact ? 1 : kSlots;
+  return CURDLE_OK;
+}
+}  // namespace curdle_api
+
+// The stream plan a context created with `hw_queues` hardware queues (GPU_MAX_HW_QUEUES) takes for pipelined whole MSMs
+// (whole_or_range = 0) or window ranges (1), under the knobs as they stand.  No device is needed.
+extern "C" int curdle_msm_stream_plan(int hw_queues, int whole_or_range, uint32_t out[4]) {
+  if (!out) return fail(CURDLE_EINVAL, "null argument");
+  if (whole_or_range != 0 && whole_or_range != 1) return fail(CURDLE_EINVAL, "whole_or_range must be 0 (whole MSM) or 1 (window range)");
+  StreamPlan sp;
+  const int rc = stream_plan(hw_queues, whole_or_range == 1, &sp);
+  if (rc) return rc;
+  const uint32_t v[4] = {sp.compact ? 2u : 1u, (uint32_t)sp.main_streams, (uint32_t)sp.pre_streams, (uint32_t)sp.tail_streams};
+  memcpy(out, v, sizeof(v));
+  return CURDLE_OK;
+}
+
 extern "C" int curdle_msm_window_widths(size_t n, int window_bits, int widths[64]) {
   return curdle_msm_window_widths_ex(n, window_bits, 0, widths);
 }

@@ -84,7 +84,7 @@ SYMBOLS = [
     "curdle_whisk_is_valid_tracker_proof_batch_combined", "curdle_whisk_is_valid_tracker_proof_batch_combined_device",
     "curdle_stat_tracker_combined", "curdle_whisk_tracker_combined_scalars", "curdle_tracker_combined_last_kernel_ms",
     "curdle_stat_transcript_paths", "curdle_keccak_permute_batch",
-    "curdle_msm_reduce_plan",
+    "curdle_msm_reduce_plan", "curdle_msm_stream_plan",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -1039,6 +1039,22 @@ def msm_reduce_plan(n: int, window_bits: int = 0, win_begin: int = 0, win_end: i
     _check(_msm_reduce_plan(n, window_bits, win_begin, win_end, 1 if pipelined else 0, out))
     names = ("reduce_bits", "two_level", "seg", "G", "NS", "window_bits", "max_small", "L")
     return {k: int(v) for k, v in zip(names, out)}
+
+
+_msm_stream_plan = _sig("curdle_msm_stream_plan", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32))
+STREAM_PLAN_AUTO, STREAM_PLAN_WIDE, STREAM_PLAN_COMPACT = 0, 1, 2      # values of the STREAM_PLAN knob
+
+
+def msm_stream_plan(hw_queues: int, window_range: bool = False) -> dict:
+    """The streams pipelined calls keep busy on a context created in a process with `hw_queues` hardware queues
+    (GPU_MAX_HW_QUEUES; the HIP runtime's default is 4), for whole MSMs or window ranges, under the knobs as they
+    stand (curdle_msm_stream_plan); no device needed."""
+    out = (C.c_uint32 * 4)()
+    _check(_msm_stream_plan(int(hw_queues), 1 if window_range else 0, out))
+    plan = {"plan": {STREAM_PLAN_WIDE: "wide", STREAM_PLAN_COMPACT: "compact"}[int(out[0])],
+            "main_streams": int(out[1]), "pre_streams": int(out[2]), "tail_streams": int(out[3])}
+    plan["busy_streams"] = plan["main_streams"] + plan["pre_streams"] + plan["tail_streams"]
+    return plan
 
 
 def keccak_permute_batch(states, form: int, reps: int = 1, want_ms: bool = False):

@@ -14,7 +14,8 @@ const char* const kNames[COUNT] = {
     "MULTI_DEVICE_MIN", "MAIN_STREAMS", "TWO_KERNEL_MAX", "QUAD_MAX_LANES", "BATCH_CHUNK", "BATCH_PRODUCERS",
     "BATCH_GROUP", "DEVICE_ACC", "HOST_DECODE", "VERIFY_EAGER", "VERIFY_TRACE", "PROVER_FOLD_BASES",
     "ACC_PRIO", "REDUCE_PRIO", "AUX_PRIO", "HOST_FOLD", "MAX_LARGE", "BATCH_CHECKERS", "TRANSCRIPT_LANES", "GPU_PRELUDE",
-    "TRACKER_DEVICE_HASH", "NORMALIZE_LANE_POINTS", "TRACKER_OWN_PAIRS", "FBASE_PASS", "TRANSCRIPT_SHEET"};
+    "TRACKER_DEVICE_HASH", "NORMALIZE_LANE_POINTS", "TRACKER_OWN_PAIRS", "FBASE_PASS", "TRANSCRIPT_SHEET",
+    "STREAM_PLAN"};
 std::atomic<long long> g_val[COUNT];
 std::once_flag g_once;
 void load() {

@@ -1042,6 +1042,14 @@ int curdle_profile_last(curdle_profile* out);
  *   out[7] sorted positions per accumulate lane
  * Nothing is launched and no device is needed.  CURDLE_EINVAL for arguments an MSM call would refuse. */
 int curdle_msm_reduce_plan(size_t n, int window_bits, int win_begin, int win_end, int pipelined, uint32_t out[8]);
+/* Diagnostics: the streams that pipelined calls (submit / wait) keep busy on a context created in a process with
+ * `hw_queues` hardware queues (GPU_MAX_HW_QUEUES as the HIP runtime reads it; 4 when unset), for whole MSMs
+ * (whole_or_range = 0) or window ranges (1), under the knobs as they stand (STREAM_PLAN, MAIN_STREAMS):
+ *   out[0] the plan: 1 wide (every slot's tail on a stream of its own), 2 compact (one tail stream for all slots)
+ *   out[1] accumulate streams   out[2] sort streams   out[3] tail streams
+ * The plan of a context is chosen once, when it is created.  Nothing is launched and no device is needed.
+ * CURDLE_EINVAL for hw_queues < 1 and for whole_or_range outside {0, 1}. */
+int curdle_msm_stream_plan(int hw_queues, int whole_or_range, uint32_t out[4]);
 
 /* Synthetic MSM bases of SURVEY.md section 8(d), generated on the GPU into
  * device memory: P_i = (k + i*q) * G for i < n, gnark G1Affine layout.  k and
