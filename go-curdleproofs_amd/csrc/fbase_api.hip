@@ -16,6 +16,10 @@
 // THE KERNEL READS TABLE ENTRIES AT ADDRESSES CHOSEN BY SCALAR DIGITS and skips zero digits: memory access pattern and
 // running time depend on the scalars.  What the library itself holds of them is overwritten on every way out: the call's
 // WipeList (api_helpers.h).
+//
+// The _ex entry points take flags.  CURDLE_FBASE_CONSTANT_TIME puts k_fbase_mul_ct (fbase_ct_kernels.hip) in k_fbase_mul's
+// place inside fb_launches and nothing else: same table, same passes, same slot hold and wipes, counters of its own
+// (curdle_stat_fbase_ct).  The entry points without flags call the _ex ones with 0.
 #include "api_helpers.h"
 #include "../host/host_ops.h"
 
@@ -33,6 +37,9 @@ constexpr size_t kFbPassDefault = (size_t)1 << 20;
 
 // scalars multiplied on the device | launches of k_fbase_mul | tables built; completed passes only
 std::atomic<unsigned long long> g_fb_stat[3];
+// scalars multiplied by k_fbase_mul_ct | its launches; completed passes only
+std::atomic<unsigned long long> g_fb_ct_stat[2];
+constexpr unsigned kFbKnownFlags = CURDLE_FBASE_CONSTANT_TIME;
 
 size_t pass_size() {
   const long long knob = knobs::get(knobs::FBASE_PASS);
@@ -120,6 +127,7 @@ const char* check_affine_host(const G1Affine& a) {
 struct FbCall {
   SlotHold& H;
   WipeList W;
+  bool ct;  // CURDLE_FBASE_CONSTANT_TIME: which launcher fb_launches takes and which counters a pass moves
   Slot& slot() { return H.slot(); }
   hipStream_t stream() { return H.stream(); }
 };
@@ -128,15 +136,16 @@ struct FbCall {
 // aligned) -> if d_comp, their encodings there (any alignment).
 int fb_launches(FbCall& C, const void* d_table, const void* d_scalars, const void* d_mults, size_t cnt, void* d_affine,
                 uint8_t* d_comp) {
-  HIP_TRY(launch_fbase_mul(d_table, d_scalars, d_mults, (uint32_t)cnt, C.slot().sorted.p, C.stream()));
+  HIP_TRY((C.ct ? launch_fbase_mul_ct : launch_fbase_mul)(d_table, d_scalars, d_mults, (uint32_t)cnt, C.slot().sorted.p, C.stream()));
   HIP_TRY(launch_g1_normalize(C.slot().sorted.p, kNormalizeXyzz, (uint32_t)cnt, d_affine, C.stream(), nullptr));
   if (d_comp) HIP_TRY(launch_g1_compress(d_affine, kCompressAffine, (uint32_t)cnt, d_comp, C.stream()));
   return CURDLE_OK;
 }
 
-void count_pass(size_t cnt) {
-  g_fb_stat[0].fetch_add(cnt, std::memory_order_relaxed);
-  g_fb_stat[1].fetch_add(1, std::memory_order_relaxed);
+void count_pass(const FbCall& C, size_t cnt) {
+  std::atomic<unsigned long long>* stat = C.ct ? g_fb_ct_stat : g_fb_stat;
+  stat[0].fetch_add(cnt, std::memory_order_relaxed);
+  stat[1].fetch_add(1, std::memory_order_relaxed);
 }
 
 // scalars / multipliers / out: host memory (resident false) or device memory.
@@ -181,14 +190,14 @@ int fb_run(FbCall& C, const void* d_table, const uint8_t* scalars, const uint8_t
     }
     HIP_TRY(hipStreamSynchronize(C.stream()));
     if (!resident) memcpy(out + rec * lo, S.h_stage[1], rec * cnt);
-    count_pass(cnt);
+    count_pass(C, cnt);
   }
   return CURDLE_OK;
 }
 
 // One call through the table's copy on the calling thread's context and an MSM slot: run(C, d_table) does the passes.
 template <class Run>
-int fb_through_slot(const curdle_fbase* base, void* user_stream, Run run) {
+int fb_through_slot(const curdle_fbase* base, void* user_stream, unsigned flags, Run run) {
   Ctx& cx = cur();
   curdle_fbase* b = base ? const_cast<curdle_fbase*>(base) : generator_base();
   if (!b) return fail(CURDLE_ENOMEM, "out of memory");
@@ -196,11 +205,16 @@ int fb_through_slot(const curdle_fbase* base, void* user_stream, Run run) {
   int rc = fbase_acquire(cx, b, &d_table);
   if (rc) return rc;
   SlotHold H(cx, true, user_stream);
-  FbCall C{H, WipeList(H.stream())};
+  FbCall C{H, WipeList(H.stream()), (flags & CURDLE_FBASE_CONSTANT_TIME) != 0};
   H.wipe_on_exit(&C.W, "fixed-base multiplication: clearing the scalars");  // nothing of the scalars stays
   rc = H.run([&]() -> int { return run(C, d_table); });
   fbase_release(b);
   return rc;
+}
+
+int check_flags(unsigned flags) {
+  if (flags & ~kFbKnownFlags) return fail(CURDLE_EINVAL, "unknown flag bits 0x%x", flags & ~kFbKnownFlags);
+  return CURDLE_OK;
 }
 
 int check_args(const void* scalars, size_t n, int out_form, const void* out) {
@@ -255,7 +269,7 @@ int trackers_run(FbCall& C, const void* d_table, const uint64_t* ks, const uint6
     HIP_TRY(hipStreamSynchronize(C.stream()));
     memcpy(trackers_out + 96 * lo, ho, 96 * m);
     if (kcomm_out) memcpy(kcomm_out + 48 * lo, ho + 96 * m, 48 * m);
-    count_pass(cols * m);
+    count_pass(C, cols * m);
   }
   return CURDLE_OK;
 }
@@ -286,37 +300,50 @@ extern "C" void curdle_fbase_free(curdle_fbase* b) {
   if (b && b->copy.free_or_defer()) delete b;
 }
 
-extern "C" int curdle_g1_fixed_base_mul_batch(const curdle_fbase* base, const uint64_t* scalars, const uint64_t* multipliers,
-                                              size_t n, int out_form, void* out) {
+extern "C" int curdle_g1_fixed_base_mul_batch_ex(const curdle_fbase* base, const uint64_t* scalars, const uint64_t* multipliers,
+                                                 size_t n, int out_form, unsigned flags, void* out) {
+  if (int rc = check_flags(flags)) return rc;
   if (n == 0) return CURDLE_OK;
   if (int rc = check_args(scalars, n, out_form, out)) return rc;
-  return fb_through_slot(base, nullptr, [&](FbCall& C, const void* d_table) {
+  return fb_through_slot(base, nullptr, flags, [&](FbCall& C, const void* d_table) {
     return fb_run(C, d_table, reinterpret_cast<const uint8_t*>(scalars), reinterpret_cast<const uint8_t*>(multipliers), n, false,
                   out_form, static_cast<uint8_t*>(out));
   });
 }
 
-extern "C" int curdle_g1_fixed_base_mul_batch_device(const curdle_fbase* base, const void* d_scalars, const void* d_multipliers,
-                                                     size_t n, int out_form, void* d_out, void* stream) {
+extern "C" int curdle_g1_fixed_base_mul_batch(const curdle_fbase* base, const uint64_t* scalars, const uint64_t* multipliers,
+                                              size_t n, int out_form, void* out) {
+  return curdle_g1_fixed_base_mul_batch_ex(base, scalars, multipliers, n, out_form, 0, out);
+}
+
+extern "C" int curdle_g1_fixed_base_mul_batch_device_ex(const curdle_fbase* base, const void* d_scalars, const void* d_multipliers,
+                                                        size_t n, int out_form, unsigned flags, void* d_out, void* stream) {
+  if (int rc = check_flags(flags)) return rc;
   if (n == 0) return CURDLE_OK;
   if (int rc = check_args(d_scalars, n, out_form, d_out)) return rc;
   if (!aligned16(d_scalars) || !aligned16(d_multipliers) || (out_form == CURDLE_G1_OUT_AFFINE && !aligned16(d_out)))
     return fail(CURDLE_EINVAL, "device pointers must be multiples of 16 (a compressed d_out may have any alignment)");
-  return fb_through_slot(base, stream, [&](FbCall& C, const void* d_table) {
+  return fb_through_slot(base, stream, flags, [&](FbCall& C, const void* d_table) {
     return fb_run(C, d_table, static_cast<const uint8_t*>(d_scalars), static_cast<const uint8_t*>(d_multipliers), n, true,
                   out_form, static_cast<uint8_t*>(d_out));
   });
 }
 
-extern "C" int curdle_whisk_compute_trackers_batch(const uint64_t* ks, const uint64_t* rs, size_t n, uint8_t* trackers_out,
-                                                   uint8_t* k_commitments_out) {
+extern "C" int curdle_g1_fixed_base_mul_batch_device(const curdle_fbase* base, const void* d_scalars, const void* d_multipliers,
+                                                     size_t n, int out_form, void* d_out, void* stream) {
+  return curdle_g1_fixed_base_mul_batch_device_ex(base, d_scalars, d_multipliers, n, out_form, 0, d_out, stream);
+}
+
+extern "C" int curdle_whisk_compute_trackers_batch_ex(const uint64_t* ks, const uint64_t* rs, size_t n, unsigned flags,
+                                                      uint8_t* trackers_out, uint8_t* k_commitments_out) {
+  if (int rc = check_flags(flags)) return rc;  // like a count beyond the limit: refused without touching the outputs
   if (n == 0) return CURDLE_OK;
   if (n > kFbMaxMembers) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^22 trackers", n);
   int rc;
   if (!ks || !trackers_out)
     rc = fail(CURDLE_EINVAL, "null argument");
   else
-    rc = fb_through_slot(nullptr, nullptr, [&](FbCall& C, const void* d_table) {
+    rc = fb_through_slot(nullptr, nullptr, flags, [&](FbCall& C, const void* d_table) {
       return trackers_run(C, d_table, ks, rs, n, trackers_out, k_commitments_out);
     });
   if (rc != CURDLE_OK) {  // a failed call leaves nothing that reads as a tracker
@@ -326,4 +353,10 @@ extern "C" int curdle_whisk_compute_trackers_batch(const uint64_t* ks, const uin
   return rc;
 }
 
+extern "C" int curdle_whisk_compute_trackers_batch(const uint64_t* ks, const uint64_t* rs, size_t n, uint8_t* trackers_out,
+                                                   uint8_t* k_commitments_out) {
+  return curdle_whisk_compute_trackers_batch_ex(ks, rs, n, 0, trackers_out, k_commitments_out);
+}
+
 extern "C" int curdle_stat_fbase(unsigned long long out[3]) { return read_stats(out, g_fb_stat, 3); }
+extern "C" int curdle_stat_fbase_ct(unsigned long long out[2]) { return read_stats(out, g_fb_ct_stat, 2); }

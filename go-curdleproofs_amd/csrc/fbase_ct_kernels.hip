@@ -1,0 +1,205 @@
+// Constant-time twin of k_fbase_mul (fbase_kernels.hip): out_i = (s_i * m_i mod r) * P from the SAME resident table,
+// same inputs, same output, with an instruction stream and an address stream that do not depend on the scalars.
+//
+// The walk.  64 unsigned 4-bit digits from window 0 upward.  The multiples a 4-bit window v needs, d 2^(4 v) P for
+// d = 1..15, are entries of the 8-bit table (table[w * 255 + e - 1] = e 2^(8 w) P, e = 1..255):
+//     d 2^(4 v) P = table[(v >> 1) * 255 + (d << (4 * (v & 1))) - 1]                      (16 * 15 = 240 <= 255)
+// For every window the lane reads ALL 15 of them -- the addresses are made of the table pointer and the loop counter
+// and of nothing else, so they are the same for every lane of every wave -- and keeps the one its digit names by mask
+// arithmetic over the 28 limbs (entry & (0 - (d == e)), OR-ed together); digit 0 keeps entry 1, a real point.  960
+// records of one 128-byte line each are read per scalar, 122,880 bytes of the 1,044,480-byte table, L2-resident and
+// shared by every lane: no LDS copy, no second table.
+//
+// One mixed addition per window, always, and the new accumulator by selection:
+//     d == 0                      keep acc                (the sum is discarded)
+//     d != 0, nothing added yet   the chosen affine entry (zz = zzz = 1, y normalised as madd's is_inf arm does)
+//     otherwise                   the sum
+// "Nothing added yet" is a mask word (started |= d != 0), never a test of zz: the accumulator's zz and zzz are ONE
+// until the first addition, and the selection of zz and zzz is a product -- zz * (sum ? PP : 1), zzz * (sum ? PPP : 1)
+// -- so neither the old zz and zzz nor a second copy of them is kept, and infinity (k = 0) is `started == 0` at the end.
+//
+// The addition is the main path of d28::madd (fp28.h) without its three exceptional arms.  Exactness (the argument of
+// fbase_kernels.hip, which holds for any window width): the scalar is canonical (k < r), the digits are unsigned and P
+// is in the prime-order subgroup, so before window v the accumulator is m P with m = k mod 2^(4 v) < 2^(4 v) <=
+// d 2^(4 v), never + the addend, and m + d 2^(4 v) <= k < r, never - the addend.  A sum that is discarded (digit 0, or
+// nothing added yet, where the accumulator is not a point at all) may be nonsense: it is integer arithmetic inside the
+// limb bounds of fp28.h (x, y < 10p, zz, zzz < 2p, an affine operand below 2p) and traps nothing.  Signed digits would
+// halve the reads and break the argument.  tests/fbase_ct_model.py asserts it on every case the tests use.
+//
+// What may depend on a scalar: data operands of arithmetic and of selects.  What may not: a branch condition, an exec
+// mask (beyond i >= n), a load, store or LDS address, a readfirstlane, a loop trip count.  Selects are written as
+// mask arithmetic, m = 0 - (cond), (a & m) | (b & ~m); the store masks the twelve words of every coordinate with
+// `started`, because is_inf is (s m = 0 mod r), a fact about the secrets -- that such a lane stores zeros is the
+// result itself.  DESIGN.md section 0 (round 21) lists every branch and every memory instruction of the build.
+//
+// The multiply-accumulate trap: no product may see a limb the compiler knows.  The
+// initial accumulator is constants, so the window loop stays rolled (#pragma unroll 1, as in k_fbase_mul): inside the
+// loop the accumulator is a loop-carried value.  The constant `one` reaches products only through a select with a
+// lane mask.
+//
+// Plain loads and stores, no LDS, no scratch, no inline assembly beyond the field layer's.
+#include <hip/hip_runtime.h>
+
+#include "msm_kernels_common.h"
+
+namespace curdle {
+
+namespace {
+__device__ __forceinline__ void load_fr_ct(Fr& f, const uint4* __restrict__ src) {
+  const uint4 lo = src[0], hi = src[1];
+  f.l[0] = lo.x; f.l[1] = lo.y; f.l[2] = lo.z; f.l[3] = lo.w;
+  f.l[4] = hi.x; f.l[5] = hi.y; f.l[6] = hi.z; f.l[7] = hi.w;
+}
+// the low 4-bit digit of k, and k >> 4: every window is read from word 0, so no register is indexed by the window
+__device__ __forceinline__ u32 next_digit4(Fr& k) {
+  const u32 d = k.l[0] & 0xfu;
+#pragma unroll
+  for (int j = 0; j < 7; j++) k.l[j] = (k.l[j] >> 4) | (k.l[j + 1] << 28);
+  k.l[7] >>= 4;
+  return d;
+}
+// r = m ? a : one limb by limb, m all ones or zero
+__device__ __forceinline__ void select_or_one(F28& r, u32 m, const F28& a) {
+#pragma unroll
+  for (int i = 0; i < d28::N; i++) r.l[i] = (a.l[i] & m) | (d28::kOne(i) & ~m);
+}
+// r = sum ? a : (first ? b : c); sum, first and ~(sum | first) are disjoint masks
+__device__ __forceinline__ void select3(F28& r, u32 sum, const F28& a, u32 first, const F28& b, const F28& c) {
+  const u32 keep = ~(sum | first);
+#pragma unroll
+  for (int i = 0; i < d28::N; i++) r.l[i] = (a.l[i] & sum) | (b.l[i] & first) | (c.l[i] & keep);
+}
+
+// One window's step.  acc: x < 10p, y < 6p, zz, zzz < 2p, limbs normalised; (x2, y2) affine below 2p, normalised.
+// nz = 0 - (d != 0), started = all ones once something was added.  d28::madd's main path (EFD madd-2008-s), then the
+// selection described at the top of the file; the bounds are madd's (X3 < 10p, Y3 < 2p, products < 2p).
+__device__ __forceinline__ void madd_select(X28& acc, const F28& x2, const F28& y2, u32 nz, u32 started) {
+  using namespace d28;
+  const u32 sum = nz & started, first = nz & ~started;
+  F28 pp, r, t, q, ppp, p;
+  mul_inl(p, x2, acc.zz);
+  sub_raw<16>(p, p, acc.x);  // P = U2 - X1 < 18p
+  mul_inl(r, y2, acc.zzz);
+  sub_raw<16>(r, r, acc.y);  // R = S2 - Y1 < 18p
+  sqr_inl(pp, p);            // PP < 2p
+  mul_inl(ppp, p, pp);       // PPP
+  mul_inl(q, acc.x, pp);     // Q
+  select_or_one(p, sum, pp);
+  mul_inl(acc.zz, acc.zz, p);    // ZZ * PP, or ZZ * 1: the same value (one until the first addition), below 2p again
+  select_or_one(p, sum, ppp);
+  mul_inl(acc.zzz, acc.zzz, p);
+  sqr_inl(t, r);
+  x3_fused(t, t, ppp, q);    // X3 = R^2 - PPP - 2Q < 10p
+  sub_raw<16>(q, q, t);      // Q - X3 < 18p
+  F28 ny, z;
+  set_zero(z);
+  sub_raw<16>(ny, z, acc.y); // 16p - Y1 (Y1 < 6p)
+  mul2_inl(p, r, q, ny, ppp);  // Y3 = R (Q - X3) - Y1 PPP  (mod p), < 2p
+  F28 yn = y2;
+  norm(yn);
+  select3(acc.x, sum, t, first, x2, acc.x);
+  select3(acc.y, sum, p, first, yn, acc.y);
+}
+
+// d28::to_gnark_msm with a masked canonical step.  d28::canonical_lt2p takes its subtraction under `if (!borrow)`,
+// which this build turned into an exec mask on whether the product's representative reached p: a property of the
+// accumulator's projective coordinates, which are made of the digits.  Here the choice is a select.
+__device__ __forceinline__ void to_gnark_msm_ct(u32* w, const F28& a, u32 role) {
+  using namespace d28;
+  F28 t, c;
+#pragma unroll
+  for (int i = 0; i < N; i++) c.l[i] = role == 0 ? kToExtX16(i) : (role == 1 ? kToExtY64(i) : kToExt(i));
+  mul(t, a, c);
+  u32 d[N], borrow = 0;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const u32 s = t.l[i] - kP(i) - borrow;
+    borrow = s >> 31;  // limbs are below 2^28 (the top one below 2^31): bit 31 of the difference is the borrow
+    d[i] = i < N - 1 ? s & MASK : s;
+  }
+  const u32 lt = 0u - borrow;  // t < p: keep t
+#pragma unroll
+  for (int i = 0; i < N; i++) t.l[i] = (t.l[i] & lt) | (d[i] & ~lt);
+  pack(w, t);
+}
+
+__device__ __forceinline__ void store12_masked(G1XYZZ* dst, int role, const u32 w[12], u32 m) {
+  uint4* d = reinterpret_cast<uint4*>(reinterpret_cast<u32*>(dst) + 12 * role);
+#pragma unroll
+  for (int i = 0; i < 3; i++) d[i] = make_uint4(w[4 * i] & m, w[4 * i + 1] & m, w[4 * i + 2] & m, w[4 * i + 3] & m);
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock, 2)
+    k_fbase_mul_ct(const A28* __restrict__ table, const uint4* __restrict__ scalars, const uint4* __restrict__ multipliers,
+                   u32 n, G1XYZZ* __restrict__ out) {
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  Fr k;
+  {
+    Fr s;
+    load_fr_ct(s, scalars + 2 * (size_t)i);
+    if (multipliers) {  // a kernel argument: uniform over the launch
+      Fr m;
+      load_fr_ct(m, multipliers + 2 * (size_t)i);
+      f_mul_inl<FrParams>(s, s, m);
+    }
+    f_from_mont<FrParams>(k, s);
+  }
+  X28 acc;  // not a point until `started`: zz = zzz = one, x and y anything below 2p
+  d28::set_one(acc.x);
+  d28::set_one(acc.y);
+  d28::set_one(acc.zz);
+  d28::set_one(acc.zzz);
+  u32 started = 0;
+#pragma unroll 1
+  for (u32 v = 0; v < 64; v++) {
+    const u32 d = next_digit4(k);
+    const u32 first_entry = (v >> 1) * 255u - 1u, shift = 4u * (v & 1u);
+    A28 pt;
+    {  // entry 1 for the digits 0 and 1
+      A28 e;
+      d28::load(e, a28_at(table, first_entry + (1u << shift)));
+      const u32 m = 0u - (u32)(d <= 1u);
+#pragma unroll
+      for (int j = 0; j < d28::N; j++) {
+        pt.x.l[j] = e.x.l[j] & m;
+        pt.y.l[j] = e.y.l[j] & m;
+      }
+    }
+#pragma unroll
+    for (u32 c = 2; c < 16; c++) {
+      A28 e;
+      d28::load(e, a28_at(table, first_entry + (c << shift)));
+      const u32 m = 0u - (u32)(d == c);
+#pragma unroll
+      for (int j = 0; j < d28::N; j++) {
+        pt.x.l[j] |= e.x.l[j] & m;
+        pt.y.l[j] |= e.y.l[j] & m;
+      }
+    }
+    const u32 nz = 0u - (u32)(d != 0u);
+    madd_select(acc, pt.x, pt.y, nz, started);
+    started |= nz;
+  }
+  u32 w12[12];
+  G1XYZZ* dst = out + i;
+  to_gnark_msm_ct(w12, acc.x, 0);
+  store12_masked(dst, 0, w12, started);
+  to_gnark_msm_ct(w12, acc.y, 1);
+  store12_masked(dst, 1, w12, started);
+  to_gnark_msm_ct(w12, acc.zz, 2);
+  store12_masked(dst, 2, w12, started);
+  to_gnark_msm_ct(w12, acc.zzz, 3);
+  store12_masked(dst, 3, w12, started);
+}
+
+hipError_t launch_fbase_mul_ct(const void* table28, const void* scalars, const void* multipliers, uint32_t n, void* out_xyzz,
+                               hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_fbase_mul_ct, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream, reinterpret_cast<const A28*>(table28),
+                     (const uint4*)scalars, (const uint4*)multipliers, (u32)n, (G1XYZZ*)out_xyzz);
+  return hipGetLastError();
+}
+
+}  // namespace curdle

@@ -320,6 +320,11 @@ hipError_t launch_g1_compress(const void* in, int form, uint32_t n, uint8_t* out
 static constexpr uint32_t kFbaseEntries = 32 * 255;
 hipError_t launch_fbase_mul(const void* table28, const void* scalars, const void* multipliers, uint32_t n, void* out_xyzz,
                             hipStream_t stream);
+// fbase_ct_kernels.hip: the same function of the same arguments over the same table, as 64 unsigned 4-bit windows:
+// every window reads all 15 of its multiples (a subset of table28) at addresses made of the window alone, selects by
+// mask and always adds.  Neither the instruction stream nor the address stream depends on scalars or multipliers.
+hipError_t launch_fbase_mul_ct(const void* table28, const void* scalars, const void* multipliers, uint32_t n, void* out_xyzz,
+                               hipStream_t stream);
 
 // normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion
 // per wave of 64 lanes with 1 or 8 points each (Montgomery's trick over a wave scan).  The forms are those of

@@ -81,6 +81,8 @@ SYMBOLS = [
     "curdle_g1_normalize_batch", "curdle_g1_normalize_batch_device", "curdle_g1_scalar_mul_batch_device", "curdle_stat_normalize",
     "curdle_fbase_create", "curdle_fbase_free", "curdle_g1_fixed_base_mul_batch", "curdle_g1_fixed_base_mul_batch_device",
     "curdle_stat_fbase", "curdle_whisk_compute_tracker", "curdle_whisk_k_commitment", "curdle_whisk_compute_trackers_batch",
+    "curdle_g1_fixed_base_mul_batch_ex", "curdle_g1_fixed_base_mul_batch_device_ex", "curdle_whisk_compute_trackers_batch_ex",
+    "curdle_stat_fbase_ct",
     "curdle_whisk_is_valid_tracker_proof_batch_combined", "curdle_whisk_is_valid_tracker_proof_batch_combined_device",
     "curdle_stat_tracker_combined", "curdle_whisk_tracker_combined_scalars", "curdle_tracker_combined_last_kernel_ms",
     "curdle_stat_transcript_paths", "curdle_keccak_permute_batch",
@@ -223,6 +225,11 @@ _stat_fbase = _sig("curdle_stat_fbase", C.c_int, C.POINTER(C.c_ulonglong))
 _whisk_compute_tracker = _sig("curdle_whisk_compute_tracker", C.c_int, _vp, _vp, _vp)
 _whisk_k_commitment = _sig("curdle_whisk_k_commitment", C.c_int, _vp, _vp)
 _whisk_compute_trackers_batch = _sig("curdle_whisk_compute_trackers_batch", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp)
+_fbase_mul_ex = _sig("curdle_g1_fixed_base_mul_batch_ex", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_uint, _vp)
+_fbase_mul_device_ex = _sig("curdle_g1_fixed_base_mul_batch_device_ex", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_uint,
+                            _vp, _vp)
+_whisk_compute_trackers_batch_ex = _sig("curdle_whisk_compute_trackers_batch_ex", C.c_int, _vp, _vp, C.c_size_t, C.c_uint, _vp, _vp)
+_stat_fbase_ct = _sig("curdle_stat_fbase_ct", C.c_int, C.POINTER(C.c_ulonglong))
 _verify_set_eager = _sig("curdle_verify_set_eager", C.c_int, C.c_int)
 _reencode = _sig("curdle_proof_reencode", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t))
 _merlin_tv = _sig("curdle_merlin_test_vector", C.c_int, C.c_char_p, C.c_char_p, _vp, C.c_size_t, C.c_char_p, _vp,
@@ -1340,6 +1347,7 @@ def stat_tracker_own() -> dict:
 
 
 G1_OUT_AFFINE, G1_OUT_COMPRESSED = 0, 1
+FBASE_CONSTANT_TIME = 1                               # CURDLE_FBASE_CONSTANT_TIME
 
 
 class FBase:
@@ -1376,28 +1384,35 @@ def _fbase_handle(base):
     return base._h
 
 
-def g1_fixed_base_mul_batch(scalars, multipliers=None, base=None, out_form=G1_OUT_AFFINE) -> np.ndarray:
+def g1_fixed_base_mul_batch(scalars, multipliers=None, base=None, out_form=G1_OUT_AFFINE, flags=None) -> np.ndarray:
     """out[i] = (scalars[i] * multipliers[i] mod r) * P on the GPU (curdle_g1_fixed_base_mul_batch): scalars and
     multipliers (n, 4) Montgomery fr limbs, multipliers may be None; base an FBase or None for the generator.  Returns
-    (n, 12) uint64 affine records or (n, 48) uint8 compressed encodings."""
+    (n, 12) uint64 affine records or (n, 48) uint8 compressed encodings.  flags: None calls the entry point without
+    flags; an integer (0, FBASE_CONSTANT_TIME) calls curdle_g1_fixed_base_mul_batch_ex with it."""
     sc = _as_u64(scalars, 4).reshape(-1, 4)
     n = len(sc)
     mu = _as_u64(multipliers, 4).reshape(-1, 4) if multipliers is not None else None
     if mu is not None and len(mu) != n:
         raise ValueError("one multiplier per scalar")
     out = np.zeros((n, 48), dtype=np.uint8) if out_form == G1_OUT_COMPRESSED else np.zeros((n, 12), dtype=np.uint64)
-    _check(_fbase_mul(_fbase_handle(base), _ptr(sc) if n else None,
-                      _ptr(mu) if mu is not None and n else None, n, int(out_form), _ptr(out) if n else None))
+    args = (_fbase_handle(base), _ptr(sc) if n else None, _ptr(mu) if mu is not None and n else None, n, int(out_form))
+    if flags is None:
+        _check(_fbase_mul(*args, _ptr(out) if n else None))
+    else:
+        _check(_fbase_mul_ex(*args, int(flags), _ptr(out) if n else None))
     return out
 
 
 def g1_fixed_base_mul_batch_device(d_scalars: int, d_multipliers: int, n: int, d_out: int, base=None,
-                                   out_form=G1_OUT_AFFINE, stream=None) -> None:
+                                   out_form=G1_OUT_AFFINE, stream=None, flags=None) -> None:
     """The same over resident arrays (curdle_g1_fixed_base_mul_batch_device): HIP device pointers, multiples of 16
     except a compressed d_out; d_multipliers may be 0.  d_out is complete when the call returns and must not overlap
-    the inputs."""
-    _check(_fbase_mul_device(_fbase_handle(base), d_scalars or None, d_multipliers or None, n,
-                             int(out_form), d_out or None, stream or None))
+    the inputs.  flags: as in g1_fixed_base_mul_batch (curdle_g1_fixed_base_mul_batch_device_ex)."""
+    args = (_fbase_handle(base), d_scalars or None, d_multipliers or None, n, int(out_form))
+    if flags is None:
+        _check(_fbase_mul_device(*args, d_out or None, stream or None))
+    else:
+        _check(_fbase_mul_device_ex(*args, int(flags), d_out or None, stream or None))
 
 
 def stat_fbase() -> dict:
@@ -1405,6 +1420,13 @@ def stat_fbase() -> dict:
     out = (C.c_ulonglong * 3)()
     _check(_stat_fbase(out))
     return {"scalars": int(out[0]), "launches": int(out[1]), "tables": int(out[2])}
+
+
+def stat_fbase_ct() -> dict:
+    """Scalars multiplied by the constant-time fixed-base kernel and its launches since the library was loaded."""
+    out = (C.c_ulonglong * 2)()
+    _check(_stat_fbase_ct(out))
+    return {"scalars": int(out[0]), "launches": int(out[1])}
 
 
 def whisk_compute_tracker(k, r) -> bytes:
@@ -1423,9 +1445,10 @@ def whisk_k_commitment(k) -> bytes:
     return bytes(out)
 
 
-def whisk_compute_trackers_batch(ks, rs=None, commitments=True):
+def whisk_compute_trackers_batch(ks, rs=None, commitments=True, flags=None):
     """n trackers and key commitments on the GPU (curdle_whisk_compute_trackers_batch): ks, rs (n, 4) Montgomery fr
-    limbs; rs None means r = 1.  Returns (trackers uint8[n, 96], commitments uint8[n, 48] or None)."""
+    limbs; rs None means r = 1.  Returns (trackers uint8[n, 96], commitments uint8[n, 48] or None).  flags: None calls
+    the entry point without flags; an integer (0, FBASE_CONSTANT_TIME) calls curdle_whisk_compute_trackers_batch_ex."""
     kk = _as_u64(ks, 4).reshape(-1, 4)
     n = len(kk)
     rr = _as_u64(rs, 4).reshape(-1, 4) if rs is not None else None
@@ -1433,8 +1456,12 @@ def whisk_compute_trackers_batch(ks, rs=None, commitments=True):
         raise ValueError("one r per k")
     trackers = np.zeros((n, 96), dtype=np.uint8)
     comms = np.zeros((n, 48), dtype=np.uint8) if commitments else None
-    _check(_whisk_compute_trackers_batch(_ptr(kk) if n else None, _ptr(rr) if rr is not None and n else None, n,
-                                         _ptr(trackers) if n else None, _ptr(comms) if comms is not None and n else None))
+    outs = (_ptr(trackers) if n else None, _ptr(comms) if comms is not None and n else None)
+    if flags is None:
+        _check(_whisk_compute_trackers_batch(_ptr(kk) if n else None, _ptr(rr) if rr is not None and n else None, n, *outs))
+    else:
+        _check(_whisk_compute_trackers_batch_ex(_ptr(kk) if n else None, _ptr(rr) if rr is not None and n else None, n,
+                                                int(flags), *outs))
     return trackers, comms
 
 

@@ -606,6 +606,36 @@ int curdle_whisk_k_commitment(const uint64_t k[4], uint8_t out[48]);
  * fallback: CURDLE_ENODEV without a device.  SECRETS: as curdle_g1_fixed_base_mul_batch. */
 int curdle_whisk_compute_trackers_batch(const uint64_t* ks, const uint64_t* rs, size_t n, uint8_t* trackers_out,
                                         uint8_t* k_commitments_out);
+/* The three batch calls above with a flags word.  flags = 0 IS the call above: same kernel, same counters (the calls
+ * above pass 0).  A bit that is not defined here: CURDLE_EINVAL before anything else is looked at, copied or launched
+ * (for the tracker batch: without touching the outputs), also with n = 0.  Everything else -- limits, passes,
+ * alignment, n = 0, CURDLE_ENODEV, the MSM slot, the wipes, the output bit for bit -- is as described above.
+ *
+ * CURDLE_FBASE_CONSTANT_TIME: the multiplication runs in a second kernel (csrc/fbase_ct_kernels.hip) over the SAME
+ * table.  It walks 64 unsigned 4-bit windows, reads ALL 15 multiples of every window (960 records, a subset of the
+ * table) at addresses made of the window number alone, chooses one by mask arithmetic, ALWAYS performs one mixed
+ * addition per window and takes the new accumulator by selection; infinity results are stored through a mask.
+ * WHAT THE FLAG PROMISES: the device code's instruction stream (every branch, every exec mask beyond the end-of-array
+ * guard, every loop count) and its address stream (every load and store address) are independent of the values of
+ * scalars and multipliers; they depend on n, on whether multipliers is null and on the pointers.  The host only copies
+ * scalars and multipliers (into the pinned staging and the device buffer that are wiped on the way out) and never
+ * looks at them.  The normalisation and the encoding that follow work on the RESULTS -- whether a result is infinity,
+ * the sign bit of its y -- which are the call's public output; they are the kernels of the default path.
+ * WHAT IT DOES NOT PROMISE: anything about data-dependent power draw and clock behaviour of the chip (a multiplier fed
+ * zeros draws less), which is not addressed; and nothing about the default path, whose warning above stays true.
+ * About twice the default kernel's work by operation count (64 additions and 64 x 15 selected records against 31.9
+ * additions on average). */
+#define CURDLE_FBASE_CONSTANT_TIME 1u
+int curdle_g1_fixed_base_mul_batch_ex(const curdle_fbase* base, const uint64_t* scalars, const uint64_t* multipliers,
+                                      size_t n, int out_form, unsigned flags, void* out);
+int curdle_g1_fixed_base_mul_batch_device_ex(const curdle_fbase* base, const void* d_scalars, const void* d_multipliers,
+                                             size_t n, int out_form, unsigned flags, void* d_out, void* stream);
+int curdle_whisk_compute_trackers_batch_ex(const uint64_t* ks, const uint64_t* rs, size_t n, unsigned flags,
+                                           uint8_t* trackers_out, uint8_t* k_commitments_out);
+/* out[0] scalars multiplied by the constant-time kernel, out[1] its launches; completed passes only.  A pass under
+ * CURDLE_FBASE_CONSTANT_TIME counts here and NOT in curdle_stat_fbase[0..1]; tables built stay in curdle_stat_fbase[2]
+ * (the table is shared). */
+int curdle_stat_fbase_ct(unsigned long long out[2]);
 /* ------------------------------------------------------------------------- *
  * Accumulator on the device
  *   msmaccumulator.AccumulateCheck / Verify (msmaccumulator/msmaccumulator.go:23-64) with
