@@ -234,9 +234,12 @@ struct TranscriptArgs {
   uint64_t tail;          // pos | pos_begin << 8 | cur_flags << 16 after the program
   uint32_t n_ctl, row_words, init_stride, k, mpw, n_challenges;
   uint32_t sheet;         // 1: k_transcript_sheet (transcript_sheet_kernels.hip), two members per wave; `mpw` is then unused
+  uint32_t max_tries;     // draws of one challenge before status 1; launch_transcript_batch fills it, never a caller
 };
 // Kernel and geometry (`sheet`, `mpw`) are the caller's, from choose_transcript_kernel (transcript_api.hip); the launch
-// dispatches on `sheet` and counts the members each kernel hashed (transcript_path_counts: lane kernel | sheet kernel).
+// fills `max_tries` (knobs::transcript_max_tries: 256 unless test hook TRANSCRIPT_MAX_TRIES lowered it) and takes the
+// kernels' build that reads it only then -- at 256 the build with the constant, the parent's code -- dispatches on
+// `sheet` and counts the members each kernel hashed (transcript_path_counts: lane kernel | sheet kernel).
 hipError_t launch_transcript_batch(const TranscriptArgs& args, hipStream_t stream);
 hipError_t launch_transcript_sheet(const TranscriptArgs& args, hipStream_t stream);
 void transcript_path_counts(unsigned long long out[2]);

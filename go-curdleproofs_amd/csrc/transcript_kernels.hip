@@ -15,6 +15,7 @@
 
 #include <atomic>
 
+#include "../host/knobs.h"
 #include "../host/transcript_batch.h"
 #include "keccak_dev.h"
 #include "msm_kernels.h"
@@ -65,7 +66,11 @@ __device__ __forceinline__ bool canonical(const uint64_t ch[4]) {
   return v0 < 0xffffffff00000001ull;
 }
 
+// kKnobBound: the retry bound is the kernel argument p.max_tries (test hook TRANSCRIPT_MAX_TRIES); otherwise the
+// constant transcript::kMaxTries, the build every call takes while the knob is unset (launch_transcript_batch).
+template <bool kKnobBound>
 __global__ __launch_bounds__(64) void k_transcript_batch(TranscriptArgs p) {
+  const uint32_t max_tries = kKnobBound ? p.max_tries : (uint32_t)transcript::kMaxTries;  // wave-uniform
   const uint32_t lane = threadIdx.x;
   if (lane >= p.mpw) return;
   const uint32_t m = blockIdx.x * p.mpw + lane;
@@ -85,8 +90,8 @@ __global__ __launch_bounds__(64) void k_transcript_batch(TranscriptArgs p) {
     // GetAndAppendChallenge.  The first try's framing ended the blocks before; every later try starts at (32, 0).
     uint64_t ch[4];
     squeeze32(st, ch);
-    for (int tries = 1; !canonical(ch); tries++) {
-      if (tries == transcript::kMaxTries) {
+    for (uint32_t tries = 1; !canonical(ch); tries++) {
+      if (tries == max_tries) {
         status = 1;
         break;
       }
@@ -127,14 +132,19 @@ __global__ __launch_bounds__(64) void k_transcript_batch(TranscriptArgs p) {
 std::atomic<unsigned long long> g_paths[2];  // members launched on k_transcript_batch | on k_transcript_sheet
 }  // namespace
 
-hipError_t launch_transcript_batch(const TranscriptArgs& args, hipStream_t stream) {
-  if (args.k == 0) return hipSuccess;
+hipError_t launch_transcript_batch(const TranscriptArgs& caller, hipStream_t stream) {
+  if (caller.k == 0) return hipSuccess;
+  TranscriptArgs args = caller;
+  args.max_tries = (uint32_t)knobs::transcript_max_tries();  // the one place: every launch of either kernel passes here
   hipError_t e;
   if (args.sheet) {
     e = launch_transcript_sheet(args, stream);
   } else {
     const uint32_t blocks = (args.k + args.mpw - 1) / args.mpw;
-    hipLaunchKernelGGL(k_transcript_batch, dim3(blocks), dim3(64), 0, stream, args);
+    if (args.max_tries == (uint32_t)transcript::kMaxTries)
+      hipLaunchKernelGGL(k_transcript_batch<false>, dim3(blocks), dim3(64), 0, stream, args);
+    else
+      hipLaunchKernelGGL(k_transcript_batch<true>, dim3(blocks), dim3(64), 0, stream, args);
     e = hipGetLastError();
   }
   if (e == hipSuccess) g_paths[args.sheet ? 1 : 0].fetch_add(args.k, std::memory_order_relaxed);

@@ -58,7 +58,11 @@ __device__ __forceinline__ bool sheet_canonical(uint64_t ch, const SheetLane& L,
   return (l & 1) || ((e & 1) && ((l & 2) || ((e & 2) && ((l & 4) || ((e & 4) && (l & 8))))));
 }
 
+// kKnobBound: as in k_transcript_batch -- the retry bound is p.max_tries under test hook TRANSCRIPT_MAX_TRIES, the
+// constant transcript::kMaxTries otherwise.
+template <bool kKnobBound>
 __global__ __launch_bounds__(64) void k_transcript_sheet(TranscriptArgs p) {
+  const uint32_t max_tries = kKnobBound ? p.max_tries : (uint32_t)transcript::kMaxTries;  // wave-uniform
   const SheetLane L = sheet_lane_setup();
   const uint32_t m = blockIdx.x * kSheetStatesPerWave + L.half;
   const bool live = m < p.k;  // per half
@@ -79,8 +83,8 @@ __global__ __launch_bounds__(64) void k_transcript_sheet(TranscriptArgs p) {
     uint64_t ch = a;
     if (L.w < 4) a = 0;
     bool need = live && !sheet_canonical(ch, L, rw);
-    for (int tries = 1; __builtin_amdgcn_ballot_w64(need) != 0; tries++) {
-      if (tries == transcript::kMaxTries) {
+    for (uint32_t tries = 1; __builtin_amdgcn_ballot_w64(need) != 0; tries++) {
+      if (tries == max_tries) {
         if (need) status = 1;
         break;
       }
@@ -147,10 +151,14 @@ __global__ __launch_bounds__(64) void k_keccak_permute_sheet(const uint64_t* in,
 }
 }  // namespace
 
+// Called by launch_transcript_batch alone (transcript_kernels.hip), which has filled args.max_tries.
 hipError_t launch_transcript_sheet(const TranscriptArgs& args, hipStream_t stream) {
   if (args.k == 0) return hipSuccess;
   const uint32_t blocks = (args.k + kSheetStatesPerWave - 1) / kSheetStatesPerWave;
-  hipLaunchKernelGGL(k_transcript_sheet, dim3(blocks), dim3(64), 0, stream, args);
+  if (args.max_tries == (uint32_t)transcript::kMaxTries)
+    hipLaunchKernelGGL(k_transcript_sheet<false>, dim3(blocks), dim3(64), 0, stream, args);
+  else
+    hipLaunchKernelGGL(k_transcript_sheet<true>, dim3(blocks), dim3(64), 0, stream, args);
   return hipGetLastError();
 }
 

@@ -15,7 +15,7 @@ const char* const kNames[COUNT] = {
     "BATCH_GROUP", "DEVICE_ACC", "HOST_DECODE", "VERIFY_EAGER", "VERIFY_TRACE", "PROVER_FOLD_BASES",
     "ACC_PRIO", "REDUCE_PRIO", "AUX_PRIO", "HOST_FOLD", "MAX_LARGE", "BATCH_CHECKERS", "TRANSCRIPT_LANES", "GPU_PRELUDE",
     "TRACKER_DEVICE_HASH", "NORMALIZE_LANE_POINTS", "TRACKER_OWN_PAIRS", "FBASE_PASS", "TRANSCRIPT_SHEET",
-    "STREAM_PLAN"};
+    "STREAM_PLAN", "TRANSCRIPT_MAX_TRIES"};
 std::atomic<long long> g_val[COUNT];
 std::once_flag g_once;
 void load() {
@@ -48,6 +48,11 @@ int set(const char* nm, long long value) {
       return 0;
     }
   return -1;
+}
+int transcript_max_tries() {
+  constexpr int kDefault = 256;  // transcript::kMaxTries, CURDLE_TRANSCRIPT_MAX_TRIES (asserted in host/transcript.cpp)
+  const long long v = get(TRANSCRIPT_MAX_TRIES);
+  return v >= 1 && v <= kDefault ? (int)v : kDefault;
 }
 }  // namespace knobs
 }  // namespace curdle

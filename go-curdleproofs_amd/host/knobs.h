@@ -50,6 +50,7 @@ enum Id {
   FBASE_PASS,             // curdle_g1_fixed_base_mul_batch, curdle_whisk_compute_trackers_batch: scalars per pass (one launch of k_fbase_mul), rounded down to a multiple of 256, at least 256; unset: 2^20 (fbase_api.hip)
   TRANSCRIPT_SHEET,       // the batched transcripts' kernel: 1 always the sheet kernel (a state spread over lanes), 0 never; unset: the library's rule, and TRANSCRIPT_LANES set means the lane kernel (choose_transcript_kernel, transcript_api.hip)
   STREAM_PLAN,            // streams of pipelined MSMs, read when the context is created: 1 wide (a tail stream per slot), 2 compact (one tail stream: four busy streams); 0 or unset: compact below 16 hardware queues (GPU_MAX_HW_QUEUES), wide from there (stream_plan, msm_plan.hip)
+  TRANSCRIPT_MAX_TRIES,   // test hook: lowers the batched transcripts' retry bound (draws of one challenge before the member is handed back with a status) to min(256, value) for value >= 1, so a test can reach the status byte; unset, 0 or above 256: 256.  The single calls ignore it (transcript_max_tries below)
   COUNT
 };
 // The knob's value, or -1 if it is not set (every knob's valid values are >= 0).
@@ -58,5 +59,8 @@ inline bool is_set(Id id) { return get(id) >= 0; }
 // name: "WINDOW_BITS" or "CURDLE_WINDOW_BITS"; value < 0 unsets.  0 on success, -1 for an unknown name.
 int set(const char* name, long long value);
 const char* name(Id id);
+// The retry bound of the batched transcripts under TRANSCRIPT_MAX_TRIES: what k_transcript_batch, k_transcript_sheet and
+// curdle_transcript_batch_host compare a challenge's draws against (transcript::kMaxTries = 256 unless a test lowered it).
+int transcript_max_tries();
 }  // namespace knobs
 }  // namespace curdle

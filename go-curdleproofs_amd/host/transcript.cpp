@@ -2,6 +2,7 @@
 #include "transcript.h"
 
 #include "keccak.h"
+#include "knobs.h"
 #include "transcript_batch.h"
 
 #include <string.h>
@@ -387,6 +388,8 @@ extern "C" int curdle_transcript_batch_host(const char* transcript_label, const 
       labels[s].assign(steps[s].label, steps[s].label_len);
       if (steps[s].op == CURDLE_TR_CHALLENGES) n_ch += steps[s].count;
     }
+    static_assert(kMaxTries == CURDLE_TRANSCRIPT_MAX_TRIES, "the header's bound is the twin's and the kernels'");
+    const int max_tries = knobs::transcript_max_tries();  // kMaxTries unless test hook TRANSCRIPT_MAX_TRIES lowered it
     const Transcript fresh = transcript_label ? Transcript(std::string(transcript_label)) : Transcript(Strobe128::Exported{init_states});
     auto member = [&](size_t i) {
       Transcript t = transcript_label ? fresh : Transcript(Strobe128::Exported{init_states + i * CURDLE_TRANSCRIPT_STATE_SIZE});
@@ -402,7 +405,7 @@ extern "C" int curdle_transcript_batch_host(const char* transcript_label, const 
           }
           int tries = 0;
           for (;; tries++) {  // GetAndAppendChallenge with its wait bounded
-            if (tries == kMaxTries) {
+            if (tries == max_tries) {
               status[i] = 1;
               break;
             }

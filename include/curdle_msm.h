@@ -456,7 +456,10 @@ int curdle_stat_tracker(unsigned long long out[3]);
  * Conventions are those of _ex / _device: results[i] = 1, 0 or CURDLE_EINVAL; k = 0: CURDLE_OK, no device needed; a
  * null pointer (the seed included) with k > 0: CURDLE_EINVAL before any device work; on a negative return every
  * results[i] holds that code.  _device: HIP device pointers of any alignment, `stream` a hipStream_t or NULL; on a
- * caller's stream the whole pass, the MSM included, runs on that stream. */
+ * caller's stream the whole pass, the MSM included, runs on that stream.  A member whose transcript draws no
+ * canonical challenge (CURDLE_TRANSCRIPT_MAX_TRIES rejected draws) takes no part in the sum and is answered by the
+ * single call on the host; in the _device form, which has no host copy of it, it fails the call (CURDLE_EHIP in
+ * every result), as in curdle_whisk_is_valid_tracker_proof_batch_device. */
 int curdle_whisk_is_valid_tracker_proof_batch_combined(const uint8_t* trackers, const uint8_t* k_commitments,
                                                        const uint8_t* proofs, size_t k, const uint8_t seed[32], int* results);
 int curdle_whisk_is_valid_tracker_proof_batch_combined_device(const void* d_trackers, const void* d_k_commitments,
@@ -972,6 +975,9 @@ int curdle_stat_check_paths(unsigned long long out[2]);
  *
  * status[i] != 0: member i drew CURDLE_TRANSCRIPT_MAX_TRIES non-canonical values for one challenge
  * (probability 0.547^256); its challenges and state are then unspecified.  Every wait is bounded.
+ * Knob TRANSCRIPT_MAX_TRIES (curdle_plan_override; a test hook) lowers this bound to min(256, value) in
+ * both kernels and the host twin so that tests reach the status byte, and the single calls that settle
+ * a handed-back member ignore it: they keep 256.
  *
  * CURDLE_EINVAL, before anything is copied or launched: an unknown op, label_len > 32, data_stride
  * below the bytes the program reads, both or neither of transcript_label and init_states, a limit

@@ -190,9 +190,13 @@ def merlin_test_vector(protocol: bytes, label: bytes, msg: bytes, challenge_labe
     return m.challenge_bytes(challenge_label, n)
 
 
-def run_program(program, data: bytes, label: bytes = None, state: bytes = None, hashing=True):
+def run_program(program, data: bytes, label: bytes = None, state: bytes = None, hashing=True, max_tries=MAX_TRIES):
     """One member.  program: [(op, label, count, len)].  Returns (challenges: [32 big-endian bytes], tries: [int],
-    exported state, status, the Merlin object).  With hashing=False every first draw counts as accepted."""
+    exported state, status, the Merlin object).  With hashing=False every first draw counts as accepted.
+    max_tries: draws of one challenge before the member gives up with status 1 (the library's bound is MAX_TRIES; its
+    test hook TRANSCRIPT_MAX_TRIES lowers it).  As in the host twin the program stops at the first challenge that gives
+    up: challenges and tries hold the accepted ones before it, and the state is unspecified."""
+    assert 1 <= max_tries <= MAX_TRIES
     m = Merlin(label, hashing) if state is None else Merlin(hashing=hashing, exported=state)
     at, challenges, tries, status = 0, [], [], 0
     for op, lab, count, ln in program:
@@ -204,7 +208,7 @@ def run_program(program, data: bytes, label: bytes = None, state: bytes = None, 
                 at += ln
                 continue
             assert op == TR_CHALLENGES
-            for t in range(1, MAX_TRIES + 1):
+            for t in range(1, max_tries + 1):
                 dest = m.challenge_bytes(lab, 32)
                 if not hashing or int.from_bytes(dest, "big") < R:       # SetBytesCanonical: equal to r is a rejection
                     m.append_message(lab, dest)                            # AppendScalars of the canonical value: the same bytes

@@ -7,8 +7,9 @@ the device and through the Whisk shuffle batch's prelude; and curdle_stat_transc
 hashed.
 
 Not provoked here: the status byte after 256 rejected draws of one challenge (probability 0.547^256).  The bound in
-k_transcript_sheet's retry loop (tries == kMaxTries, the status set on the half that still needs a draw) is checked by
-reading, against k_transcript_batch's."""
+k_transcript_sheet's retry loop (the status set on the half that still needs a draw, the other half keeping its state
+and its challenge) is run by tests/test_transcript_status_gpu.py, which lowers it through the test hook
+TRANSCRIPT_MAX_TRIES and puts every pair of the retry fixture's members on the two halves of a wave."""
 import os
 import threading
 
