@@ -11,6 +11,14 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // the body of every curdle_stat_* reader: n counters into out[]
 int read_stats(unsigned long long* out, const std::atomic<unsigned long long>* counters, int n);
 
+// What the flagged tracker-proof generator (tracker_api.hip) borrows from two other families.  fbase_api.hip: the
+// generator's fixed-base table on context cx (built on first use, a user reference that generator_table_release gives
+// back) and the counters of a completed pass of k_fbase_mul_ct; g1_mul_ct_api.hip: those of a pass of k_g1_mul_ct.
+int generator_table_acquire(Ctx& cx, void** d_table);
+void generator_table_release();
+void count_fbase_ct_pass(size_t n);
+void count_g1_mul_ct_pass(size_t n);
+
 // A free slot, marked as acquire_slot marks it, or -1: never waits, brings no context up and leaves the error text alone.
 int try_acquire_slot(Ctx& cx);
 

@@ -275,6 +275,19 @@ int trackers_run(FbCall& C, const void* d_table, const uint64_t* ks, const uint6
 }
 }  // namespace
 
+namespace curdle_api {
+int generator_table_acquire(Ctx& cx, void** d_table) {
+  curdle_fbase* b = generator_base();
+  if (!b) return fail(CURDLE_ENOMEM, "out of memory");
+  return fbase_acquire(cx, b, d_table);
+}
+void generator_table_release() { fbase_release(generator_base()); }
+void count_fbase_ct_pass(size_t n) {
+  g_fb_ct_stat[0].fetch_add(n, std::memory_order_relaxed);
+  g_fb_ct_stat[1].fetch_add(1, std::memory_order_relaxed);
+}
+}  // namespace curdle_api
+
 extern "C" int curdle_fbase_create(const uint64_t point_affine[12], curdle_fbase** out) {
   if (!out || !point_affine) return fail(CURDLE_EINVAL, "null argument");
   *out = nullptr;

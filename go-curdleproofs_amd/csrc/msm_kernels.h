@@ -329,6 +329,15 @@ hipError_t launch_fbase_mul(const void* table28, const void* scalars, const void
 hipError_t launch_fbase_mul_ct(const void* table28, const void* scalars, const void* multipliers, uint32_t n, void* out_xyzz,
                                hipStream_t stream);
 
+// g1_mul_ct_kernels.hip: out_affine[i] = scalars[i or 0] * points[i * point_stride], the constant-time twin of
+// launch_scalar_mul_batch without addends, one lane per pair and 255 double-and-always-add steps.  points: gnark
+// G1Affine records ((0, 0): infinity), point_stride records apart; scalars: Montgomery fr.Elements below r; the result
+// is n normalised gnark G1Affine records, 96 bytes apart (the lane inverts its own denominator), and out_affine may be
+// points when point_stride is 1.  Every pointer is a multiple of 16.  Neither the instruction stream nor the address
+// stream depends on the scalars.
+hipError_t launch_g1_mul_ct(const void* points, uint32_t point_stride, const void* scalars, int shared_scalar, uint32_t n,
+                            void* out_affine, hipStream_t stream);
+
 // normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion
 // per wave of 64 lanes with 1 or 8 points each (Montgomery's trick over a wave scan).  The forms are those of
 // launch_g1_compress; a denominator (Z, or ZZ ZZZ) that is 0 mod p is infinity.  `in` and `out` are multiples of 16

@@ -601,6 +601,10 @@ int tracker_batch_combined(const uint8_t* trackers, const uint8_t* k_comms, cons
 //      3 m results, k_tracker_prove_rows, the verifier's tape on launch_transcript_batch, k_tracker_response;
 //   4. 128 m + 5 m bytes come back; the buffers that held k, b and the XYZZ results are overwritten.
 // A member whose transcript comes back with a status (256 rejected draws) is generated by the single path on the host.
+// CURDLE_TRACKER_PROVE_CONSTANT_TIME (the _ex entry points; d_table is then the generator's fixed-base table) changes
+// step 3 alone: launch_fbase_mul_ct over k | b (2 m scalars, XYZZ) and launch_g1_normalize put kG and A, launch_g1_mul_ct
+// over the decoded rG records (every second record) and b puts B, as affine records where the pairs' points would lie,
+// and launch_g1_compress encodes the 3 m of them as kCompressAffine; k_tracker_prove_pairs and the chain do not run.
 std::atomic<unsigned long long> g_tp_stat[2];  // members generated on the device | handed to the host single path
 
 struct ProvePass {
@@ -611,7 +615,7 @@ struct ProvePass {
 };
 
 int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders,
-                   curdle_rand* rand, uint8_t* proofs_out, int* results) {
+                   curdle_rand* rand, const void* d_table, uint8_t* proofs_out, int* results) {
   static const TrackerTape T;
   Slot& A = P.A;
   const hipStream_t sa = P.sa;
@@ -678,10 +682,17 @@ int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, cons
   }
   G1Affine gen;
   g1_generator(gen);
-  HIP_TRY(launch_tracker_prove_pairs(d_dec, gen, (uint32_t)m, d_pairs, d_sc, sa));
   P.W.note_device(d_xyzz, 576 * m);
-  HIP_TRY(launch_scalar_mul_batch(d_pairs, d_sc, 0, nullptr, (uint32_t)(3 * m), d_xyzz, sa));
-  HIP_TRY(launch_g1_compress(d_xyzz, kCompressXyzz, (uint32_t)(3 * m), d_comp, sa));
+  if (d_table) {  // kG | A | B as affine records at d_pairs: nothing unnormalised is made of b and rG
+    HIP_TRY(launch_fbase_mul_ct(d_table, d_sc, nullptr, (uint32_t)(2 * m), d_xyzz, sa));
+    HIP_TRY(launch_g1_normalize(d_xyzz, kNormalizeXyzz, (uint32_t)(2 * m), d_pairs, sa, nullptr));
+    HIP_TRY(launch_g1_mul_ct(d_dec, 2, d_sc + 32 * m, 0, (uint32_t)m, d_pairs + 192 * m, sa));
+    HIP_TRY(launch_g1_compress(d_pairs, kCompressAffine, (uint32_t)(3 * m), d_comp, sa));
+  } else {
+    HIP_TRY(launch_tracker_prove_pairs(d_dec, gen, (uint32_t)m, d_pairs, d_sc, sa));
+    HIP_TRY(launch_scalar_mul_batch(d_pairs, d_sc, 0, nullptr, (uint32_t)(3 * m), d_xyzz, sa));
+    HIP_TRY(launch_g1_compress(d_xyzz, kCompressXyzz, (uint32_t)(3 * m), d_comp, sa));
+  }
   HIP_TRY(launch_tracker_prove_rows(d_trk, d_comp, d_tape + T.gen_off, (uint32_t)m, d_rows, sa));
   TranscriptArgs ta = {};
   ta.ctl = reinterpret_cast<const curdle::transcript::TapeCtl*>(d_tape);
@@ -730,16 +741,25 @@ int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, cons
   }
   g_tp_stat[0].fetch_add(m - handed, std::memory_order_relaxed);
   g_tp_stat[1].fetch_add(handed, std::memory_order_relaxed);
+  if (d_table) {  // a completed pass: one launch of each constant-time kernel
+    count_fbase_ct_pass(2 * m);
+    count_g1_mul_ct_pass(m);
+  }
   return CURDLE_OK;
 }
 
 // The whole call; exactly one of blinders / rand is given.
 int tracker_prove_batch(const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders, curdle_rand* rand, size_t k,
-                        uint8_t* proofs_out, int* results) {
+                        unsigned flags, uint8_t* proofs_out, int* results) {
   int rc = CURDLE_OK;
+  void* d_table = nullptr;
+  bool table_held = false;
   if (!trackers || !ks || (!blinders && !rand) || !proofs_out || !results) {
     rc = fail(CURDLE_EINVAL, "null argument");
+  } else if ((flags & CURDLE_TRACKER_PROVE_CONSTANT_TIME) && (rc = generator_table_acquire(cur(), &d_table))) {
+    // no device, or the table could not be made: rc says which
   } else {
+    table_held = d_table != nullptr;
     Ctx& cx = cur();
     SlotHold H(cx, true, nullptr);
     Slot* B = H.try_second();  // a second slot only lends its stream and an event to the subgroup test
@@ -748,7 +768,7 @@ int tracker_prove_batch(const uint8_t* trackers, const uint64_t* ks, const uint6
         for (size_t lo = 0; lo < k; lo += kTrackerPass) {
           ProvePass P{H.slot(), H.stream(), std::min(kTrackerPass, k - lo), WipeList(H.stream())};
           int r = prove_pass_run(cx, P, B, trackers + 96 * lo, ks + 4 * lo, blinders ? blinders + 4 * lo : nullptr, rand,
-                                 proofs_out + 128 * lo, results + lo);
+                                 d_table, proofs_out + 128 * lo, results + lo);
           if (r && B) (void)hipStreamSynchronize(B->stream);
           const int w = P.W.wipe("tracker proofs: clearing the secrets");  // nothing of k and b stays behind in the slot
           if (r || w) return r ? r : w;
@@ -757,6 +777,7 @@ int tracker_prove_batch(const uint8_t* trackers, const uint64_t* ks, const uint6
       });
     });
   }
+  if (table_held) generator_table_release();
   if (rc != CURDLE_OK) {  // "could not compute" must never read as a proof
     if (results)
       for (size_t i = 0; i < k; i++) results[i] = rc;
@@ -829,17 +850,32 @@ extern "C" int curdle_whisk_tracker_combined_scalars(const uint8_t* trackers, co
   return tracker_batch_combined(trackers, k_commitments, proofs, k, seed, false, nullptr, nullptr, &diag);
 }
 
+extern "C" int curdle_whisk_generate_tracker_proof_batch_blinders_ex(const uint8_t* trackers, const uint64_t* ks,
+                                                                     const uint64_t* blinders, size_t k, unsigned flags,
+                                                                     uint8_t* proofs_out, int* results) {
+  if (flags & ~CURDLE_TRACKER_PROVE_CONSTANT_TIME)  // refused without touching the outputs
+    return fail(CURDLE_EINVAL, "unknown flag bits 0x%x", flags & ~CURDLE_TRACKER_PROVE_CONSTANT_TIME);
+  if (k == 0) return CURDLE_OK;
+  return tracker_prove_batch(trackers, ks, blinders, nullptr, k, flags, proofs_out, results);
+}
+
+extern "C" int curdle_whisk_generate_tracker_proof_batch_ex(const uint8_t* trackers, const uint64_t* ks, curdle_rand* rand,
+                                                            size_t k, unsigned flags, uint8_t* proofs_out, int* results) {
+  if (flags & ~CURDLE_TRACKER_PROVE_CONSTANT_TIME)
+    return fail(CURDLE_EINVAL, "unknown flag bits 0x%x", flags & ~CURDLE_TRACKER_PROVE_CONSTANT_TIME);
+  if (k == 0) return CURDLE_OK;
+  return tracker_prove_batch(trackers, ks, nullptr, rand, k, flags, proofs_out, results);
+}
+
 extern "C" int curdle_whisk_generate_tracker_proof_batch_blinders(const uint8_t* trackers, const uint64_t* ks,
                                                                   const uint64_t* blinders, size_t k, uint8_t* proofs_out,
                                                                   int* results) {
-  if (k == 0) return CURDLE_OK;
-  return tracker_prove_batch(trackers, ks, blinders, nullptr, k, proofs_out, results);
+  return curdle_whisk_generate_tracker_proof_batch_blinders_ex(trackers, ks, blinders, k, 0, proofs_out, results);
 }
 
 extern "C" int curdle_whisk_generate_tracker_proof_batch(const uint8_t* trackers, const uint64_t* ks, curdle_rand* rand,
                                                          size_t k, uint8_t* proofs_out, int* results) {
-  if (k == 0) return CURDLE_OK;
-  return tracker_prove_batch(trackers, ks, nullptr, rand, k, proofs_out, results);
+  return curdle_whisk_generate_tracker_proof_batch_ex(trackers, ks, rand, k, 0, proofs_out, results);
 }
 
 extern "C" int curdle_stat_tracker_prove(unsigned long long out[2]) { return read_stats(out, g_tp_stat, 2); }

@@ -83,6 +83,8 @@ SYMBOLS = [
     "curdle_stat_fbase", "curdle_whisk_compute_tracker", "curdle_whisk_k_commitment", "curdle_whisk_compute_trackers_batch",
     "curdle_g1_fixed_base_mul_batch_ex", "curdle_g1_fixed_base_mul_batch_device_ex", "curdle_whisk_compute_trackers_batch_ex",
     "curdle_stat_fbase_ct",
+    "curdle_g1_scalar_mul_batch_ex", "curdle_g1_scalar_mul_batch_device_ex", "curdle_stat_g1_mul_ct",
+    "curdle_whisk_generate_tracker_proof_batch_blinders_ex", "curdle_whisk_generate_tracker_proof_batch_ex",
     "curdle_whisk_is_valid_tracker_proof_batch_combined", "curdle_whisk_is_valid_tracker_proof_batch_combined_device",
     "curdle_stat_tracker_combined", "curdle_whisk_tracker_combined_scalars", "curdle_tracker_combined_last_kernel_ms",
     "curdle_stat_transcript_paths", "curdle_keccak_permute_batch",
@@ -213,6 +215,10 @@ _whisk_gen_tracker_batch_blinders = _sig("curdle_whisk_generate_tracker_proof_ba
                                          _vp, _vp)
 _whisk_gen_tracker_batch = _sig("curdle_whisk_generate_tracker_proof_batch", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp)
 _stat_tracker_prove = _sig("curdle_stat_tracker_prove", C.c_int, C.POINTER(C.c_ulonglong))
+_whisk_gen_tracker_batch_blinders_ex = _sig("curdle_whisk_generate_tracker_proof_batch_blinders_ex", C.c_int, _vp, _vp, _vp,
+                                            C.c_size_t, C.c_uint, _vp, _vp)
+_whisk_gen_tracker_batch_ex = _sig("curdle_whisk_generate_tracker_proof_batch_ex", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_uint,
+                                   _vp, _vp)
 _whisk_is_own_tracker = _sig("curdle_whisk_is_own_tracker", C.c_int, _vp, _vp, C.POINTER(C.c_int))
 _whisk_find_own = _sig("curdle_whisk_find_own_trackers", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp)
 _whisk_find_own_device = _sig("curdle_whisk_find_own_trackers_device", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp)
@@ -242,6 +248,10 @@ _g1_normalize_batch = _sig("curdle_g1_normalize_batch", C.c_int, _vp, C.c_int, C
 _g1_normalize_batch_device = _sig("curdle_g1_normalize_batch_device", C.c_int, _vp, C.c_int, C.c_size_t, _vp, _vp)
 _scalar_mul_batch_device = _sig("curdle_g1_scalar_mul_batch_device", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp)
 _stat_normalize = _sig("curdle_stat_normalize", C.c_int, C.POINTER(C.c_ulonglong))
+_scalar_mul_batch_ex = _sig("curdle_g1_scalar_mul_batch_ex", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint, _vp)
+_scalar_mul_batch_device_ex = _sig("curdle_g1_scalar_mul_batch_device_ex", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t,
+                                   C.c_uint, _vp, _vp)
+_stat_g1_mul_ct = _sig("curdle_stat_g1_mul_ct", C.c_int, C.POINTER(C.c_ulonglong))
 G1_FORM_JAC, G1_FORM_XYZZ = 0, 1
 
 
@@ -1264,11 +1274,15 @@ def whisk_generate_tracker_proof(tracker: bytes, k, rand: Rand) -> bytes:
     return out.tobytes()
 
 
-def whisk_generate_tracker_proof_batch(trackers, ks, rand: "Rand" = None, blinders=None):
+TRACKER_PROVE_CONSTANT_TIME = 1                       # CURDLE_TRACKER_PROVE_CONSTANT_TIME
+
+
+def whisk_generate_tracker_proof_batch(trackers, ks, rand: "Rand" = None, blinders=None, flags=None):
     """k tracker proofs at once on the GPU (curdle_whisk_generate_tracker_proof_batch / _blinders): a list of 96-byte
     trackers and ks (k, 4), Montgomery fr limbs.  Exactly one of rand (the blinders are drawn as k single calls on it
     would draw them) and blinders (k, 4) is given.  Returns (proofs uint8[k, 128], results int32[k]): results[i] is OK,
-    or EINVAL with a zero proof where whisk_generate_tracker_proof raises CurdleError with EINVAL."""
+    or EINVAL with a zero proof where whisk_generate_tracker_proof raises CurdleError with EINVAL.  flags: None calls
+    the entry point without flags; an integer (0, TRACKER_PROVE_CONSTANT_TIME) calls the _ex one with it."""
     if (rand is None) == (blinders is None):
         raise ValueError("give either rand or blinders")
     k = len(trackers)
@@ -1279,16 +1293,23 @@ def whisk_generate_tracker_proof_batch(trackers, ks, rand: "Rand" = None, blinde
         raise ValueError("trackers and ks need the same count")
     proofs = np.zeros((k, WHISK_TRACKER_PROOF_SIZE), dtype=np.uint8)
     results = np.zeros(k, dtype=np.int32)
-    if k == 0:
+    if k == 0 and flags is None:
         return proofs, results
-    t = _bytes_arr(b"".join(trackers))
+    t = _bytes_arr(b"".join(trackers)) if k else None
+    ptrs = (_ptr(t) if k else None, _ptr(kk) if k else None)
+    outs = (_ptr(proofs) if k else None, _ptr(results) if k else None)
     if blinders is not None:
         bb = _as_u64(blinders, 4).reshape(-1, 4)
         if bb.shape[0] != k:
             raise ValueError("trackers and blinders need the same count")
-        _check(_whisk_gen_tracker_batch_blinders(_ptr(t), _ptr(kk), _ptr(bb), k, _ptr(proofs), _ptr(results)))
+        if flags is None:
+            _check(_whisk_gen_tracker_batch_blinders(*ptrs, _ptr(bb), k, *outs))
+        else:
+            _check(_whisk_gen_tracker_batch_blinders_ex(*ptrs, _ptr(bb) if k else None, k, int(flags), *outs))
+    elif flags is None:
+        _check(_whisk_gen_tracker_batch(*ptrs, rand._h, k, *outs))
     else:
-        _check(_whisk_gen_tracker_batch(_ptr(t), _ptr(kk), rand._h, k, _ptr(proofs), _ptr(results)))
+        _check(_whisk_gen_tracker_batch_ex(*ptrs, rand._h, k, int(flags), *outs))
     return proofs, results
 
 
@@ -1626,15 +1647,24 @@ def g1_check_jac_batch_device(ptr: int, n: int, subgroup_check: bool = True, str
 _scalar_mul_batch = _sig("curdle_g1_scalar_mul_batch", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp)
 
 
-def g1_scalar_mul_batch(points, scalars, addends=None) -> np.ndarray:
-    """out[i] = addends[i] + scalars[i] * points[i] on the GPU; scalars (n, 4) or one shared (4,)."""
+G1_MUL_CONSTANT_TIME = 1                              # CURDLE_G1_MUL_CONSTANT_TIME
+
+
+def g1_scalar_mul_batch(points, scalars, addends=None, flags=None) -> np.ndarray:
+    """out[i] = addends[i] + scalars[i] * points[i] on the GPU; scalars (n, 4) or one shared (4,).  flags: None calls
+    the entry point without flags; an integer (0, G1_MUL_CONSTANT_TIME) calls curdle_g1_scalar_mul_batch_ex with it
+    (the constant-time kernel takes no addends)."""
     points = _as_u64(points, 12)
     n = points.shape[0] if points.size else 0
     sc = _as_u64(scalars, 4)
     ns = (1 if sc.ndim == 1 else sc.shape[0]) if sc.size else 0
     add = _as_u64(addends, 12) if addends is not None else None
     out = np.zeros((n, 12), dtype=np.uint64)
-    _check(_scalar_mul_batch(_ptr(points), _ptr(sc), ns, _ptr(add) if add is not None else None, n, _ptr(out)))
+    if flags is None:
+        _check(_scalar_mul_batch(_ptr(points), _ptr(sc), ns, _ptr(add) if add is not None else None, n, _ptr(out)))
+    else:
+        _check(_scalar_mul_batch_ex(_ptr(points), _ptr(sc), ns, _ptr(add) if add is not None else None, n, int(flags),
+                                    _ptr(out)))
     return out
 
 
@@ -1681,11 +1711,23 @@ def g1_normalize_batch_device(ptr: int, form: int, n: int, out_ptr: int, stream=
 
 
 def g1_scalar_mul_batch_device(d_points: int, d_scalars: int, n_scalars: int, d_addends: int, n: int, d_out: int,
-                               stream=None) -> None:
+                               stream=None, flags=None) -> None:
     """g1_scalar_mul_batch with everything resident (curdle_g1_scalar_mul_batch_device): d_out[i] = d_addends[i] +
-    d_scalars[i or 0] * d_points[i] as gnark affine records; d_addends may be 0, d_out may be d_points or d_addends."""
-    _check(_scalar_mul_batch_device(d_points or None, d_scalars or None, n_scalars, d_addends or None, n, d_out or None,
-                                    stream or None))
+    d_scalars[i or 0] * d_points[i] as gnark affine records; d_addends may be 0, d_out may be d_points or d_addends.
+    flags: as in g1_scalar_mul_batch (curdle_g1_scalar_mul_batch_device_ex; with G1_MUL_CONSTANT_TIME d_addends is 0)."""
+    if flags is None:
+        _check(_scalar_mul_batch_device(d_points or None, d_scalars or None, n_scalars, d_addends or None, n, d_out or None,
+                                        stream or None))
+    else:
+        _check(_scalar_mul_batch_device_ex(d_points or None, d_scalars or None, n_scalars, d_addends or None, n, int(flags),
+                                           d_out or None, stream or None))
+
+
+def stat_g1_mul_ct() -> dict:
+    """Scalars multiplied by the constant-time variable-base kernel and its launches since the library was loaded."""
+    out = (C.c_ulonglong * 2)()
+    _check(_stat_g1_mul_ct(out))
+    return {"scalars": int(out[0]), "launches": int(out[1])}
 
 
 def stat_normalize() -> dict:

@@ -499,7 +499,8 @@ int curdle_whisk_generate_tracker_proof(const uint8_t tracker[CURDLE_WHISK_TRACK
  * SECRETS.  ks and blinders are secrets.  The device buffers and the pinned staging that held them, and the
  * unnormalised results of the scalar multiplications, are overwritten (on the stream that used them) before the call
  * returns on every path.  The scalar-multiplication chain BRANCHES ON SCALAR BITS, as the host path and gnark's
- * ScalarMultiplication do: its running time depends on k and b. */
+ * ScalarMultiplication do: its running time depends on k and b.  CURDLE_TRACKER_PROVE_CONSTANT_TIME on the _ex forms
+ * below puts constant-time kernels in the chain's place. */
 int curdle_whisk_generate_tracker_proof_batch_blinders(const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders,
                                                        size_t k, uint8_t* proofs_out, int* results);
 /* The same, drawing the blinders from rand exactly as k successive single calls on that rand would: the single call
@@ -511,6 +512,35 @@ int curdle_whisk_generate_tracker_proof_batch(const uint8_t* trackers, const uin
 /* Diagnostics: members of generated batches since the library was loaded, out[0] generated on the device, out[1]
  * handed to the host single path after a non-zero transcript status. */
 int curdle_stat_tracker_prove(unsigned long long out[2]);
+/* The two generators above with a flags word.  flags = 0 IS the call above: same kernels, same counters (the calls
+ * above pass 0).  A bit that is not defined here: CURDLE_EINVAL before anything else is looked at, copied or launched,
+ * also with k = 0, and WITHOUT touching proofs_out or results.  Everything else -- passes, k = 0, null pointers,
+ * CURDLE_ENODEV, results, zeroed members, the wipes, the output byte for byte -- is as described above.
+ *
+ * CURDLE_TRACKER_PROVE_CONSTANT_TIME changes the three scalar multiplications of a pass and nothing else: kG = k G and
+ * A = b G run through k_fbase_mul_ct over the generator's resident table (CURDLE_FBASE_CONSTANT_TIME's kernel, with
+ * that flag's promise and its normalisation), B = b rG through k_g1_mul_ct over the decoded rG records
+ * (CURDLE_G1_MUL_CONSTANT_TIME's kernel, below), and the 3 m results are encoded from AFFINE records, which inverts
+ * nothing.  The GLV chain and the kernel that lays out its pairs do not run.  Decoding, transcript rows, the batched
+ * Merlin kernel, s = b - c k, the hand-back of a member with a transcript status, results and wipes are unchanged.  A
+ * flagged pass of m members moves curdle_stat_fbase_ct[0] by 2 m and curdle_stat_g1_mul_ct[0] by m, one launch each,
+ * and neither curdle_stat_fbase[0..1] nor curdle_stat_normalize.
+ * WHAT THE FLAG PROMISES: the instruction stream (every branch, every exec mask beyond the end-of-array guard, every
+ * loop count) and the address stream (every load and store address) of k_fbase_mul_ct, k_g1_mul_ct and
+ * k_tracker_response -- the three kernels that read ks or blinders -- are independent of the values of ks and
+ * blinders.  The host only copies ks and blinders (into the pinned staging and the device buffer that are wiped on the
+ * way out) and never looks at them.  What follows those kernels works on kG, A, B, the challenge and s, which are the
+ * call's public output.
+ * WHAT IT DOES NOT PROMISE: anything about data-dependent power draw and clock behaviour of the chip, which is not
+ * addressed; and nothing about the default path, whose warning above stays true.
+ * OUTSIDE THE PROMISE: the host's draw of the blinders in the rand form (curdle_rand_get_fr, one per decodable member),
+ * and the member handed to the host single path after CURDLE_TRANSCRIPT_MAX_TRIES rejected draws (probability
+ * 0.547^256), whose multiplications are the host's. */
+#define CURDLE_TRACKER_PROVE_CONSTANT_TIME 1u
+int curdle_whisk_generate_tracker_proof_batch_blinders_ex(const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders,
+                                                          size_t k, unsigned flags, uint8_t* proofs_out, int* results);
+int curdle_whisk_generate_tracker_proof_batch_ex(const uint8_t* trackers, const uint64_t* ks, curdle_rand* rand, size_t k,
+                                                 unsigned flags, uint8_t* proofs_out, int* results);
 /* Which trackers does a key own?  A tracker is (rG, krG) with krG = k rG (computeTracker, whisk_test.go:98-104); a
  * client that did not make the tracker learns whether it is its own by evaluating k rG == krG.
  * The single form, host only, no device needed: *owned = 1 iff k rG and krG are the same group element, infinity a
@@ -907,9 +937,46 @@ int curdle_g1_normalize_batch_device(const void* d_points, int form, size_t n, v
  * to curdle_msm_g1_device as bases.  `stream`, completion and the pointer rule (every device pointer a multiple of
  * 16) are those of curdle_g1_normalize_batch_device; n > 2^24 or n_scalars neither n nor 1: CURDLE_EINVAL before any
  * device work.  Like curdle_g1_scalar_mul_batch it is NOT constant time in the scalars (the chain branches on their
- * bits), and the workspace that held the unnormalised results is not wiped. */
+ * bits), and the workspace that held the unnormalised results is not wiped: for secret scalars there is
+ * CURDLE_G1_MUL_CONSTANT_TIME on the _ex forms below. */
 int curdle_g1_scalar_mul_batch_device(const void* d_points, const void* d_scalars, size_t n_scalars,
                                       const void* d_addends, size_t n, void* d_out_affine, void* stream);
+/* curdle_g1_scalar_mul_batch and curdle_g1_scalar_mul_batch_device with a flags word.  flags = 0 IS the call without
+ * flags: same kernel, same counters, same bytes.  A bit that is not defined here: CURDLE_EINVAL before anything else
+ * is looked at, copied or launched, also with n = 0.
+ *
+ * CURDLE_G1_MUL_CONSTANT_TIME: out[i] = scalars[i or 0] * points[i] by a second kernel (csrc/g1_mul_ct_kernels.hip), one
+ * lane per pair: the 255 bits of the scalar MSB first, every step one doubling and ALWAYS one mixed addition of the
+ * lane's own point, the new accumulator taken by mask selection; the lane then normalises its own result (one
+ * fixed-exponent inversion) and writes the canonical affine record through a mask, so k = 0 or an infinity point
+ * stores twelve zero words and NOTHING unnormalised leaves the kernel: no normalisation kernel runs.  The records are
+ * bit for bit those of the call without flags.
+ * addends must be NULL: CURDLE_EINVAL before any device work otherwise (a final addition addend + k P can be
+ * exceptional depending on the secret).  n_scalars is n or 1.  d_out_affine may be d_points: a lane reads its record
+ * before it writes it.  Limits (n <= 2^24), the pointer rule, n = 0, CURDLE_ENODEV and the stream semantics are those
+ * of the calls without flags.  The call works in passes of at most CURDLE_G1_MUL_CT_PASS pairs (knob; 1,048,576;
+ * rounded down to a multiple of 256, at least 256), one launch each.  The host form stages the scalars through pinned
+ * memory and a device buffer and overwrites both, on the stream that used them, before it returns on every path; the
+ * device form reads the caller's scalars where they are and copies nothing.  points must be in the prime-order
+ * subgroup for the result to be right and are NOT checked (the kernel's exactness argument needs the subgroup); any
+ * other input gives an unspecified record and no fault.
+ * WHAT THE FLAG PROMISES: the kernel's instruction stream (every branch, every exec mask beyond the end-of-array guard,
+ * every loop count) and its address stream (every load and store address) are independent of the values of scalars;
+ * they depend on n, n_scalars, the pointers and on which points are infinity, which is public.  The host only copies
+ * scalars and never looks at them.
+ * WHAT IT DOES NOT PROMISE: anything about data-dependent power draw and clock behaviour of the chip (a multiplier fed
+ * zeros draws less), which is not addressed; and nothing about the default path, whose warning above stays true.
+ * Cost: 255 doublings, 255 additions and an inversion in ONE lane per pair, a chain of about 5,300 dependent field
+ * products: measured 5.3 ms for any n up to 65,536 and 1.3 times the default call from there (profiles/r24_g1_mul_ct.json). */
+#define CURDLE_G1_MUL_CONSTANT_TIME 1u
+int curdle_g1_scalar_mul_batch_ex(const uint64_t* points, const uint64_t* scalars, size_t n_scalars,
+                                  const uint64_t* addends, size_t n, unsigned flags, uint64_t* out_affine);
+int curdle_g1_scalar_mul_batch_device_ex(const void* d_points, const void* d_scalars, size_t n_scalars,
+                                         const void* d_addends, size_t n, unsigned flags, void* d_out_affine, void* stream);
+/* out[0] scalars multiplied by k_g1_mul_ct, out[1] its launches; completed passes only.  A pass under
+ * CURDLE_G1_MUL_CONSTANT_TIME (or the rG column of a pass under CURDLE_TRACKER_PROVE_CONSTANT_TIME) counts here and
+ * NOT in curdle_stat_normalize: it runs no normalisation kernel. */
+int curdle_stat_g1_mul_ct(unsigned long long out[2]);
 /* Diagnostics: out[0] points normalised on the device since the library was loaded, out[1] inversion groups run
  * (one Fermat inversion each; at most one per 64 points of a launch). */
 int curdle_stat_normalize(unsigned long long out[2]);
