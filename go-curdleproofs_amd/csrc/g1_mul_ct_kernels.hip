@@ -3,26 +3,9 @@
 // (group_kernels.hip), whose GLV chain branches on scalar bits, in the manner of k_fbase_mul_ct (fbase_ct_kernels.hip).
 // P_i: a gnark G1Affine record, canonical Montgomery limbs, (0, 0) = infinity; k_i: a Montgomery fr.Element below r.
 //
-// The walk.  The 255 bits of k (r < 2^255) MSB first, a rolled loop.  Every step does ONE XYZZ doubling (d28::dbl,
-// which has no exceptional arm) and ALWAYS one mixed addition of the lane's own affine point (the main path of
-// d28::madd without its three exceptional arms, as madd_select of fbase_ct_kernels.hip); the new accumulator is taken
-// by mask selection:
-//     bit == 0                      keep the doubled accumulator            (the sum is discarded)
-//     bit == 1, nothing added yet   the affine point, zz = zzz = one
-//     otherwise                     the sum
-// "Nothing added yet" is a mask word (started |= bit), never a test of zz: until the first set bit the accumulator is
-// not a point at all (it starts as four ones and is doubled as field arithmetic), and k = 0 is `started == 0` at the
-// end.  The next bit is bit 255 of the eight scalar words, which are shifted left every step: no register is indexed
-// by the step.
-//
-// Exactness.  P has prime order r and 0 < k < r.  Before a step the accumulator is m P with m the prefix of k read so
-// far (0 < m once started).  The doubling gives 2m P, never infinity for m != 0 because r is odd and 2m < 2r.  A KEPT
-// sum is 2m P + P with the bit set: 2m >= 2 != 1, so the addend is not the accumulator, and 2m + 1 <= k < r, so it is
-// not its negative.  A DISCARDED sum may be nonsense: it is integer arithmetic inside the limb bounds of fp28.h (x, y
-// < 10p, zz, zzz < 2p, the affine operand below 2p) and traps nothing.  k = r - 1 is where that happens with real
-// points: its last bit is 0, the prefix is (r - 1) / 2 and the last step discards exactly (r - 1) P + P = -P + P.
-// tests/g1_mul_ct_model.py asserts the argument on every kept sum of every case the tests use and reports the
-// exceptional discarded ones.  A point outside the prime-order subgroup gives an unspecified record and no fault.
+// The walk, its exactness argument (P of prime order r, 0 < k < r; k = r - 1 is where a DISCARDED sum is exceptional
+// with real points) and the rule of what may depend on a scalar are at the top of g1_walk_ct.h, with the walk's
+// helpers: k_tracker_own_ct (tracker_own_ct_kernels.hip) walks the same way.
 //
 // The exit.  The lane normalises its own result: ONE Fermat inversion of zz zzz on the fixed exponent chain of
 // invert28.h (the exponent is p - 2 for every lane: its window switch is wave-uniform and public), x = X zzz / (zz zzz),
@@ -32,19 +15,11 @@
 // behind it sees a value that depends on the path the bits chose (projective coordinates do), which is what the
 // in-lane inversion, about a tenth of the walk's products, pays for.  Whether P is infinity is public.
 //
-// What may depend on a scalar: data operands of arithmetic and of selects written as mask arithmetic, m = 0 - (cond),
-// (a & m) | (b & ~m).  What may not: a branch condition, an exec mask (beyond i >= n), a load, store or LDS address, a
-// readfirstlane, a loop trip count.
-//
 // One shared scalar.  The scalar of lane i is read at scalars + 32 i scalar_stride with scalar_stride a kernel
 // ARGUMENT (1, or 0 for one scalar shared by the launch): the address is made of the lane index, so the load is a
 // per-lane vector load in both cases and the scalar lives in VGPRs.  A wave-uniform load would put it in SGPRs, where
 // the compiler is free to turn a select into a scalar branch on the bit; there is ONE instantiation of the kernel and
 // DESIGN.md section 0 (round 24) reads its assembly.  point_stride (in records) lets a caller walk every second record.
-//
-// The multiply-accumulate trap: no product may see a limb the compiler knows.  The
-// initial accumulator is constants, so the bit loop stays rolled (#pragma unroll 1); the constant `one` reaches
-// products only through a select under a lane mask.
 //
 // Not built: a fixed-window form (15 projective multiples per lane are 3,360 bytes: workspace traffic or LDS for about
 // 1.4x fewer operations), GLV (its chains take exceptional additions: tests/glv_chain_model.py) and a lane-quad form.
@@ -53,66 +28,12 @@
 #include <hip/hip_runtime.h>
 
 #include "msm_kernels_common.h"
+#include "g1_walk_ct.h"
 #include "invert28.h"
 
 namespace curdle {
 
 namespace {
-__device__ __forceinline__ void load_fr_lane(Fr& f, const uint4* src) {
-  const uint4 lo = src[0], hi = src[1];
-  f.l[0] = lo.x; f.l[1] = lo.y; f.l[2] = lo.z; f.l[3] = lo.w;
-  f.l[4] = hi.x; f.l[5] = hi.y; f.l[6] = hi.z; f.l[7] = hi.w;
-}
-// bit 255 of k, and k << 1: every bit is read from the top of word 7, so no register is indexed by the step
-__device__ __forceinline__ u32 next_bit_msb(Fr& k) {
-  const u32 b = k.l[7] >> 31;
-#pragma unroll
-  for (int j = 7; j > 0; j--) k.l[j] = (k.l[j] << 1) | (k.l[j - 1] >> 31);
-  k.l[0] <<= 1;
-  return b;
-}
-// r = sum ? a : (first ? b : c); sum, first and ~(sum | first) are disjoint masks
-__device__ __forceinline__ void select3(F28& r, u32 sum, const F28& a, u32 first, const F28& b, const F28& c) {
-  const u32 keep = ~(sum | first);
-#pragma unroll
-  for (int i = 0; i < d28::N; i++) r.l[i] = (a.l[i] & sum) | (b.l[i] & first) | (c.l[i] & keep);
-}
-// r = sum ? a : (first ? one : r)
-__device__ __forceinline__ void select3_one(F28& r, u32 sum, const F28& a, u32 first) {
-  const u32 keep = ~(sum | first);
-#pragma unroll
-  for (int i = 0; i < d28::N; i++) r.l[i] = (a.l[i] & sum) | (d28::kOne(i) & first) | (r.l[i] & keep);
-}
-
-// One step's addition.  acc: x < 10p, y < 6p, zz, zzz < 2p, limbs normalised (what d28::dbl leaves); (x2, y2) affine
-// below 2p, normalised.  bit = 0 - (the scalar's bit), started = all ones once something was added.  d28::madd's main
-// path (EFD madd-2008-s) with madd's bounds (X3 < 10p, Y3 < 2p, products < 2p), then the selection described at the top.
-__device__ __forceinline__ void madd_bit(X28& acc, const F28& x2, const F28& y2, u32 bit, u32 started) {
-  using namespace d28;
-  const u32 sum = bit & started, first = bit & ~started;
-  F28 pp, r, t, q, ppp, p;
-  mul_inl(p, x2, acc.zz);
-  sub_raw<16>(p, p, acc.x);  // P = U2 - X1 < 18p
-  mul_inl(r, y2, acc.zzz);
-  sub_raw<16>(r, r, acc.y);  // R = S2 - Y1 < 18p
-  sqr_inl(pp, p);            // PP < 2p
-  mul_inl(ppp, p, pp);       // PPP
-  mul_inl(q, acc.x, pp);     // Q
-  mul_inl(p, acc.zz, pp);
-  select3_one(acc.zz, sum, p, first);
-  mul_inl(p, acc.zzz, ppp);
-  select3_one(acc.zzz, sum, p, first);
-  sqr_inl(t, r);
-  x3_fused(t, t, ppp, q);    // X3 = R^2 - PPP - 2Q < 10p
-  sub_raw<16>(q, q, t);      // Q - X3 < 18p
-  F28 ny, z;
-  set_zero(z);
-  sub_raw<16>(ny, z, acc.y); // 16p - Y1 (Y1 < 6p)
-  mul2_inl(p, r, q, ny, ppp);  // Y3 = R (Q - X3) - Y1 PPP  (mod p), < 2p
-  select3(acc.x, sum, t, first, x2, acc.x);
-  select3(acc.y, sum, p, first, y2, acc.y);
-}
-
 // d28::to_gnark with a masked canonical step (to_gnark_msm_ct of fbase_ct_kernels.hip with the plain constant): the
 // choice between t and t - p is a select on the borrow, never an exec mask.
 __device__ __forceinline__ void to_gnark_ct(u32* w, const F28& a) {

@@ -306,6 +306,13 @@ hipError_t launch_tracker_combine(const uint8_t* status, const uint8_t* sub, con
 // out[key * stride + t] = CURDLE_TRACKER_NOT_OWNED / _OWNED / _BAD (a status beyond CURDLE_DECODE_INFINITY: no chain).
 hipError_t launch_tracker_own(const void* points, const uint8_t* status, const void* keys, uint32_t t0, uint32_t cnt,
                               uint32_t key0, uint32_t nkeys, uint8_t* out, size_t stride, hipStream_t stream);
+// tracker_own_ct_kernels.hip: the same verdicts over the same arguments by the constant-time twin, one LANE per (key,
+// tracker) pair, flattened (lane g: key0 + g / tc, t0 + g % tc) so that the key's address is made of the lane index;
+// 255 double-and-always-add steps on rG and a projective equality test against krG, no inversion.  One launch covers
+// trackers [t0, t0 + tc) of keys [key0, key0 + kc), tc kc <= 2^31.  Neither the instruction stream nor the address
+// stream depends on the keys.
+hipError_t launch_tracker_own_ct(const void* points, const uint8_t* status, const void* keys, uint32_t t0, uint32_t tc,
+                                 uint32_t key0, uint32_t kc, uint8_t* out, size_t stride, hipStream_t stream);
 
 // compress_kernels.hip: n points in memory -> n x 48 bytes of gnark's compressed encoding (G1Affine.Bytes), one lane
 // per point.  form kCompressJac: gnark G1Jac, 144 bytes each (Z = 0: infinity); kCompressXyzz: G1XYZZ in gnark limbs,

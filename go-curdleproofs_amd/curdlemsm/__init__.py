@@ -78,6 +78,7 @@ SYMBOLS = [
     "curdle_g1_compress_batch", "curdle_g1_compress_batch_device",
     "curdle_whisk_generate_tracker_proof_batch_blinders", "curdle_whisk_generate_tracker_proof_batch", "curdle_stat_tracker_prove",
     "curdle_whisk_is_own_tracker", "curdle_whisk_find_own_trackers", "curdle_whisk_find_own_trackers_device", "curdle_stat_tracker_own",
+    "curdle_whisk_find_own_trackers_ex", "curdle_whisk_find_own_trackers_device_ex", "curdle_stat_tracker_own_ct",
     "curdle_g1_normalize_batch", "curdle_g1_normalize_batch_device", "curdle_g1_scalar_mul_batch_device", "curdle_stat_normalize",
     "curdle_fbase_create", "curdle_fbase_free", "curdle_g1_fixed_base_mul_batch", "curdle_g1_fixed_base_mul_batch_device",
     "curdle_stat_fbase", "curdle_whisk_compute_tracker", "curdle_whisk_k_commitment", "curdle_whisk_compute_trackers_batch",
@@ -223,6 +224,10 @@ _whisk_is_own_tracker = _sig("curdle_whisk_is_own_tracker", C.c_int, _vp, _vp, C
 _whisk_find_own = _sig("curdle_whisk_find_own_trackers", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp)
 _whisk_find_own_device = _sig("curdle_whisk_find_own_trackers_device", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp)
 _stat_tracker_own = _sig("curdle_stat_tracker_own", C.c_int, C.POINTER(C.c_ulonglong))
+_whisk_find_own_ex = _sig("curdle_whisk_find_own_trackers_ex", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint)
+_whisk_find_own_device_ex = _sig("curdle_whisk_find_own_trackers_device_ex", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp,
+                                 C.c_uint)
+_stat_tracker_own_ct = _sig("curdle_stat_tracker_own_ct", C.c_int, C.POINTER(C.c_ulonglong))
 _fbase_create = _sig("curdle_fbase_create", C.c_int, _vp, C.POINTER(_vp))
 _fbase_free = _sig("curdle_fbase_free", None, _vp)
 _fbase_mul = _sig("curdle_g1_fixed_base_mul_batch", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, _vp)
@@ -1321,6 +1326,7 @@ def stat_tracker_prove() -> dict:
 
 
 TRACKER_NOT_OWNED, TRACKER_OWNED, TRACKER_BAD, TRACKER_UNKNOWN = 0, 1, 2, 255
+TRACKER_OWN_CONSTANT_TIME = 1                         # CURDLE_TRACKER_OWN_CONSTANT_TIME
 
 
 def whisk_is_own_tracker(tracker: bytes, k) -> bool:
@@ -1334,10 +1340,11 @@ def whisk_is_own_tracker(tracker: bytes, k) -> bool:
     return bool(owned.value)
 
 
-def whisk_find_own_trackers(trackers, ks) -> np.ndarray:
+def whisk_find_own_trackers(trackers, ks, flags=None) -> np.ndarray:
     """m keys against n trackers on the GPU (curdle_whisk_find_own_trackers): a list of 96-byte trackers (or a uint8
     array of n x 96 bytes) and ks (m, 4), Montgomery fr limbs.  Returns uint8[m, n]: TRACKER_OWNED, TRACKER_NOT_OWNED,
-    or TRACKER_BAD in the whole column of a tracker with a record that does not decode."""
+    or TRACKER_BAD in the whole column of a tracker with a record that does not decode.  flags: None calls the entry
+    point without flags; an integer (0, TRACKER_OWN_CONSTANT_TIME) calls curdle_whisk_find_own_trackers_ex with it."""
     if isinstance(trackers, np.ndarray):
         t = np.ascontiguousarray(trackers, dtype=np.uint8).reshape(-1)
         if t.size % 96:
@@ -1349,21 +1356,30 @@ def whisk_find_own_trackers(trackers, ks) -> np.ndarray:
     kk = _as_u64(ks, 4).reshape(-1, 4)
     n, m = t.size // 96, len(kk)
     owned = np.full((m, n), TRACKER_UNKNOWN, dtype=np.uint8)
-    _check(_whisk_find_own(_ptr(t) if n else None, n, _ptr(kk) if m else None, m, _ptr(owned) if m * n else None))
+    args = (_ptr(t) if n else None, n, _ptr(kk) if m else None, m, _ptr(owned) if m * n else None)
+    _check(_whisk_find_own(*args) if flags is None else _whisk_find_own_ex(*args, flags))
     return owned
 
 
-def whisk_find_own_trackers_device(d_trackers: int, n: int, d_ks: int, m: int, d_owned: int, stream=None) -> None:
+def whisk_find_own_trackers_device(d_trackers: int, n: int, d_ks: int, m: int, d_owned: int, stream=None, flags=None) -> None:
     """The same over resident arrays (curdle_whisk_find_own_trackers_device): HIP device pointers to n x 96 bytes,
     m x 32 bytes (both multiples of 16) and m x n bytes; stream: a hipStream_t or None.  d_owned is complete when the
-    call returns."""
-    _check(_whisk_find_own_device(d_trackers or None, n, d_ks or None, m, d_owned or None, stream or None))
+    call returns.  flags: as in whisk_find_own_trackers (curdle_whisk_find_own_trackers_device_ex)."""
+    args = (d_trackers or None, n, d_ks or None, m, d_owned or None, stream or None)
+    _check(_whisk_find_own_device(*args) if flags is None else _whisk_find_own_device_ex(*args, flags))
 
 
 def stat_tracker_own() -> dict:
     """(key, tracker) pairs answered on the device, launches of the ownership kernel, pairs answered TRACKER_BAD."""
     out = (C.c_ulonglong * 3)()
     _check(_stat_tracker_own(out))
+    return {"pairs": int(out[0]), "launches": int(out[1]), "bad": int(out[2])}
+
+
+def stat_tracker_own_ct() -> dict:
+    """stat_tracker_own's counters for the passes under TRACKER_OWN_CONSTANT_TIME (k_tracker_own_ct)."""
+    out = (C.c_ulonglong * 3)()
+    _check(_stat_tracker_own_ct(out))
     return {"pairs": int(out[0]), "launches": int(out[1]), "bad": int(out[2])}
 
 

@@ -46,7 +46,7 @@ enum Id {
   GPU_PRELUDE,        // 1: the Whisk batch verifier takes its members' transcript preludes from curdle_transcript_batch, a chunk at a time; unset or 0: on the host
   TRACKER_DEVICE_HASH,  // the tracker batch's transcripts under CURDLE_TRACKER_HASH_DEFAULT: 1 hashed on the device, 0 on the host; unset: by the batch's size (tracker_api.hip)
   NORMALIZE_LANE_POINTS,  // k_g1_normalize: points per lane, 1 or 8 (any other value: as unset); unset: 8 beyond 65,536 points (normalize_kernels.hip)
-  TRACKER_OWN_PAIRS,      // curdle_whisk_find_own_trackers: (key, tracker) quads per launch of k_tracker_own, rounded down to whole waves of 16, at least 16; unset: 2^18 (tracker_own_api.hip)
+  TRACKER_OWN_PAIRS,      // curdle_whisk_find_own_trackers: (key, tracker) quads per launch of k_tracker_own, rounded down to whole waves of 16, at least 16; unset: 2^18 (tracker_own_api.hip).  Under CURDLE_TRACKER_OWN_CONSTANT_TIME: (key, tracker) LANES per launch of k_tracker_own_ct, rounded down to a multiple of 256, at least 256; unset: 2^18
   FBASE_PASS,             // curdle_g1_fixed_base_mul_batch, curdle_whisk_compute_trackers_batch: scalars per pass (one launch of k_fbase_mul), rounded down to a multiple of 256, at least 256; unset: 2^20 (fbase_api.hip)
   TRANSCRIPT_SHEET,       // the batched transcripts' kernel: 1 always the sheet kernel (a state spread over lanes), 0 never; unset: the library's rule, and TRANSCRIPT_LANES set means the lane kernel (choose_transcript_kernel, transcript_api.hip)
   STREAM_PLAN,            // streams of pipelined MSMs, read when the context is created: 1 wide (a tail stream per slot), 2 compact (one tail stream: four busy streams); 0 or unset: compact below 16 hardware queues (GPU_MAX_HW_QUEUES), wide from there (stream_plan, msm_plan.hip)

@@ -566,7 +566,8 @@ int curdle_whisk_is_own_tracker(const uint8_t tracker[CURDLE_WHISK_TRACKER_SIZE]
  * SECRETS.  ks are secrets.  The device buffer and the pinned staging that held them are overwritten (on the stream
  * that used them) before the call returns on every path; the kernel keeps a key and the two halves of its split in
  * registers only.  The scalar-multiplication chain BRANCHES ON KEY BITS, as the host path and gnark's
- * ScalarMultiplication do: its running time depends on the keys. */
+ * ScalarMultiplication do: its running time depends on the keys.  CURDLE_TRACKER_OWN_CONSTANT_TIME on the _ex forms below
+ * puts a constant-time kernel in the chain's place. */
 int curdle_whisk_find_own_trackers(const uint8_t* trackers, size_t n, const uint64_t* ks, size_t m, uint8_t* owned);
 /* The same over arrays resident in device memory: HIP device pointers to n x 96 bytes, m x 32 bytes and m x n bytes.
  * d_trackers and d_ks must be multiples of 16 (CURDLE_EINVAL otherwise); d_owned may have any alignment.  `stream` is
@@ -579,6 +580,43 @@ int curdle_whisk_find_own_trackers_device(const void* d_trackers, size_t n, cons
  * the ownership kernel, out[2] those of the pairs that were answered CURDLE_TRACKER_BAD without a chain.  The counters
  * move when a tracker pass has completed: a pass that fails midway leaves its pairs and launches uncounted. */
 int curdle_stat_tracker_own(unsigned long long out[3]);
+/* The two searches above with a flags word.  flags = 0 IS the call above: same kernel, same counters, same bytes (the
+ * calls above pass 0).  A bit that is not defined here: CURDLE_EINVAL before anything else is looked at, copied or
+ * launched, also with n = 0 or m = 0; the host form then fills `owned` with CURDLE_TRACKER_UNKNOWN like every negative
+ * return.  Everything else -- the limits, n = 0 or m = 0, null pointers, the pointer rule, CURDLE_ENODEV, the one decode
+ * per pass of 131,072 trackers, the slot, the staging and the wipes of the keys' copies, the stream semantics, the
+ * verdict bytes byte for byte -- is as described above.
+ *
+ * CURDLE_TRACKER_OWN_CONSTANT_TIME changes the ownership kernel and nothing else: a second kernel
+ * (csrc/tracker_own_ct_kernels.hip, k_tracker_own_ct), one LANE per (key, tracker) pair: the 255 bits of the key MSB
+ * first, every step one doubling and ALWAYS one mixed addition of the lane's rG, the new accumulator taken by mask
+ * selection (the walk of CURDLE_G1_MUL_CONSTANT_TIME's kernel, below), and at the end a projective equality test
+ * against krG -- x ZZ = X and y ZZZ = Y mod p, decided by mask arithmetic -- in the place of an inversion.  The GLV chain
+ * does not run.  Launches hold at most CURDLE_TRACKER_OWN_PAIRS lanes (the same knob; 262,144; rounded down to a
+ * multiple of 256, at least 256): tc = min(trackers of the pass, that) trackers of max(1, that / tc) keys each, back to
+ * back on the one stream.  A flagged pass moves curdle_stat_tracker_own_ct and never curdle_stat_tracker_own,
+ * curdle_stat_g1_mul_ct or curdle_stat_normalize.
+ * WHAT THE FLAG PROMISES: the instruction stream (every branch, every exec mask, every loop count) and the address
+ * stream (every load and store address) of the ownership kernel are independent of the values of ks.  The host only
+ * copies ks (into the pinned staging and the device buffer that are wiped on the way out; the _device form reads them
+ * where they are) and never looks at them.
+ * WHAT IS PUBLIC, and does shape both streams: n, m, the pointers, the trackers, their decode statuses (a record that
+ * does not decode is answered CURDLE_TRACKER_BAD without a chain), which of rG and krG are infinity -- and the verdicts,
+ * which are the call's output: the byte stored for a pair depends on the key, its address does not.
+ * WHAT IT DOES NOT PROMISE: anything about data-dependent power draw and clock behaviour of the chip, which is not
+ * addressed; and nothing about the default path, whose warning above stays true.
+ * OUTSIDE THE PROMISE: the host single call curdle_whisk_is_own_tracker, whose multiplication is the host's and branches
+ * on key bits.
+ * The flag is NOT a default and nothing is routed through it automatically.  Cost: one lane walks about 4,850
+ * dependent field products, about 5 ms however few pairs a launch has. */
+#define CURDLE_TRACKER_OWN_CONSTANT_TIME 1u
+int curdle_whisk_find_own_trackers_ex(const uint8_t* trackers, size_t n, const uint64_t* ks, size_t m, uint8_t* owned,
+                                      unsigned flags);
+int curdle_whisk_find_own_trackers_device_ex(const void* d_trackers, size_t n, const void* d_ks, size_t m,
+                                             void* d_owned, void* stream, unsigned flags);
+/* curdle_stat_tracker_own's three counters for the passes under CURDLE_TRACKER_OWN_CONSTANT_TIME: out[0] pairs, out[1]
+ * launches of k_tracker_own_ct, out[2] the pairs answered CURDLE_TRACKER_BAD; completed passes only. */
+int curdle_stat_tracker_own_ct(unsigned long long out[3]);
 /* ------------------------------------------------------------------------- *
  * Fixed-base scalar multiplication in G1 ON THE GPU; Whisk trackers in bulk
  *   The first step of the tracker life cycle: tracker = (r G, k r G), commitment = k G (computeTracker and getKComm,
