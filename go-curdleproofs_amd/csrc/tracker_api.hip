@@ -3,7 +3,8 @@
 // second half of the file, of the batched generator curdle_whisk_generate_tracker_proof_batch (_blinders), k calls of
 // GenerateWhiskTrackerProof (:149-175) in one, on the same tape and slots (tracker_prove_kernels.hip).
 //
-// Two forms.  HOST-HASHED (tracker_pass), per pass of at most kTrackerPass members, on the calling thread's context:
+// Three forms of the check, each per pass of at most kTrackerPass members, on the calling thread's context.
+// HOST-HASHED (tracker_pass):
 //   1. the 5 k records (rG, krG, kG, A, B per member) go up once; the square roots (launch_g1_decompress) run on
 //      the held slot's stream and the subgroup test from the same bytes (launch_g1_subgroup_from_bytes) beside it
 //      on a second slot's stream when one is free -- the two chains overlap, as in the two-step decoding;
@@ -16,12 +17,16 @@
 // DEVICE-HASHED (tracker_pass_device): from bytes to verdicts with no host arithmetic and no host thread.  The three
 // arrays go up as they are (or are read where the caller keeps them: _device) behind the constant tape of the
 // transcript program; k_tracker_gather writes the records, the transcript rows and S / skip; the transcript kernel
-// (launch_transcript_batch, the tape compiled once per process) and the subgroup test run on the second slot's stream
-// beside the square roots; k_tracker_challenge puts c next to s, k_tracker_check runs as above.  Tape, start state,
-// rows and challenges live in the held slot's buffers: the transcript context (TrCtx) and its lock are not touched.
-// COMBINED (tracker_pass_combined, curdle_whisk_is_valid_tracker_proof_batch_combined / _device): the device-hashed
-// pass up to k_tracker_challenge, then ONE randomly weighted MSM over the decoded records settles the pass;
+// (launch_transcript_batch over tracker_tape(), compiled once per process) and the subgroup test run on the second
+// slot's stream beside the square roots; k_tracker_challenge puts c next to s -- all of that is hashed_prelude --
+// and k_tracker_check runs as above.  Tape, start state, rows and challenges live in the held slot's buffers: the
+// transcript context (TrCtx) and its lock are not touched.
+// COMBINED (tracker_pass_combined, curdle_whisk_is_valid_tracker_proof_batch_combined / _device): hashed_prelude into
+// buffers the MSM leaves alone, then ONE randomly weighted MSM over the decoded records settles the pass;
 // k_tracker_check runs only when the sum is not infinity (the section before the generation half has the layout).
+// What the forms share stands once: decode_beside (the square roots with the side chain beside them on the lent
+// stream, or behind them when no slot was lent) and join_side, tracker_tape / tape_args, bad_records and settle_pass
+// (a member's answer from the bytes that came back; hand_back where its transcript gave up), fill_results.
 // No stream is made here and no device memory is allocated once the slots' buffers have grown to the batch.  Both
 // halves hold their slot, and the second one when one is free, with a SlotHold (api_helpers.h).
 #include "api_helpers.h"
@@ -117,69 +122,6 @@ void hash_members(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t
   if (err) std::rethrow_exception(err);
 }
 
-// One pass: members [0, m) of the given arrays, verdicts into results.  A holds the buffers and runs the square
-// roots and the check; B (may be null) runs the subgroup test.
-int tracker_pass(Ctx& cx, Slot& A, Slot* B, const uint8_t* trackers, const uint8_t* k_comms, const uint8_t* proofs,
-                 size_t m, int* results) {
-  const size_t nrec = 5 * m;
-  int r;
-  if ((r = ensure(A.scalars, nrec * kRec))) return r;   // compressed records
-  if ((r = ensure(A.points, nrec * 96))) return r;      // decoded records
-  if ((r = ensure(A.counts, 2 * nrec + m))) return r;   // statuses | subgroup verdicts | member verdicts
-  if ((r = ensure(A.digits, 64 * m + m))) return r;     // s, c | skip
-  if ((r = ensure_pinned(A, 0, nrec * kRec + 65 * m))) return r;
-  if ((r = ensure_pinned(A, 1, 2 * nrec + m))) return r;
-  uint8_t* h_in = static_cast<uint8_t*>(A.h_stage[0]);
-  uint8_t* h_sc = h_in + nrec * kRec;
-  uint8_t* h_out = static_cast<uint8_t*>(A.h_stage[1]);
-  uint8_t* d_rec = static_cast<uint8_t*>(A.scalars.p);
-  uint8_t* d_status = static_cast<uint8_t*>(A.counts.p);
-  uint8_t* d_sub = d_status + nrec;
-  uint8_t* d_out = d_sub + nrec;
-  uint8_t* d_sc = static_cast<uint8_t*>(A.digits.p);
-  for (size_t i = 0; i < m; i++) {
-    uint8_t* d = h_in + 5 * kRec * i;
-    memcpy(d, trackers + 96 * i, 2 * kRec);          // rG, krG
-    memcpy(d + 2 * kRec, k_comms + kRec * i, kRec);  // kG
-    memcpy(d + 3 * kRec, proofs + 128 * i, 2 * kRec);  // A, B
-  }
-  HIP_TRY(hipMemcpyAsync(d_rec, h_in, nrec * kRec, hipMemcpyHostToDevice, A.stream));
-  if (B) {
-    HIP_TRY(hipEventRecord(A.pre_done, A.stream));
-    HIP_TRY(hipStreamWaitEvent(B->stream, A.pre_done, 0));
-    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, B->stream));
-    HIP_TRY(hipEventRecord(B->acc_done, B->stream));
-  }
-  HIP_TRY(launch_g1_decompress(d_rec, (uint32_t)nrec, 0, (uint32_t*)A.points.p, d_status, A.stream));
-  if (!B) HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, A.stream));
-  // the host's share, while the GPU decodes
-  hash_members(trackers, k_comms, proofs, m, reinterpret_cast<uint32_t*>(h_sc), h_sc + 64 * m);
-  HIP_TRY(hipMemcpyAsync(d_sc, h_sc, 65 * m, hipMemcpyHostToDevice, A.stream));
-  G1Affine gen;
-  g1_generator(gen);
-  HIP_TRY(launch_tracker_check(A.points.p, d_status, d_sc, d_sc + 64 * m, gen, (uint32_t)m, d_out, A.stream));
-  if (B) HIP_TRY(hipStreamWaitEvent(A.stream, B->acc_done, 0));
-  HIP_TRY(hipMemcpyAsync(h_out, d_status, 2 * nrec + m, hipMemcpyDeviceToHost, A.stream));
-  HIP_TRY(hipStreamSynchronize(A.stream));
-  const uint8_t* st = h_out;
-  const uint8_t* sub = h_out + nrec;
-  const uint8_t* verdict = h_out + 2 * nrec;
-  const uint8_t* skip = h_sc + 64 * m;
-  for (size_t i = 0; i < m; i++) {
-    bool err = skip[i] != 0;
-    for (size_t j = 5 * i; j < 5 * i + 5; j++) err |= st[j] > CURDLE_DECODE_INFINITY || (st[j] == CURDLE_DECODE_OK && !sub[j]);
-    if (err) {
-      results[i] = CURDLE_EINVAL;
-    } else if (verdict[i] == kTrackerAccept || verdict[i] == kTrackerReject) {
-      results[i] = verdict[i];
-    } else {
-      return fail(CURDLE_EHIP, "tracker check: member %zu of a pass has no verdict", i);
-    }
-  }
-  g_tk_stat[1].fetch_add(m, std::memory_order_relaxed);
-  return CURDLE_OK;
-}
-
 // The constant part of the device-hashed form, compiled once per process: the tape of
 //   Transcript("whisk_opening_proof"); AppendPoints("tracker_opening_proof", kG g1Gen krG rG A B);
 //   GetAndAppendChallenge("tracker_opening_proof_challenge")                                  (whisk.go:15-17, 131-134)
@@ -219,41 +161,16 @@ struct TrackerTape {
 };
 constexpr size_t kRowBytes = 8 * (2 + 6 * kRec / 8);  // transcript::TapeRowWords(288) words
 
-// One device-hashed pass.  `resident`: the three arrays are device pointers, read where they are.  `sa` is the
-// stream the pass runs on: the held slot's, or the caller's (then B is null and everything runs on that stream).
-int tracker_pass_device(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8_t* trackers, const uint8_t* k_comms,
-                        const uint8_t* proofs, bool resident, size_t m, int* results) {
+// The one instance.  Every caller stands inside guarded(...), where a tape that did not compile becomes CURDLE_EHIP.
+const TrackerTape& tracker_tape() {
   static const TrackerTape T;
-  const size_t nrec = 5 * m, tape_bytes = T.bytes.size(), raw_bytes = resident ? 0 : 272 * m;
-  int r;
-  if ((r = ensure(A.scalars, nrec * kRec))) return r;     // compressed records
-  if ((r = ensure(A.points, nrec * 96))) return r;        // decoded records
-  if ((r = ensure(A.counts, 2 * nrec + 2 * m))) return r;  // statuses | subgroup verdicts | member verdicts | transcript statuses
-  if ((r = ensure(A.digits, 64 * m + m))) return r;       // s, c | skip
-  if ((r = ensure(A.sorted, tape_bytes + raw_bytes + (kRowBytes + 32) * m))) return r;  // tape | the arrays | rows | challenges
-  if ((r = ensure_pinned(A, 0, tape_bytes + raw_bytes))) return r;
-  if ((r = ensure_pinned(A, 1, 2 * nrec + 2 * m))) return r;
-  uint8_t* h_in = static_cast<uint8_t*>(A.h_stage[0]);
-  uint8_t* h_out = static_cast<uint8_t*>(A.h_stage[1]);
-  uint8_t* d_tape = static_cast<uint8_t*>(A.sorted.p);
-  uint8_t* d_raw = d_tape + tape_bytes;
-  uint8_t* d_rows = d_raw + raw_bytes;
-  uint8_t* d_ch = d_rows + kRowBytes * m;
-  uint8_t* d_rec = static_cast<uint8_t*>(A.scalars.p);
-  uint8_t* d_status = static_cast<uint8_t*>(A.counts.p);
-  uint8_t* d_sub = d_status + nrec;
-  uint8_t* d_out = d_sub + nrec;
-  uint8_t* d_trst = d_out + m;
-  uint8_t* d_sc = static_cast<uint8_t*>(A.digits.p);
-  memcpy(h_in, T.bytes.data(), tape_bytes);
-  if (!resident) {  // as the caller laid them out: nothing is repacked
-    memcpy(h_in + tape_bytes, trackers, 96 * m);
-    memcpy(h_in + tape_bytes + 96 * m, k_comms, kRec * m);
-    memcpy(h_in + tape_bytes + 144 * m, proofs, 128 * m);
-    trackers = d_raw, k_comms = d_raw + 96 * m, proofs = d_raw + 144 * m;
-  }
-  HIP_TRY(hipMemcpyAsync(d_tape, h_in, tape_bytes + raw_bytes, hipMemcpyHostToDevice, sa));
-  HIP_TRY(launch_tracker_gather(trackers, k_comms, proofs, d_tape + T.gen_off, (uint32_t)m, d_rec, d_rows, d_sc, d_sc + 64 * m, sa));
+  return T;
+}
+
+// The transcript launch of an m-member pass over the copy of the tape at d_tape: rows in, challenges and one status
+// byte per member out.
+TranscriptArgs tape_args(const uint8_t* d_tape, const uint8_t* d_rows, uint8_t* d_ch, uint8_t* d_trst, size_t m) {
+  const TrackerTape& T = tracker_tape();
   TranscriptArgs ta = {};
   ta.ctl = reinterpret_cast<const curdle::transcript::TapeCtl*>(d_tape);
   ta.pool = reinterpret_cast<const curdle::transcript::TapeBlock*>(d_tape + T.pool_off);
@@ -269,55 +186,233 @@ int tracker_pass_device(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8_t
   ta.k = (uint32_t)m;
   choose_transcript_kernel(m, &ta);
   ta.n_challenges = 1;
-  if (B) {  // transcripts, then the subgroup test, beside the square roots
+  return ta;
+}
+
+// The side chain of a pass on stream st: the transcripts, where the pass hashes on the device (ta), then the subgroup
+// test of the nrec records from their bytes.  On a lent slot's stream (B) that slot's events mark the two ends.
+int side_chain(const TranscriptArgs* ta, const uint8_t* d_rec, size_t nrec, uint8_t* d_sub, Slot* B, hipStream_t st) {
+  if (ta) {
+    HIP_TRY(launch_transcript_batch(*ta, st));
+    if (B) HIP_TRY(hipEventRecord(B->pre_done, st));
+  }
+  HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, st));
+  if (B) HIP_TRY(hipEventRecord(B->acc_done, st));
+  return CURDLE_OK;
+}
+
+// The square roots of nrec records on sa with the side chain beside them: on the lent slot's stream, behind what sa
+// holds so far -- or, when no slot was lent (B null), on sa behind the square roots.  With transcripts in the chain, sa
+// waits for them (B->pre_done) before it goes on; the subgroup verdicts are waited for where the pass first reads
+// them (join_side), which is a different place in every form and is the overlap the forms were measured with.
+int decode_beside(Slot& A, Slot* B, hipStream_t sa, const uint8_t* d_rec, size_t nrec, void* d_points, uint8_t* d_status,
+                  uint8_t* d_sub, const TranscriptArgs* ta) {
+  int r;
+  if (B) {
     HIP_TRY(hipEventRecord(A.pre_done, sa));
     HIP_TRY(hipStreamWaitEvent(B->stream, A.pre_done, 0));
-    HIP_TRY(launch_transcript_batch(ta, B->stream));
-    HIP_TRY(hipEventRecord(B->pre_done, B->stream));
-    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, B->stream));
-    HIP_TRY(hipEventRecord(B->acc_done, B->stream));
+    if ((r = side_chain(ta, d_rec, nrec, d_sub, B, B->stream))) return r;
   }
-  HIP_TRY(launch_g1_decompress(d_rec, (uint32_t)nrec, 0, (uint32_t*)A.points.p, d_status, sa));
-  if (B) {
-    HIP_TRY(hipStreamWaitEvent(sa, B->pre_done, 0));
-  } else {
-    HIP_TRY(launch_transcript_batch(ta, sa));
-    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, sa));
-  }
-  HIP_TRY(launch_tracker_challenge(d_ch, d_trst, (uint32_t)m, d_sc, d_sc + 64 * m, sa));
-  G1Affine gen;
-  g1_generator(gen);
-  HIP_TRY(launch_tracker_check(A.points.p, d_status, d_sc, d_sc + 64 * m, gen, (uint32_t)m, d_out, sa));
+  HIP_TRY(launch_g1_decompress(d_rec, (uint32_t)nrec, 0, (uint32_t*)d_points, d_status, sa));
+  if (!B) return side_chain(ta, d_rec, nrec, d_sub, nullptr, sa);
+  if (ta) HIP_TRY(hipStreamWaitEvent(sa, B->pre_done, 0));
+  return CURDLE_OK;
+}
+
+int join_side(Slot* B, hipStream_t sa) {
   if (B) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));
-  HIP_TRY(hipMemcpyAsync(h_out, d_status, 2 * nrec + 2 * m, hipMemcpyDeviceToHost, sa));
-  HIP_TRY(hipStreamSynchronize(sa));
-  const uint8_t* st = h_out;
-  const uint8_t* sub = h_out + nrec;
-  const uint8_t* verdict = h_out + 2 * nrec;
-  const uint8_t* trst = verdict + m;
-  unsigned long long handed_back = 0;
+  return CURDLE_OK;
+}
+
+// Where a device-hashed pass of m members keeps what its prelude reads and writes: device memory, but for h_raw.
+struct HashedPass {
+  size_t m;
+  uint8_t *tape, *raw, *rows, *ch;  // the constant tape | the three arrays (host form) | transcript rows | challenges
+  uint8_t* h_raw;                   // the three arrays as staged on the host; null in the resident form
+  uint8_t* rec;                     // the 5 m compressed records ...
+  void* points;                     // ... and decoded
+  uint8_t *status, *sub, *trst;     // decoding statuses | subgroup verdicts (5 m each) | transcript statuses (m)
+  uint8_t *sc, *skip;               // s, c (64 m) | S was not canonical (m)
+};
+
+// A record that does not decode, or decodes to a point outside the subgroup, among `count` records from `first`.
+bool bad_records(const uint8_t* st, const uint8_t* sub, size_t first, size_t count) {
+  bool bad = false;
+  for (size_t j = first; j < first + count; j++) bad |= st[j] > CURDLE_DECODE_INFINITY || (st[j] == CURDLE_DECODE_OK && !sub[j]);
+  return bad;
+}
+
+// Member i's transcript gave up (256 rejected draws, 0.547^256): the single call settles the member on the host, from
+// the arrays as they were staged.  The resident form has no host copy and refuses.
+int hand_back(const HashedPass& L, size_t i, int* result) {
+  if (!L.h_raw) return fail(CURDLE_EHIP, "tracker check: member %zu of a pass drew no canonical challenge", i);
+  int ok = 0;
+  const int rc = curdle_whisk_is_valid_tracker_proof(L.h_raw + 96 * i, L.h_raw + 96 * L.m + kRec * i,
+                                                     L.h_raw + 144 * L.m + 128 * i, &ok);
+  *result = rc ? rc : ok;
+  return CURDLE_OK;
+}
+
+// What came back from a pass of m members, on the host.
+struct PassBytes {
+  const uint8_t *st, *sub;  // decoding statuses and subgroup verdicts of the 5 m records
+  const uint8_t* verdict;   // k_tracker_check's; not read where the sum settled the pass
+  const uint8_t* skip;      // S >= r; null where verdict == kTrackerError says so (the plain device-hashed form)
+  const uint8_t* trst;      // transcript statuses; null where the host hashed
+  bool settled;             // the combined form's sum was the point at infinity: who is not an error is accepted
+};
+struct Settled {
+  unsigned long long handed_back = 0, errors = 0;
+};
+
+// Every member's answer.  L: the staging of a device-hashed pass (for hand_back), null where the host hashed.
+int settle_pass(const PassBytes& V, const HashedPass* L, size_t m, int* results, Settled* n) {
+  int r;
   for (size_t i = 0; i < m; i++) {
-    if (trst[i]) {  // 256 rejected draws (0.547^256): the single call settles the member on the host
-      if (resident) return fail(CURDLE_EHIP, "tracker check: member %zu of a pass drew no canonical challenge", i);
-      int ok = 0;
-      const int rc = curdle_whisk_is_valid_tracker_proof(h_in + tape_bytes + 96 * i, h_in + tape_bytes + 96 * m + kRec * i,
-                                                         h_in + tape_bytes + 144 * m + 128 * i, &ok);
-      results[i] = rc ? rc : ok;
-      handed_back++;
+    if (V.trst && V.trst[i]) {
+      if ((r = hand_back(*L, i, &results[i]))) return r;
+      n->handed_back++;
       continue;
     }
-    bool err = verdict[i] == kTrackerError;  // S >= r, or a record that does not decode
-    for (size_t j = 5 * i; j < 5 * i + 5; j++) err |= st[j] > CURDLE_DECODE_INFINITY || (st[j] == CURDLE_DECODE_OK && !sub[j]);
-    if (err) {
+    const bool s_bad = V.skip ? V.skip[i] != 0 : V.verdict[i] == kTrackerError;  // the latter: or a record that does not decode
+    if (s_bad || bad_records(V.st, V.sub, 5 * i, 5)) {
       results[i] = CURDLE_EINVAL;
-    } else if (verdict[i] == kTrackerAccept || verdict[i] == kTrackerReject) {
-      results[i] = verdict[i];
+      n->errors++;
+    } else if (V.settled) {
+      results[i] = kTrackerAccept;
+    } else if (V.verdict[i] == kTrackerAccept || V.verdict[i] == kTrackerReject) {
+      results[i] = V.verdict[i];
     } else {
       return fail(CURDLE_EHIP, "tracker check: member %zu of a pass has no verdict", i);
     }
   }
-  g_tk_stat[0].fetch_add(m - handed_back, std::memory_order_relaxed);
-  g_tk_stat[2].fetch_add(handed_back, std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+// "could not compute" must never read as a verdict, or as a proof's result
+void fill_results(int* results, size_t k, int rc) {
+  if (results)
+    for (size_t i = 0; i < k; i++) results[i] = rc;
+}
+
+// One host-hashed pass: members [0, m) of the given arrays, verdicts into results.  A holds the buffers and runs the
+// square roots and the check; B (may be null) lends its stream to the subgroup test.
+int tracker_pass(Slot& A, Slot* B, const uint8_t* trackers, const uint8_t* k_comms, const uint8_t* proofs, size_t m,
+                 int* results) {
+  const size_t nrec = 5 * m;
+  int r;
+  if ((r = ensure(A.scalars, nrec * kRec))) return r;   // compressed records
+  if ((r = ensure(A.points, nrec * 96))) return r;      // decoded records
+  if ((r = ensure(A.counts, 2 * nrec + m))) return r;   // statuses | subgroup verdicts | member verdicts
+  if ((r = ensure(A.digits, 64 * m + m))) return r;     // s, c | skip
+  if ((r = ensure_pinned(A, 0, nrec * kRec + 65 * m))) return r;
+  if ((r = ensure_pinned(A, 1, 2 * nrec + m))) return r;
+  uint8_t* h_in = static_cast<uint8_t*>(A.h_stage[0]);
+  uint8_t* h_sc = h_in + nrec * kRec;
+  uint8_t* h_out = static_cast<uint8_t*>(A.h_stage[1]);
+  uint8_t* d_rec = static_cast<uint8_t*>(A.scalars.p);
+  uint8_t* d_status = static_cast<uint8_t*>(A.counts.p);
+  uint8_t* d_sub = d_status + nrec;
+  uint8_t* d_out = d_sub + nrec;
+  uint8_t* d_sc = static_cast<uint8_t*>(A.digits.p);
+  for (size_t i = 0; i < m; i++) {
+    uint8_t* d = h_in + 5 * kRec * i;
+    memcpy(d, trackers + 96 * i, 2 * kRec);          // rG, krG
+    memcpy(d + 2 * kRec, k_comms + kRec * i, kRec);  // kG
+    memcpy(d + 3 * kRec, proofs + 128 * i, 2 * kRec);  // A, B
+  }
+  HIP_TRY(hipMemcpyAsync(d_rec, h_in, nrec * kRec, hipMemcpyHostToDevice, A.stream));
+  if ((r = decode_beside(A, B, A.stream, d_rec, nrec, A.points.p, d_status, d_sub, nullptr))) return r;
+  // the host's share, while the GPU decodes
+  hash_members(trackers, k_comms, proofs, m, reinterpret_cast<uint32_t*>(h_sc), h_sc + 64 * m);
+  HIP_TRY(hipMemcpyAsync(d_sc, h_sc, 65 * m, hipMemcpyHostToDevice, A.stream));
+  G1Affine gen;
+  g1_generator(gen);
+  HIP_TRY(launch_tracker_check(A.points.p, d_status, d_sc, d_sc + 64 * m, gen, (uint32_t)m, d_out, A.stream));
+  if ((r = join_side(B, A.stream))) return r;  // behind the check, which does not read the subgroup verdicts
+  HIP_TRY(hipMemcpyAsync(h_out, d_status, 2 * nrec + m, hipMemcpyDeviceToHost, A.stream));
+  HIP_TRY(hipStreamSynchronize(A.stream));
+  const PassBytes V{h_out, h_out + nrec, h_out + 2 * nrec, h_sc + 64 * m, nullptr, false};
+  Settled n;
+  if ((r = settle_pass(V, nullptr, m, results, &n))) return r;
+  g_tk_stat[1].fetch_add(m, std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+// tape | the three arrays | rows | challenges in the held slot's `sorted`, tape | the arrays in its first pinned
+// stage: the same in both device-hashed forms.  Grows the two and fills L's share of them.
+int hashed_staging(Slot& A, bool resident, size_t m, HashedPass* L) {
+  const size_t tape_bytes = tracker_tape().bytes.size(), raw_bytes = resident ? 0 : 272 * m;
+  int r;
+  if ((r = ensure(A.sorted, tape_bytes + raw_bytes + (kRowBytes + 32) * m))) return r;
+  if ((r = ensure_pinned(A, 0, tape_bytes + raw_bytes))) return r;
+  L->m = m;
+  L->tape = static_cast<uint8_t*>(A.sorted.p);
+  L->raw = L->tape + tape_bytes;
+  L->rows = L->raw + raw_bytes;
+  L->ch = L->rows + kRowBytes * m;
+  L->h_raw = resident ? nullptr : static_cast<uint8_t*>(A.h_stage[0]) + tape_bytes;
+  return CURDLE_OK;
+}
+
+// The device-hashed prelude on sa, from the three arrays (host memory, or resident: L.h_raw null) to s, c and skip:
+// upload, gather, the transcripts and the subgroup test beside the square roots, the challenge.  The subgroup verdicts
+// are not waited for: join_side, where the form first reads them.
+int hashed_prelude(Slot& A, Slot* B, hipStream_t sa, const HashedPass& L, const uint8_t* trackers, const uint8_t* k_comms,
+                   const uint8_t* proofs) {
+  const TrackerTape& T = tracker_tape();
+  const size_t m = L.m, tape_bytes = T.bytes.size();
+  int r;
+  memcpy(A.h_stage[0], T.bytes.data(), tape_bytes);
+  if (L.h_raw) {  // as the caller laid them out: nothing is repacked
+    memcpy(L.h_raw, trackers, 96 * m);
+    memcpy(L.h_raw + 96 * m, k_comms, kRec * m);
+    memcpy(L.h_raw + 144 * m, proofs, 128 * m);
+    trackers = L.raw, k_comms = L.raw + 96 * m, proofs = L.raw + 144 * m;
+  }
+  HIP_TRY(hipMemcpyAsync(L.tape, A.h_stage[0], tape_bytes + (L.h_raw ? 272 * m : 0), hipMemcpyHostToDevice, sa));
+  HIP_TRY(launch_tracker_gather(trackers, k_comms, proofs, L.tape + T.gen_off, (uint32_t)m, L.rec, L.rows, L.sc, L.skip, sa));
+  const TranscriptArgs ta = tape_args(L.tape, L.rows, L.ch, L.trst, m);
+  if ((r = decode_beside(A, B, sa, L.rec, 5 * m, L.points, L.status, L.sub, &ta))) return r;
+  HIP_TRY(launch_tracker_challenge(L.ch, L.trst, (uint32_t)m, L.sc, L.skip, sa));
+  return CURDLE_OK;
+}
+
+// One device-hashed pass.  `resident`: the three arrays are device pointers, read where they are.  `sa` is the
+// stream the pass runs on: the held slot's, or the caller's (then B is null and everything runs on that stream).
+int tracker_pass_device(Slot& A, Slot* B, hipStream_t sa, const uint8_t* trackers, const uint8_t* k_comms,
+                        const uint8_t* proofs, bool resident, size_t m, int* results) {
+  const size_t nrec = 5 * m;
+  HashedPass L;
+  int r;
+  if ((r = ensure(A.scalars, nrec * kRec))) return r;     // compressed records
+  if ((r = ensure(A.points, nrec * 96))) return r;        // decoded records
+  if ((r = ensure(A.counts, 2 * nrec + 2 * m))) return r;  // statuses | subgroup verdicts | member verdicts | transcript statuses
+  if ((r = ensure(A.digits, 64 * m + m))) return r;       // s, c | skip
+  if ((r = hashed_staging(A, resident, m, &L))) return r;
+  if ((r = ensure_pinned(A, 1, 2 * nrec + 2 * m))) return r;
+  uint8_t* h_out = static_cast<uint8_t*>(A.h_stage[1]);
+  L.rec = static_cast<uint8_t*>(A.scalars.p);
+  L.points = A.points.p;
+  L.status = static_cast<uint8_t*>(A.counts.p);
+  L.sub = L.status + nrec;
+  uint8_t* d_out = L.sub + nrec;
+  L.trst = d_out + m;
+  L.sc = static_cast<uint8_t*>(A.digits.p);
+  L.skip = L.sc + 64 * m;
+  if ((r = hashed_prelude(A, B, sa, L, trackers, k_comms, proofs))) return r;
+  G1Affine gen;
+  g1_generator(gen);
+  HIP_TRY(launch_tracker_check(L.points, L.status, L.sc, L.skip, gen, (uint32_t)m, d_out, sa));
+  if ((r = join_side(B, sa))) return r;  // behind the check, which does not read the subgroup verdicts
+  HIP_TRY(hipMemcpyAsync(h_out, L.status, 2 * nrec + 2 * m, hipMemcpyDeviceToHost, sa));
+  HIP_TRY(hipStreamSynchronize(sa));
+  // skip stays on the device: k_tracker_check's kTrackerError covers S >= r
+  const PassBytes V{h_out, h_out + nrec, h_out + 2 * nrec, nullptr, h_out + 2 * nrec + m, false};
+  Settled n;
+  if ((r = settle_pass(V, &L, m, results, &n))) return r;
+  g_tk_stat[0].fetch_add(m - n.handed_back, std::memory_order_relaxed);
+  g_tk_stat[2].fetch_add(n.handed_back, std::memory_order_relaxed);
   return CURDLE_OK;
 }
 
@@ -347,9 +442,9 @@ int tracker_batch(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t
         const hipStream_t sa = H.stream();
         for (size_t lo = 0; lo < k; lo += kTrackerPass) {
           const size_t m = std::min(kTrackerPass, k - lo);
-          const int r = hash_device ? tracker_pass_device(cx, A, B, sa, trackers + 96 * lo, k_comms + kRec * lo,
+          const int r = hash_device ? tracker_pass_device(A, B, sa, trackers + 96 * lo, k_comms + kRec * lo,
                                                           proofs + 128 * lo, resident, m, results + lo)
-                                    : tracker_pass(cx, A, B, trackers + 96 * lo, k_comms + kRec * lo, proofs + 128 * lo, m,
+                                    : tracker_pass(A, B, trackers + 96 * lo, k_comms + kRec * lo, proofs + 128 * lo, m,
                                                    results + lo);
           if (r) return r;
         }
@@ -357,15 +452,14 @@ int tracker_batch(const uint8_t* trackers, const uint8_t* k_comms, const uint8_t
       });
     });
   }
-  if (rc != CURDLE_OK && results)  // "could not compute" must never read as a verdict
-    for (size_t i = 0; i < k; i++) results[i] = rc;
+  if (rc != CURDLE_OK) fill_results(results, k, rc);
   return rc;
 }
 
 // --- the combined form: a pass settled by ONE randomly weighted MSM -----------------------------------------------------
 //
-// curdle_whisk_is_valid_tracker_proof_batch_combined (_device).  A pass starts as tracker_pass_device does (upload,
-// gather, transcripts and subgroup test beside the square roots, k_tracker_challenge); then k_tracker_combine
+// curdle_whisk_is_valid_tracker_proof_batch_combined (_device).  A pass starts with hashed_prelude (upload, gather,
+// transcripts and subgroup test beside the square roots, k_tracker_challenge); then k_tracker_combine
 // (tracker_combine_kernels.hip) writes the 5 m scalars of the weighted sum of the members' 2 m equations and one
 // (G, partial sum) pair per block, and the library's own MSM (enqueue_slot / finish_slot) runs over the decoded records
 // on the pass's stream.  Infinity: every member that was not excluded is accepted.  Anything else: k_tracker_check
@@ -402,74 +496,30 @@ struct CombineDiag {  // curdle_whisk_tracker_combined_scalars: the pass stops b
 int tracker_pass_combined(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8_t* trackers, const uint8_t* k_comms,
                           const uint8_t* proofs, bool resident, size_t m, size_t first, const TrackerCombineSeed& seed,
                           int* results, const CombineDiag* diag) {
-  static const TrackerTape T;
-  const size_t nrec = 5 * m, tape_bytes = T.bytes.size(), raw_bytes = resident ? 0 : 272 * m;
+  const size_t nrec = 5 * m;
   const size_t nblk = tracker_combine_blocks((uint32_t)m), npairs = nrec + nblk;
   const size_t bytes_out = 2 * nrec + 3 * m;          // statuses | subgroup verdicts | member verdicts | transcript statuses | skip
   const size_t sc_off = (bytes_out + 15) / 16 * 16;  // s, c behind them
+  HashedPass L;
   int r;
   if ((r = ensure(A.scalars, nrec * kRec + npairs * 32))) return r;
   if ((r = ensure(A.points, npairs * 96))) return r;
   if ((r = ensure(A.tracker_keep, sc_off + 64 * m))) return r;
-  if ((r = ensure(A.sorted, tape_bytes + raw_bytes + (kRowBytes + 32) * m))) return r;  // tape | the arrays | rows | challenges
-  if ((r = ensure_pinned(A, 0, tape_bytes + raw_bytes))) return r;
+  if ((r = hashed_staging(A, resident, m, &L))) return r;
   if ((r = ensure_pinned(A, 1, bytes_out + (diag ? nblk * 32 : 0)))) return r;
-  uint8_t* h_in = static_cast<uint8_t*>(A.h_stage[0]);
   uint8_t* h_out = static_cast<uint8_t*>(A.h_stage[1]);
-  uint8_t* d_tape = static_cast<uint8_t*>(A.sorted.p);
-  uint8_t* d_raw = d_tape + tape_bytes;
-  uint8_t* d_rows = d_raw + raw_bytes;
-  uint8_t* d_ch = d_rows + kRowBytes * m;
-  uint8_t* d_rec = static_cast<uint8_t*>(A.scalars.p);
-  uint8_t* d_msm_sc = d_rec + nrec * kRec;
-  uint8_t* d_status = static_cast<uint8_t*>(A.tracker_keep.p);
-  uint8_t* d_sub = d_status + nrec;
-  uint8_t* d_out = d_sub + nrec;
-  uint8_t* d_trst = d_out + m;
-  uint8_t* d_skip = d_trst + m;
-  uint8_t* d_sc = d_status + sc_off;
-  memcpy(h_in, T.bytes.data(), tape_bytes);
-  if (!resident) {
-    memcpy(h_in + tape_bytes, trackers, 96 * m);
-    memcpy(h_in + tape_bytes + 96 * m, k_comms, kRec * m);
-    memcpy(h_in + tape_bytes + 144 * m, proofs, 128 * m);
-    trackers = d_raw, k_comms = d_raw + 96 * m, proofs = d_raw + 144 * m;
-  }
-  HIP_TRY(hipMemcpyAsync(d_tape, h_in, tape_bytes + raw_bytes, hipMemcpyHostToDevice, sa));
-  HIP_TRY(launch_tracker_gather(trackers, k_comms, proofs, d_tape + T.gen_off, (uint32_t)m, d_rec, d_rows, d_sc, d_skip, sa));
-  TranscriptArgs ta = {};
-  ta.ctl = reinterpret_cast<const curdle::transcript::TapeCtl*>(d_tape);
-  ta.pool = reinterpret_cast<const curdle::transcript::TapeBlock*>(d_tape + T.pool_off);
-  ta.data = reinterpret_cast<const uint64_t*>(d_rows);
-  ta.init = reinterpret_cast<const uint64_t*>(d_tape + T.init_off);
-  ta.challenges = reinterpret_cast<uint64_t*>(d_ch);
-  ta.states = nullptr;
-  ta.status = d_trst;
-  ta.tail = T.tail;
-  ta.n_ctl = T.n_ctl;
-  ta.row_words = (uint32_t)(kRowBytes / 8);
-  ta.init_stride = 0;
-  ta.k = (uint32_t)m;
-  choose_transcript_kernel(m, &ta);
-  ta.n_challenges = 1;
-  if (B) {  // transcripts, then the subgroup test, beside the square roots
-    HIP_TRY(hipEventRecord(A.pre_done, sa));
-    HIP_TRY(hipStreamWaitEvent(B->stream, A.pre_done, 0));
-    HIP_TRY(launch_transcript_batch(ta, B->stream));
-    HIP_TRY(hipEventRecord(B->pre_done, B->stream));
-    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, B->stream));
-    HIP_TRY(hipEventRecord(B->acc_done, B->stream));
-  }
-  HIP_TRY(launch_g1_decompress(d_rec, (uint32_t)nrec, 0, (uint32_t*)A.points.p, d_status, sa));
-  if (B) {
-    HIP_TRY(hipStreamWaitEvent(sa, B->pre_done, 0));
-  } else {
-    HIP_TRY(launch_transcript_batch(ta, sa));
-    HIP_TRY(launch_g1_subgroup_from_bytes(d_rec, (uint32_t)nrec, d_sub, sa));
-  }
-  HIP_TRY(launch_tracker_challenge(d_ch, d_trst, (uint32_t)m, d_sc, d_skip, sa));
+  L.rec = static_cast<uint8_t*>(A.scalars.p);
+  uint8_t* d_msm_sc = L.rec + nrec * kRec;
+  L.points = A.points.p;
+  L.status = static_cast<uint8_t*>(A.tracker_keep.p);
+  L.sub = L.status + nrec;
+  uint8_t* d_out = L.sub + nrec;
+  L.trst = d_out + m;
+  L.skip = L.trst + m;
+  L.sc = L.status + sc_off;
+  if ((r = hashed_prelude(A, B, sa, L, trackers, k_comms, proofs))) return r;
   // the scalars wait for the subgroup verdicts too: a record outside the subgroup must get a zero scalar
-  if (B) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));
+  if ((r = join_side(B, sa))) return r;
   G1Affine gen;
   g1_generator(gen);
   if (diag) {  // the diagnostic brackets the kernel with the slot's profiling events (made on their first use, like Prof's)
@@ -479,7 +529,7 @@ int tracker_pass_combined(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8
     }
     HIP_TRY(hipEventRecord(A.ev[0], sa));
   }
-  HIP_TRY(launch_tracker_combine(d_status, d_sub, d_sc, d_skip, seed, (uint64_t)first, (uint32_t)m, gen, d_msm_sc, A.points.p, sa));
+  HIP_TRY(launch_tracker_combine(L.status, L.sub, L.sc, L.skip, seed, (uint64_t)first, (uint32_t)m, gen, d_msm_sc, L.points, sa));
   if (diag) {
     HIP_TRY(hipEventRecord(A.ev[1], sa));
     HIP_TRY(hipMemcpyAsync(diag->scalars_out, d_msm_sc, nrec * 32, hipMemcpyDeviceToHost, sa));
@@ -499,7 +549,7 @@ int tracker_pass_combined(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8
     return CURDLE_OK;
   }
   // everything but the chains' verdicts comes back behind the scalars, ahead of the MSM: finish_slot's wait covers it
-  HIP_TRY(hipMemcpyAsync(h_out, d_status, bytes_out, hipMemcpyDeviceToHost, sa));
+  HIP_TRY(hipMemcpyAsync(h_out, L.status, bytes_out, hipMemcpyDeviceToHost, sa));
   const uint32_t off[2] = {0, (uint32_t)npairs};
   MsmCall call{off};
   MsmInputs in;
@@ -510,43 +560,17 @@ int tracker_pass_combined(Ctx& cx, Slot& A, Slot* B, hipStream_t sa, const uint8
   if ((r = finish_slot(cx, A, sum))) return r;
   bool settled = true;  // Z = 0: the weighted sum is the point at infinity
   for (int w = 12; w < 18; w++) settled &= sum[w] == 0;
-  const uint8_t* st = h_out;
-  const uint8_t* sub = h_out + nrec;
-  const uint8_t* verdict = h_out + 2 * nrec;
-  const uint8_t* trst = verdict + m;
-  const uint8_t* skip = trst + m;
   if (!settled) {
-    HIP_TRY(launch_tracker_check(A.points.p, d_status, d_sc, d_skip, gen, (uint32_t)m, d_out, sa));
+    HIP_TRY(launch_tracker_check(L.points, L.status, L.sc, L.skip, gen, (uint32_t)m, d_out, sa));
     HIP_TRY(hipMemcpyAsync(h_out + 2 * nrec, d_out, m, hipMemcpyDeviceToHost, sa));
     HIP_TRY(hipStreamSynchronize(sa));
   }
-  unsigned long long accepted = 0, excluded = 0;
-  for (size_t i = 0; i < m; i++) {
-    if (trst[i]) {  // 256 rejected draws (0.547^256): the single call settles the member on the host
-      if (resident) return fail(CURDLE_EHIP, "tracker check: member %zu of a pass drew no canonical challenge", i);
-      int ok = 0;
-      const int rc = curdle_whisk_is_valid_tracker_proof(h_in + tape_bytes + 96 * i, h_in + tape_bytes + 96 * m + kRec * i,
-                                                         h_in + tape_bytes + 144 * m + 128 * i, &ok);
-      results[i] = rc ? rc : ok;
-      excluded++;
-      continue;
-    }
-    bool err = skip[i] != 0;  // S >= r
-    for (size_t j = 5 * i; j < 5 * i + 5; j++) err |= st[j] > CURDLE_DECODE_INFINITY || (st[j] == CURDLE_DECODE_OK && !sub[j]);
-    if (err) {
-      results[i] = CURDLE_EINVAL;
-      excluded++;
-    } else if (settled) {
-      results[i] = kTrackerAccept;
-      accepted++;
-    } else if (verdict[i] == kTrackerAccept || verdict[i] == kTrackerReject) {
-      results[i] = verdict[i];
-    } else {
-      return fail(CURDLE_EHIP, "tracker check: member %zu of a pass has no verdict", i);
-    }
-  }
+  const PassBytes V{h_out, h_out + nrec, h_out + 2 * nrec, h_out + 2 * nrec + 2 * m, h_out + 2 * nrec + m, settled};
+  Settled n;
+  if ((r = settle_pass(V, &L, m, results, &n))) return r;
+  const unsigned long long excluded = n.handed_back + n.errors;  // from the sum: handed to the host, or refused
   g_tc_stat[settled ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
-  g_tc_stat[2].fetch_add(accepted, std::memory_order_relaxed);
+  g_tc_stat[2].fetch_add(settled ? m - excluded : 0, std::memory_order_relaxed);
   g_tc_stat[3].fetch_add(excluded, std::memory_order_relaxed);
   return CURDLE_OK;
 }
@@ -583,8 +607,7 @@ int tracker_batch_combined(const uint8_t* trackers, const uint8_t* k_comms, cons
       });
     }, SlotHold::kDrainSlot);
   }
-  if (rc != CURDLE_OK && results)  // "could not compute" must never read as a verdict
-    for (size_t i = 0; i < k; i++) results[i] = rc;
+  if (rc != CURDLE_OK) fill_results(results, k, rc);
   return rc;
 }
 
@@ -614,9 +637,9 @@ struct ProvePass {
   WipeList W;  // the places a secret was written to in this pass; wiped on every way out of the pass
 };
 
-int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders,
+int prove_pass_run(ProvePass& P, Slot* B, const uint8_t* trackers, const uint64_t* ks, const uint64_t* blinders,
                    curdle_rand* rand, const void* d_table, uint8_t* proofs_out, int* results) {
-  static const TrackerTape T;
+  const TrackerTape& T = tracker_tape();
   Slot& A = P.A;
   const hipStream_t sa = P.sa;
   const size_t m = P.m, nrec = 2 * m, tape_bytes = T.bytes.size();
@@ -655,27 +678,14 @@ int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, cons
   HIP_TRY(hipMemcpyAsync(d_tape, h_in, tape_bytes + 96 * m, hipMemcpyHostToDevice, sa));
   P.W.note_device(d_sc, 96 * m);
   HIP_TRY(hipMemcpyAsync(d_sc, h_k, (blinders ? 64 : 32) * m, hipMemcpyHostToDevice, sa));
-  if (B) {
-    HIP_TRY(hipEventRecord(A.pre_done, sa));
-    HIP_TRY(hipStreamWaitEvent(B->stream, A.pre_done, 0));
-    HIP_TRY(launch_g1_subgroup_from_bytes(d_trk, (uint32_t)nrec, d_sub, B->stream));
-    HIP_TRY(hipEventRecord(B->acc_done, B->stream));
-  }
-  HIP_TRY(launch_g1_decompress(d_trk, (uint32_t)nrec, 0, (uint32_t*)d_dec, d_status, sa));
-  if (!B) HIP_TRY(launch_g1_subgroup_from_bytes(d_trk, (uint32_t)nrec, d_sub, sa));
-  auto bad_member = [&](size_t i) {
-    bool bad = false;
-    for (size_t j = 2 * i; j < 2 * i + 2; j++)
-      bad |= h_st[j] > CURDLE_DECODE_INFINITY || (h_st[j] == CURDLE_DECODE_OK && !h_st[nrec + j]);
-    return bad;
-  };
-  if (!blinders) {
-    if (B) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));
+  if ((r = decode_beside(A, B, sa, d_trk, nrec, d_dec, d_status, d_sub, nullptr))) return r;
+  if (!blinders) {  // the draws need the subgroup verdicts now; with blinders they are first read by the response
+    if ((r = join_side(B, sa))) return r;
     HIP_TRY(hipMemcpyAsync(h_st, d_status, 2 * nrec, hipMemcpyDeviceToHost, sa));
     HIP_TRY(hipStreamSynchronize(sa));
     for (size_t i = 0; i < m; i++) {
       uint64_t b[4] = {0, 0, 0, 0};
-      if (!bad_member(i) && (r = curdle_rand_get_fr(rand, b))) return r;
+      if (!bad_records(h_st, h_st + nrec, 2 * i, 2) && (r = curdle_rand_get_fr(rand, b))) return r;
       memcpy(h_b + 32 * i, b, 32);
     }
     HIP_TRY(hipMemcpyAsync(d_sc + 32 * m, h_b, 32 * m, hipMemcpyHostToDevice, sa));
@@ -694,23 +704,8 @@ int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, cons
     HIP_TRY(launch_g1_compress(d_xyzz, kCompressXyzz, (uint32_t)(3 * m), d_comp, sa));
   }
   HIP_TRY(launch_tracker_prove_rows(d_trk, d_comp, d_tape + T.gen_off, (uint32_t)m, d_rows, sa));
-  TranscriptArgs ta = {};
-  ta.ctl = reinterpret_cast<const curdle::transcript::TapeCtl*>(d_tape);
-  ta.pool = reinterpret_cast<const curdle::transcript::TapeBlock*>(d_tape + T.pool_off);
-  ta.data = reinterpret_cast<const uint64_t*>(d_rows);
-  ta.init = reinterpret_cast<const uint64_t*>(d_tape + T.init_off);
-  ta.challenges = reinterpret_cast<uint64_t*>(d_ch);
-  ta.states = nullptr;
-  ta.status = d_trst;
-  ta.tail = T.tail;
-  ta.n_ctl = T.n_ctl;
-  ta.row_words = (uint32_t)(kRowBytes / 8);
-  ta.init_stride = 0;
-  ta.k = (uint32_t)m;
-  choose_transcript_kernel(m, &ta);
-  ta.n_challenges = 1;
-  HIP_TRY(launch_transcript_batch(ta, sa));
-  if (B && blinders) HIP_TRY(hipStreamWaitEvent(sa, B->acc_done, 0));
+  HIP_TRY(launch_transcript_batch(tape_args(d_tape, d_rows, d_ch, d_trst, m), sa));
+  if (blinders && (r = join_side(B, sa))) return r;
   HIP_TRY(launch_tracker_response(d_comp, d_ch, d_sc, d_status, d_sub, (uint32_t)m, d_proofs, sa));
   HIP_TRY(hipMemcpyAsync(h_out, d_proofs, 128 * m, hipMemcpyDeviceToHost, sa));
   HIP_TRY(hipMemcpyAsync(h_st, d_status, 2 * nrec + m, hipMemcpyDeviceToHost, sa));
@@ -719,7 +714,7 @@ int prove_pass_run(Ctx& cx, ProvePass& P, Slot* B, const uint8_t* trackers, cons
   unsigned long long handed = 0;
   for (size_t i = 0; i < m; i++) {
     uint8_t* out = proofs_out + 128 * i;
-    if (bad_member(i)) {  // where the single call fails to set rG or krG
+    if (bad_records(h_st, h_st + nrec, 2 * i, 2)) {  // where the single call fails to set rG or krG
       memset(out, 0, 128);
       results[i] = CURDLE_EINVAL;
     } else if (trst[i]) {  // 256 rejected draws (0.547^256): the single path settles the member on the host
@@ -767,7 +762,7 @@ int tracker_prove_batch(const uint8_t* trackers, const uint64_t* ks, const uint6
       return guarded("tracker proofs", [&]() -> int {
         for (size_t lo = 0; lo < k; lo += kTrackerPass) {
           ProvePass P{H.slot(), H.stream(), std::min(kTrackerPass, k - lo), WipeList(H.stream())};
-          int r = prove_pass_run(cx, P, B, trackers + 96 * lo, ks + 4 * lo, blinders ? blinders + 4 * lo : nullptr, rand,
+          int r = prove_pass_run(P, B, trackers + 96 * lo, ks + 4 * lo, blinders ? blinders + 4 * lo : nullptr, rand,
                                  d_table, proofs_out + 128 * lo, results + lo);
           if (r && B) (void)hipStreamSynchronize(B->stream);
           const int w = P.W.wipe("tracker proofs: clearing the secrets");  // nothing of k and b stays behind in the slot
@@ -779,8 +774,7 @@ int tracker_prove_batch(const uint8_t* trackers, const uint64_t* ks, const uint6
   }
   if (table_held) generator_table_release();
   if (rc != CURDLE_OK) {  // "could not compute" must never read as a proof
-    if (results)
-      for (size_t i = 0; i < k; i++) results[i] = rc;
+    fill_results(results, k, rc);
     if (proofs_out) memset(proofs_out, 0, 128 * k);
   }
   return rc;
@@ -792,8 +786,7 @@ extern "C" int curdle_whisk_is_valid_tracker_proof_batch_ex(const uint8_t* track
                                                             const uint8_t* proofs, size_t k, unsigned flags, int* results) {
   if (flags > CURDLE_TRACKER_HASH_DEVICE) {
     const int rc = fail(CURDLE_EINVAL, "unknown flags %u", flags);
-    if (results)
-      for (size_t i = 0; i < k; i++) results[i] = rc;
+    fill_results(results, k, rc);
     return rc;
   }
   if (k == 0) return CURDLE_OK;
