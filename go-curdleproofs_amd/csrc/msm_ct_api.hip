@@ -1,0 +1,230 @@
+// C ABI of the constant-time MSM (msm_ct_kernels.hip): curdle_msm_g1_ct / _device, curdle_stat_msm_ct, and the device
+// flagged shuffle step (curdle_shuffle_permute_commit_ex), its first user; that call's host part -- the range check of the
+// permutation and the draw of the blinders -- is in host/proto_api.cpp.
+//
+// A call takes ONE MSM slot, held by a SlotHold (api_helpers.h), for its stream and its buffers.  The terms k_i P_i live
+// in the slot's `partials` buffer, 224 bytes each, and never leave the device: the ONLY device-to-host copy of an MSM is
+// the 160-byte block k_msm_ct_finish wrote (the 18 words of the result and the violation word).  The term workspace is
+// on the call's WipeList in both forms; the host form's scalars go through the slot's pinned staging and a device
+// buffer, both on the list too.  Everything runs on one stream, the caller's if it gave one.  No stream is made here and
+// nothing is allocated once the slot's buffers have grown.
+#include "api_helpers.h"
+
+#include <algorithm>
+
+namespace {
+constexpr size_t kMsmCtMax = 65536;       // one pass: 256 blocks
+constexpr size_t kShuffleCtMax = 4096;    // the oblivious gather is quadratic
+constexpr size_t kOutBytes = 160;         // 36 words of result, the violation word, three words of padding
+constexpr size_t kStatusOffset = 192;     // the walks' status word, in the same small buffer behind the block
+
+// pairs walked | walk launches | sums finished; completed calls only
+std::atomic<unsigned long long> g_msm_ct_stat[3];
+
+void count_msm_ct(size_t pairs, unsigned walks) {
+  g_msm_ct_stat[0].fetch_add(pairs, std::memory_order_relaxed);
+  g_msm_ct_stat[1].fetch_add(walks, std::memory_order_relaxed);
+  g_msm_ct_stat[2].fetch_add(1, std::memory_order_relaxed);
+}
+
+int check_args(const void* points, const void* scalars, size_t n, unsigned bits, const void* out) {
+  if (!out || (n && (!points || !scalars))) return fail(CURDLE_EINVAL, "null argument");
+  if (bits < 1 || bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", bits);
+  if (n > kMsmCtMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 65,536 pairs", n);
+  return CURDLE_OK;
+}
+
+// the slot's small buffer: zeroes the status word on st
+int prepare_out(Slot& S, hipStream_t st) {
+  if (int r = ensure(S.results, 256)) return r;
+  HIP_TRY(hipMemsetAsync(static_cast<uint8_t*>(S.results.p) + kStatusOffset, 0, 16, st));
+  return CURDLE_OK;
+}
+uint32_t* status_word(Slot& S) { return reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(S.results.p) + kStatusOffset); }
+
+// Behind the walks: the sum over m terms, the block's copy (the call's only copy of anything the terms made), the wait,
+// the verdict.  h_out: pinned, kOutBytes.
+int sum_and_fetch(Slot& S, size_t m, void* h_out, uint64_t out_jac[18], hipStream_t st) {
+  HIP_TRY(launch_msm_ct_sum(S.partials.p, (uint32_t)m, status_word(S), S.results.p, st));
+  HIP_TRY(hipMemcpyAsync(h_out, S.results.p, kOutBytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (static_cast<const uint32_t*>(h_out)[36]) return fail(CURDLE_EINVAL, "a scalar is not below 2^scalar_bits");
+  memcpy(out_jac, h_out, 144);
+  return CURDLE_OK;
+}
+
+unsigned bit_length(size_t v) {
+  unsigned b = 0;
+  for (; v; v >>= 1) b++;
+  return b;
+}
+}  // namespace
+
+extern "C" int curdle_msm_g1_ct(const uint64_t* points, const uint64_t* scalars, size_t n, unsigned scalar_bits,
+                                uint64_t out_jac[18]) {
+  if (int rc = check_args(points, scalars, n, scalar_bits, out_jac)) return rc;
+  if (n == 0) {
+    set_out_infinity(out_jac);
+    return CURDLE_OK;
+  }
+  SlotHold H(cur(), true, nullptr);
+  WipeList W(H.stream());
+  H.wipe_on_exit(&W, "constant-time MSM: clearing the scalars and the terms");
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
+    int r;
+    if ((r = ensure(S.points, n * 96))) return r;
+    if ((r = ensure(S.scalars, n * 32))) return r;
+    if ((r = ensure(S.partials, n * kMsmCtTermBytes))) return r;
+    if ((r = ensure_pinned(S, 0, n * 32 + n * 96))) return r;  // scalars | points
+    if ((r = ensure_pinned(S, 1, kOutBytes))) return r;
+    W.note_device(S.scalars.p, n * 32);
+    W.note_device(S.partials.p, n * kMsmCtTermBytes);
+    W.note_host(S.h_stage[0], n * 32);
+    uint8_t* h_sc = static_cast<uint8_t*>(S.h_stage[0]);
+    uint8_t* h_pt = h_sc + n * 32;
+    memcpy(h_sc, scalars, n * 32);
+    memcpy(h_pt, points, n * 96);
+    if ((r = prepare_out(S, st))) return r;
+    HIP_TRY(hipMemcpyAsync(S.scalars.p, h_sc, n * 32, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S.points.p, h_pt, n * 96, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_msm_ct_walk(S.points.p, S.scalars.p, kMsmCtScalarFr, scalar_bits, (uint32_t)n, S.partials.p, status_word(S), st));
+    if ((r = sum_and_fetch(S, n, S.h_stage[1], out_jac, st))) return r;
+    count_msm_ct(n, 1);
+    return CURDLE_OK;
+  });
+}
+
+extern "C" int curdle_msm_g1_ct_device(const void* d_points, const void* d_scalars, size_t n, unsigned scalar_bits,
+                                       uint64_t out_jac[18], void* stream) {
+  if (int rc = check_args(d_points, d_scalars, n, scalar_bits, out_jac)) return rc;
+  if (n == 0) {
+    set_out_infinity(out_jac);
+    return CURDLE_OK;
+  }
+  if (!aligned16(d_points) || !aligned16(d_scalars)) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
+  SlotHold H(cur(), true, stream);
+  WipeList W(H.stream());
+  H.wipe_on_exit(&W, "constant-time MSM: clearing the terms");
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
+    int r;
+    if ((r = ensure(S.partials, n * kMsmCtTermBytes))) return r;
+    if ((r = ensure_pinned(S, 1, kOutBytes))) return r;
+    W.note_device(S.partials.p, n * kMsmCtTermBytes);
+    if ((r = prepare_out(S, st))) return r;
+    // the caller's scalars are read where they are: nothing of them is copied
+    HIP_TRY(launch_msm_ct_walk(d_points, d_scalars, kMsmCtScalarFr, scalar_bits, (uint32_t)n, S.partials.p, status_word(S), st));
+    if ((r = sum_and_fetch(S, n, S.h_stage[1], out_jac, st))) return r;
+    count_msm_ct(n, 1);
+    return CURDLE_OK;
+  });
+}
+
+extern "C" int curdle_stat_msm_ct(unsigned long long out[3]) { return read_stats(out, g_msm_ct_stat, 3); }
+
+// The oblivious gather of the flagged shuffle step on its own, resident: d_out[i] = d_in[d_perm[i]], 96-byte records.
+extern "C" int curdle_g1_permute_ct_device(const void* d_in, const void* d_perm, size_t n, void* d_out, void* stream) {
+  if (n == 0) return CURDLE_OK;
+  if (!d_in || !d_perm || !d_out) return fail(CURDLE_EINVAL, "null argument");
+  if (n > kShuffleCtMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 4,096 records", n);
+  if (!aligned16(d_in) || !aligned16(d_out) || ((uintptr_t)d_perm & 3u))
+    return fail(CURDLE_EINVAL, "record pointers must be multiples of 16, the permutation's of 4");
+  SlotHold H(cur(), true, stream);
+  return H.run([&]() -> int {
+    HIP_TRY(launch_g1_permute_ct(d_in, static_cast<const uint32_t*>(d_perm), (uint32_t)n, 1, d_out, H.stream()));
+    HIP_TRY(hipStreamSynchronize(H.stream()));
+    return CURDLE_OK;
+  });
+}
+
+// The device work of curdle_shuffle_permute_commit_ex under CURDLE_SHUFFLE_CONSTANT_TIME (the entry point below checked the
+// arguments; host/proto_api.cpp the permutation's range, and drew rs_m):
+//   Ts | Us   one k_g1_mul_ct with the shared scalar k over the 2 ell records Rs | Ss, in place, then ONE
+//             k_g1_permute_ct over both halves with the same perm;
+//   M         k_msm_ct_walk over Gs with the permutation as plain uint32 scalars at bit_length(ell - 1) steps (public, at
+//             least 1), a second walk over Hs with rs_m at 255 steps into the same workspace behind the first, ONE sum
+//             over the ell + 4 terms and the finish.  M1 = sum perm[i] Gs[i] exists nowhere: not as a term, not on the host.
+// The only device-to-host copies are Ts | Us and the 160-byte block (M and the violation word).  k, perm and rs_m go
+// through the slot's pinned staging into ONE device buffer; that buffer, the staging, the unpermuted k R_i | k S_i and
+// the term workspace are wiped on every way out.  Both walks run on the call's one stream: they are 5 ms chains of one
+// and of ell / 64 waves, so a second stream would buy the shorter walk's length; not built, not measured.
+static int shuffle_commit_ct(const uint64_t* Gs, const uint64_t* Hs, const uint64_t* Rs, const uint64_t* Ss, size_t ell,
+                             const uint32_t* perm, const uint64_t k[4], const uint64_t rs_m[16], uint64_t* Ts_out,
+                             uint64_t* Us_out, uint64_t M_out[18]) {
+  SlotHold H(cur(), true, nullptr);
+  WipeList W(H.stream());
+  H.wipe_on_exit(&W, "constant-time shuffle step: clearing k, the permutation, the blinders and the terms");
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
+    const size_t m = ell + 4, sec = 32 + 128 + 4 * ell, sec_pad = (sec + 15) / 16 * 16, rec = 2 * ell * 96;
+    int r;
+    if ((r = ensure(S.points, rec))) return r;      // Rs | Ss, multiplied in place
+    if ((r = ensure(S.sorted, rec))) return r;      // Ts | Us
+    if ((r = ensure(S.tmp, m * 96))) return r;      // Gs | Hs
+    if ((r = ensure(S.scalars, sec_pad))) return r; // k | rs_m | perm
+    if ((r = ensure(S.partials, m * kMsmCtTermBytes))) return r;
+    if ((r = ensure_pinned(S, 0, sec_pad + rec + m * 96))) return r;
+    if ((r = ensure_pinned(S, 1, rec + kOutBytes))) return r;
+    W.note_device(S.scalars.p, sec_pad);
+    W.note_device(S.points.p, rec);
+    W.note_device(S.partials.p, m * kMsmCtTermBytes);
+    W.note_host(S.h_stage[0], sec_pad);
+    uint8_t* h = static_cast<uint8_t*>(S.h_stage[0]);
+    memcpy(h, k, 32);
+    memcpy(h + 32, rs_m, 128);
+    memcpy(h + 160, perm, 4 * ell);
+    uint8_t* h_pub = h + sec_pad;
+    memcpy(h_pub, Rs, ell * 96);
+    memcpy(h_pub + ell * 96, Ss, ell * 96);
+    memcpy(h_pub + rec, Gs, ell * 96);
+    memcpy(h_pub + rec + ell * 96, Hs, 4 * 96);
+    uint8_t* d_sec = static_cast<uint8_t*>(S.scalars.p);
+    uint8_t* d_term = static_cast<uint8_t*>(S.partials.p);
+    uint8_t* h_out = static_cast<uint8_t*>(S.h_stage[1]);
+    if ((r = prepare_out(S, st))) return r;
+    HIP_TRY(hipMemcpyAsync(d_sec, h, sec, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S.points.p, h_pub, rec, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S.tmp.p, h_pub + rec, m * 96, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_g1_mul_ct(S.points.p, 1, d_sec, 1, (uint32_t)(2 * ell), S.points.p, st));
+    HIP_TRY(launch_g1_permute_ct(S.points.p, reinterpret_cast<const uint32_t*>(d_sec + 160), (uint32_t)ell, 2, S.sorted.p, st));
+    const unsigned pbits = std::max(1u, bit_length(ell - 1));
+    HIP_TRY(launch_msm_ct_walk(S.tmp.p, d_sec + 160, kMsmCtScalarU32, pbits, (uint32_t)ell, d_term, status_word(S), st));
+    HIP_TRY(launch_msm_ct_walk(static_cast<uint8_t*>(S.tmp.p) + ell * 96, d_sec + 32, kMsmCtScalarFr, 255, 4,
+                               d_term + ell * kMsmCtTermBytes, status_word(S), st));
+    HIP_TRY(hipMemcpyAsync(h_out + kOutBytes, S.sorted.p, rec, hipMemcpyDeviceToHost, st));
+    if ((r = sum_and_fetch(S, m, h_out, M_out, st))) return r;
+    memcpy(Ts_out, h_out + kOutBytes, ell * 96);
+    memcpy(Us_out, h_out + kOutBytes + ell * 96, ell * 96);
+    count_g1_mul_ct_pass(2 * ell);
+    count_msm_ct(m, 2);
+    return CURDLE_OK;
+  });
+}
+
+// host/proto_api.cpp
+int curdle_shuffle_commit_ct_host_part(const curdle_crs* crs, size_t ell, const uint32_t* perm, curdle_rand* rand,
+                                       const uint64_t** Gs, const uint64_t** Hs, uint64_t rs_m[16]);
+
+extern "C" int curdle_shuffle_permute_commit_ex(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, size_t ell,
+                                                const uint32_t* perm, const uint64_t k[4], curdle_rand* rand, unsigned flags,
+                                                uint64_t* Ts_out, uint64_t* Us_out, uint64_t M_out[18],
+                                                uint64_t rs_m_out[16]) {
+  if (flags & ~CURDLE_SHUFFLE_CONSTANT_TIME)
+    return fail(CURDLE_EINVAL, "unknown flag bits 0x%x", flags & ~CURDLE_SHUFFLE_CONSTANT_TIME);
+  if (!flags) return curdle_shuffle_permute_commit(crs, Rs, Ss, ell, perm, k, rand, Ts_out, Us_out, M_out, rs_m_out);
+  if (!crs || !Rs || !Ss || !perm || !k || !rand || !Ts_out || !Us_out || !M_out || !rs_m_out)
+    return fail(CURDLE_EINVAL, "null argument");
+  if (ell == 0 || ell > kShuffleCtMax)
+    return fail(CURDLE_EINVAL, "ell = %zu is not in 1...4,096 under CURDLE_SHUFFLE_CONSTANT_TIME", ell);
+  const uint64_t *Gs = nullptr, *Hs = nullptr;
+  uint64_t rs_m[16];
+  int rc = curdle_shuffle_commit_ct_host_part(crs, ell, perm, rand, &Gs, &Hs, rs_m);
+  if (rc == CURDLE_OK) rc = shuffle_commit_ct(Gs, Hs, Rs, Ss, ell, perm, k, rs_m, Ts_out, Us_out, M_out);
+  if (rc == CURDLE_OK) memcpy(rs_m_out, rs_m, sizeof(rs_m));
+  explicit_bzero(rs_m, sizeof(rs_m));
+  return rc;
+}

@@ -1,0 +1,222 @@
+// Constant-time multi-scalar multiplication: sum_i k_i P_i with an instruction stream and an address stream that do
+// not depend on the scalars.  The twin of the bucket MSM (msm_sort_kernels.hip, msm_accumulate_kernel.hip), whose sort,
+// bucket addresses and large-bucket queue are all functions of the scalars, in the manner of k_g1_mul_ct
+// (g1_mul_ct_kernels.hip).  Four kernels; the rule of what may depend on a secret is the one of g1_walk_ct.h.
+//
+// k_msm_ct_walk.  One lane per (base, scalar) pair: the walk of g1_walk_ct.h with a PUBLIC step count `bits` (1...255,
+// a kernel argument): the scalar is first shifted left by 256 - bits, one bit a step in a rolled loop whose trip count
+// is the argument alone, and every bit shifted out is OR-ed into the lane's violation word; then `bits` steps of
+// d28::dbl and madd_bit with started |= bit.  The exactness argument of g1_walk_ct.h holds for every prefix of a scalar
+// below r, so it holds for the low `bits` bits walked here.  The scalar is a gnark Montgomery fr.Element (32 bytes,
+// f_from_mont in the lane) or a plain uint32 (the shuffle's permutation, so that the host does no field arithmetic on
+// it): a kernel argument says which, and both loads are at addresses made of the lane index.  The violation word goes
+// into ONE status word by an unconditional per-lane atomic OR of 0 or 1: no branch is taken on it.  The lane writes its term, an
+// X28 record (224 bytes, not normalised), to term[i]: all-zero words when nothing was added (k = 0) or the base is
+// infinity, which is public.  Nothing is normalised here: the terms never leave the workspace.
+//
+// k_g1_sum_ct.  One level of the FIXED fold-in-half order over the m terms: h = ceil(m / 2) and
+// term[i] = add_ct(term[i], term[i + h]) for i < m - h, one lane per i; the host launches level after level with
+// m <- h while m > kSumTail.  A level reads term[i + h] with i + h >= h and writes term[i] with i < m - h <= h: no lane
+// reads what another writes.  Addresses and trip counts are functions of m alone.
+//
+// k_msm_ct_finish.  ONE block: the remaining levels (m <= kSumTail, so at most one addition per lane and level) with a
+// barrier between them, then lane 0 normalises term[0] as k_g1_mul_ct does -- one Fermat inversion of zz zzz on the
+// fixed exponent chain of invert28.h -- and writes the 18 words curdle_msm_g1 returns, canonical (x, y, 1) or (1, 1, 0)
+// for infinity, chosen by a mask on zz, through the masked canonical step, and the status word behind them.
+//
+// k_g1_permute_ct.  out[i] = in[perm[i]] over 96-byte records with perm secret: lane i loads its own perm[i] (an
+// address made of the lane index) and walks j = 0 ... n - 1, a public trip count with the address of in[j] made of j,
+// accumulating in[j] & mask(perm[i] == j): n^2 record reads and no address made of perm.  `halves` record arrays of n
+// records lie behind each other and are permuted alike (the shuffle's Ts | Us).
+//
+// Plain loads and stores, one atomic OR, no LDS, no inline assembly beyond the field layer's.
+#include <hip/hip_runtime.h>
+
+#include "msm_kernels_common.h"
+#include "g1_walk_ct.h"
+#include "g1_add_ct.h"
+#include "invert28.h"
+
+namespace curdle {
+
+namespace {
+// to_gnark_ct of g1_mul_ct_kernels.hip: d28::to_gnark with a masked canonical step, the choice between t and t - p a
+// select on the borrow, never an exec mask.
+__device__ __forceinline__ void to_gnark_ct(u32* w, const F28& a) {
+  using namespace d28;
+  F28 t, c;
+#pragma unroll
+  for (int i = 0; i < N; i++) c.l[i] = kToExt(i);
+  mul(t, a, c);
+  u32 d[N], borrow = 0;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const u32 s = t.l[i] - kP(i) - borrow;
+    borrow = s >> 31;  // limbs are below 2^28 (the top one below 2^31): bit 31 of the difference is the borrow
+    d[i] = i < N - 1 ? s & MASK : s;
+  }
+  const u32 lt = 0u - borrow;  // t < p: keep t
+#pragma unroll
+  for (int i = 0; i < N; i++) t.l[i] = (t.l[i] & lt) | (d[i] & ~lt);
+  pack(w, t);
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock, 2)
+    k_msm_ct_walk(const uint4* __restrict__ points, const void* __restrict__ scalars, u32 form, u32 bits, u32 n,
+                  X28* __restrict__ term, u32* status) {
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  u32 pw[24];
+  d28::load_words<24>(pw, points + 6 * (size_t)i);
+  const u32 finite = finite_mask(pw);  // public
+  F28 x2, y2;
+  d28::from_gnark(x2, pw);
+  d28::from_gnark(y2, pw + 12);
+  Fr k;
+  if (form == kMsmCtScalarU32) {  // a kernel argument: wave-uniform and public
+#pragma unroll
+    for (int j = 1; j < 8; j++) k.l[j] = 0;
+    k.l[0] = static_cast<const u32*>(scalars)[i];  // an address made of the lane index: a vector load
+  } else {
+    Fr s;
+    load_fr_lane(s, static_cast<const uint4*>(scalars) + 2 * (size_t)i);
+    f_from_mont<FrParams>(k, s);
+  }
+  // k << (256 - bits): the trip count is the argument alone; a set bit at or above `bits` is the violation
+  u32 over = 0;
+#pragma unroll 1
+  for (u32 s = bits; s < 256; s++) over |= next_bit_msb(k);
+  X28 acc;  // not a point until `started`
+  d28::set_one(acc.x);
+  d28::set_one(acc.y);
+  d28::set_one(acc.zz);
+  d28::set_one(acc.zzz);
+  u32 started = 0;
+#pragma unroll 1
+  for (u32 step = 0; step < bits; step++) {
+    const u32 bit = 0u - next_bit_msb(k);
+    d28::dbl(acc);
+    madd_bit(acc, x2, y2, bit, started);
+    started |= bit;
+  }
+  // Unconditional, 0 or 1.  The address is made of the lane index (i < 2^31: always word 0) so that it is a per-lane
+  // atomic: on a wave-uniform address the compiler first folds the wave's values through v_readlane into SGPRs.
+  atomicOr(status + (i >> 31), over);
+  const u32 m = started & finite;
+  const u32* w = reinterpret_cast<const u32*>(&acc);
+  uint4* dst = reinterpret_cast<uint4*>(term + i);
+#pragma unroll
+  for (int j = 0; j < 14; j++) dst[j] = make_uint4(w[4 * j] & m, w[4 * j + 1] & m, w[4 * j + 2] & m, w[4 * j + 3] & m);
+}
+
+__global__ void __launch_bounds__(kBlock, 1) k_g1_sum_ct(X28* term, u32 m) {
+  const u32 h = (m + 1) / 2;
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= m - h) return;
+  X28 a, b;
+  d28::load(a, term + i);
+  d28::load(b, term + i + h);
+  add_ct(a, b);
+  d28::store(term + i, a);
+}
+
+__global__ void __launch_bounds__(kBlock, 1) k_msm_ct_finish(X28* term, u32 m, const u32* status, u32* out) {
+#pragma unroll 1
+  while (m > 1) {
+    const u32 h = (m + 1) / 2;
+#pragma unroll 1
+    for (u32 i = threadIdx.x; i < m - h; i += kBlock) {
+      X28 a, b;
+      d28::load(a, term + i);
+      d28::load(b, term + i + h);
+      add_ct(a, b);
+      d28::store(term + i, a);
+    }
+    __threadfence_block();
+    __syncthreads();
+    m = h;
+  }
+  if (threadIdx.x != 0) return;
+  X28 acc;
+  d28::load(acc, term);
+  const u32 fin = ~zero_mask(acc.zz);
+  // x = X / zz, y = Y / zzz with one inversion; infinity inverts 0 (which gives 0) and is masked away
+  F28 d, inv, ix, iy;
+  d28::mul(d, acc.zz, acc.zzz);
+  invert(inv, d);
+  d28::mul(ix, inv, acc.zzz);
+  d28::mul(iy, inv, acc.zz);
+  d28::mul(ix, acc.x, ix);
+  d28::mul(iy, acc.y, iy);
+  u32 w[24];
+  to_gnark_ct(w, ix);
+  to_gnark_ct(w + 12, iy);
+#pragma unroll
+  for (int j = 0; j < 12; j++) {
+    const u32 one = FpParams::one(j);  // gnark's Montgomery 1
+    out[j] = (w[j] & fin) | (one & ~fin);
+    out[12 + j] = (w[12 + j] & fin) | (one & ~fin);
+    out[24 + j] = one & fin;
+  }
+  out[36] = *status;
+}
+
+__global__ void __launch_bounds__(kBlock)
+    k_g1_permute_ct(const uint4* __restrict__ in, const u32* __restrict__ perm, u32 n, u32 halves, uint4* __restrict__ out) {
+  const u32 g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= n * halves) return;
+  const u32 half = g / n, i = g - half * n;  // public
+  const u32 p = perm[i];                     // an address made of the lane index
+  const uint4* src = in + 6 * (size_t)half * n;
+  u32 acc[24];
+#pragma unroll
+  for (int w = 0; w < 24; w++) acc[w] = 0;
+#pragma unroll 1
+  for (u32 j = 0; j < n; j++) {
+    const u32 d = p ^ j;
+    const u32 m = ((d | (0u - d)) >> 31) - 1u;  // all ones iff perm[i] == j
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+      const uint4 v = src[6 * (size_t)j + q];  // an address made of j
+      acc[4 * q] |= v.x & m;
+      acc[4 * q + 1] |= v.y & m;
+      acc[4 * q + 2] |= v.z & m;
+      acc[4 * q + 3] |= v.w & m;
+    }
+  }
+  uint4* dst = out + 6 * (size_t)g;
+#pragma unroll
+  for (int q = 0; q < 6; q++) dst[q] = make_uint4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+}
+
+hipError_t launch_msm_ct_walk(const void* points, const void* scalars, int scalar_form, uint32_t bits, uint32_t n, void* term,
+                              uint32_t* status, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (n > (1u << 31) || bits < 1 || bits > 255 || (scalar_form != kMsmCtScalarFr && scalar_form != kMsmCtScalarU32)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_msm_ct_walk, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream, (const uint4*)points, scalars,
+                     (u32)scalar_form, (u32)bits, (u32)n, (X28*)term, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_msm_ct_sum(void* term, uint32_t m, const uint32_t* status, void* out40, hipStream_t stream) {
+  if (m == 0) return hipErrorInvalidValue;
+  while (m > kMsmCtSumTail) {
+    const u32 h = (m + 1) / 2;
+    hipLaunchKernelGGL(k_g1_sum_ct, dim3(cdiv(m - h, kBlock)), dim3(kBlock), 0, stream, (X28*)term, (u32)m);
+    if (hipError_t e = hipGetLastError()) return e;
+    m = h;
+  }
+  hipLaunchKernelGGL(k_msm_ct_finish, dim3(1), dim3(kBlock), 0, stream, (X28*)term, (u32)m, status, (u32*)out40);
+  return hipGetLastError();
+}
+
+hipError_t launch_g1_permute_ct(const void* in, const uint32_t* perm, uint32_t n, uint32_t halves, void* out, hipStream_t stream) {
+  if (n == 0 || halves == 0) return hipSuccess;
+  if ((u64)n * halves > ((u64)1 << 31)) return hipErrorInvalidValue;  // the lane index is 32 bits
+  hipLaunchKernelGGL(k_g1_permute_ct, dim3(cdiv((u64)n * halves, kBlock)), dim3(kBlock), 0, stream, (const uint4*)in, perm,
+                     (u32)n, (u32)halves, (uint4*)out);
+  return hipGetLastError();
+}
+
+}  // namespace curdle

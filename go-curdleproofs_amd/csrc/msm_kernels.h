@@ -345,6 +345,25 @@ hipError_t launch_fbase_mul_ct(const void* table28, const void* scalars, const v
 hipError_t launch_g1_mul_ct(const void* points, uint32_t point_stride, const void* scalars, int shared_scalar, uint32_t n,
                             void* out_affine, hipStream_t stream);
 
+// msm_ct_kernels.hip: the constant-time MSM, sum_i scalars[i] * points[i], in three steps over a workspace of X28 terms
+// (kMsmCtTermBytes each, 16-byte aligned).  Neither the instruction stream nor the address stream of any of them
+// depends on the scalars or on the terms.
+//   launch_msm_ct_walk: term[i] = scalars[i] * points[i] for i < n by `bits` (1...255, public) double-and-always-add
+//     steps, one lane per pair; scalars are Montgomery fr.Elements (kMsmCtScalarFr) or plain uint32 (kMsmCtScalarU32);
+//     a scalar with a bit at or above `bits` ORs 1 into *status (which the caller zeroes first).
+//   launch_msm_ct_sum: folds term[0, m) in place in the fixed fold-in-half order (h = ceil(m / 2), term[i] += term[i + h]
+//     for i < m - h, m <- h), one launch per level above kMsmCtSumTail terms and one block for the rest, which then
+//     normalises term[0] and writes out40: the 36 words of curdle_msm_g1's result, *status behind them, three words untouched.
+//   launch_g1_permute_ct: out[h n + i] = in[h n + perm[i]] for i < n, h < halves, 96-byte records, perm secret: every
+//     lane reads all n records of its half.  out must not overlap in.
+enum { kMsmCtScalarFr = 0, kMsmCtScalarU32 = 1 };
+static constexpr uint32_t kMsmCtTermBytes = 224;
+static constexpr uint32_t kMsmCtSumTail = 512;
+hipError_t launch_msm_ct_walk(const void* points, const void* scalars, int scalar_form, uint32_t bits, uint32_t n, void* term,
+                              uint32_t* status, hipStream_t stream);
+hipError_t launch_msm_ct_sum(void* term, uint32_t m, const uint32_t* status, void* out40, hipStream_t stream);
+hipError_t launch_g1_permute_ct(const void* in, const uint32_t* perm, uint32_t n, uint32_t halves, void* out, hipStream_t stream);
+
 // normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion
 // per wave of 64 lanes with 1 or 8 points each (Montgomery's trick over a wave scan).  The forms are those of
 // launch_g1_compress; a denominator (Z, or ZZ ZZZ) that is 0 mod p is infinity.  `in` and `out` are multiples of 16

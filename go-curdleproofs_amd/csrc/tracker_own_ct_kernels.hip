@@ -34,35 +34,9 @@
 #include "../../include/curdle_msm.h"
 #include "msm_kernels_common.h"
 #include "g1_walk_ct.h"
+#include "g1_add_ct.h"  // finite_mask, equal_mod_p
 
 namespace curdle {
-
-namespace {
-// all ones iff the 24 words of a gnark affine record are not all zero ((0, 0) = infinity); public
-__device__ __forceinline__ u32 finite_mask(const u32* w) {
-  u32 any = 0;
-#pragma unroll
-  for (int j = 0; j < 24; j++) any |= w[j];
-  return 0u - ((any | (0u - any)) >> 31);
-}
-// all ones iff a - b == 0 mod p; a < 2p, b < 10p, both normalised.  No comparison instruction: masks only.
-__device__ __forceinline__ u32 equal_mod_p(const F28& a, const F28& b) {
-  using namespace d28;
-  F28 d, e, c;
-  sub_raw<16>(d, a, b);  // a - b + 16p < 18p
-#pragma unroll
-  for (int i = 0; i < N; i++) c.l[i] = kOne(i);
-  mul(e, d, c);  // the same residue, below 2p and normalised: 0 or p iff a == b mod p
-  u32 o0 = 0, op = 0;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    o0 |= e.l[i];
-    op |= e.l[i] ^ kP(i);
-  }
-  const u32 neither = ((o0 | (0u - o0)) & (op | (0u - op))) >> 31;  // 1 iff e is neither 0 nor p
-  return neither - 1u;
-}
-}  // namespace
 
 // points: the decoded records of a pass (gnark affine, (0, 0) = infinity), rG_t at 2 t and krG_t at 2 t + 1; status:
 // their CURDLE_DECODE_* bytes (subgroup test included); keys: Montgomery fr.Elements.  The launch covers trackers

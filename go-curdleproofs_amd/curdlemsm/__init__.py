@@ -90,6 +90,8 @@ SYMBOLS = [
     "curdle_stat_tracker_combined", "curdle_whisk_tracker_combined_scalars", "curdle_tracker_combined_last_kernel_ms",
     "curdle_stat_transcript_paths", "curdle_keccak_permute_batch",
     "curdle_msm_reduce_plan", "curdle_msm_stream_plan",
+    "curdle_msm_g1_ct", "curdle_msm_g1_ct_device", "curdle_stat_msm_ct", "curdle_shuffle_permute_commit_ex",
+    "curdle_g1_permute_ct_device",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -257,6 +259,11 @@ _scalar_mul_batch_ex = _sig("curdle_g1_scalar_mul_batch_ex", C.c_int, _vp, _vp, 
 _scalar_mul_batch_device_ex = _sig("curdle_g1_scalar_mul_batch_device_ex", C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t,
                                    C.c_uint, _vp, _vp)
 _stat_g1_mul_ct = _sig("curdle_stat_g1_mul_ct", C.c_int, C.POINTER(C.c_ulonglong))
+_msm_g1_ct = _sig("curdle_msm_g1_ct", C.c_int, _vp, _vp, C.c_size_t, C.c_uint, _vp)
+_msm_g1_ct_device = _sig("curdle_msm_g1_ct_device", C.c_int, _vp, _vp, C.c_size_t, C.c_uint, _vp, _vp)
+_stat_msm_ct = _sig("curdle_stat_msm_ct", C.c_int, C.POINTER(C.c_ulonglong))
+_g1_permute_ct_device = _sig("curdle_g1_permute_ct_device", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp)
+_spc_ex = _sig("curdle_shuffle_permute_commit_ex", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp)
 G1_FORM_JAC, G1_FORM_XYZZ = 0, 1
 
 
@@ -403,6 +410,41 @@ def msm_g1_device(d_points: int, d_scalars: int, n: int, stream: int = 0, window
         _check(_msm_g1_device_windows(d_points, d_scalars, n, window_bits, win_begin, win_end, _ptr(out),
                                       stream or None))
     return out
+
+
+def msm_g1_ct(points, scalars, scalar_bits: int = 255) -> np.ndarray:
+    """msm_g1 for SECRET scalars (curdle_msm_g1_ct): the same 18 words by kernels whose instruction and address streams
+    do not depend on the scalars.  scalar_bits (1...255) is the caller's public bound: a scalar at or above
+    2^scalar_bits fails the call with EINVAL.  At most 65,536 pairs; bases in the prime-order subgroup."""
+    points = _as_u64(points, 12)
+    scalars = _as_u64(scalars, 4)
+    n = points.shape[0] if points.size else 0
+    ns = scalars.shape[0] if scalars.size else 0
+    if n != ns:
+        raise CurdleError(EINVAL, "len(points) != len(scalars)")
+    out = np.zeros(18, dtype=np.uint64)
+    _check(_msm_g1_ct(_ptr(points), _ptr(scalars), n, int(scalar_bits), _ptr(out)))
+    return out
+
+
+def msm_g1_ct_device(d_points: int, d_scalars: int, n: int, scalar_bits: int = 255, stream: int = 0) -> np.ndarray:
+    """msm_g1_ct on device-resident inputs (curdle_msm_g1_ct_device; raw device pointers, multiples of 16)."""
+    out = np.zeros(18, dtype=np.uint64)
+    _check(_msm_g1_ct_device(d_points or None, d_scalars or None, n, int(scalar_bits), _ptr(out), stream or None))
+    return out
+
+
+def g1_permute_ct_device(d_in: int, d_perm: int, n: int, d_out: int, stream: int = 0) -> None:
+    """d_out[i] = d_in[d_perm[i]] over 96-byte records by the oblivious gather of the flagged shuffle step
+    (curdle_g1_permute_ct_device): no address is made of the permutation."""
+    _check(_g1_permute_ct_device(d_in or None, d_perm or None, n, d_out or None, stream or None))
+
+
+def stat_msm_ct() -> dict:
+    """Pairs walked by the constant-time MSM, its walk launches and its finished sums since the library was loaded."""
+    out = (C.c_ulonglong * 3)()
+    _check(_stat_msm_ct(out))
+    return {"pairs": int(out[0]), "walks": int(out[1]), "sums": int(out[2])}
 
 
 def msm_g1_device_submit(d_points: int, d_scalars: int, n: int, window_bits: int = 0, win_begin: int = 0,
@@ -792,8 +834,12 @@ class CRS:
             _crs_free(h)
 
 
-def shuffle_permute_commit(crs: CRS, Rs, Ss, perm, k, rand: Rand):
-    """common.ShufflePermuteCommit (common/util.go:45) -> (Ts, Us, M, rs_m)."""
+SHUFFLE_CONSTANT_TIME = 1                             # CURDLE_SHUFFLE_CONSTANT_TIME
+
+
+def shuffle_permute_commit(crs: CRS, Rs, Ss, perm, k, rand: Rand, flags=None):
+    """common.ShufflePermuteCommit (common/util.go:45) -> (Ts, Us, M, rs_m).  flags: None calls the entry point without
+    flags; an integer (0, SHUFFLE_CONSTANT_TIME) calls curdle_shuffle_permute_commit_ex with it."""
     Rs, Ss = _as_u64(Rs, 12), _as_u64(Ss, 12)
     perm = np.ascontiguousarray(perm, dtype=np.uint32)
     k = _as_u64(k)
@@ -802,7 +848,11 @@ def shuffle_permute_commit(crs: CRS, Rs, Ss, perm, k, rand: Rand):
     Us = np.zeros((ell, 12), dtype=np.uint64)
     M = np.zeros(18, dtype=np.uint64)
     rs_m = np.zeros((4, 4), dtype=np.uint64)
-    _check(_spc(crs._h, _ptr(Rs), _ptr(Ss), ell, _ptr(perm), _ptr(k), rand._h, _ptr(Ts), _ptr(Us), _ptr(M), _ptr(rs_m)))
+    if flags is None:
+        _check(_spc(crs._h, _ptr(Rs), _ptr(Ss), ell, _ptr(perm), _ptr(k), rand._h, _ptr(Ts), _ptr(Us), _ptr(M), _ptr(rs_m)))
+    else:
+        _check(_spc_ex(crs._h, _ptr(Rs), _ptr(Ss), ell, _ptr(perm), _ptr(k), rand._h, int(flags), _ptr(Ts), _ptr(Us), _ptr(M),
+                       _ptr(rs_m)))
     return Ts, Us, M, rs_m
 
 

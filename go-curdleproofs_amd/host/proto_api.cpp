@@ -88,6 +88,28 @@ extern "C" int curdle_shuffle_permute_commit(const curdle_crs* crs, const uint64
   });
 }
 
+// The host's part of curdle_shuffle_permute_commit_ex under CURDLE_SHUFFLE_CONSTANT_TIME (csrc/msm_ct_api.hip owns the entry
+// point and the device work): ell against the CRS, the permutation's range (the existing check: a failure reveals only
+// that the input was invalid), then the blinders, drawn at the point where the call without flags draws them --
+// GetFrs(N_BLINDERS), nothing before it.  Hands out the CRS's Gs and Hs as gnark records.  This, the draw's own code and
+// the caller's copies are what lies outside the flag's promise.
+int curdle_shuffle_commit_ct_host_part(const curdle_crs* crs, size_t ell, const uint32_t* perm, curdle_rand* rand,
+                                       const uint64_t** Gs, const uint64_t** Hs, uint64_t rs_m[16]) {
+  if (ell != crs->crs.Gs.size()) return curdle_set_last_error(CURDLE_EINVAL, "ell does not match the CRS");
+  return Guard([&]() {
+    for (size_t i = 0; i < ell; i++)
+      if (perm[i] >= ell) throw std::runtime_error("permutation entry out of range");
+    static_assert(proto::N_BLINDERS == 4 && sizeof(Fr) == 32, "rs_m holds four blinders");
+    std::vector<Fr> drawn;
+    rand->r.GetFrs(proto::N_BLINDERS, drawn);
+    memcpy(rs_m, drawn.data(), 128);
+    explicit_bzero(drawn.data(), 128);
+    *Gs = reinterpret_cast<const uint64_t*>(crs->crs.Gs.data());
+    *Hs = reinterpret_cast<const uint64_t*>(crs->crs.Hs.data());
+    return CURDLE_OK;
+  });
+}
+
 extern "C" int curdle_prove(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, const uint64_t* Ts,
                             const uint64_t* Us, size_t ell, const uint64_t M[18], const uint32_t* perm,
                             const uint64_t k[4], const uint64_t rs_m[16], curdle_rand* rand, uint8_t* proof_out,

@@ -1015,6 +1015,76 @@ int curdle_g1_scalar_mul_batch_device_ex(const void* d_points, const void* d_sca
  * CURDLE_G1_MUL_CONSTANT_TIME (or the rG column of a pass under CURDLE_TRACKER_PROVE_CONSTANT_TIME) counts here and
  * NOT in curdle_stat_normalize: it runs no normalisation kernel. */
 int curdle_stat_g1_mul_ct(unsigned long long out[2]);
+/* -------------------------------------------------------------------------
+ * Constant-time MSM for SECRET scalars: out = sum_i scalars[i] * points[i], the result bit for bit the 18 words
+ * curdle_msm_g1 returns on the same input (canonical (x, y, 1), or its encoding of infinity).  curdle_msm_g1 is NOT
+ * constant time in the scalars: its sort, its bucket addresses and its large-bucket queue are functions of them.  Here
+ * (csrc/msm_ct_kernels.hip) one lane per pair walks the low scalar_bits bits of its scalar MSB first (k_msm_ct_walk:
+ * every step one doubling and ALWAYS one mixed addition, the accumulator taken by mask selection, the walk of
+ * CURDLE_G1_MUL_CONSTANT_TIME's kernel) and leaves its term k_i P_i unnormalised in a device workspace; the terms are
+ * folded in a FIXED order (k_g1_sum_ct: h = ceil(m / 2), term[i] += term[i + h] for i < m - h, m <- h until m = 1) by ONE
+ * complete addition that computes the sum, the double and four masks every time and takes b, a, the double, infinity or
+ * the sum by mask arithmetic (csrc/g1_add_ct.h); one lane normalises the last term (k_msm_ct_finish, a fixed-exponent
+ * inversion) and writes the result through a masked canonical step.
+ * Layouts are curdle_msm_g1's: gnark G1Affine records with (0, 0) = infinity, Montgomery fr.Elements.
+ * scalar_bits is the caller's PUBLIC bound on the scalars, 1...255 (0 or more: CURDLE_EINVAL); the walk takes that many
+ * steps.  PRECONDITIONS, as for CURDLE_G1_MUL_CONSTANT_TIME: the bases lie in the prime-order subgroup and are NOT
+ * checked (bases outside it give an unspecified result and no fault); the scalars are canonical, below r.
+ * n <= 65,536 (one pass); more is CURDLE_EINVAL: larger sizes are not what secrets come in.  n = 0 returns the
+ * infinity encoding without a device.  A scalar at or above 2^scalar_bits makes the call fail with CURDLE_EINVAL and
+ * out_jac untouched: the lanes OR a violation word into one status word, without a branch, and the host reads that word
+ * beside the result.  THIS VERDICT IS THE ONLY THING ABOUT THE SCALARS THE CALL REVEALS.
+ * Refusals happen before any device work, in this order: a null argument, scalar_bits, n, and (the _device form) device
+ * pointers that are not multiples of 16.  `stream` is as in curdle_msm_g1_device.  One MSM slot is held for the call.
+ * The host form stages the scalars through pinned memory and a device buffer and overwrites both, and both forms
+ * overwrite the term workspace (it holds k_i P_i), on the stream that used them, before they return on every path.
+ * The call's only device-to-host copy is one block of 160 bytes: the 18 words and the violation word.
+ * WHAT THE FLAG PROMISES (there is no flag: these entry points ARE the constant-time form): the instruction stream of
+ * the kernels (every branch, every exec mask beyond the end-of-array guard, every loop count) and their address stream
+ * (every load, store and atomic address) are independent of the values of scalars and of the terms made from them;
+ * they depend on n, scalar_bits, the pointers and on which points are infinity, which is public.  The host only copies
+ * scalars and never looks at them; of what the device computed it reads the violation word and the result.
+ * WHAT IT DOES NOT PROMISE: anything about data-dependent power draw and clock behaviour of the chip (a multiplier fed
+ * zeros draws less), which is not addressed; and nothing about curdle_msm_g1, whose warning above stays true.
+ * OUTSIDE THE PROMISE: the result itself and the verdict on scalar_bits; whatever the caller does with the scalars
+ * before and after.  It is NOT A DEFAULT: nothing in the library routes to it but curdle_shuffle_permute_commit_ex under
+ * its flag.
+ * Cost: one lane's chain of scalar_bits doublings and additions, then ceil(log2 n) levels of additions and one inversion:
+ * measured 5.5 ... 6.8 ms at 255 bits and 0.9 ... 2.0 ms at 9 bits for n = 4 ... 65,536, 12 to 27 times curdle_msm_g1_device
+ * (profiles/r27_msm_ct.json); the flagged shuffle step below 11.2 ... 12.0 ms at ell = 124 ... 508 against 1.4 ... 1.6 ms.
+ * ------------------------------------------------------------------------- */
+int curdle_msm_g1_ct(const uint64_t* points, const uint64_t* scalars, size_t n, unsigned scalar_bits, uint64_t out_jac[18]);
+int curdle_msm_g1_ct_device(const void* d_points, const void* d_scalars, size_t n, unsigned scalar_bits, uint64_t out_jac[18], void* stream);
+/* out[0] pairs walked by k_msm_ct_walk, out[1] its launches, out[2] sums finished; completed calls only. */
+int curdle_stat_msm_ct(unsigned long long out[3]);
+/* curdle_shuffle_permute_commit with a flags word.  flags = 0 IS that call.  A bit that is not defined here:
+ * CURDLE_EINVAL before anything else is looked at, with the outputs untouched.
+ * CURDLE_SHUFFLE_CONSTANT_TIME: the outputs and rand's state afterwards are bit for bit those of the call without
+ * flags (the same draw of the blinders at the same point); only the device work differs.  Ts | Us: ONE launch of
+ * CURDLE_G1_MUL_CONSTANT_TIME's kernel with the shared scalar k over the 2 ell records Rs | Ss, then an oblivious gather
+ * (k_g1_permute_ct: every output lane reads all ell records and keeps the one whose index equals its perm[i] by a mask:
+ * ell^2 record reads, no address made of perm).  M: k_msm_ct_walk over the CRS's Gs with the permutation as plain
+ * uint32 scalars at bit_length(ell - 1) steps, a second walk over its Hs with the blinders at 255 steps into the same
+ * workspace, ONE k_g1_sum_ct over the ell + 4 terms and the finish: M1 = sum perm[i] Gs[i], the UNBLINDED commitment to
+ * the permutation, which the call without flags brings to the host, never exists outside the device workspace.
+ * ell <= 4,096 under the flag (the gather is quadratic); more is CURDLE_EINVAL.  The range check of perm is the host's
+ * existing one: a failing check reveals only that the input was invalid.  k, perm and the blinders' staging, the
+ * unpermuted k R_i | k S_i and the term workspace are overwritten on every way out; the only device-to-host copies are
+ * Ts | Us and the 160-byte block of M and the violation word.  A flagged call moves curdle_stat_g1_mul_ct by
+ * (2 ell, 1), curdle_stat_msm_ct by (ell + 4, 2, 1) and curdle_stat_normalize not at all.
+ * The promise, what it does not cover (power draw and clock behaviour) and what is outside it are those of
+ * curdle_msm_g1_ct above, for k, perm and the blinders; the host's part outside the promise is the range check of perm,
+ * the draw of the blinders from rand and the copies.  NOT covered: curdle_prove and curdle_whisk_generate_shuffle_proof,
+ * whose MSMs see the same permutation and blinders on the default path.  It is not a default. */
+/* The gather of the flagged step on its own, everything resident: d_out[i] = d_in[d_perm[i]] for i < n, 96-byte records,
+ * d_perm n uint32 below n (an entry at or above n gives a zero record).  Every lane reads all n records; no address is
+ * made of d_perm.  n <= 4,096; d_in and d_out multiples of 16 and not overlapping, d_perm a multiple of 4; `stream` as in
+ * curdle_msm_g1_device; d_out is complete when the call returns.  Nothing is copied or wiped: the arrays are the caller's. */
+int curdle_g1_permute_ct_device(const void* d_in, const void* d_perm, size_t n, void* d_out, void* stream);
+#define CURDLE_SHUFFLE_CONSTANT_TIME 1u
+int curdle_shuffle_permute_commit_ex(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, size_t ell,
+                                     const uint32_t* perm, const uint64_t k[4], curdle_rand* rand, unsigned flags,
+                                     uint64_t* Ts_out, uint64_t* Us_out, uint64_t M_out[18], uint64_t rs_m_out[16]);
 /* Diagnostics: out[0] points normalised on the device since the library was loaded, out[1] inversion groups run
  * (one Fermat inversion each; at most one per 64 points of a launch). */
 int curdle_stat_normalize(unsigned long long out[2]);
