@@ -1,4 +1,5 @@
-// C ABI of the constant-time MSM (msm_ct_kernels.hip): curdle_msm_g1_ct / _device, curdle_stat_msm_ct, and the device
+// C ABI of the constant-time MSM (msm_ct_kernels.hip): curdle_msm_g1_ct / _device, curdle_stat_msm_ct, the batched forms
+// (curdle_msm_g1_ct_batch / _batch_device / _multi, curdle_stat_msm_ct_batch: further down, with their own notes) and the
 // flagged shuffle step (curdle_shuffle_permute_commit_ex), its first user; that call's host part -- the range check of the
 // permutation and the draw of the blinders -- is in host/proto_api.cpp.
 //
@@ -124,6 +125,184 @@ extern "C" int curdle_msm_g1_ct_device(const void* d_points, const void* d_scala
 }
 
 extern "C" int curdle_stat_msm_ct(unsigned long long out[3]) { return read_stats(out, g_msm_ct_stat, 3); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The batched forms: k MSMs (curdle_msm_g1_ct_batch / _device), or one scalar vector against k base sets
+// (curdle_msm_g1_ct_multi), in ONE launch of k_msm_ct_walk over the concatenated pairs, the segmented sum
+// (k_g1_sum_ct_seg per level, k_msm_ct_finish_seg) and ONE copy back of 144 k + 4 bytes: the k results and the violation
+// word.  The slot's small buffer holds, in this order, the results, the word the finish kernel copies the violation word
+// to, and -- from the next multiple of 16 -- the walk's status word; the table of (begin, count) goes through the second
+// pinned staging (behind the block that comes back) into the slot's `offsets` buffer.  It is made of `offsets`: public.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t kMsmCtBatchMax = 4096;  // MSMs of one call
+
+// batched calls | MSMs in them | level launches (k_g1_sum_ct_seg); completed calls that ran on a device only
+std::atomic<unsigned long long> g_msm_ct_batch_stat[3];
+
+struct BatchShape {
+  size_t k = 0, lo = 0, total = 0;
+  std::vector<uint32_t> seg;     // (begin, count) per MSM, begin relative to the call's first pair
+  std::vector<uint32_t> counts;  // count per MSM
+  size_t nonempty = 0;
+};
+
+// What the batch refuses after the null arguments: scalar_bits, k, offsets that decrease, the total.
+int batch_shape(const size_t* offsets, size_t k, unsigned bits, BatchShape* sh) {
+  if (bits < 1 || bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", bits);
+  if (k > kMsmCtBatchMax) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
+  for (size_t j = 0; j < k; j++)
+    if (offsets[j + 1] < offsets[j]) return fail(CURDLE_EINVAL, "offsets decrease at %zu", j);
+  sh->k = k;
+  sh->lo = k ? offsets[0] : 0;
+  sh->total = k ? offsets[k] - offsets[0] : 0;
+  if (sh->total > kMsmCtMax) return fail(CURDLE_EINVAL, "%zu pairs in all exceed the supported 65,536 pairs", sh->total);
+  sh->seg.resize(2 * k);
+  sh->counts.resize(k);
+  for (size_t j = 0; j < k; j++) {
+    sh->seg[2 * j] = (uint32_t)(offsets[j] - sh->lo);
+    sh->seg[2 * j + 1] = sh->counts[j] = (uint32_t)(offsets[j + 1] - offsets[j]);
+    sh->nonempty += offsets[j + 1] != offsets[j];
+  }
+  return CURDLE_OK;
+}
+
+size_t batch_out_bytes(size_t k) { return 144 * k + 4; }                         // what comes back
+size_t batch_status_offset(size_t k) { return (144 * k + 4 + 15) / 16 * 16; }    // the walk's status word
+
+// On the call's stream, behind the scalars and the points: the status word, the table, the walk, the sum, the copy, the
+// wait, the verdict.  h_block: pinned, batch_out_bytes(k) and the table behind it (from the next multiple of 16).
+int batch_walk_sum_fetch(Slot& S, const BatchShape& sh, const void* d_points, const void* d_scalars, unsigned bits,
+                         uint64_t* out_jac, hipStream_t st) {
+  const size_t k = sh.k, status_off = batch_status_offset(k), table_bytes = 8 * k;
+  int r;
+  if ((r = ensure(S.results, status_off + 16))) return r;
+  if ((r = ensure(S.offsets, table_bytes))) return r;
+  if ((r = ensure_pinned(S, 1, status_off + table_bytes))) return r;
+  uint8_t* h_block = static_cast<uint8_t*>(S.h_stage[1]);
+  uint8_t* d_res = static_cast<uint8_t*>(S.results.p);
+  uint32_t* d_status = reinterpret_cast<uint32_t*>(d_res + status_off);
+  memcpy(h_block + status_off, sh.seg.data(), table_bytes);
+  HIP_TRY(hipMemsetAsync(d_status, 0, 16, st));
+  HIP_TRY(hipMemcpyAsync(S.offsets.p, h_block + status_off, table_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(launch_msm_ct_walk(d_points, d_scalars, kMsmCtScalarFr, bits, (uint32_t)sh.total, S.partials.p, d_status, st));
+  uint32_t levels = 0;
+  HIP_TRY(launch_msm_ct_sum_seg(S.partials.p, S.offsets.p, sh.counts.data(), (uint32_t)k, d_status, d_res, &levels, st));
+  HIP_TRY(hipMemcpyAsync(h_block, d_res, batch_out_bytes(k), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint32_t verdict;
+  memcpy(&verdict, h_block + 144 * k, 4);
+  if (verdict) return fail(CURDLE_EINVAL, "a scalar is not below 2^scalar_bits");
+  memcpy(out_jac, h_block, 144 * k);
+  g_msm_ct_stat[0].fetch_add(sh.total, std::memory_order_relaxed);
+  g_msm_ct_stat[1].fetch_add(1, std::memory_order_relaxed);
+  g_msm_ct_stat[2].fetch_add(sh.nonempty, std::memory_order_relaxed);
+  g_msm_ct_batch_stat[0].fetch_add(1, std::memory_order_relaxed);
+  g_msm_ct_batch_stat[1].fetch_add(k, std::memory_order_relaxed);
+  g_msm_ct_batch_stat[2].fetch_add(levels, std::memory_order_relaxed);
+  return CURDLE_OK;
+}
+
+// The host forms behind their checks: `fill` writes the scalars (sh.total records of 32 bytes) and then the points
+// (96 bytes each) into the pinned staging it is handed.
+template <class Fill>
+int batch_from_host(const BatchShape& sh, unsigned bits, uint64_t* out_jac, const char* what, Fill&& fill) {
+  const size_t n = sh.total;
+  SlotHold H(cur(), true, nullptr);
+  WipeList W(H.stream());
+  H.wipe_on_exit(&W, what);
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
+    int r;
+    if ((r = ensure(S.points, n * 96))) return r;
+    if ((r = ensure(S.scalars, n * 32))) return r;
+    if ((r = ensure(S.partials, n * kMsmCtTermBytes))) return r;
+    if ((r = ensure_pinned(S, 0, n * 32 + n * 96))) return r;  // scalars | points
+    W.note_device(S.scalars.p, n * 32);
+    W.note_device(S.partials.p, n * kMsmCtTermBytes);
+    W.note_host(S.h_stage[0], n * 32);
+    uint8_t* h_sc = static_cast<uint8_t*>(S.h_stage[0]);
+    uint8_t* h_pt = h_sc + n * 32;
+    fill(h_sc, h_pt);
+    HIP_TRY(hipMemcpyAsync(S.scalars.p, h_sc, n * 32, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S.points.p, h_pt, n * 96, hipMemcpyHostToDevice, st));
+    return batch_walk_sum_fetch(S, sh, S.points.p, S.scalars.p, bits, out_jac, st);
+  });
+}
+}  // namespace
+
+extern "C" int curdle_msm_g1_ct_batch(const uint64_t* points, const uint64_t* scalars, const size_t* offsets, size_t k,
+                                      unsigned scalar_bits, uint64_t* out_jac) {
+  if (!offsets || (k && (!out_jac || !points || !scalars))) return fail(CURDLE_EINVAL, "null argument");
+  BatchShape sh;
+  if (int rc = batch_shape(offsets, k, scalar_bits, &sh)) return rc;
+  if (k == 0) return CURDLE_OK;
+  if (sh.total == 0) {
+    for (size_t j = 0; j < k; j++) set_out_infinity(out_jac + 18 * j);
+    return CURDLE_OK;
+  }
+  return batch_from_host(sh, scalar_bits, out_jac, "batched constant-time MSM: clearing the scalars and the terms",
+                         [&](uint8_t* h_sc, uint8_t* h_pt) {
+                           memcpy(h_sc, scalars + 4 * sh.lo, sh.total * 32);
+                           memcpy(h_pt, points + 12 * sh.lo, sh.total * 96);
+                         });
+}
+
+extern "C" int curdle_msm_g1_ct_batch_device(const void* d_points, const void* d_scalars, const size_t* offsets, size_t k,
+                                             unsigned scalar_bits, uint64_t* out_jac, void* stream) {
+  if (!offsets || (k && (!out_jac || !d_points || !d_scalars))) return fail(CURDLE_EINVAL, "null argument");
+  BatchShape sh;
+  if (int rc = batch_shape(offsets, k, scalar_bits, &sh)) return rc;
+  if (k == 0) return CURDLE_OK;
+  if (!aligned16(d_points) || !aligned16(d_scalars)) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
+  if (sh.total == 0) {
+    for (size_t j = 0; j < k; j++) set_out_infinity(out_jac + 18 * j);
+    return CURDLE_OK;
+  }
+  SlotHold H(cur(), true, stream);
+  WipeList W(H.stream());
+  H.wipe_on_exit(&W, "batched constant-time MSM: clearing the terms");
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    if (int r = ensure(S.partials, sh.total * kMsmCtTermBytes)) return r;
+    W.note_device(S.partials.p, sh.total * kMsmCtTermBytes);
+    // the caller's arrays are read where they are, from the call's first pair (96 and 32 bytes a record keep the alignment)
+    return batch_walk_sum_fetch(S, sh, static_cast<const uint8_t*>(d_points) + 96 * sh.lo,
+                                static_cast<const uint8_t*>(d_scalars) + 32 * sh.lo, scalar_bits, out_jac, H.stream());
+  });
+}
+
+// One scalar vector against k base sets: the vector is replicated k times in the pinned staging (a host copy of public
+// length) and the call is the batch of k MSMs of n pairs; the replicas are the staging's scalars and are wiped with it.
+extern "C" int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t k, const uint64_t* scalars, size_t n,
+                                      unsigned scalar_bits, uint64_t* out_jac) {
+  if (k && (!out_jac || !points_sets || (n && !scalars))) return fail(CURDLE_EINVAL, "null argument");
+  if (scalar_bits < 1 || scalar_bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", scalar_bits);
+  if (k > kMsmCtBatchMax) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
+  if (k == 0) return CURDLE_OK;
+  if (n > kMsmCtMax / k) return fail(CURDLE_EINVAL, "k n = %zu x %zu exceeds the supported 65,536 pairs", k, n);
+  if (n == 0) {
+    for (size_t j = 0; j < k; j++) set_out_infinity(out_jac + 18 * j);
+    return CURDLE_OK;
+  }
+  for (size_t j = 0; j < k; j++)
+    if (!points_sets[j]) return fail(CURDLE_EINVAL, "null argument: base set %zu", j);
+  std::vector<size_t> offsets(k + 1);
+  for (size_t j = 0; j <= k; j++) offsets[j] = j * n;
+  BatchShape sh;
+  if (int rc = batch_shape(offsets.data(), k, scalar_bits, &sh)) return rc;
+  return batch_from_host(sh, scalar_bits, out_jac,
+                         "constant-time MSM over k base sets: clearing the replicated scalars and the terms",
+                         [&](uint8_t* h_sc, uint8_t* h_pt) {
+                           for (size_t j = 0; j < k; j++) {
+                             memcpy(h_sc + j * n * 32, scalars, n * 32);
+                             memcpy(h_pt + j * n * 96, points_sets[j], n * 96);
+                           }
+                         });
+}
+
+extern "C" int curdle_stat_msm_ct_batch(unsigned long long out[3]) { return read_stats(out, g_msm_ct_batch_stat, 3); }
 
 // The oblivious gather of the flagged shuffle step on its own, resident: d_out[i] = d_in[d_perm[i]], 96-byte records.
 extern "C" int curdle_g1_permute_ct_device(const void* d_in, const void* d_perm, size_t n, void* d_out, void* stream) {

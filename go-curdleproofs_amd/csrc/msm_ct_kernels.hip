@@ -1,7 +1,7 @@
 // Constant-time multi-scalar multiplication: sum_i k_i P_i with an instruction stream and an address stream that do
 // not depend on the scalars.  The twin of the bucket MSM (msm_sort_kernels.hip, msm_accumulate_kernel.hip), whose sort,
 // bucket addresses and large-bucket queue are all functions of the scalars, in the manner of k_g1_mul_ct
-// (g1_mul_ct_kernels.hip).  Four kernels; the rule of what may depend on a secret is the one of g1_walk_ct.h.
+// (g1_mul_ct_kernels.hip).  Six kernels; the rule of what may depend on a secret is the one of g1_walk_ct.h.
 //
 // k_msm_ct_walk.  One lane per (base, scalar) pair: the walk of g1_walk_ct.h with a PUBLIC step count `bits` (1...255,
 // a kernel argument): the scalar is first shifted left by 256 - bits, one bit a step in a rolled loop whose trip count
@@ -29,8 +29,20 @@
 // accumulating in[j] & mask(perm[i] == j): n^2 record reads and no address made of perm.  `halves` record arrays of n
 // records lie behind each other and are permuted alike (the shuffle's Ts | Us).
 //
+// k_g1_sum_ct_seg, k_msm_ct_finish_seg.  The same sum over k segments of ONE term array (the batched call: one walk over
+// the concatenated pairs of k MSMs): MSM j owns term[begin_j, begin_j + count_j) and a PUBLIC table of (begin, count)
+// says so.  Block (x, j) of k_g1_sum_ct_seg reads its entry at a wave-uniform address, derives the segment's size at
+// this level from count_j and the level's number alone (m <- ceil(m / 2) once per earlier level, while m > kSumTail)
+// and, if that is still above kSumTail, runs k_g1_sum_ct's level on the segment; the host launches levels while any
+// segment is above kSumTail.  Block j of k_msm_ct_finish_seg recomputes where the levels left its segment
+// (while m > kSumTail: m <- ceil(m / 2)), runs k_msm_ct_finish's tail on it and writes result j, 36 words, at
+// out + 36 j; an empty segment (public) gives the infinity encoding; the status word follows the k results.  Per
+// segment the order of additions is exactly k_g1_sum_ct's and k_msm_ct_finish's on that segment alone.
+//
 // Plain loads and stores, one atomic OR, no LDS, no inline assembly beyond the field layer's.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "msm_kernels_common.h"
 #include "g1_walk_ct.h"
@@ -121,23 +133,31 @@ __global__ void __launch_bounds__(kBlock, 1) k_g1_sum_ct(X28* term, u32 m) {
   d28::store(term + i, a);
 }
 
-__global__ void __launch_bounds__(kBlock, 1) k_msm_ct_finish(X28* term, u32 m, const u32* status, u32* out) {
+namespace {
+// One level of the fold on one lane: term[i] = add_ct(term[i], term[i + h]).
+__device__ __forceinline__ void sum_pair(X28* term, u32 i, u32 h) {
+  X28 a, b;
+  d28::load(a, term + i);
+  d28::load(b, term + i + h);
+  add_ct(a, b);
+  d28::store(term + i, a);
+}
+
+// The levels one block runs, m <= kSumTail terms at `term`, with a barrier between them: every lane of the block.
+__device__ __forceinline__ void sum_tail(X28* term, u32 m) {
 #pragma unroll 1
   while (m > 1) {
     const u32 h = (m + 1) / 2;
 #pragma unroll 1
-    for (u32 i = threadIdx.x; i < m - h; i += kBlock) {
-      X28 a, b;
-      d28::load(a, term + i);
-      d28::load(b, term + i + h);
-      add_ct(a, b);
-      d28::store(term + i, a);
-    }
+    for (u32 i = threadIdx.x; i < m - h; i += kBlock) sum_pair(term, i, h);
     __threadfence_block();
     __syncthreads();
     m = h;
   }
-  if (threadIdx.x != 0) return;
+}
+
+// One lane: *term normalised into the 36 words curdle_msm_g1 returns.
+__device__ __forceinline__ void write_result(const X28* term, u32* out) {
   X28 acc;
   d28::load(acc, term);
   const u32 fin = ~zero_mask(acc.zz);
@@ -159,7 +179,49 @@ __global__ void __launch_bounds__(kBlock, 1) k_msm_ct_finish(X28* term, u32 m, c
     out[12 + j] = (w[12 + j] & fin) | (one & ~fin);
     out[24 + j] = one & fin;
   }
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock, 1) k_msm_ct_finish(X28* term, u32 m, const u32* status, u32* out) {
+  sum_tail(term, m);
+  if (threadIdx.x != 0) return;
+  write_result(term, out);
   out[36] = *status;
+}
+
+// seg[j] = (begin_j, count_j), public.  `level` counts the launches before this one.
+__global__ void __launch_bounds__(kBlock, 1) k_g1_sum_ct_seg(X28* term, const uint2* __restrict__ seg, u32 level) {
+  const uint2 s = seg[blockIdx.y];  // a wave-uniform address
+  u32 m = s.y;
+#pragma unroll 1
+  for (u32 l = 0; l < level && m > kMsmCtSumTail; l++) m = (m + 1) / 2;
+  if (m <= kMsmCtSumTail) return;
+  const u32 h = (m + 1) / 2;
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= m - h) return;
+  sum_pair(term + s.x, i, h);
+}
+
+__global__ void __launch_bounds__(kBlock, 1)
+    k_msm_ct_finish_seg(X28* term, const uint2* __restrict__ seg, const u32* status, u32* out) {
+  const uint2 s = seg[blockIdx.x];  // a wave-uniform address
+  u32* res = out + 36 * (size_t)blockIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[36 * (size_t)gridDim.x] = *status;
+  if (s.y == 0) {  // an empty MSM: public
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int j = 0; j < 12; j++) {
+      res[j] = res[12 + j] = FpParams::one(j);
+      res[24 + j] = 0;
+    }
+    return;
+  }
+  u32 m = s.y;
+#pragma unroll 1
+  while (m > kMsmCtSumTail) m = (m + 1) / 2;  // where the level launches left the segment
+  sum_tail(term + s.x, m);
+  if (threadIdx.x != 0) return;
+  write_result(term + s.x, res);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -208,6 +270,27 @@ hipError_t launch_msm_ct_sum(void* term, uint32_t m, const uint32_t* status, voi
     m = h;
   }
   hipLaunchKernelGGL(k_msm_ct_finish, dim3(1), dim3(kBlock), 0, stream, (X28*)term, (u32)m, status, (u32*)out40);
+  return hipGetLastError();
+}
+
+hipError_t launch_msm_ct_sum_seg(void* term, const void* seg, const uint32_t* counts, uint32_t k, const uint32_t* status,
+                                 void* out, uint32_t* levels, hipStream_t stream) {
+  if (k == 0 || k > 65535) return hipErrorInvalidValue;
+  u32 level = 0;
+  for (;; level++) {
+    // the widest addition count of this level, by the kernel's own rule
+    u32 widest = 0;
+    for (u32 j = 0; j < k; j++) {
+      u32 m = counts[j];
+      for (u32 l = 0; l < level && m > kMsmCtSumTail; l++) m = (m + 1) / 2;
+      if (m > kMsmCtSumTail) widest = std::max(widest, m - (m + 1) / 2);
+    }
+    if (widest == 0) break;
+    hipLaunchKernelGGL(k_g1_sum_ct_seg, dim3(cdiv(widest, kBlock), k), dim3(kBlock), 0, stream, (X28*)term, (const uint2*)seg, level);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  if (levels) *levels = level;
+  hipLaunchKernelGGL(k_msm_ct_finish_seg, dim3(k), dim3(kBlock), 0, stream, (X28*)term, (const uint2*)seg, status, (u32*)out);
   return hipGetLastError();
 }
 

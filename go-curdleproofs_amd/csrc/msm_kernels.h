@@ -354,6 +354,12 @@ hipError_t launch_g1_mul_ct(const void* points, uint32_t point_stride, const voi
 //   launch_msm_ct_sum: folds term[0, m) in place in the fixed fold-in-half order (h = ceil(m / 2), term[i] += term[i + h]
 //     for i < m - h, m <- h), one launch per level above kMsmCtSumTail terms and one block for the rest, which then
 //     normalises term[0] and writes out40: the 36 words of curdle_msm_g1's result, *status behind them, three words untouched.
+//   launch_msm_ct_sum_seg: the same sum over k segments of one term array, 1 <= k <= 65,535.  seg: k device records
+//     (begin, count), two uint32 each; counts: the same counts on the host, which decide how many level launches there
+//     are (k_g1_sum_ct_seg, one per level while any segment is above kMsmCtSumTail; *levels receives the number).  One
+//     block per segment then finishes it as launch_msm_ct_sum does and writes 36 words at out + 36 j (the infinity
+//     encoding for an empty segment); *status follows the k results.  Per segment the order of additions is
+//     launch_msm_ct_sum's on that segment alone.
 //   launch_g1_permute_ct: out[h n + i] = in[h n + perm[i]] for i < n, h < halves, 96-byte records, perm secret: every
 //     lane reads all n records of its half.  out must not overlap in.
 enum { kMsmCtScalarFr = 0, kMsmCtScalarU32 = 1 };
@@ -362,6 +368,8 @@ static constexpr uint32_t kMsmCtSumTail = 512;
 hipError_t launch_msm_ct_walk(const void* points, const void* scalars, int scalar_form, uint32_t bits, uint32_t n, void* term,
                               uint32_t* status, hipStream_t stream);
 hipError_t launch_msm_ct_sum(void* term, uint32_t m, const uint32_t* status, void* out40, hipStream_t stream);
+hipError_t launch_msm_ct_sum_seg(void* term, const void* seg, const uint32_t* counts, uint32_t k, const uint32_t* status,
+                                 void* out, uint32_t* levels, hipStream_t stream);
 hipError_t launch_g1_permute_ct(const void* in, const uint32_t* perm, uint32_t n, uint32_t halves, void* out, hipStream_t stream);
 
 // normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion

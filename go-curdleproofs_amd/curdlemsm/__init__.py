@@ -92,6 +92,8 @@ SYMBOLS = [
     "curdle_msm_reduce_plan", "curdle_msm_stream_plan",
     "curdle_msm_g1_ct", "curdle_msm_g1_ct_device", "curdle_stat_msm_ct", "curdle_shuffle_permute_commit_ex",
     "curdle_g1_permute_ct_device",
+    "curdle_msm_g1_ct_batch", "curdle_msm_g1_ct_batch_device", "curdle_msm_g1_ct_multi", "curdle_stat_msm_ct_batch",
+    "curdle_prove_ex", "curdle_stat_alg_msm",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -445,6 +447,67 @@ def stat_msm_ct() -> dict:
     out = (C.c_ulonglong * 3)()
     _check(_stat_msm_ct(out))
     return {"pairs": int(out[0]), "walks": int(out[1]), "sums": int(out[2])}
+
+
+_msm_g1_ct_batch = _sig("curdle_msm_g1_ct_batch", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_uint, _vp)
+_msm_g1_ct_batch_device = _sig("curdle_msm_g1_ct_batch_device", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_uint, _vp, _vp)
+_msm_g1_ct_multi = _sig("curdle_msm_g1_ct_multi", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint, _vp)
+_stat_msm_ct_batch = _sig("curdle_stat_msm_ct_batch", C.c_int, C.POINTER(C.c_ulonglong))
+_stat_alg_msm = _sig("curdle_stat_alg_msm", C.c_int, C.POINTER(C.c_ulonglong))
+
+
+def msm_g1_ct_batch(points, scalars, offsets, scalar_bits: int = 255) -> np.ndarray:
+    """msm_g1_batch for SECRET scalars (curdle_msm_g1_ct_batch): k MSMs in one constant-time walk -> uint64[k, 18], row j
+    bit for bit msm_g1_ct on MSM j.  At most 65,536 pairs in all and 4,096 MSMs; one scalar_bits for the call."""
+    points = _as_u64(points, 12)
+    scalars = _as_u64(scalars, 4)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)  # size_t
+    k = len(offs) - 1
+    out = np.zeros((k, 18), dtype=np.uint64)
+    _check(_msm_g1_ct_batch(_ptr(points), _ptr(scalars), _ptr(offs), k, int(scalar_bits), _ptr(out)))
+    return out
+
+
+def msm_g1_ct_batch_device(d_points: int, d_scalars: int, offsets, scalar_bits: int = 255, stream: int = 0) -> np.ndarray:
+    """msm_g1_ct_batch on device-resident, concatenated inputs (curdle_msm_g1_ct_batch_device; raw device pointers,
+    multiples of 16; offsets stays a host array)."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    k = len(offs) - 1
+    out = np.zeros((k, 18), dtype=np.uint64)
+    _check(_msm_g1_ct_batch_device(d_points or None, d_scalars or None, _ptr(offs), k, int(scalar_bits), _ptr(out),
+                                   stream or None))
+    return out
+
+
+def msm_g1_ct_multi(points_sets, scalars, scalar_bits: int = 255) -> np.ndarray:
+    """msm_g1_multi for SECRET scalars (curdle_msm_g1_ct_multi): one scalar vector against k base sets of n points each
+    -> uint64[k, 18]; k n <= 65,536."""
+    sets = [_as_u64(p, 12) for p in points_sets]
+    scalars = _as_u64(scalars, 4)
+    n = scalars.shape[0] if scalars.size else 0
+    for s in sets:
+        if (s.shape[0] if s.size else 0) != n:
+            raise CurdleError(EINVAL, "len(points) != len(scalars)")
+    arr = (_vp * len(sets))(*[s.ctypes.data for s in sets])
+    out = np.zeros((len(sets), 18), dtype=np.uint64)
+    _check(_msm_g1_ct_multi(C.cast(arr, _vp), len(sets), _ptr(scalars), n, int(scalar_bits), _ptr(out)))
+    return out
+
+
+def stat_msm_ct_batch() -> dict:
+    """Batched constant-time MSM calls, the MSMs in them and the level launches of k_g1_sum_ct_seg since the library
+    was loaded."""
+    out = (C.c_ulonglong * 3)()
+    _check(_stat_msm_ct_batch(out))
+    return {"calls": int(out[0]), "msms": int(out[1]), "levels": int(out[2])}
+
+
+def stat_alg_msm() -> dict:
+    """The protocol code's MSM funnel (alg::MultiExp / MultiExpBatch / MultiExpShared): calls and pairs that went to the
+    bucket MSM, and calls and pairs that went to the constant-time MSM."""
+    out = (C.c_ulonglong * 4)()
+    _check(_stat_alg_msm(out))
+    return {"bucket_calls": int(out[0]), "bucket_pairs": int(out[1]), "ct_calls": int(out[2]), "ct_pairs": int(out[3])}
 
 
 def msm_g1_device_submit(d_points: int, d_scalars: int, n: int, window_bits: int = 0, win_begin: int = 0,
@@ -856,16 +919,26 @@ def shuffle_permute_commit(crs: CRS, Rs, Ss, perm, k, rand: Rand, flags=None):
     return Ts, Us, M, rs_m
 
 
-def prove(crs: CRS, Rs, Ss, Ts, Us, M, perm, k, rs_m, rand: Rand) -> bytes:
-    """curdleproof.Prove (curdleproof.go:38); returns the serialised proof."""
+PROVE_MSM_CONSTANT_TIME = 1                           # CURDLE_PROVE_MSM_CONSTANT_TIME
+_prove_ex = _sig("curdle_prove_ex", C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_uint, _vp,
+                 C.c_size_t, C.POINTER(C.c_size_t))
+
+
+def prove(crs: CRS, Rs, Ss, Ts, Us, M, perm, k, rs_m, rand: Rand, flags=None) -> bytes:
+    """curdleproof.Prove (curdleproof.go:38); returns the serialised proof.  flags: None calls the entry point without
+    flags; an integer (0, PROVE_MSM_CONSTANT_TIME) calls curdle_prove_ex with it."""
     Rs, Ss, Ts, Us = (_as_u64(a, 12) for a in (Rs, Ss, Ts, Us))
     M, k, rs_m = _as_u64(M), _as_u64(k), _as_u64(rs_m)
     perm = np.ascontiguousarray(perm, dtype=np.uint32)
     cap = 1 << 16
     buf = np.zeros(cap, dtype=np.uint8)
     n = C.c_size_t(0)
-    _check(_prove(crs._h, _ptr(Rs), _ptr(Ss), _ptr(Ts), _ptr(Us), crs.ell, _ptr(M), _ptr(perm), _ptr(k), _ptr(rs_m),
-                  rand._h, _ptr(buf), cap, C.byref(n)))
+    if flags is None:
+        _check(_prove(crs._h, _ptr(Rs), _ptr(Ss), _ptr(Ts), _ptr(Us), crs.ell, _ptr(M), _ptr(perm), _ptr(k), _ptr(rs_m),
+                      rand._h, _ptr(buf), cap, C.byref(n)))
+    else:
+        _check(_prove_ex(crs._h, _ptr(Rs), _ptr(Ss), _ptr(Ts), _ptr(Us), crs.ell, _ptr(M), _ptr(perm), _ptr(k),
+                         _ptr(rs_m), rand._h, int(flags), _ptr(buf), cap, C.byref(n)))
     return bytes(buf[: n.value])
 
 

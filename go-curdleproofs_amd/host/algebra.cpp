@@ -5,9 +5,22 @@
 
 #include "host_ops.h"
 
+#include <string.h>
+
+#include <atomic>
 #include <stdexcept>
 
 #include "../../include/curdle_msm.h"
+
+// The constant-time MSM lives in the GPU backend (csrc/msm_ct_api.hip).  Weak here: a backend without it -- the host
+// layer linked over a plain CPU backend, as the sanitizer builds are -- still links, and an MSM under a
+// ConstantTimeMsmScope fails with CURDLE_ENODEV instead of running anywhere else.
+extern "C" int curdle_msm_g1_ct(const uint64_t* points, const uint64_t* scalars, size_t n, unsigned scalar_bits,
+                                uint64_t out_jac[18]) __attribute__((weak));
+extern "C" int curdle_msm_g1_ct_batch(const uint64_t* points, const uint64_t* scalars, const size_t* offsets, size_t k,
+                                      unsigned scalar_bits, uint64_t* out_jac) __attribute__((weak));
+extern "C" int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t k, const uint64_t* scalars, size_t n,
+                                      unsigned scalar_bits, uint64_t* out_jac) __attribute__((weak));
 
 namespace curdle {
 namespace alg {
@@ -307,18 +320,47 @@ static MsmError msm_error(int rc) {
   return MsmError(std::string("computing msm: ") + buf + " (rc " + std::to_string(rc) + ")", rc);
 }
 
+static thread_local bool t_msm_ct = false;
+static std::atomic<unsigned long long> g_msm_counters[4];
+static constexpr unsigned kCtScalarBits = 255;  // every canonical scalar: r < 2^255
+
+ConstantTimeMsmScope::ConstantTimeMsmScope() : prev_(t_msm_ct) { t_msm_ct = true; }
+ConstantTimeMsmScope::~ConstantTimeMsmScope() { t_msm_ct = prev_; }
+bool ConstantTimeMsmScope::Available() { return curdle_msm_g1_ct && curdle_msm_g1_ct_batch && curdle_msm_g1_ct_multi; }
+
+void ReadMsmCounters(unsigned long long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_msm_counters[i].load(std::memory_order_relaxed);
+}
+
+static void count_msm(bool ct, size_t pairs) {
+  g_msm_counters[ct ? 2 : 0].fetch_add(1, std::memory_order_relaxed);
+  g_msm_counters[ct ? 3 : 1].fetch_add(pairs, std::memory_order_relaxed);
+}
+
+static int no_ct_backend() {
+  return curdle_set_last_error(CURDLE_ENODEV, "the constant-time MSM is not part of this backend: no device code to run it on");
+}
+
 Point MultiExp(const std::vector<G1Affine>& points, const std::vector<Scalar>& scalars) {
   if (points.size() != scalars.size()) throw std::runtime_error("computing msm: len(points) != len(scalars)");
+  const bool ct = t_msm_ct;
+  const uint64_t* P = reinterpret_cast<const uint64_t*>(points.data());
+  const uint64_t* S = reinterpret_cast<const uint64_t*>(scalars.data());
   uint64_t out[18];
-  int rc = curdle_msm_g1(reinterpret_cast<const uint64_t*>(points.data()),
-                         reinterpret_cast<const uint64_t*>(scalars.data()), points.size(), out);
+  int rc;
+  if (!ct)
+    rc = curdle_msm_g1(P, S, points.size(), out);
+  else
+    rc = curdle_msm_g1_ct ? curdle_msm_g1_ct(P, S, points.size(), kCtScalarBits, out) : no_ct_backend();
   if (rc != CURDLE_OK) throw msm_error(rc);
+  count_msm(ct, points.size());
   return Point::FromJac(out);
 }
 
 std::vector<Point> MultiExpBatch(const std::vector<const std::vector<G1Affine>*>& points,
                                  const std::vector<const std::vector<Scalar>*>& scalars) {
   if (points.size() != scalars.size()) throw std::runtime_error("computing msm: batch shape");
+  const bool ct = t_msm_ct;
   const size_t k = points.size();
   std::vector<size_t> off(k + 1, 0);
   for (size_t j = 0; j < k; j++) {
@@ -327,14 +369,27 @@ std::vector<Point> MultiExpBatch(const std::vector<const std::vector<G1Affine>*>
   }
   std::vector<G1Affine> P(off[k]);
   std::vector<Scalar> S(off[k]);
+  struct Clear {  // the concatenated copy of the scalars does not outlive a constant-time call
+    std::vector<Scalar>& v;
+    bool on;
+    ~Clear() {
+      if (on && !v.empty()) explicit_bzero(v.data(), v.size() * sizeof(Scalar));
+    }
+  } clear{S, ct};
   for (size_t j = 0; j < k; j++) {
     std::copy(points[j]->begin(), points[j]->end(), P.begin() + off[j]);
     std::copy(scalars[j]->begin(), scalars[j]->end(), S.begin() + off[j]);
   }
   std::vector<uint64_t> out(18 * k);
-  int rc = curdle_msm_g1_batch(reinterpret_cast<const uint64_t*>(P.data()), reinterpret_cast<const uint64_t*>(S.data()),
-                               off.data(), k, out.data());
+  const uint64_t* Pw = reinterpret_cast<const uint64_t*>(P.data());
+  const uint64_t* Sw = reinterpret_cast<const uint64_t*>(S.data());
+  int rc;
+  if (!ct)
+    rc = curdle_msm_g1_batch(Pw, Sw, off.data(), k, out.data());
+  else
+    rc = curdle_msm_g1_ct_batch ? curdle_msm_g1_ct_batch(Pw, Sw, off.data(), k, kCtScalarBits, out.data()) : no_ct_backend();
   if (rc != CURDLE_OK) throw msm_error(rc);
+  count_msm(ct, off[k]);
   std::vector<Point> res(k);
   for (size_t j = 0; j < k; j++) res[j] = Point::FromJac(out.data() + 18 * j);
   return res;
@@ -342,6 +397,7 @@ std::vector<Point> MultiExpBatch(const std::vector<const std::vector<G1Affine>*>
 
 std::vector<Point> MultiExpShared(const std::vector<const std::vector<G1Affine>*>& sets,
                                   const std::vector<Scalar>& scalars) {
+  const bool ct = t_msm_ct;
   const size_t k = sets.size();
   std::vector<const uint64_t*> ptrs(k);
   for (size_t j = 0; j < k; j++) {
@@ -353,8 +409,15 @@ std::vector<Point> MultiExpShared(const std::vector<const std::vector<G1Affine>*
     std::vector<Point> res(k, Point::Infinity());
     return res;
   }
-  int rc = curdle_msm_g1_multi(ptrs.data(), k, reinterpret_cast<const uint64_t*>(scalars.data()), scalars.size(), out.data());
+  const uint64_t* Sw = reinterpret_cast<const uint64_t*>(scalars.data());
+  int rc;
+  if (!ct)
+    rc = curdle_msm_g1_multi(ptrs.data(), k, Sw, scalars.size(), out.data());
+  else
+    rc = curdle_msm_g1_ct_multi ? curdle_msm_g1_ct_multi(ptrs.data(), k, Sw, scalars.size(), kCtScalarBits, out.data())
+                                : no_ct_backend();
   if (rc != CURDLE_OK) throw msm_error(rc);
+  count_msm(ct, k * scalars.size());
   std::vector<Point> res(k);
   for (size_t j = 0; j < k; j++) res[j] = Point::FromJac(out.data() + 18 * j);
   return res;

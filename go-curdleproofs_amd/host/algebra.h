@@ -168,6 +168,25 @@ std::vector<Point> MultiExpBatch(const std::vector<const std::vector<G1Affine>*>
 std::vector<Point> MultiExpShared(const std::vector<const std::vector<G1Affine>*>& sets,
                                   const std::vector<Scalar>& scalars);
 
+// While one of these lives on a thread, the three functions above send that thread's MSMs to the constant-time
+// primitive (curdle_msm_g1_ct, _ct_batch, _ct_multi at scalar_bits = 255) instead of the bucket MSM: same results, bit
+// for bit.  Thread-local and scoped: other threads, and this one afterwards, are as before.  A backend without the
+// primitive makes the first such MSM throw MsmError(CURDLE_ENODEV); Available() says so beforehand.
+class ConstantTimeMsmScope {
+ public:
+  ConstantTimeMsmScope();
+  ~ConstantTimeMsmScope();
+  ConstantTimeMsmScope(const ConstantTimeMsmScope&) = delete;
+  ConstantTimeMsmScope& operator=(const ConstantTimeMsmScope&) = delete;
+  static bool Available();
+
+ private:
+  bool prev_;
+};
+// bucket-MSM calls | their pairs | constant-time calls | their pairs, counted in the three functions above when the
+// call they made succeeded; one scalar vector against k sets of n counts k n pairs.
+void ReadMsmCounters(unsigned long long out[4]);
+
 // out[i] = addends[i] + scalars[i] * points[i]; scalars.size() is points.size(), or 1 for one
 // scalar shared by all; addends may be null.  The independent scalar multiplications that
 // dominate the prover: a batch of at least kScalarMulBatchMin goes to

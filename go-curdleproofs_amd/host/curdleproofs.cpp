@@ -115,6 +115,7 @@ bool ProverFoldsBases() { return knobs::get(knobs::PROVER_FOLD_BASES) > 0; }
 
 }  // namespace
 
+bool ProverFoldBasesEnabled() { return ProverFoldsBases(); }
 int SetEagerChecks(int eager) { return EagerFlag().exchange(eager ? 1 : 0); }
 bool EagerChecksEnabled() { return EagerChecks(); }
 

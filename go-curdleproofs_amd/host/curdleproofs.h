@@ -383,6 +383,9 @@ Proof Prove(const CRS& crs, const std::vector<G1Affine>& Rs, const std::vector<G
             const std::vector<G1Affine>& Ts, const std::vector<G1Affine>& Us, const Point& M,
             const std::vector<uint32_t>& perm, const Scalar& k, const std::vector<Scalar>& rs_m,
             common::Rand& rand);                                            // :38
+// Knob PROVER_FOLD_BASES is on: the recursive provers multiply H by a secret inner product on the host, so a Prove
+// whose MSMs are to be constant time is refused (curdle_prove_ex).
+bool ProverFoldBasesEnabled();
 bool Verify(const Proof& proof, const CRS& crs, const std::vector<G1Affine>& Rs, const std::vector<G1Affine>& Ss,
             const std::vector<G1Affine>& Ts, const std::vector<G1Affine>& Us, const Point& M,
             common::Rand& rand);                                            // :199

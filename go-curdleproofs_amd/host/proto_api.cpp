@@ -1,6 +1,7 @@
 // C ABI of the host-side protocol restatement (curdleproofs.h): CRS, the shuffle
 // instance, curdleproof.Prove / Verify on serialised proofs.  Declared in
 // include/curdle_msm.h under "Protocol layers".
+#include <stdio.h>
 #include <string.h>
 
 #include <atomic>
@@ -129,6 +130,39 @@ extern "C" int curdle_prove(const curdle_crs* crs, const uint64_t* Rs, const uin
     memcpy(proof_out, bytes.data(), bytes.size());
     return CURDLE_OK;
   });
+}
+
+// curdle_prove with a flags word.  Under CURDLE_PROVE_MSM_CONSTANT_TIME the body is curdle_prove's under an
+// alg::ConstantTimeMsmScope on this thread (Prove starts no threads): every MSM of the proof goes to the constant-time
+// primitive and nothing else differs, so the proof and rand's state afterwards are the unflagged call's.
+extern "C" int curdle_prove_ex(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, const uint64_t* Ts,
+                               const uint64_t* Us, size_t ell, const uint64_t M[18], const uint32_t* perm,
+                               const uint64_t k[4], const uint64_t rs_m[16], curdle_rand* rand, unsigned flags,
+                               uint8_t* proof_out, size_t cap, size_t* proof_len) {
+  if (flags & ~CURDLE_PROVE_MSM_CONSTANT_TIME) {
+    char msg[64];
+    snprintf(msg, sizeof(msg), "unknown flag bits 0x%x", flags & ~CURDLE_PROVE_MSM_CONSTANT_TIME);
+    return curdle_set_last_error(CURDLE_EINVAL, msg);
+  }
+  if (!flags) return curdle_prove(crs, Rs, Ss, Ts, Us, ell, M, perm, k, rs_m, rand, proof_out, cap, proof_len);
+  if (!crs || !Rs || !Ss || !Ts || !Us || !M || !perm || !k || !rs_m || !rand || !proof_len)
+    return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  if (ell != crs->crs.Gs.size()) return curdle_set_last_error(CURDLE_EINVAL, "ell does not match the CRS");
+  if (proto::ProverFoldBasesEnabled())
+    return curdle_set_last_error(CURDLE_EINVAL,
+                                 "CURDLE_PROVE_MSM_CONSTANT_TIME with PROVER_FOLD_BASES set: that prover multiplies H by a "
+                                 "secret inner product on the host");
+  if (!alg::ConstantTimeMsmScope::Available())
+    return curdle_set_last_error(CURDLE_ENODEV,
+                                 "CURDLE_PROVE_MSM_CONSTANT_TIME: the constant-time MSM is not part of this backend");
+  alg::ConstantTimeMsmScope scope;
+  return curdle_prove(crs, Rs, Ss, Ts, Us, ell, M, perm, k, rs_m, rand, proof_out, cap, proof_len);
+}
+
+extern "C" int curdle_stat_alg_msm(unsigned long long out[4]) {
+  if (!out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  alg::ReadMsmCounters(out);
+  return CURDLE_OK;
 }
 
 extern "C" int curdle_verify(const curdle_crs* crs, const uint8_t* proof, size_t proof_len, const uint64_t* Rs,

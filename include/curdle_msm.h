@@ -1047,8 +1047,8 @@ int curdle_stat_g1_mul_ct(unsigned long long out[2]);
  * WHAT IT DOES NOT PROMISE: anything about data-dependent power draw and clock behaviour of the chip (a multiplier fed
  * zeros draws less), which is not addressed; and nothing about curdle_msm_g1, whose warning above stays true.
  * OUTSIDE THE PROMISE: the result itself and the verdict on scalar_bits; whatever the caller does with the scalars
- * before and after.  It is NOT A DEFAULT: nothing in the library routes to it but curdle_shuffle_permute_commit_ex under
- * its flag.
+ * before and after.  It is NOT A DEFAULT: nothing in the library routes to it but curdle_shuffle_permute_commit_ex and
+ * curdle_prove_ex, each under its flag.
  * Cost: one lane's chain of scalar_bits doublings and additions, then ceil(log2 n) levels of additions and one inversion:
  * measured 5.5 ... 6.8 ms at 255 bits and 0.9 ... 2.0 ms at 9 bits for n = 4 ... 65,536, 12 to 27 times curdle_msm_g1_device
  * (profiles/r27_msm_ct.json); the flagged shuffle step below 11.2 ... 12.0 ms at ell = 124 ... 508 against 1.4 ... 1.6 ms.
@@ -1057,6 +1057,63 @@ int curdle_msm_g1_ct(const uint64_t* points, const uint64_t* scalars, size_t n, 
 int curdle_msm_g1_ct_device(const void* d_points, const void* d_scalars, size_t n, unsigned scalar_bits, uint64_t out_jac[18], void* stream);
 /* out[0] pairs walked by k_msm_ct_walk, out[1] its launches, out[2] sums finished; completed calls only. */
 int curdle_stat_msm_ct(unsigned long long out[3]);
+/* The constant-time MSM, BATCHED: k independent MSMs in ONE walk.  curdle_msm_g1_ct_batch is curdle_msm_g1_batch's shape:
+ * `offsets` has k + 1 non-decreasing entries and MSM j covers the pairs [offsets[j], offsets[j+1]) of the concatenated
+ * arrays; curdle_msm_g1_ct_multi is curdle_msm_g1_multi's: k base sets of n points against ONE scalar vector.  Layouts,
+ * preconditions and scalar_bits (ONE public bound for the whole call) are curdle_msm_g1_ct's; out_jac receives k results
+ * of 18 words, result j bit for bit what curdle_msm_g1_ct returns on MSM j alone (an empty MSM: the infinity encoding).
+ * A walk costs one lane's chain whether it has 4 pairs or 65,536, so k_msm_ct_walk is launched ONCE over all the pairs
+ * of the call; the terms are then folded per MSM, each segment in exactly the order of the single call, by a segmented
+ * form of the sum (k_g1_sum_ct_seg: one launch per level for all segments still above 512 terms, from a PUBLIC table of
+ * (begin, count) made of `offsets`; k_msm_ct_finish_seg: one block per MSM for the rest, the inversion and the masked
+ * canonical step).
+ * Limits: at most 65,536 pairs in all (one pass), k <= 4,096, for _multi k n <= 65,536.  k = 0 returns CURDLE_OK and
+ * writes nothing; a call whose MSMs are all empty needs no device.  Refusals happen before any device work, in this
+ * order: a null argument (offsets always; out_jac, the points and the scalars when k > 0), scalar_bits, k, offsets that
+ * decrease, the total, and (the _device form) device pointers that are not multiples of 16; _multi: a null argument,
+ * scalar_bits, k, k n, then a null base set.  A scalar at or above 2^scalar_bits ANYWHERE in the call fails the whole
+ * call with CURDLE_EINVAL and EVERY word of out_jac stays untouched: there is one status word for the call, and this
+ * verdict is the only thing about the scalars the call reveals.
+ * One MSM slot is held for the call.  The terms, and for the host forms the scalar staging and its device copy (for
+ * _multi: the k replicas of the scalar vector, a host copy of public length), are overwritten on the stream that used
+ * them on every way out.  The call's only device-to-host copy is one block of 144 k bytes and the status word.
+ * WHAT THE FLAG PROMISES, WHAT IT DOES NOT PROMISE and what is OUTSIDE THE PROMISE are curdle_msm_g1_ct's, word for word,
+ * with "n" read as "k and the offsets": the instruction stream and the address stream of the three kernels depend on k,
+ * the offsets, scalar_bits, the pointers and on which points are infinity, and on nothing made of the scalars.  It is
+ * not a default: nothing routes to it but curdle_prove_ex under its flag.
+ * A completed call that ran on the device moves curdle_stat_msm_ct by (pairs walked, 1, MSMs that are not empty). */
+int curdle_msm_g1_ct_batch(const uint64_t* points, const uint64_t* scalars, const size_t* offsets, size_t k,
+                           unsigned scalar_bits, uint64_t* out_jac);
+int curdle_msm_g1_ct_batch_device(const void* d_points, const void* d_scalars, const size_t* offsets, size_t k,
+                                  unsigned scalar_bits, uint64_t* out_jac, void* stream);
+int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t k, const uint64_t* scalars, size_t n,
+                           unsigned scalar_bits, uint64_t* out_jac);
+int curdle_stat_msm_ct_batch(unsigned long long out[3]);   /* batched calls | MSMs in them | level launches (k_g1_sum_ct_seg) */
+/* curdle_prove with a flags word.  flags = 0 IS curdle_prove.  A bit that is not defined here: CURDLE_EINVAL before
+ * anything else is looked at, with proof_out and *proof_len untouched.
+ * CURDLE_PROVE_MSM_CONSTANT_TIME: every MSM of the proof -- the prover funnels them through three functions,
+ * alg::MultiExp, MultiExpBatch and MultiExpShared (host/algebra.cpp) -- goes to curdle_msm_g1_ct, _ct_batch and
+ * _ct_multi at scalar_bits = 255 instead of the bucket MSM, by a scoped switch on the calling thread.  The proof bytes
+ * and rand's state afterwards are bit for bit those of the call without flags.
+ * WHAT THE FLAG PROMISES: the DEVICE WORK OF PROVE'S MSMs, and only that, is curdle_msm_g1_ct's: the witness, the
+ * blinders and the permuted challenges reach the device as MSM scalars of kernels whose instruction stream and address
+ * stream do not depend on them, through staging that is overwritten on every way out; the host's concatenated copy of
+ * a batch's scalars is overwritten too.
+ * WHAT IT DOES NOT PROMISE: power draw and clock behaviour, as above; and NOTHING ABOUT THE HOST.
+ * OUTSIDE THE PROMISE: the host-side operations of Prove on the same secrets are outside and run as they do without the
+ * flag: the host Point::Mul calls on r_k, k, r_t and r_u and GroupCommitment::New, the Fr vector arithmetic (the
+ * permutation of the challenges is an indexed gather by perm), the generation of the blinders, the ordinary heap
+ * copies of the witness, and the alg::ScalarMulBatch calls (their scalars are public challenges).  DESIGN.md section 0
+ * lists every one with its line.  They are the next follow-up.  Under CURDLE_PROVER_FOLD_BASES=1 the recursive provers
+ * multiply H by a secret inner product on the host, so there the flagged call is refused with CURDLE_EINVAL.  Linked over
+ * a backend without the constant-time MSM, and without a device, the flagged call fails with CURDLE_ENODEV: no fallback.
+ * ell is bounded by the primitive: the largest batch of a round must fit 65,536 pairs.  It is not a default. */
+#define CURDLE_PROVE_MSM_CONSTANT_TIME 1u
+int curdle_prove_ex(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, const uint64_t* Ts, const uint64_t* Us,
+                    size_t ell, const uint64_t M[18], const uint32_t* perm, const uint64_t k[4], const uint64_t rs_m[16],
+                    curdle_rand* rand, unsigned flags, uint8_t* proof_out, size_t cap, size_t* proof_len);
+int curdle_stat_alg_msm(unsigned long long out[4]);   /* bucket-MSM calls | their pairs | constant-time calls | their pairs,
+                                                         counted in alg::MultiExp / MultiExpBatch / MultiExpShared */
 /* curdle_shuffle_permute_commit with a flags word.  flags = 0 IS that call.  A bit that is not defined here:
  * CURDLE_EINVAL before anything else is looked at, with the outputs untouched.
  * CURDLE_SHUFFLE_CONSTANT_TIME: the outputs and rand's state afterwards are bit for bit those of the call without
