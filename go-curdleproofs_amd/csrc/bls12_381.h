@@ -116,8 +116,20 @@ CURDLE_HD void f_cond_sub(Mont<PR>& r, const u32* a, u32 top) {
   }
   // a >= p  <=>  top set or no final borrow
   bool ge = (top != 0) | (borrow == 0);
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
   for (int i = 0; i < PR::N; i++) r.l[i] = ge ? d[i] : a[i];
+#else
+  if constexpr (PR::N == FrParams::N) {
+    // Host, the scalar field: the prover's secrets pass through here.  The choice as a mask, so that the compiler has
+    // no select to turn into a jump (the x86 build of the ternary did: DESIGN.md section 0, round 29).  The base
+    // field keeps the ternary: the host's point arithmetic runs on public points and is on the MSM's host combine.
+    const u32 m = (u32)0 - (u32)ge;
+    for (int i = 0; i < PR::N; i++) r.l[i] = (d[i] & m) | (a[i] & ~m);
+  } else {
+    for (int i = 0; i < PR::N; i++) r.l[i] = ge ? d[i] : a[i];
+  }
+#endif
 }
 
 template <class PR>
@@ -493,8 +505,11 @@ CURDLE_HD void fr_mul(Fr& r, const Fr& a, const Fr& b) {
     d[i] = (u64)s;
     borrow = (u64)(s >> 64) & 1;
   }
-  const bool ge = t[4] != 0 || borrow == 0;
-  __builtin_memcpy(r.l, ge ? d : t, 32);
+  // t >= r: take d.  As a mask over both, not a choice of which buffer to copy: that choice compiled to a conditional
+  // move of the SOURCE ADDRESS, and the prover's secrets pass through here.
+  const u64 ge = (u64)0 - (u64)((t[4] != 0) | (borrow == 0));
+  for (int i = 0; i < 4; i++) d[i] = (d[i] & ge) | (t[i] & ~ge);
+  __builtin_memcpy(r.l, d, 32);
 }
 #endif
 CURDLE_HD void fr_add(Fr& r, const Fr& a, const Fr& b) { f_add<FrParams>(r, a, b); }

@@ -319,6 +319,81 @@ extern "C" int curdle_g1_permute_ct_device(const void* d_in, const void* d_perm,
   });
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The oblivious gather over 32-byte records (k_fr_permute_ct): out[i] = in[perm[i]] with perm secret, what Prove's two
+// permutations of the challenges become under curdle_prove_ct (alg::PermuteSecret, host/algebra.cpp).  The host form
+// stages perm | in through the first pinned staging and the output through the second; perm's two copies and the output's
+// two copies are on the WipeList (the input is not: in Prove it is the public challenge vector, and a caller whose input
+// is secret wipes its own).  The _device form reads and writes the caller's arrays where they are.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+// records gathered | launches; completed calls only
+std::atomic<unsigned long long> g_fr_permute_ct_stat[2];
+
+void count_fr_permute_ct(size_t n) {
+  g_fr_permute_ct_stat[0].fetch_add(n, std::memory_order_relaxed);
+  g_fr_permute_ct_stat[1].fetch_add(1, std::memory_order_relaxed);
+}
+
+// What both forms refuse first: a null argument, then n.
+int fr_permute_check(const void* in, const void* perm, size_t n, const void* out) {
+  if (!in || !perm || !out) return fail(CURDLE_EINVAL, "null argument");
+  if (n > kShuffleCtMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 4,096 records", n);
+  return CURDLE_OK;
+}
+}  // namespace
+
+extern "C" int curdle_fr_permute_ct(const uint64_t* in, const uint32_t* perm, size_t n, uint64_t* out) {
+  if (n == 0) return CURDLE_OK;
+  if (int rc = fr_permute_check(in, perm, n, out)) return rc;
+  SlotHold H(cur(), true, nullptr);
+  WipeList W(H.stream());
+  H.wipe_on_exit(&W, "constant-time scalar gather: clearing the permutation and the gathered records");
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
+    const size_t rec = n * 32, perm_pad = (4 * n + 15) / 16 * 16;
+    int r;
+    if ((r = ensure(S.tmp, perm_pad))) return r;    // perm
+    if ((r = ensure(S.scalars, rec))) return r;     // in
+    if ((r = ensure(S.sorted, rec))) return r;      // out
+    if ((r = ensure_pinned(S, 0, perm_pad + rec))) return r;  // perm | in
+    if ((r = ensure_pinned(S, 1, rec))) return r;             // out
+    W.note_device(S.tmp.p, perm_pad);
+    W.note_device(S.sorted.p, rec);
+    W.note_host(S.h_stage[0], perm_pad);
+    W.note_host(S.h_stage[1], rec);
+    uint8_t* h = static_cast<uint8_t*>(S.h_stage[0]);
+    memcpy(h, perm, 4 * n);
+    memcpy(h + perm_pad, in, rec);
+    HIP_TRY(hipMemcpyAsync(S.tmp.p, h, 4 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S.scalars.p, h + perm_pad, rec, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_fr_permute_ct(S.scalars.p, static_cast<const uint32_t*>(S.tmp.p), (uint32_t)n, S.sorted.p, st));
+    HIP_TRY(hipMemcpyAsync(S.h_stage[1], S.sorted.p, rec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(out, S.h_stage[1], rec);
+    count_fr_permute_ct(n);
+    return CURDLE_OK;
+  });
+}
+
+extern "C" int curdle_fr_permute_ct_device(const void* d_in, const void* d_perm, size_t n, void* d_out, void* stream) {
+  if (n == 0) return CURDLE_OK;
+  if (int rc = fr_permute_check(d_in, d_perm, n, d_out)) return rc;
+  const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out;
+  if (!aligned16(d_in) || !aligned16(d_out) || (a < b + 32 * n && b < a + 32 * n) || ((uintptr_t)d_perm & 3u))
+    return fail(CURDLE_EINVAL, "record pointers must be multiples of 16 and must not overlap, the permutation's a multiple of 4");
+  SlotHold H(cur(), true, stream);
+  return H.run([&]() -> int {
+    HIP_TRY(launch_fr_permute_ct(d_in, static_cast<const uint32_t*>(d_perm), (uint32_t)n, d_out, H.stream()));
+    HIP_TRY(hipStreamSynchronize(H.stream()));
+    count_fr_permute_ct(n);
+    return CURDLE_OK;
+  });
+}
+
+extern "C" int curdle_stat_fr_permute_ct(unsigned long long out[2]) { return read_stats(out, g_fr_permute_ct_stat, 2); }
+
 // The device work of curdle_shuffle_permute_commit_ex under CURDLE_SHUFFLE_CONSTANT_TIME (the entry point below checked the
 // arguments; host/proto_api.cpp the permutation's range, and drew rs_m):
 //   Ts | Us   one k_g1_mul_ct with the shared scalar k over the 2 ell records Rs | Ss, in place, then ONE

@@ -1,7 +1,7 @@
 // Constant-time multi-scalar multiplication: sum_i k_i P_i with an instruction stream and an address stream that do
 // not depend on the scalars.  The twin of the bucket MSM (msm_sort_kernels.hip, msm_accumulate_kernel.hip), whose sort,
 // bucket addresses and large-bucket queue are all functions of the scalars, in the manner of k_g1_mul_ct
-// (g1_mul_ct_kernels.hip).  Six kernels; the rule of what may depend on a secret is the one of g1_walk_ct.h.
+// (g1_mul_ct_kernels.hip).  Seven kernels; the rule of what may depend on a secret is the one of g1_walk_ct.h.
 //
 // k_msm_ct_walk.  One lane per (base, scalar) pair: the walk of g1_walk_ct.h with a PUBLIC step count `bits` (1...255,
 // a kernel argument): the scalar is first shifted left by 256 - bits, one bit a step in a rolled loop whose trip count
@@ -28,6 +28,9 @@
 // address made of the lane index) and walks j = 0 ... n - 1, a public trip count with the address of in[j] made of j,
 // accumulating in[j] & mask(perm[i] == j): n^2 record reads and no address made of perm.  `halves` record arrays of n
 // records lie behind each other and are permuted alike (the shuffle's Ts | Us).
+//
+// k_fr_permute_ct.  The same gather over 32-byte records (Prove's permuted challenges; the records are bytes to it, not
+// field elements): both kernels are instantiations of ONE body, gather_ct<W>, W the record's size in 16-byte words.
 //
 // k_g1_sum_ct_seg, k_msm_ct_finish_seg.  The same sum over k segments of ONE term array (the batched call: one walk over
 // the concatenated pairs of k MSMs): MSM j owns term[begin_j, begin_j + count_j) and a PUBLIC table of (begin, count)
@@ -224,32 +227,48 @@ __global__ void __launch_bounds__(kBlock, 1)
   write_result(term + s.x, res);
 }
 
-__global__ void __launch_bounds__(kBlock)
-    k_g1_permute_ct(const uint4* __restrict__ in, const u32* __restrict__ perm, u32 n, u32 halves, uint4* __restrict__ out) {
-  const u32 g = blockIdx.x * kBlock + threadIdx.x;
-  if (g >= n * halves) return;
-  const u32 half = g / n, i = g - half * n;  // public
-  const u32 p = perm[i];                     // an address made of the lane index
-  const uint4* src = in + 6 * (size_t)half * n;
-  u32 acc[24];
+namespace {
+// The oblivious gather on one lane, over records of W 16-byte words: *dst = src[p] for p < n, a zero record otherwise.
+// The lane walks j = 0 ... n - 1 (a public trip count), reads record j at an address made of j and keeps it under a
+// mask made of p ^ j: p, the secret, reaches nothing but that mask.
+template <int W>
+__device__ __forceinline__ void gather_ct(const uint4* __restrict__ src, u32 p, u32 n, uint4* __restrict__ dst) {
+  u32 acc[4 * W];
 #pragma unroll
-  for (int w = 0; w < 24; w++) acc[w] = 0;
+  for (int w = 0; w < 4 * W; w++) acc[w] = 0;
 #pragma unroll 1
   for (u32 j = 0; j < n; j++) {
     const u32 d = p ^ j;
-    const u32 m = ((d | (0u - d)) >> 31) - 1u;  // all ones iff perm[i] == j
+    const u32 m = ((d | (0u - d)) >> 31) - 1u;  // all ones iff p == j
 #pragma unroll
-    for (int q = 0; q < 6; q++) {
-      const uint4 v = src[6 * (size_t)j + q];  // an address made of j
+    for (int q = 0; q < W; q++) {
+      const uint4 v = src[W * (size_t)j + q];  // an address made of j
       acc[4 * q] |= v.x & m;
       acc[4 * q + 1] |= v.y & m;
       acc[4 * q + 2] |= v.z & m;
       acc[4 * q + 3] |= v.w & m;
     }
   }
-  uint4* dst = out + 6 * (size_t)g;
 #pragma unroll
-  for (int q = 0; q < 6; q++) dst[q] = make_uint4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+  for (int q = 0; q < W; q++) dst[q] = make_uint4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock)
+    k_g1_permute_ct(const uint4* __restrict__ in, const u32* __restrict__ perm, u32 n, u32 halves, uint4* __restrict__ out) {
+  const u32 g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= n * halves) return;
+  const u32 half = g / n, i = g - half * n;  // public
+  const u32 p = perm[i];                     // an address made of the lane index
+  gather_ct<6>(in + 6 * (size_t)half * n, p, n, out + 6 * (size_t)g);
+}
+
+__global__ void __launch_bounds__(kBlock)
+    k_fr_permute_ct(const uint4* __restrict__ in, const u32* __restrict__ perm, u32 n, uint4* __restrict__ out) {
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const u32 p = perm[i];  // an address made of the lane index
+  gather_ct<2>(in, p, n, out + 2 * (size_t)i);
 }
 
 hipError_t launch_msm_ct_walk(const void* points, const void* scalars, int scalar_form, uint32_t bits, uint32_t n, void* term,
@@ -299,6 +318,13 @@ hipError_t launch_g1_permute_ct(const void* in, const uint32_t* perm, uint32_t n
   if ((u64)n * halves > ((u64)1 << 31)) return hipErrorInvalidValue;  // the lane index is 32 bits
   hipLaunchKernelGGL(k_g1_permute_ct, dim3(cdiv((u64)n * halves, kBlock)), dim3(kBlock), 0, stream, (const uint4*)in, perm,
                      (u32)n, (u32)halves, (uint4*)out);
+  return hipGetLastError();
+}
+
+hipError_t launch_fr_permute_ct(const void* in, const uint32_t* perm, uint32_t n, void* out, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (n > (1u << 31)) return hipErrorInvalidValue;  // the lane index is 32 bits
+  hipLaunchKernelGGL(k_fr_permute_ct, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream, (const uint4*)in, perm, (u32)n, (uint4*)out);
   return hipGetLastError();
 }
 

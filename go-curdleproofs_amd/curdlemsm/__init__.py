@@ -94,6 +94,8 @@ SYMBOLS = [
     "curdle_g1_permute_ct_device",
     "curdle_msm_g1_ct_batch", "curdle_msm_g1_ct_batch_device", "curdle_msm_g1_ct_multi", "curdle_stat_msm_ct_batch",
     "curdle_prove_ex", "curdle_stat_alg_msm",
+    "curdle_fr_permute_ct", "curdle_fr_permute_ct_device", "curdle_stat_fr_permute_ct",
+    "curdle_prove_ct", "curdle_whisk_generate_shuffle_proof_ct", "curdle_stat_host_point_mul",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -942,6 +944,62 @@ def prove(crs: CRS, Rs, Ss, Ts, Us, M, perm, k, rs_m, rand: Rand, flags=None) ->
     return bytes(buf[: n.value])
 
 
+_prove_ct = _sig("curdle_prove_ct", C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                 C.POINTER(C.c_size_t))
+_stat_host_point_mul = _sig("curdle_stat_host_point_mul", C.c_int, C.POINTER(C.c_ulonglong))
+_fr_permute_ct = _sig("curdle_fr_permute_ct", C.c_int, _vp, _vp, C.c_size_t, _vp)
+_fr_permute_ct_device = _sig("curdle_fr_permute_ct_device", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp)
+_stat_fr_permute_ct = _sig("curdle_stat_fr_permute_ct", C.c_int, C.POINTER(C.c_ulonglong))
+
+
+def prove_ct(crs: CRS, Rs, Ss, Ts, Us, M, perm, k, rs_m, rand: Rand) -> bytes:
+    """prove() in constant-time form (curdle_prove_ct): the same proof bytes and the same draws from rand, with the
+    prover's MSMs, its scalar multiplications by secrets and its gathers by the permutation on kernels whose
+    instruction and address streams do not depend on them.  ell <= 4,096; no fallback without a device."""
+    Rs, Ss, Ts, Us = (_as_u64(a, 12) for a in (Rs, Ss, Ts, Us))
+    M, k, rs_m = _as_u64(M), _as_u64(k), _as_u64(rs_m)
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    cap = 1 << 16
+    buf = np.zeros(cap, dtype=np.uint8)
+    n = C.c_size_t(0)
+    _check(_prove_ct(crs._h, _ptr(Rs), _ptr(Ss), _ptr(Ts), _ptr(Us), crs.ell, _ptr(M), _ptr(perm), _ptr(k), _ptr(rs_m),
+                     rand._h, _ptr(buf), cap, C.byref(n)))
+    return bytes(buf[: n.value])
+
+
+def stat_host_point_mul() -> int:
+    """Calls of the host's double-and-add scalar multiplication (alg::Point::Mul) on the CALLING THREAD so far."""
+    out = C.c_ulonglong(0)
+    _check(_stat_host_point_mul(C.byref(out)))
+    return int(out.value)
+
+
+def fr_permute_ct(records, perm) -> np.ndarray:
+    """out[i] = records[perm[i]] over 32-byte records with perm secret (curdle_fr_permute_ct): every output reads every
+    record and no address is made of perm; an entry at or above n gives a zero record.  n <= 4,096."""
+    records = _as_u64(records, 4)
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    n = records.shape[0] if records.size else 0
+    if len(perm) != n:
+        raise CurdleError(EINVAL, "len(perm) != len(records)")
+    out = np.zeros((n, 4), dtype=np.uint64)
+    _check(_fr_permute_ct(_ptr(records), _ptr(perm), n, _ptr(out)))
+    return out
+
+
+def fr_permute_ct_device(d_in: int, d_perm: int, n: int, d_out: int, stream: int = 0) -> None:
+    """fr_permute_ct on device-resident arrays (curdle_fr_permute_ct_device; raw device pointers, the records'
+    multiples of 16 and not overlapping, the permutation's a multiple of 4)."""
+    _check(_fr_permute_ct_device(d_in or None, d_perm or None, n, d_out or None, stream or None))
+
+
+def stat_fr_permute_ct() -> dict:
+    """Records gathered by the oblivious scalar gather and its launches since the library was loaded."""
+    out = (C.c_ulonglong * 2)()
+    _check(_stat_fr_permute_ct(out))
+    return {"records": int(out[0]), "launches": int(out[1])}
+
+
 def verify(crs: CRS, proof: bytes, Rs, Ss, Ts, Us, M, rand: Rand) -> bool:
     """curdleproof.Verify (curdleproof.go:199): the accept bit; raises CurdleError for (false, err)."""
     Rs, Ss, Ts, Us = (_as_u64(a, 12) for a in (Rs, Ss, Ts, Us))
@@ -1270,6 +1328,20 @@ def whisk_generate_shuffle_proof(crs: CRS, pre_trackers, rand: Rand):
     post = np.zeros(96 * len(pre_trackers), dtype=np.uint8)
     proof = np.zeros(WHISK_SHUFFLE_PROOF_SIZE, dtype=np.uint8)
     _check(_whisk_gen_shuffle(crs._h, _ptr(pre), len(pre_trackers), rand._h, _ptr(post), _ptr(proof)))
+    pb = post.tobytes()
+    return [pb[96 * i: 96 * (i + 1)] for i in range(len(pre_trackers))], proof.tobytes()
+
+
+_whisk_gen_shuffle_ct = _sig("curdle_whisk_generate_shuffle_proof_ct", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, _vp)
+
+
+def whisk_generate_shuffle_proof_ct(crs: CRS, pre_trackers, rand: Rand):
+    """whisk_generate_shuffle_proof in constant-time form (curdle_whisk_generate_shuffle_proof_ct): the same
+    post-trackers, proof bytes and draws, through the flagged shuffle step and prove_ct."""
+    pre = _bytes_arr(b"".join(pre_trackers))
+    post = np.zeros(96 * len(pre_trackers), dtype=np.uint8)
+    proof = np.zeros(WHISK_SHUFFLE_PROOF_SIZE, dtype=np.uint8)
+    _check(_whisk_gen_shuffle_ct(crs._h, _ptr(pre), len(pre_trackers), rand._h, _ptr(post), _ptr(proof)))
     pb = post.tobytes()
     return [pb[96 * i: 96 * (i + 1)] for i in range(len(pre_trackers))], proof.tobytes()
 

@@ -21,6 +21,8 @@ extern "C" int curdle_msm_g1_ct_batch(const uint64_t* points, const uint64_t* sc
                                       unsigned scalar_bits, uint64_t* out_jac) __attribute__((weak));
 extern "C" int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t k, const uint64_t* scalars, size_t n,
                                       unsigned scalar_bits, uint64_t* out_jac) __attribute__((weak));
+// ... and so does the oblivious gather over scalars, which PermuteSecret uses under a SecretOpsScope.
+extern "C" int curdle_fr_permute_ct(const uint64_t* in, const uint32_t* perm, size_t n, uint64_t* out) __attribute__((weak));
 
 namespace curdle {
 namespace alg {
@@ -190,8 +192,12 @@ Point Point::Generator() {
   return FromAffine(g);
 }
 
+static thread_local unsigned long long t_point_mul_calls = 0;
+unsigned long long PointMulCalls() { return t_point_mul_calls; }
+
 Point Point::Mul(const Scalar& k) const {
   NeedValue();
+  t_point_mul_calls++;
   u32 c[8];
   k.Canonical(c);
   Point r;
@@ -421,6 +427,36 @@ std::vector<Point> MultiExpShared(const std::vector<const std::vector<G1Affine>*
   std::vector<Point> res(k);
   for (size_t j = 0; j < k; j++) res[j] = Point::FromJac(out.data() + 18 * j);
   return res;
+}
+
+// ------------------------------------------------------- the second switch ---
+static thread_local bool t_secret_ops = false;
+
+SecretOpsScope::SecretOpsScope() : prev_(t_secret_ops) { t_secret_ops = true; }
+SecretOpsScope::~SecretOpsScope() { t_secret_ops = prev_; }
+bool SecretOpsScope::Active() { return t_secret_ops; }
+bool SecretOpsScope::Available() { return curdle_fr_permute_ct && ConstantTimeMsmScope::Available(); }
+
+std::vector<Scalar> PermuteSecret(const std::vector<Scalar>& vs, const std::vector<uint32_t>& perm) {
+  std::vector<Scalar> out(vs.size());
+  if (!t_secret_ops) {
+    for (size_t i = 0; i < perm.size(); i++) out[i] = vs[perm[i]];
+    return out;
+  }
+  if (perm.size() != vs.size()) throw std::runtime_error("permuting: len(perm) != len(values)");
+  static_assert(sizeof(Scalar) == 32, "the gather's record is an fr.Element");
+  // perm goes to the device from where it lies and the records arrive in `out`, the prover's own vector: nothing is
+  // created here that would have to be wiped (the call wipes its staging).
+  const int rc = curdle_fr_permute_ct
+                     ? curdle_fr_permute_ct(reinterpret_cast<const uint64_t*>(vs.data()), perm.data(), vs.size(),
+                                            reinterpret_cast<uint64_t*>(out.data()))
+                     : curdle_set_last_error(CURDLE_ENODEV, "the oblivious gather is not part of this backend: no device code to run it on");
+  if (rc != CURDLE_OK) {
+    char buf[256];
+    curdle_last_error(buf, sizeof(buf));
+    throw MsmError(std::string("permuting: ") + buf + " (rc " + std::to_string(rc) + ")", rc);
+  }
+  return out;
 }
 
 std::vector<G1Affine> ScalarMulBatch(const std::vector<G1Affine>& points, const std::vector<Scalar>& scalars,

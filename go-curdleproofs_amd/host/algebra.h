@@ -187,6 +187,32 @@ class ConstantTimeMsmScope {
 // call they made succeeded; one scalar vector against k sets of n counts k n pairs.
 void ReadMsmCounters(unsigned long long out[4]);
 
+// The second switch of the constant-time prover (curdle_prove_ct), thread-local and scoped like the first: while one
+// lives on a thread, the prover's operations on secrets that are NOT MSMs leave the host too -- its scalar
+// multiplications by r_k, k, r_a, r_b, r_t, r_u become MSMs of one and two terms (curdleproofs.cpp), its gathers by the
+// secret permutation go through PermuteSecret to the oblivious gather, and an MSM pair whose first half alone would be an
+// unblinded commitment is ONE MSM.  Without it every site runs as it always did.  Meant to live inside a
+// ConstantTimeMsmScope: alone it would send the new MSMs to the bucket MSM.
+class SecretOpsScope {
+ public:
+  SecretOpsScope();
+  ~SecretOpsScope();
+  SecretOpsScope(const SecretOpsScope&) = delete;
+  SecretOpsScope& operator=(const SecretOpsScope&) = delete;
+  static bool Active();     // on this thread
+  static bool Available();  // the backend has the gather and the constant-time MSMs
+
+ private:
+  bool prev_;
+};
+// common.Permute for a SECRET permutation: out[i] = vs[perm[i]].  Under a SecretOpsScope one curdle_fr_permute_ct (every
+// output reads every record; no address is made of perm; a backend without it: MsmError(CURDLE_ENODEV)); otherwise the
+// indexed gather the prover always ran.  perm.size() == vs.size(), entries below it (the caller's check).
+std::vector<Scalar> PermuteSecret(const std::vector<Scalar>& vs, const std::vector<uint32_t>& perm);
+// Calls of Point::Mul on the calling thread since it started (a thread-local counter, no atomic: the batch verifiers
+// multiply on many threads): the diagnostic that shows which route a Prove took.
+unsigned long long PointMulCalls();
+
 // out[i] = addends[i] + scalars[i] * points[i]; scalars.size() is points.size(), or 1 for one
 // scalar shared by all; addends may be null.  The independent scalar multiplications that
 // dominate the prover: a batch of at least kScalarMulBatchMin goes to

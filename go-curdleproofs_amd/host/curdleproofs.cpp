@@ -113,6 +113,51 @@ const G1Affine kZeroPoint = [] {
 // reference's order of operations (A/B and tests, which flip it through curdle_plan_override).
 bool ProverFoldsBases() { return knobs::get(knobs::PROVER_FOLD_BASES) > 0; }
 
+// ---- what the prover does instead of a host operation on a secret while an alg::SecretOpsScope lives (curdle_prove_ct) ----
+// Scalar vectors the routes below create: overwritten on every way out, an exception included.
+struct ScalarWipe {
+  std::vector<std::vector<Scalar>*> vs;
+  ~ScalarWipe() {
+    for (std::vector<Scalar>* v : vs)
+      if (!v->empty()) explicit_bzero(v->data(), v->size() * sizeof(Scalar));
+  }
+};
+
+// MultiExp(P1 | P2, s1 | s2) as ONE MSM where the prover otherwise runs a batch of two and adds the results on the
+// host: the first result alone is an unblinded commitment to s1 and never exists outside the device.
+Point MultiExpJoined(const std::vector<G1Affine>& P1, const std::vector<G1Affine>& P2, const std::vector<Scalar>& s1,
+                     const std::vector<Scalar>& s2) {
+  std::vector<Scalar> s;
+  ScalarWipe wipe{{&s}};
+  s.reserve(s1.size() + s2.size());  // no reallocation: no unwiped copy is left behind
+  s.insert(s.end(), s1.begin(), s1.end());
+  s.insert(s.end(), s2.begin(), s2.end());
+  return alg::MultiExp(Concat(P1, P2), s);
+}
+
+// The pair GroupCommitment::New(G1, H, s X1, r1), GroupCommitment::New(G2, H, s X2, r2) without a host multiplication:
+// (r1 G1, s X1 + r1 H, r2 G2, s X2 + r2 H) is one batch of four MSMs over six pairs -- under the constant-time scope ONE
+// walk -- and s X1, s X2 never exist unblinded.  Infinity among the bases (X1, X2 are public) is a zero term.
+void CommitPairSecret(const Point& G1, const Point& G2, const Point& H, const Point& X1, const Point& X2, const Scalar& s,
+                      const Scalar& r1, const Scalar& r2, GroupCommitment* c1, GroupCommitment* c2) {
+  const G1Affine h = AffineOf(H);
+  const std::vector<G1Affine> b0{AffineOf(G1)}, b1{AffineOf(X1), h}, b2{AffineOf(G2)}, b3{AffineOf(X2), h};
+  std::vector<Scalar> s0, s1, s2, s3;
+  ScalarWipe wipe{{&s0, &s1, &s2, &s3}};
+  for (std::vector<Scalar>* v : wipe.vs) v->reserve(2);  // filled in place: no reallocation, no temporary array
+  s0.push_back(r1);
+  s1.push_back(s);
+  s1.push_back(r1);
+  s2.push_back(r2);
+  s3.push_back(s);
+  s3.push_back(r2);
+  const std::vector<Point> m = alg::MultiExpBatch({&b0, &b1, &b2, &b3}, {&s0, &s1, &s2, &s3});
+  c1->T_1 = m[0];
+  c1->T_2 = m[1];
+  c2->T_1 = m[2];
+  c2->T_2 = m[3];
+}
+
 }  // namespace
 
 bool ProverFoldBasesEnabled() { return ProverFoldsBases(); }
@@ -472,8 +517,12 @@ Proof Prove(const Point& Gt, const Point& Gu, const Point& H, const Point& R, co
   // samescalarargument.go:34-81
   const Scalar r_a = GetFr(rand), r_b = GetFr(rand), r_k = GetFr(rand);
   Proof p;
-  p.A = GroupCommitment::New(Gt, H, R.Mul(r_k), r_a);
-  p.B = GroupCommitment::New(Gu, H, S.Mul(r_k), r_b);
+  if (alg::SecretOpsScope::Active()) {
+    CommitPairSecret(Gt, Gu, H, R, S, r_k, r_a, r_b, &p.A, &p.B);
+  } else {
+    p.A = GroupCommitment::New(Gt, H, R.Mul(r_k), r_a);
+    p.B = GroupCommitment::New(Gu, H, S.Mul(r_k), r_b);
+  }
   AppendStatement(tr, R, S, T, U, p.A, p.B);
   const Scalar alpha = tr.GetAndAppendChallenge(kAlpha);
   p.Z_k = r_k + k * alpha;
@@ -805,7 +854,11 @@ Proof Prove(const std::vector<G1Affine>& Gs, const std::vector<G1Affine>& Hs, co
   for (size_t i = 1; i < ell; i++) cs[i] = cs[i - 1] * bs[i - 1];
   const std::vector<Scalar> r_cs = GetFrs(rand, nb);
   Proof proof;
-  {
+  if (alg::SecretOpsScope::Active()) {
+    // cc[0] below is the unblinded commitment to the partial products of the b_i, which are made of the permuted
+    // challenges: one MSM over Gs | Hs instead, the same C
+    proof.C = MultiExpJoined(Gs, Hs, cs, r_cs);
+  } else {
     std::vector<Point> cc = alg::MultiExpBatch({&Gs, &Hs}, {&cs, &r_cs});  // :67, :70
     proof.C = cc[0] + cc[1];
   }
@@ -933,7 +986,7 @@ Proof Prove(const std::vector<G1Affine>& Gs, const std::vector<G1Affine>& Hs, co
   const Scalar alpha = tr.GetAndAppendChallenge(kAlpha);
   const Scalar beta = tr.GetAndAppendChallenge(kBeta);
 
-  const std::vector<Scalar> permutedAs = Permute(as, permutation);
+  const std::vector<Scalar> permutedAs = alg::SecretOpsScope::Active() ? alg::PermuteSecret(as, permutation) : Permute(as, permutation);
   std::vector<Scalar> bs(as.size());
   Scalar p = Scalar::One();
   for (size_t i = 0; i < as.size(); i++) {
@@ -1210,9 +1263,13 @@ Proof Prove(const CRS& crs, const std::vector<G1Affine>& Rs, const std::vector<G
   std::vector<Scalar> rs_a_prime(rs_a);
   rs_a_prime.push_back(Scalar::Zero());
   rs_a_prime.push_back(Scalar::Zero());
-  const std::vector<Scalar> perm_as = Permute(as, perm);
+  const bool secret_ops = alg::SecretOpsScope::Active();  // curdle_prove_ct: see algebra.h
+  const std::vector<Scalar> perm_as = secret_ops ? alg::PermuteSecret(as, perm) : Permute(as, perm);
   Proof proof;
-  {
+  if (secret_ops) {
+    // aa[0] below is the unblinded commitment to the permuted challenges: one MSM over Gs | Hs instead, the same A
+    proof.A = MultiExpJoined(crs.Gs, crs.Hs, perm_as, rs_a_prime);
+  } else {
     std::vector<Point> aa = alg::MultiExpBatch({&crs.Gs, &crs.Hs}, {&perm_as, &rs_a_prime});  // :73, :76
     proof.A = aa[0] + aa[1];
   }
@@ -1226,8 +1283,12 @@ Proof Prove(const CRS& crs, const std::vector<G1Affine>& Rs, const std::vector<G
     proof.R = rs[0];
     proof.S = rs[1];
   }
-  proof.T = GroupCommitment::New(crs.Gt, crs.H, proof.R.Mul(k), r_t);
-  proof.U = GroupCommitment::New(crs.Gu, crs.H, proof.S.Mul(k), r_u);
+  if (secret_ops) {
+    CommitPairSecret(crs.Gt, crs.Gu, crs.H, proof.R, proof.S, k, r_t, r_u, &proof.T, &proof.U);
+  } else {
+    proof.T = GroupCommitment::New(crs.Gt, crs.H, proof.R.Mul(k), r_t);
+    proof.U = GroupCommitment::New(crs.Gu, crs.H, proof.S.Mul(k), r_u);
+  }
   proof.proofSameScalar =
       samescalar::Prove(crs.Gt, crs.Gu, crs.H, proof.R, proof.S, proof.T, proof.U, k, r_t, r_u, tr, rand);
 

@@ -159,6 +159,52 @@ extern "C" int curdle_prove_ex(const curdle_crs* crs, const uint64_t* Rs, const 
   return curdle_prove(crs, Rs, Ss, Ts, Us, ell, M, perm, k, rs_m, rand, proof_out, cap, proof_len);
 }
 
+// Device-backed entry points the constant-time prover and shuffle call.  Weak, as host/algebra.cpp names the
+// constant-time MSMs: linked over a backend without them the two calls below fail with CURDLE_ENODEV.
+extern "C" int curdle_device_available(void) __attribute__((weak));
+extern "C" int curdle_shuffle_permute_commit_ex(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, size_t ell,
+                                                const uint32_t* perm, const uint64_t k[4], curdle_rand* rand, unsigned flags,
+                                                uint64_t* Ts_out, uint64_t* Us_out, uint64_t M_out[18],
+                                                uint64_t rs_m_out[16]) __attribute__((weak));
+
+static constexpr size_t kProveCtMaxEll = 4096;  // the oblivious gather is quadratic: the shuffle step's cap
+
+// Whether the constant-time prover can run at all, asked before anything is drawn from rand.
+static bool ProveCtBackend() {
+  return alg::SecretOpsScope::Available() && curdle_device_available && curdle_device_available();
+}
+
+// curdle_prove with every operation on a secret off the host's branches and addresses: the body is curdle_prove's under
+// an alg::ConstantTimeMsmScope (every MSM to the constant-time primitive) and an alg::SecretOpsScope (the secret scalar
+// multiplications as MSMs, the gathers by the permutation through the oblivious gather, no unblinded commitment on the
+// host), both on this thread.  Same draws in the same order, same proof bytes.
+extern "C" int curdle_prove_ct(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, const uint64_t* Ts,
+                               const uint64_t* Us, size_t ell, const uint64_t M[18], const uint32_t* perm,
+                               const uint64_t k[4], const uint64_t rs_m[16], curdle_rand* rand, uint8_t* proof_out,
+                               size_t cap, size_t* proof_len) {
+  if (!crs || !Rs || !Ss || !Ts || !Us || !M || !perm || !k || !rs_m || !rand || !proof_len)  // proof_out: as curdle_prove
+    return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  if (ell != crs->crs.Gs.size()) return curdle_set_last_error(CURDLE_EINVAL, "ell does not match the CRS");
+  if (ell > kProveCtMaxEll)
+    return curdle_set_last_error(CURDLE_EINVAL, "ell exceeds the 4,096 the constant-time prover supports");
+  if (proto::ProverFoldBasesEnabled())
+    return curdle_set_last_error(CURDLE_EINVAL,
+                                 "CURDLE_PROVE_MSM_CONSTANT_TIME with PROVER_FOLD_BASES set: that prover multiplies H by a "
+                                 "secret inner product on the host");
+  if (!ProveCtBackend())
+    return curdle_set_last_error(CURDLE_ENODEV,
+                                 "curdle_prove_ct: the constant-time MSM and the oblivious gather need the device backend and a device");
+  alg::ConstantTimeMsmScope msms;
+  alg::SecretOpsScope secret_ops;
+  return curdle_prove(crs, Rs, Ss, Ts, Us, ell, M, perm, k, rs_m, rand, proof_out, cap, proof_len);
+}
+
+extern "C" int curdle_stat_host_point_mul(unsigned long long* out) {
+  if (!out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  *out = alg::PointMulCalls();
+  return CURDLE_OK;
+}
+
 extern "C" int curdle_stat_alg_msm(unsigned long long out[4]) {
   if (!out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
   alg::ReadMsmCounters(out);
@@ -458,6 +504,61 @@ extern "C" int curdle_whisk_generate_shuffle_proof(const curdle_crs* crs, const 
   return Guard([&]() {
     std::vector<whisk::WhiskTracker> post = whisk::GenerateWhiskShuffleProof(crs->crs, Trackers(pre_trackers, n), rand->r, proof_out);
     memcpy(post_trackers_out, post.data(), post.size() * 96);
+    return CURDLE_OK;
+  });
+}
+
+// GenerateWhiskShuffleProof with the secrets -- the permutation, k, the blinders -- kept off the host's branches and
+// addresses: the draws and their order are the unflagged call's, the decode is public, the shuffle step runs under
+// CURDLE_SHUFFLE_CONSTANT_TIME and the proof through curdle_prove_ct.  This call's own copies of k, the permutation and
+// rs_m are overwritten on every way out.
+extern "C" int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, const uint8_t* pre_trackers, size_t n,
+                                                      curdle_rand* rand, uint8_t* post_trackers_out, uint8_t* proof_out) {
+  if (!crs || !pre_trackers || !rand || !post_trackers_out || !proof_out)
+    return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  if (!curdle_shuffle_permute_commit_ex || !ProveCtBackend())
+    return curdle_set_last_error(CURDLE_ENODEV,
+                                 "curdle_whisk_generate_shuffle_proof_ct: the constant-time shuffle step and prover need the "
+                                 "device backend and a device");
+  struct Secrets {
+    std::vector<uint32_t> permutation;
+    uint64_t k[4] = {0, 0, 0, 0};
+    uint64_t rs_m[16] = {};
+    ~Secrets() {
+      if (!permutation.empty()) explicit_bzero(permutation.data(), permutation.size() * sizeof(uint32_t));
+      explicit_bzero(k, sizeof(k));
+      explicit_bzero(rs_m, sizeof(rs_m));
+    }
+  } s;
+  return Guard([&]() -> int {
+    rand->r.GeneratePermutation(whisk::ELL, s.permutation);  // whisk.go:64
+    static_assert(sizeof(Fr) == sizeof(s.k), "k is one fr.Element");
+    Fr drawn;
+    rand->r.GetFr(drawn);                                    // :68
+    memcpy(s.k, &drawn, sizeof(s.k));
+    explicit_bzero(&drawn, sizeof(drawn));
+    whisk::CheckShuffleSize(n);
+    std::vector<G1Affine> Rs, Ss;
+    whisk::DecodeTrackers(Trackers(pre_trackers, n), &Rs, &Ss);
+    std::vector<G1Affine> Ts(n), Us(n);
+    uint64_t M[18];
+    const uint64_t* R64 = reinterpret_cast<const uint64_t*>(Rs.data());
+    const uint64_t* S64 = reinterpret_cast<const uint64_t*>(Ss.data());
+    uint64_t* T64 = reinterpret_cast<uint64_t*>(Ts.data());
+    uint64_t* U64 = reinterpret_cast<uint64_t*>(Us.data());
+    int rc = curdle_shuffle_permute_commit_ex(crs, R64, S64, n, s.permutation.data(), s.k, rand, CURDLE_SHUFFLE_CONSTANT_TIME,
+                                              T64, U64, M, s.rs_m);  // :83
+    if (rc != CURDLE_OK) return rc;
+    std::vector<uint8_t> body(whisk::WHISK_SHUFFLE_PROOF_SIZE);
+    size_t body_len = 0;
+    rc = curdle_prove_ct(crs, R64, S64, T64, U64, n, M, s.permutation.data(), s.k, s.rs_m, rand, body.data(), body.size(),
+                         &body_len);  // :88
+    if (rc != CURDLE_OK) return rc;
+    whisk::SerializeShuffleProof(Point::FromJac(M), body.data(), body_len, proof_out);
+    for (size_t i = 0; i < n; i++) {  // :109-112
+      const whisk::WhiskTracker t = whisk::NewWhiskTracker(Ts[i], Us[i]);
+      memcpy(post_trackers_out + 96 * i, &t, 96);
+    }
     return CURDLE_OK;
   });
 }

@@ -375,6 +375,38 @@ std::vector<int> IsValidWhiskShuffleProofBatch(const proto::CRS& crs, const std:
   return oks;
 }
 
+void CheckShuffleSize(size_t n) {
+  if (n != ELL) throw err("shuffling and permuting: the whisk shuffle works on ELL trackers");  // permutation length, util.go:49
+}
+
+void DecodeTrackers(const std::vector<WhiskTracker>& trackers, std::vector<G1Affine>* Rs, std::vector<G1Affine>* Ss) {
+  // The 2n tracker points in ONE batched decoding (square roots + subgroup tests on the GPU,
+  // 0.6 ms) -- the reference decodes them one by one (types.go:39-51), 49 us each on a host core
+  const size_t n = trackers.size();
+  Rs->resize(n);
+  Ss->resize(n);
+  proto::PointDecoder dec(/*subgroup_check=*/true);
+  for (size_t i = 0; i < n; i++) {
+    dec.Add(trackers[i].rG);
+    dec.Add(trackers[i].krG);
+  }
+  dec.Run();
+  for (size_t i = 0; i < n; i++) {  // the same errors as WhiskTracker.getPoints, types.go:85-95
+    if (!dec.GetAffine(2 * i, &(*Rs)[i])) throw err("getting points: failed to set rG");
+    if (!dec.GetAffine(2 * i + 1, &(*Ss)[i])) throw err("getting points: failed to set krG");
+  }
+}
+
+void SerializeShuffleProof(const Point& M, const uint8_t* body, size_t body_len, uint8_t proof_out[WHISK_SHUFFLE_PROOF_SIZE]) {
+  // WhiskShuffleProof.Serialize, types.go:53-71: M, the proof, zero padding up to the array size
+  proto::Writer w;
+  w.PutPoint(M);
+  if (w.buf.size() + body_len > WHISK_SHUFFLE_PROOF_SIZE) throw err("serializing proof: larger than WHISK_SHUFFLE_PROOF_SIZE");
+  memset(proof_out, 0, WHISK_SHUFFLE_PROOF_SIZE);
+  memcpy(proof_out, w.buf.data(), w.buf.size());
+  memcpy(proof_out + w.buf.size(), body, body_len);
+}
+
 std::vector<WhiskTracker> GenerateWhiskShuffleProof(const proto::CRS& crs, const std::vector<WhiskTracker>& preTrackers,
                                                     common::Rand& rand, uint8_t proof_out[WHISK_SHUFFLE_PROOF_SIZE]) {
   std::vector<uint32_t> permutation;
@@ -382,33 +414,14 @@ std::vector<WhiskTracker> GenerateWhiskShuffleProof(const proto::CRS& crs, const
   Scalar k;
   rand.GetFr(k.v);                             // :68
   const size_t n = preTrackers.size();
-  if (n != ELL) throw err("shuffling and permuting: the whisk shuffle works on ELL trackers");  // permutation length, util.go:49
-  // The 2n tracker points in ONE batched decoding (square roots + subgroup tests on the GPU,
-  // 0.6 ms) -- the reference decodes them one by one (types.go:39-51), 49 us each on a host core
-  std::vector<G1Affine> Rs(n), Ss(n);
-  {
-    proto::PointDecoder dec(/*subgroup_check=*/true);
-    for (size_t i = 0; i < n; i++) {
-      dec.Add(preTrackers[i].rG);
-      dec.Add(preTrackers[i].krG);
-    }
-    dec.Run();
-    for (size_t i = 0; i < n; i++) {  // the same errors as WhiskTracker.getPoints, types.go:85-95
-      if (!dec.GetAffine(2 * i, &Rs[i])) throw err("getting points: failed to set rG");
-      if (!dec.GetAffine(2 * i + 1, &Ss[i])) throw err("getting points: failed to set krG");
-    }
-  }
+  CheckShuffleSize(n);
+  std::vector<G1Affine> Rs, Ss;
+  DecodeTrackers(preTrackers, &Rs, &Ss);
   proto::ShuffleCommit sc = proto::ShufflePermuteCommit(crs.Gs, crs.Hs, Rs, Ss, permutation, k, rand);  // :83
   proto::Proof proof = proto::Prove(crs, Rs, Ss, sc.Ts, sc.Us, sc.M, permutation, k, sc.rs_m, rand);      // :88
 
-  // WhiskShuffleProof.Serialize, types.go:53-71: M, the proof, zero padding up to the array size
-  proto::Writer w;
-  w.PutPoint(sc.M);
   const std::vector<uint8_t> body = proof.Serialize();
-  if (w.buf.size() + body.size() > WHISK_SHUFFLE_PROOF_SIZE) throw err("serializing proof: larger than WHISK_SHUFFLE_PROOF_SIZE");
-  memset(proof_out, 0, WHISK_SHUFFLE_PROOF_SIZE);
-  memcpy(proof_out, w.buf.data(), w.buf.size());
-  memcpy(proof_out + w.buf.size(), body.data(), body.size());
+  SerializeShuffleProof(sc.M, body.data(), body.size(), proof_out);
 
   std::vector<WhiskTracker> post(n);
   for (size_t i = 0; i < n; i++) post[i] = NewWhiskTracker(sc.Ts[i], sc.Us[i]);  // :109-112

@@ -50,6 +50,13 @@ struct ShuffleBatchItem {
 };
 std::vector<int> IsValidWhiskShuffleProofBatch(const proto::CRS& crs, const std::vector<ShuffleBatchItem>& items,
                                                common::Rand& rand, int nthreads);
+// The steps of GenerateWhiskShuffleProof that handle nothing secret, shared with the constant-time form of the call
+// (curdle_whisk_generate_shuffle_proof_ct, proto_api.cpp): the size rule (throws the reference's error unless n is ELL),
+// the batched decoding of the 2n tracker points (throws getPoints' errors) and WhiskShuffleProof.Serialize (M, the
+// serialised curdleproof, zero padding).
+void CheckShuffleSize(size_t n);
+void DecodeTrackers(const std::vector<WhiskTracker>& trackers, std::vector<G1Affine>* Rs, std::vector<G1Affine>* Ss);
+void SerializeShuffleProof(const alg::Point& M, const uint8_t* body, size_t body_len, uint8_t proof_out[WHISK_SHUFFLE_PROOF_SIZE]);
 // whisk.go:63 -- returns the post-shuffle trackers, writes the 4,576-byte proof.
 std::vector<WhiskTracker> GenerateWhiskShuffleProof(const proto::CRS& crs, const std::vector<WhiskTracker>& preTrackers,
                                                     common::Rand& rand, uint8_t proof_out[WHISK_SHUFFLE_PROOF_SIZE]);

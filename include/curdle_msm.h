@@ -1048,7 +1048,8 @@ int curdle_stat_g1_mul_ct(unsigned long long out[2]);
  * zeros draws less), which is not addressed; and nothing about curdle_msm_g1, whose warning above stays true.
  * OUTSIDE THE PROMISE: the result itself and the verdict on scalar_bits; whatever the caller does with the scalars
  * before and after.  It is NOT A DEFAULT: nothing in the library routes to it but curdle_shuffle_permute_commit_ex and
- * curdle_prove_ex, each under its flag.
+ * curdle_prove_ex, each under its flag.  (Since then also curdle_prove_ct and curdle_whisk_generate_shuffle_proof_ct,
+ * below: entry points that ARE constant-time forms, not defaults either.)
  * Cost: one lane's chain of scalar_bits doublings and additions, then ceil(log2 n) levels of additions and one inversion:
  * measured 5.5 ... 6.8 ms at 255 bits and 0.9 ... 2.0 ms at 9 bits for n = 4 ... 65,536, 12 to 27 times curdle_msm_g1_device
  * (profiles/r27_msm_ct.json); the flagged shuffle step below 11.2 ... 12.0 ms at ell = 124 ... 508 against 1.4 ... 1.6 ms.
@@ -1104,7 +1105,8 @@ int curdle_stat_msm_ct_batch(unsigned long long out[3]);   /* batched calls | MS
  * flag: the host Point::Mul calls on r_k, k, r_t and r_u and GroupCommitment::New, the Fr vector arithmetic (the
  * permutation of the challenges is an indexed gather by perm), the generation of the blinders, the ordinary heap
  * copies of the witness, and the alg::ScalarMulBatch calls (their scalars are public challenges).  DESIGN.md section 0
- * lists every one with its line.  They are the next follow-up.  Under CURDLE_PROVER_FOLD_BASES=1 the recursive provers
+ * lists every one with its line.  They are the next follow-up.  (Built since as curdle_prove_ct, below: this flag's
+ * promise is unchanged.)  Under CURDLE_PROVER_FOLD_BASES=1 the recursive provers
  * multiply H by a secret inner product on the host, so there the flagged call is refused with CURDLE_EINVAL.  Linked over
  * a backend without the constant-time MSM, and without a device, the flagged call fails with CURDLE_ENODEV: no fallback.
  * ell is bounded by the primitive: the largest batch of a round must fit 65,536 pairs.  It is not a default. */
@@ -1132,7 +1134,8 @@ int curdle_stat_alg_msm(unsigned long long out[4]);   /* bucket-MSM calls | thei
  * The promise, what it does not cover (power draw and clock behaviour) and what is outside it are those of
  * curdle_msm_g1_ct above, for k, perm and the blinders; the host's part outside the promise is the range check of perm,
  * the draw of the blinders from rand and the copies.  NOT covered: curdle_prove and curdle_whisk_generate_shuffle_proof,
- * whose MSMs see the same permutation and blinders on the default path.  It is not a default. */
+ * whose MSMs see the same permutation and blinders on the default path.  It is not a default.  (Their constant-time
+ * forms, built since: curdle_prove_ct and curdle_whisk_generate_shuffle_proof_ct, below.) */
 /* The gather of the flagged step on its own, everything resident: d_out[i] = d_in[d_perm[i]] for i < n, 96-byte records,
  * d_perm n uint32 below n (an entry at or above n gives a zero record).  Every lane reads all n records; no address is
  * made of d_perm.  n <= 4,096; d_in and d_out multiples of 16 and not overlapping, d_perm a multiple of 4; `stream` as in
@@ -1142,6 +1145,70 @@ int curdle_g1_permute_ct_device(const void* d_in, const void* d_perm, size_t n, 
 int curdle_shuffle_permute_commit_ex(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, size_t ell,
                                      const uint32_t* perm, const uint64_t k[4], curdle_rand* rand, unsigned flags,
                                      uint64_t* Ts_out, uint64_t* Us_out, uint64_t M_out[18], uint64_t rs_m_out[16]);
+/* The oblivious gather over 32-byte records: out[i] = in[perm[i]] for i < n with perm SECRET; an entry at or above n gives
+ * a zero record.  The records are bytes to it (Prove hands it fr.Elements, it knows nothing of the field).  The kernel,
+ * k_fr_permute_ct (csrc/msm_ct_kernels.hip), is k_g1_permute_ct's body at another record size: lane i loads its own
+ * perm[i], walks j = 0 ... n - 1, reads record j and keeps it under a mask made of perm[i] ^ j: n^2 record reads.
+ * n <= 4,096 (the gather is quadratic; the shuffle step's cap): more is CURDLE_EINVAL.  n = 0 returns CURDLE_OK without a
+ * device, looks at no pointer and writes nothing.  Refusals happen before any device work, in this order: a null
+ * argument, n, and (the _device form) d_in / d_out that are not multiples of 16 or that overlap and a d_perm that is
+ * not a multiple of 4.  `stream` is as in curdle_msm_g1_device; d_out is complete when the call returns.  One MSM slot is
+ * held for the call.  The host form stages perm and the output through the slot's pinned memory and device buffers and
+ * overwrites all four, on the stream that used them, on every way out; the input's staging is not overwritten (a caller
+ * whose records are secret too uses the _device form on arrays it wipes itself).  The _device form copies and wipes
+ * nothing: the arrays are the caller's.
+ * WHAT THE FLAG PROMISES (there is no flag: these entry points ARE the constant-time form): no address, branch, loop
+ * count or exec mask of the kernel is made of perm or of the records; they depend on n and the pointers.  The host only
+ * copies perm and never looks at it.
+ * WHAT IT DOES NOT PROMISE: power draw and clock behaviour, as for curdle_msm_g1_ct.
+ * OUTSIDE THE PROMISE: the output itself; whatever the caller does with perm before and after.  It is not a default:
+ * nothing routes to it but curdle_prove_ct. */
+int curdle_fr_permute_ct(const uint64_t* in, const uint32_t* perm, size_t n, uint64_t* out);
+int curdle_fr_permute_ct_device(const void* d_in, const void* d_perm, size_t n, void* d_out, void* stream);
+int curdle_stat_fr_permute_ct(unsigned long long out[2]);   /* records gathered | launches; completed calls only */
+/* curdle_prove in constant-time form: the same arguments, the same proof bytes, rand in the same state afterwards (r_a,
+ * r_b, r_k, r_t, r_u and every other draw at the same point); only where the computations on secrets run differs.  There
+ * is no flags word.  The body is curdle_prove's under two scoped switches on the calling thread (Prove starts no
+ * threads): CURDLE_PROVE_MSM_CONSTANT_TIME's, and a second one (alg::SecretOpsScope) under which
+ *   - the twelve host Point::Mul calls on r_k, k, r_a, r_b, r_t, r_u are gone: each pair of GroupCommitment::New is one
+ *     batch of four MSMs over six pairs, {Gt}, {R, H}, {Gu}, {S, H}, hence one walk; k R and r_k R never exist unblinded;
+ *   - the two gathers by the secret permutation go to curdle_fr_permute_ct: two launches of ell records a Prove;
+ *   - proof.A is ONE MSM over the ell + 4 pairs (Gs | Hs; permuted challenges | blinders) and the grand-product
+ *     argument's C one MSM over (Gs | Hs; partial products | blinders): the commitments to the first halves alone,
+ *     which curdle_prove brings to the host and blinds there, never leave the device workspace;
+ *   - the scalar vectors this route creates are overwritten on every way out.
+ * Refusals, in this order, with proof_out and *proof_len untouched and nothing drawn from rand: a null argument
+ * (proof_out may be null, as for curdle_prove), ell against the CRS, ell > 4,096, CURDLE_PROVER_FOLD_BASES=1 (CURDLE_EINVAL,
+ * curdle_prove_ex's message), and a backend without the primitives or no device: CURDLE_ENODEV, no fallback.
+ * curdle_whisk_generate_shuffle_proof_ct is curdle_whisk_generate_shuffle_proof in that form: the same arguments and
+ * rule for n, the same post-trackers and proof bytes, rand in the same state: GeneratePermutation and GetFr(k) in that
+ * order, the batched decode (public), the shuffle step under CURDLE_SHUFFLE_CONSTANT_TIME, curdle_prove_ct, the
+ * serialisation.  Its own copies of k, the permutation and the blinders are overwritten on every way out; without a
+ * device: CURDLE_ENODEV.
+ * WHAT THE FLAG PROMISES (there is no flag: these entry points ARE the constant-time form): on the device, what
+ * curdle_msm_g1_ct, CURDLE_SHUFFLE_CONSTANT_TIME and curdle_fr_permute_ct promise; on the host, no branch, loop count or
+ * memory address in Prove is made of the witness, the blinders or the permutation, except those listed as outside: what
+ * the host still does with them is straight-line field arithmetic in mask form (f_add, f_sub, f_cond_sub, f_neg, fr_mul of
+ * csrc/bls12_381.h), copies, and the draws.
+ * WHAT IT DOES NOT PROMISE: power draw and clock behaviour, as above; and what the host compiler made of the mask
+ * arithmetic (DESIGN.md section 0 records what the shipped x86 code of those five functions shows; read, not tested).
+ * OUTSIDE THE PROMISE: rand's own code (GeneratePermutation is a Fisher-Yates that indexes by what it draws); the range
+ * check of perm in the shuffle step (curdle_prove_ct, like curdle_prove, makes none: an entry at or above ell gathers a
+ * zero record); `if (den.IsZero()) throw` and the constraint self-check in the inner-product argument's GenerateBlinders,
+ * branches on a secret-derived value that are taken with negligible probability and reveal only that generation failed;
+ * likewise the grand-product prover's self-check `IPA(C, D) != z`, never taken for a well-formed witness;
+ * the prover's ordinary std::vector copies of the witness, which are not wiped; the proof itself.  Neither call is a
+ * default: nothing routes to them.
+ * curdle_stat_host_point_mul: calls of alg::Point::Mul on the CALLING THREAD since it started (a thread-local counter:
+ * the batch verifiers multiply on many threads).  A curdle_prove makes 14, a curdle_prove_ct 2 -- Hcrs.Mul(beta) and
+ * M.Mul(alpha), both by public challenges.
+ * Cost: profiles/r29_prove_ct.json. */
+int curdle_prove_ct(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, const uint64_t* Ts, const uint64_t* Us,
+                    size_t ell, const uint64_t M[18], const uint32_t* perm, const uint64_t k[4], const uint64_t rs_m[16],
+                    curdle_rand* rand, uint8_t* proof_out, size_t cap, size_t* proof_len);
+int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, const uint8_t* pre_trackers, size_t n, curdle_rand* rand,
+                                           uint8_t* post_trackers_out, uint8_t* proof_out);
+int curdle_stat_host_point_mul(unsigned long long* out);   /* calls of alg::Point::Mul on the CALLING THREAD */
 /* Diagnostics: out[0] points normalised on the device since the library was loaded, out[1] inversion groups run
  * (one Fermat inversion each; at most one per 64 points of a launch). */
 int curdle_stat_normalize(unsigned long long out[2]);
