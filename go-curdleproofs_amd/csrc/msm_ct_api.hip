@@ -392,6 +392,83 @@ extern "C" int curdle_fr_permute_ct_device(const void* d_in, const void* d_perm,
   });
 }
 
+// The batched gather (k_permute_ct_seg): k members of one n in ONE launch, member j's records, entries and outputs the
+// j-th run of n in each array -- what a lockstep group's k PermuteSecret calls become (alg::Lockstep, host/algebra.cpp).
+// Staging, wiping and the slot hold are curdle_fr_permute_ct's over k n records, and the host form wipes the INPUT's two
+// staging copies as well; the counter moves by (k n, 1).
+namespace {
+constexpr size_t kPermuteBatchMaxK = 4096;
+constexpr size_t kPermuteBatchMaxRecords = (size_t)1 << 20;
+
+// null, n, k, k n: the single call's order with k behind n
+int permute_batch_check(const void* in, const void* perm, size_t n, size_t k, const void* out) {
+  if (int rc = fr_permute_check(in, perm, n, out)) return rc;
+  if (k > kPermuteBatchMaxK) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 members", k);
+  if (k * n > kPermuteBatchMaxRecords) return fail(CURDLE_EINVAL, "k n = %zu exceeds the supported 2^20 records", k * n);
+  return CURDLE_OK;
+}
+
+int permute_batch_device(const void* d_in, const void* d_perm, size_t n, size_t k, size_t record, void* d_out, void* stream) {
+  if (n == 0 || k == 0) return CURDLE_OK;
+  if (int rc = permute_batch_check(d_in, d_perm, n, k, d_out)) return rc;
+  const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out;
+  const size_t bytes = record * k * n;
+  if (!aligned16(d_in) || !aligned16(d_out) || (a < b + bytes && b < a + bytes) || ((uintptr_t)d_perm & 3u))
+    return fail(CURDLE_EINVAL, "record pointers must be multiples of 16 and must not overlap, the permutation's a multiple of 4");
+  SlotHold H(cur(), true, stream);
+  return H.run([&]() -> int {
+    HIP_TRY(launch_permute_ct_seg(d_in, static_cast<const uint32_t*>(d_perm), (uint32_t)n, (uint32_t)k, (uint32_t)record, d_out,
+                                  H.stream()));
+    HIP_TRY(hipStreamSynchronize(H.stream()));
+    if (record == 32) count_fr_permute_ct(k * n);
+    return CURDLE_OK;
+  });
+}
+}  // namespace
+
+extern "C" int curdle_fr_permute_ct_batch(const uint64_t* in, const uint32_t* perm, size_t n, size_t k, uint64_t* out) {
+  if (n == 0 || k == 0) return CURDLE_OK;
+  if (int rc = permute_batch_check(in, perm, n, k, out)) return rc;
+  SlotHold H(cur(), true, nullptr);
+  WipeList W(H.stream());
+  H.wipe_on_exit(&W, "constant-time scalar gather batch: clearing the permutations and the gathered records");
+  return H.run([&]() -> int {
+    Slot& S = H.slot();
+    const hipStream_t st = H.stream();
+    const size_t m = k * n, rec = m * 32, perm_pad = (4 * m + 15) / 16 * 16;
+    int r;
+    if ((r = ensure(S.tmp, perm_pad))) return r;    // perm
+    if ((r = ensure(S.scalars, rec))) return r;     // in
+    if ((r = ensure(S.sorted, rec))) return r;      // out
+    if ((r = ensure_pinned(S, 0, perm_pad + rec))) return r;  // perm | in
+    if ((r = ensure_pinned(S, 1, rec))) return r;             // out
+    W.note_device(S.tmp.p, perm_pad);
+    W.note_device(S.scalars.p, rec);  // unlike the single call: a group's input may be secret (the shuffle step's unpermuted records)
+    W.note_device(S.sorted.p, rec);
+    W.note_host(S.h_stage[0], perm_pad + rec);
+    W.note_host(S.h_stage[1], rec);
+    uint8_t* h = static_cast<uint8_t*>(S.h_stage[0]);
+    memcpy(h, perm, 4 * m);
+    memcpy(h + perm_pad, in, rec);
+    HIP_TRY(hipMemcpyAsync(S.tmp.p, h, 4 * m, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S.scalars.p, h + perm_pad, rec, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_permute_ct_seg(S.scalars.p, static_cast<const uint32_t*>(S.tmp.p), (uint32_t)n, (uint32_t)k, 32, S.sorted.p, st));
+    HIP_TRY(hipMemcpyAsync(S.h_stage[1], S.sorted.p, rec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(out, S.h_stage[1], rec);
+    count_fr_permute_ct(m);
+    return CURDLE_OK;
+  });
+}
+
+extern "C" int curdle_fr_permute_ct_batch_device(const void* d_in, const void* d_perm, size_t n, size_t k, void* d_out, void* stream) {
+  return permute_batch_device(d_in, d_perm, n, k, 32, d_out, stream);
+}
+
+extern "C" int curdle_g1_permute_ct_batch_device(const void* d_in, const void* d_perm, size_t n, size_t k, void* d_out, void* stream) {
+  return permute_batch_device(d_in, d_perm, n, k, 96, d_out, stream);
+}
+
 extern "C" int curdle_stat_fr_permute_ct(unsigned long long out[2]) { return read_stats(out, g_fr_permute_ct_stat, 2); }
 
 // The device work of curdle_shuffle_permute_commit_ex under CURDLE_SHUFFLE_CONSTANT_TIME (the entry point below checked the

@@ -32,6 +32,14 @@
 // k_fr_permute_ct.  The same gather over 32-byte records (Prove's permuted challenges; the records are bytes to it, not
 // field elements): both kernels are instantiations of ONE body, gather_ct<W>, W the record's size in 16-byte words.
 //
+// k_permute_ct_seg<RecordBytes>.  k gathers of one n in one launch, over the same body: block (x, j) serves member j, whose
+// records, entries and outputs are the j-th run of n in each array.  Lane i < n loads perm[j n + i] and walks
+// t = 0 ... n - 1 over in[j n + t]: t is the same on every lane of a wave and j is the block's, so a record's address is
+// wave-uniform and made of public values alone.  The mask is made of perm ^ t with t < n INSIDE the member's segment: an
+// entry at or above n matches no t and gives a zero record, never a neighbour's.  One wave per block (kPermuteSegBlock):
+// the gather is a chain of n dependent-free loads per lane and what it needs is waves on many CUs, not lanes per block --
+// k members of n <= 64 are k waves on k CUs' SIMDs, where blocks of kBlock would leave three waves in four empty.
+//
 // k_g1_sum_ct_seg, k_msm_ct_finish_seg.  The same sum over k segments of ONE term array (the batched call: one walk over
 // the concatenated pairs of k MSMs): MSM j owns term[begin_j, begin_j + count_j) and a PUBLIC table of (begin, count)
 // says so.  Block (x, j) of k_g1_sum_ct_seg reads its entry at a wave-uniform address, derives the segment's size at
@@ -271,6 +279,20 @@ __global__ void __launch_bounds__(kBlock)
   gather_ct<2>(in, p, n, out + 2 * (size_t)i);
 }
 
+static constexpr u32 kPermuteSegBlock = 64;
+
+template <int RecordBytes>
+__global__ void __launch_bounds__(kPermuteSegBlock)
+    k_permute_ct_seg(const uint4* __restrict__ in, const u32* __restrict__ perm, u32 n, uint4* __restrict__ out) {
+  static_assert(RecordBytes % 16 == 0, "records are whole 16-byte words");
+  constexpr int W = RecordBytes / 16;
+  const u32 i = blockIdx.x * kPermuteSegBlock + threadIdx.x;
+  if (i >= n) return;                          // public
+  const size_t base = (size_t)blockIdx.y * n;  // the member's segment: public, the block's
+  const u32 p = perm[base + i];                // an address made of the lane index
+  gather_ct<W>(in + W * base, p, n, out + W * (base + i));
+}
+
 hipError_t launch_msm_ct_walk(const void* points, const void* scalars, int scalar_form, uint32_t bits, uint32_t n, void* term,
                               uint32_t* status, hipStream_t stream) {
   if (n == 0) return hipSuccess;
@@ -325,6 +347,20 @@ hipError_t launch_fr_permute_ct(const void* in, const uint32_t* perm, uint32_t n
   if (n == 0) return hipSuccess;
   if (n > (1u << 31)) return hipErrorInvalidValue;  // the lane index is 32 bits
   hipLaunchKernelGGL(k_fr_permute_ct, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream, (const uint4*)in, perm, (u32)n, (uint4*)out);
+  return hipGetLastError();
+}
+
+hipError_t launch_permute_ct_seg(const void* in, const uint32_t* perm, uint32_t n, uint32_t k, uint32_t record_bytes, void* out,
+                                 hipStream_t stream) {
+  if (n == 0 || k == 0) return hipSuccess;
+  if (n > 65535 || k > 65535) return hipErrorInvalidValue;  // k is the grid's y
+  const dim3 grid(cdiv(n, kPermuteSegBlock), k);
+  if (record_bytes == 32)
+    hipLaunchKernelGGL(k_permute_ct_seg<32>, grid, dim3(kPermuteSegBlock), 0, stream, (const uint4*)in, perm, (u32)n, (uint4*)out);
+  else if (record_bytes == 96)
+    hipLaunchKernelGGL(k_permute_ct_seg<96>, grid, dim3(kPermuteSegBlock), 0, stream, (const uint4*)in, perm, (u32)n, (uint4*)out);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

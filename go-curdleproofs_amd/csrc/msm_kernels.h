@@ -364,6 +364,9 @@ hipError_t launch_g1_mul_ct(const void* points, uint32_t point_stride, const voi
 //     lane reads all n records of its half.  out must not overlap in.
 //   launch_fr_permute_ct: out[i] = in[perm[i]] for i < n over 32-byte records by the same gather (an entry at or above n:
 //     a zero record).  out must not overlap in.
+//   launch_permute_ct_seg: k gathers of one n in ONE launch: out[j n + i] = in[j n + perm[j n + i]] for i < n, j < k, over
+//     records of record_bytes = 32 or 96; an entry at or above n gives a zero record, never another member's.  n and k
+//     at most 65,535 each.  out must not overlap in.
 enum { kMsmCtScalarFr = 0, kMsmCtScalarU32 = 1 };
 static constexpr uint32_t kMsmCtTermBytes = 224;
 static constexpr uint32_t kMsmCtSumTail = 512;
@@ -374,6 +377,8 @@ hipError_t launch_msm_ct_sum_seg(void* term, const void* seg, const uint32_t* co
                                  void* out, uint32_t* levels, hipStream_t stream);
 hipError_t launch_g1_permute_ct(const void* in, const uint32_t* perm, uint32_t n, uint32_t halves, void* out, hipStream_t stream);
 hipError_t launch_fr_permute_ct(const void* in, const uint32_t* perm, uint32_t n, void* out, hipStream_t stream);
+hipError_t launch_permute_ct_seg(const void* in, const uint32_t* perm, uint32_t n, uint32_t k, uint32_t record_bytes, void* out,
+                                 hipStream_t stream);
 
 // normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion
 // per wave of 64 lanes with 1 or 8 points each (Montgomery's trick over a wave scan).  The forms are those of

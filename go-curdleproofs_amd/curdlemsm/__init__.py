@@ -96,6 +96,8 @@ SYMBOLS = [
     "curdle_prove_ex", "curdle_stat_alg_msm",
     "curdle_fr_permute_ct", "curdle_fr_permute_ct_device", "curdle_stat_fr_permute_ct",
     "curdle_prove_ct", "curdle_whisk_generate_shuffle_proof_ct", "curdle_stat_host_point_mul",
+    "curdle_fr_permute_ct_batch", "curdle_fr_permute_ct_batch_device", "curdle_g1_permute_ct_batch_device",
+    "curdle_prove_batch", "curdle_whisk_generate_shuffle_proof_batch", "curdle_stat_prove_batch",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -1000,6 +1002,79 @@ def stat_fr_permute_ct() -> dict:
     return {"records": int(out[0]), "launches": int(out[1])}
 
 
+_fr_permute_ct_batch = _sig("curdle_fr_permute_ct_batch", C.c_int, _vp, _vp, C.c_size_t, C.c_size_t, _vp)
+_fr_permute_ct_batch_device = _sig("curdle_fr_permute_ct_batch_device", C.c_int, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp)
+_g1_permute_ct_batch_device = _sig("curdle_g1_permute_ct_batch_device", C.c_int, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp)
+
+
+def fr_permute_ct_batch(records, perm, n: int, k: int) -> np.ndarray:
+    """k oblivious gathers of one n in one launch (curdle_fr_permute_ct_batch): out[j n + i] = records[j n + perm[j n + i]]
+    over 32-byte records; an entry at or above n gives a zero record, never another member's.  records: (k n, 4) uint64,
+    perm: k n uint32.  n <= 4,096, k <= 4,096, k n <= 2^20."""
+    records = _as_u64(records, 4)
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    if k * n and (records.shape[0] != k * n or len(perm) != k * n):
+        raise CurdleError(EINVAL, "records and perm need k n entries")
+    out = np.zeros((k * n, 4), dtype=np.uint64)
+    _check(_fr_permute_ct_batch(_ptr(records), _ptr(perm), n, k, _ptr(out)))
+    return out
+
+
+def fr_permute_ct_batch_device(d_in: int, d_perm: int, n: int, k: int, d_out: int, stream: int = 0) -> None:
+    """fr_permute_ct_batch on device-resident arrays (curdle_fr_permute_ct_batch_device; the pointer rules of
+    fr_permute_ct_device)."""
+    _check(_fr_permute_ct_batch_device(d_in or None, d_perm or None, n, k, d_out or None, stream or None))
+
+
+def g1_permute_ct_batch_device(d_in: int, d_perm: int, n: int, k: int, d_out: int, stream: int = 0) -> None:
+    """The same batched gather over 96-byte records, device-resident (curdle_g1_permute_ct_batch_device)."""
+    _check(_g1_permute_ct_batch_device(d_in or None, d_perm or None, n, k, d_out or None, stream or None))
+
+
+PROVE_BATCH_CONSTANT_TIME = 1                         # CURDLE_PROVE_BATCH_CONSTANT_TIME
+_prove_batch = _sig("curdle_prove_batch", C.c_int, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                    C.c_uint, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int))
+_stat_prove_batch = _sig("curdle_stat_prove_batch", C.c_int, C.POINTER(C.c_ulonglong))
+
+
+def prove_batch(crs: CRS, members, flags: int = 0):
+    """k proofs over one CRS in lockstep (curdle_prove_batch): members is a list of (Rs, Ss, Ts, Us, M, perm, k, rs_m,
+    rand) as prove() takes them, with k distinct Rand objects.  flags: 0 gives prove()'s bytes per member,
+    PROVE_BATCH_CONSTANT_TIME prove_ct()'s.  Returns (proofs, status): a list of bytes (empty for a member that failed
+    on its own) and the list of per-member codes; raises CurdleError when the call itself is refused or the device fails."""
+    k = len(members)
+    keep, cols = [], [[] for _ in range(6)]
+    Ms = np.zeros((k, 18), dtype=np.uint64)
+    ks = np.zeros((k, 4), dtype=np.uint64)
+    rs_ms = np.zeros((k, 16), dtype=np.uint64)
+    rands = (C.c_void_p * max(k, 1))()
+    for i, (Rs, Ss, Ts, Us, M, perm, kk, rs_m, rand) in enumerate(members):
+        arrs = [_as_u64(a, 12) for a in (Rs, Ss, Ts, Us)] + [np.ascontiguousarray(perm, dtype=np.uint32)]
+        keep.append(arrs)
+        for c, a in zip(cols, arrs):
+            c.append(a.ctypes.data)
+        Ms[i], ks[i], rs_ms[i] = _as_u64(M).reshape(18), _as_u64(kk).reshape(4), _as_u64(rs_m).reshape(16)
+        rands[i] = rand._h
+    ptrs = [(C.c_void_p * max(k, 1))(*c) for c in cols[:5]]
+    stride = 1 << 16
+    buf = np.zeros(max(k, 1) * stride, dtype=np.uint8)
+    lens = (C.c_size_t * max(k, 1))()
+    status = (C.c_int * max(k, 1))()
+    ell = keep[0][0].shape[0] if k else crs.ell          # the members' ell: the call checks it against the CRS
+    if any(a.shape[0] != ell for arrs in keep for a in arrs):
+        raise CurdleError(EINVAL, "every member needs ell points in Rs, Ss, Ts, Us and ell entries in perm")
+    _check(_prove_batch(crs._h, k, ell, ptrs[0], ptrs[1], ptrs[2], ptrs[3], _ptr(Ms), ptrs[4], _ptr(ks), _ptr(rs_ms),
+                        rands, int(flags), _ptr(buf), stride, lens, status))
+    return [bytes(buf[stride * i: stride * i + lens[i]]) for i in range(k)], [int(status[i]) for i in range(k)]
+
+
+def stat_prove_batch() -> dict:
+    """Batch proving since the library was loaded: calls, members, lockstep groups, coalesced device calls."""
+    out = (C.c_ulonglong * 4)()
+    _check(_stat_prove_batch(out))
+    return {"calls": int(out[0]), "members": int(out[1]), "groups": int(out[2]), "device_calls": int(out[3])}
+
+
 def verify(crs: CRS, proof: bytes, Rs, Ss, Ts, Us, M, rand: Rand) -> bool:
     """curdleproof.Verify (curdleproof.go:199): the accept bit; raises CurdleError for (false, err)."""
     Rs, Ss, Ts, Us = (_as_u64(a, 12) for a in (Rs, Ss, Ts, Us))
@@ -1344,6 +1419,32 @@ def whisk_generate_shuffle_proof_ct(crs: CRS, pre_trackers, rand: Rand):
     _check(_whisk_gen_shuffle_ct(crs._h, _ptr(pre), len(pre_trackers), rand._h, _ptr(post), _ptr(proof)))
     pb = post.tobytes()
     return [pb[96 * i: 96 * (i + 1)] for i in range(len(pre_trackers))], proof.tobytes()
+
+
+_whisk_gen_shuffle_batch = _sig("curdle_whisk_generate_shuffle_proof_batch", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp,
+                                C.c_uint, _vp, _vp, C.POINTER(C.c_int))
+
+
+def whisk_generate_shuffle_proof_batch(crs: CRS, pre_sets, rands, flags: int = 0):
+    """whisk_generate_shuffle_proof for k pre-tracker lists of one length in lockstep
+    (curdle_whisk_generate_shuffle_proof_batch), with k distinct Rand objects; under PROVE_BATCH_CONSTANT_TIME
+    whisk_generate_shuffle_proof_ct's results.  Returns (post_sets, proofs, status); a member with a non-zero status has
+    None for both."""
+    k = len(pre_sets)
+    n = len(pre_sets[0]) if k else 0
+    pre = [_bytes_arr(b"".join(s)) for s in pre_sets]
+    if any(len(a) != 96 * n for a in pre):
+        raise ValueError("every tracker set needs the same length")
+    ptrs = (C.c_void_p * max(k, 1))(*[a.ctypes.data for a in pre])
+    rh = (C.c_void_p * max(k, 1))(*[r._h for r in rands])
+    post = np.zeros(max(1, 96 * n * k), dtype=np.uint8)
+    proofs = np.zeros(max(1, WHISK_SHUFFLE_PROOF_SIZE * k), dtype=np.uint8)
+    status = (C.c_int * max(k, 1))()
+    _check(_whisk_gen_shuffle_batch(crs._h, k, ptrs, n, rh, int(flags), _ptr(post), _ptr(proofs), status))
+    pb, fb = post.tobytes(), proofs.tobytes()
+    posts = [[pb[96 * (n * i + t): 96 * (n * i + t + 1)] for t in range(n)] if status[i] == 0 else None for i in range(k)]
+    prs = [fb[WHISK_SHUFFLE_PROOF_SIZE * i: WHISK_SHUFFLE_PROOF_SIZE * (i + 1)] if status[i] == 0 else None for i in range(k)]
+    return posts, prs, [int(status[i]) for i in range(k)]
 
 
 def whisk_is_valid_tracker_proof(tracker: bytes, k_commitment: bytes, proof: bytes) -> bool:

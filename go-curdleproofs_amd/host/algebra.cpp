@@ -4,11 +4,15 @@
 #include <stdlib.h>
 
 #include "host_ops.h"
+#include "knobs.h"
 
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <stdexcept>
+#include <system_error>
+#include <thread>
 
 #include "../../include/curdle_msm.h"
 
@@ -23,6 +27,14 @@ extern "C" int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t
                                       unsigned scalar_bits, uint64_t* out_jac) __attribute__((weak));
 // ... and so does the oblivious gather over scalars, which PermuteSecret uses under a SecretOpsScope.
 extern "C" int curdle_fr_permute_ct(const uint64_t* in, const uint32_t* perm, size_t n, uint64_t* out) __attribute__((weak));
+
+// What a lockstep group's coalesced requests go to besides the calls above (alg::Lockstep): the batched gather, and the
+// constant-time multiplication for a scalar multiplication batch whose scalars are secrets.
+extern "C" int curdle_fr_permute_ct_batch(const uint64_t* in, const uint32_t* perm, size_t n, size_t k, uint64_t* out)
+    __attribute__((weak));
+extern "C" int curdle_g1_scalar_mul_batch_ex(const uint64_t* points, const uint64_t* scalars, size_t n_scalars,
+                                             const uint64_t* addends, size_t n, unsigned flags, uint64_t* out_affine)
+    __attribute__((weak));
 
 namespace curdle {
 namespace alg {
@@ -343,12 +355,57 @@ static void count_msm(bool ct, size_t pairs) {
   g_msm_counters[ct ? 3 : 1].fetch_add(pairs, std::memory_order_relaxed);
 }
 
+// ------------------------------------------------------------ the third switch ---
+static thread_local Lockstep* t_lockstep = nullptr;
+static thread_local size_t t_lockstep_member = 0;
+static bool secret_ops_on();
+
+struct Lockstep::Request {
+  enum Funnel { kMultiExp, kMultiExpBatch, kMultiExpShared, kScalarMul, kPermute } funnel;
+  bool ct = false, secret = false;  // the member thread's two switches
+  struct Msm {
+    const G1Affine* P;
+    const Scalar* S;
+    size_t n;
+  };
+  std::vector<Msm> msms;  // the MSM funnels: member-major, in the call's order
+  std::vector<Point> msm_out;
+  const G1Affine* points = nullptr;  // ScalarMulBatch
+  const Scalar* scalars = nullptr;
+  const G1Affine* addends = nullptr;
+  size_t n_scalars = 0, n = 0;  // n: also PermuteSecret's
+  G1Affine* mul_out = nullptr;
+  const Scalar* vs = nullptr;  // PermuteSecret
+  const uint32_t* perm = nullptr;
+  Scalar* perm_out = nullptr;
+  bool failed = false;  // the step's verdict, the same for every member of it
+  int rc = 0;
+  std::string what;
+};
+
+struct LockstepAccess {
+  static void Go(Lockstep::Request* r) {
+    r->ct = t_msm_ct;
+    r->secret = secret_ops_on();
+    t_lockstep->Rendezvous(t_lockstep_member, r);
+  }
+};
+
+static std::vector<Point> LockstepMsms(Lockstep::Request::Funnel funnel, std::vector<Lockstep::Request::Msm> msms) {
+  Lockstep::Request r;
+  r.funnel = funnel;
+  r.msms = std::move(msms);
+  LockstepAccess::Go(&r);
+  return std::move(r.msm_out);
+}
+
 static int no_ct_backend() {
   return curdle_set_last_error(CURDLE_ENODEV, "the constant-time MSM is not part of this backend: no device code to run it on");
 }
 
 Point MultiExp(const std::vector<G1Affine>& points, const std::vector<Scalar>& scalars) {
   if (points.size() != scalars.size()) throw std::runtime_error("computing msm: len(points) != len(scalars)");
+  if (t_lockstep) return LockstepMsms(Lockstep::Request::kMultiExp, {{points.data(), scalars.data(), points.size()}})[0];
   const bool ct = t_msm_ct;
   const uint64_t* P = reinterpret_cast<const uint64_t*>(points.data());
   const uint64_t* S = reinterpret_cast<const uint64_t*>(scalars.data());
@@ -372,6 +429,11 @@ std::vector<Point> MultiExpBatch(const std::vector<const std::vector<G1Affine>*>
   for (size_t j = 0; j < k; j++) {
     if (points[j]->size() != scalars[j]->size()) throw std::runtime_error("computing msm: len(points) != len(scalars)");
     off[j + 1] = off[j] + points[j]->size();
+  }
+  if (t_lockstep) {
+    std::vector<Lockstep::Request::Msm> msms(k);
+    for (size_t j = 0; j < k; j++) msms[j] = {points[j]->data(), scalars[j]->data(), points[j]->size()};
+    return LockstepMsms(Lockstep::Request::kMultiExpBatch, std::move(msms));
   }
   std::vector<G1Affine> P(off[k]);
   std::vector<Scalar> S(off[k]);
@@ -415,6 +477,11 @@ std::vector<Point> MultiExpShared(const std::vector<const std::vector<G1Affine>*
     std::vector<Point> res(k, Point::Infinity());
     return res;
   }
+  if (t_lockstep) {
+    std::vector<Lockstep::Request::Msm> msms(k);
+    for (size_t j = 0; j < k; j++) msms[j] = {sets[j]->data(), scalars.data(), scalars.size()};
+    return LockstepMsms(Lockstep::Request::kMultiExpShared, std::move(msms));
+  }
   const uint64_t* Sw = reinterpret_cast<const uint64_t*>(scalars.data());
   int rc;
   if (!ct)
@@ -435,6 +502,7 @@ static thread_local bool t_secret_ops = false;
 SecretOpsScope::SecretOpsScope() : prev_(t_secret_ops) { t_secret_ops = true; }
 SecretOpsScope::~SecretOpsScope() { t_secret_ops = prev_; }
 bool SecretOpsScope::Active() { return t_secret_ops; }
+static bool secret_ops_on() { return t_secret_ops; }
 bool SecretOpsScope::Available() { return curdle_fr_permute_ct && ConstantTimeMsmScope::Available(); }
 
 std::vector<Scalar> PermuteSecret(const std::vector<Scalar>& vs, const std::vector<uint32_t>& perm) {
@@ -445,6 +513,16 @@ std::vector<Scalar> PermuteSecret(const std::vector<Scalar>& vs, const std::vect
   }
   if (perm.size() != vs.size()) throw std::runtime_error("permuting: len(perm) != len(values)");
   static_assert(sizeof(Scalar) == 32, "the gather's record is an fr.Element");
+  if (t_lockstep) {
+    Lockstep::Request r;
+    r.funnel = Lockstep::Request::kPermute;
+    r.vs = vs.data();
+    r.perm = perm.data();
+    r.n = vs.size();
+    r.perm_out = out.data();
+    LockstepAccess::Go(&r);
+    return out;
+  }
   // perm goes to the device from where it lies and the records arrive in `out`, the prover's own vector: nothing is
   // created here that would have to be wiped (the call wipes its staging).
   const int rc = curdle_fr_permute_ct
@@ -466,6 +544,28 @@ std::vector<G1Affine> ScalarMulBatch(const std::vector<G1Affine>& points, const 
   if (addends && addends->size() != n) throw std::runtime_error("scalar mul batch: len(addends) != len(points)");
   std::vector<G1Affine> out(n);
   if (n == 0) return out;
+  if (t_lockstep) {
+    Lockstep::Request r;
+    r.funnel = Lockstep::Request::kScalarMul;
+    r.points = points.data();
+    r.scalars = scalars.data();
+    r.n_scalars = scalars.size();
+    r.addends = addends ? addends->data() : nullptr;
+    r.n = n;
+    r.mul_out = out.data();
+    LockstepAccess::Go(&r);
+    return out;
+  }
+  if (t_secret_ops) {  // the scalars are secrets: the constant-time multiplication at every size, never the host loop
+    if (addends) throw std::runtime_error("scalar mul batch: the constant-time multiplication takes no addends");
+    const int rc = curdle_g1_scalar_mul_batch_ex
+                       ? curdle_g1_scalar_mul_batch_ex(reinterpret_cast<const uint64_t*>(points.data()),
+                                                       reinterpret_cast<const uint64_t*>(scalars.data()), scalars.size(), nullptr, n,
+                                                       CURDLE_G1_MUL_CONSTANT_TIME, reinterpret_cast<uint64_t*>(out.data()))
+                       : curdle_set_last_error(CURDLE_ENODEV, "the constant-time multiplication is not part of this backend: no device code to run it on");
+    if (rc != CURDLE_OK) throw msm_error(rc);
+    return out;
+  }
   if (n >= kScalarMulBatchMin) {
     int rc = curdle_g1_scalar_mul_batch(reinterpret_cast<const uint64_t*>(points.data()),
                                         reinterpret_cast<const uint64_t*>(scalars.data()), scalars.size(),
@@ -480,6 +580,255 @@ std::vector<G1Affine> ScalarMulBatch(const std::vector<G1Affine>& points, const 
     out[i] = r.Affine();
   }
   return out;
+}
+
+// ------------------------------------------------------------ the lockstep group ---
+Lockstep::Lockstep(size_t members) : reqs_(members, nullptr), live_flag_(members, 1), live_(members) {}
+Lockstep::~Lockstep() {}
+
+unsigned long long Lockstep::DeviceCalls() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return device_calls_;
+}
+
+unsigned long long Lockstep::Disagreements() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return disagreements_;
+}
+
+void Lockstep::Leave(size_t member) {
+  std::lock_guard<std::mutex> lk(mu_);
+  if (member >= live_flag_.size() || !live_flag_[member]) return;
+  live_flag_[member] = 0;
+  live_--;
+  if (arrived_ && arrived_ == live_) cv_.notify_all();  // the step was waiting for this member alone: a waiter runs it
+}
+
+LockstepScope::LockstepScope(Lockstep& group, size_t member) : prev_group_(t_lockstep), prev_member_(t_lockstep_member) {
+  t_lockstep = &group;
+  t_lockstep_member = member;
+}
+LockstepScope::~LockstepScope() {
+  t_lockstep->Leave(t_lockstep_member);
+  t_lockstep = prev_group_;
+  t_lockstep_member = prev_member_;
+}
+
+void Lockstep::Rendezvous(size_t member, Request* r) {
+  {
+    std::unique_lock<std::mutex> lk(mu_);
+    reqs_[member] = r;
+    arrived_++;
+    const unsigned long long step = step_;
+    while (step_ == step) {
+      if (arrived_ == live_) {
+        // Every live member is in this loop, so nobody else wants the lock while the step runs under it.
+        RunStep();
+        std::fill(reqs_.begin(), reqs_.end(), nullptr);
+        arrived_ = 0;
+        step_++;
+        cv_.notify_all();
+        break;
+      }
+      cv_.wait(lk);
+    }
+  }
+  if (r->failed) throw MsmError(r->what, r->rc);
+}
+
+namespace {
+template <class T>
+struct WipeOnExit {  // a concatenated copy of secrets does not outlive the coalesced call
+  std::vector<T>& v;
+  bool on;
+  ~WipeOnExit() {
+    if (on && !v.empty()) explicit_bzero(v.data(), v.size() * sizeof(T));
+  }
+};
+
+// Members per coalesced call: as many whole members as fit `cap` units (and `cap_members`), at least one -- a member
+// that alone is too large for the primitive gets the primitive's own refusal, as its single call would.
+size_t members_per_call(size_t unit, size_t cap, size_t cap_members) {
+  const long long knob = knobs::get(knobs::PROVE_BATCH_PAIRS);
+  if (knob > 0 && (size_t)knob < cap) cap = (size_t)knob;
+  size_t m = unit ? cap / unit : cap_members;
+  if (m > cap_members) m = cap_members;
+  return m ? m : 1;
+}
+
+std::string last_error_text(const char* what, int rc) {
+  char buf[256];
+  curdle_last_error(buf, sizeof(buf));
+  return std::string(what) + buf + " (rc " + std::to_string(rc) + ")";
+}
+}  // namespace
+
+void Lockstep::RunStep() {
+  using R = Request;
+  std::vector<R*> rs;
+  for (R* r : reqs_)
+    if (r) rs.push_back(r);
+  if (rs.empty()) return;
+  auto fail_all = [&](int rc, const std::string& what) {
+    for (R* r : rs) {
+      r->failed = true;
+      r->rc = rc;
+      r->what = what;
+    }
+  };
+  const R& a = *rs[0];
+  for (const R* r : rs) {  // funnel, switches and shapes: public, and the same for every member of a sound group
+    bool same = r->funnel == a.funnel && r->ct == a.ct && r->secret == a.secret && r->msms.size() == a.msms.size() &&
+                r->n == a.n && r->n_scalars == a.n_scalars && !r->addends == !a.addends;
+    for (size_t j = 0; same && j < a.msms.size(); j++) same = r->msms[j].n == a.msms[j].n;
+    if (!same) {
+      disagreements_++;
+      return fail_all(CURDLE_EINVAL, "lockstep: the members' requests disagree at step " + std::to_string(step_) +
+                                         " (funnel, shapes or constant-time switches)");
+    }
+  }
+  try {
+    const size_t k = rs.size();
+    if (a.funnel == R::kMultiExp || a.funnel == R::kMultiExpBatch || a.funnel == R::kMultiExpShared) {
+      const size_t per = a.msms.size();
+      size_t unit = 0;
+      for (const R::Msm& m : a.msms) unit += m.n;
+      if (a.funnel == R::kMultiExpShared && unit == 0) {  // as MultiExpShared: no call for an empty scalar vector
+        for (R* r : rs) r->msm_out.assign(per, Point::Infinity());
+        return;
+      }
+      // curdle_msm_g1_ct_batch: 65,536 pairs and 4,096 MSMs a call; the bucket MSM splits a batch into passes itself
+      const size_t step_members = a.ct ? members_per_call(unit, 65536, std::max<size_t>(1, 4096 / std::max<size_t>(1, per)))
+                                       : members_per_call(unit, (size_t)1 << 24, k);
+      for (size_t lo = 0; lo < k; lo += step_members) {
+        const size_t hi = std::min(k, lo + step_members), nm = (hi - lo) * per;
+        std::vector<size_t> off(nm + 1, 0);
+        std::vector<G1Affine> P((hi - lo) * unit);
+        std::vector<Scalar> S((hi - lo) * unit);
+        WipeOnExit<Scalar> wipe{S, a.ct};
+        size_t q = 0;
+        for (size_t i = lo; i < hi; i++)
+          for (const R::Msm& m : rs[i]->msms) {
+            std::copy(m.P, m.P + m.n, P.begin() + off[q]);
+            std::copy(m.S, m.S + m.n, S.begin() + off[q]);
+            off[q + 1] = off[q] + m.n;
+            q++;
+          }
+        std::vector<uint64_t> out(18 * nm);
+        const uint64_t* Pw = reinterpret_cast<const uint64_t*>(P.data());
+        const uint64_t* Sw = reinterpret_cast<const uint64_t*>(S.data());
+        int rc;
+        if (!a.ct)
+          rc = curdle_msm_g1_batch(Pw, Sw, off.data(), nm, out.data());
+        else
+          rc = curdle_msm_g1_ct_batch ? curdle_msm_g1_ct_batch(Pw, Sw, off.data(), nm, kCtScalarBits, out.data()) : no_ct_backend();
+        if (rc != CURDLE_OK) return fail_all(rc, last_error_text("computing msm: ", rc));
+        count_msm(a.ct, off[nm]);
+        device_calls_++;
+        for (size_t i = lo; i < hi; i++) {
+          rs[i]->msm_out.resize(per);
+          for (size_t j = 0; j < per; j++) rs[i]->msm_out[j] = Point::FromJac(out.data() + 18 * ((i - lo) * per + j));
+        }
+      }
+      return;
+    }
+    if (a.funnel == R::kScalarMul) {
+      const size_t n = a.n;
+      if (a.secret && a.addends)
+        return fail_all(CURDLE_EINVAL, "scalar mul batch: the constant-time multiplication takes no addends");
+      const size_t step_members = members_per_call(n, (size_t)1 << 24, k);
+      for (size_t lo = 0; lo < k; lo += step_members) {
+        const size_t hi = std::min(k, lo + step_members), m = (hi - lo) * n;
+        std::vector<G1Affine> P(m), A(a.addends ? m : 0), out(m);
+        std::vector<Scalar> S(m);
+        WipeOnExit<Scalar> wipe{S, a.secret || a.ct};
+        WipeOnExit<G1Affine> wipe_out{out, a.secret};  // multiples by a secret: the members keep (and wipe) their own
+        for (size_t i = lo; i < hi; i++) {
+          const R& r = *rs[i];
+          std::copy(r.points, r.points + n, P.begin() + (i - lo) * n);
+          if (r.addends) std::copy(r.addends, r.addends + n, A.begin() + (i - lo) * n);
+          for (size_t t = 0; t < n; t++) S[(i - lo) * n + t] = r.scalars[r.n_scalars == 1 ? 0 : t];
+        }
+        const uint64_t* Pw = reinterpret_cast<const uint64_t*>(P.data());
+        const uint64_t* Sw = reinterpret_cast<const uint64_t*>(S.data());
+        uint64_t* Ow = reinterpret_cast<uint64_t*>(out.data());
+        int rc;
+        if (!a.secret)
+          rc = curdle_g1_scalar_mul_batch(Pw, Sw, m, a.addends ? reinterpret_cast<const uint64_t*>(A.data()) : nullptr, m, Ow);
+        else
+          rc = curdle_g1_scalar_mul_batch_ex
+                   ? curdle_g1_scalar_mul_batch_ex(Pw, Sw, m, nullptr, m, CURDLE_G1_MUL_CONSTANT_TIME, Ow)
+                   : curdle_set_last_error(CURDLE_ENODEV, "the constant-time multiplication is not part of this backend: no device code to run it on");
+        if (rc != CURDLE_OK) return fail_all(rc, last_error_text("computing msm: ", rc));
+        device_calls_++;
+        for (size_t i = lo; i < hi; i++) std::copy(out.begin() + (i - lo) * n, out.begin() + (i - lo + 1) * n, rs[i]->mul_out);
+      }
+      return;
+    }
+    // PermuteSecret under a SecretOpsScope (without one the members never come here)
+    const size_t n = a.n;
+    if (n == 0) return;
+    const size_t step_members = members_per_call(n, (size_t)1 << 20, 4096);  // curdle_fr_permute_ct_batch's limits
+    for (size_t lo = 0; lo < k; lo += step_members) {
+      const size_t hi = std::min(k, lo + step_members), m = (hi - lo) * n;
+      std::vector<Scalar> in(m), out(m);
+      std::vector<uint32_t> perm(m);
+      WipeOnExit<Scalar> wipe_in{in, true}, wipe_out{out, true};
+      WipeOnExit<uint32_t> wipe_perm{perm, true};
+      for (size_t i = lo; i < hi; i++) {
+        std::copy(rs[i]->vs, rs[i]->vs + n, in.begin() + (i - lo) * n);
+        std::copy(rs[i]->perm, rs[i]->perm + n, perm.begin() + (i - lo) * n);
+      }
+      const int rc = curdle_fr_permute_ct_batch
+                         ? curdle_fr_permute_ct_batch(reinterpret_cast<const uint64_t*>(in.data()), perm.data(), n, hi - lo,
+                                                      reinterpret_cast<uint64_t*>(out.data()))
+                         : curdle_set_last_error(CURDLE_ENODEV, "the batched oblivious gather is not part of this backend: no device code to run it on");
+      if (rc != CURDLE_OK) return fail_all(rc, last_error_text("permuting: ", rc));
+      device_calls_++;
+      for (size_t i = lo; i < hi; i++) std::copy(out.begin() + (i - lo) * n, out.begin() + (i - lo + 1) * n, rs[i]->perm_out);
+    }
+  } catch (const std::bad_alloc&) {
+    fail_all(CURDLE_ENOMEM, "lockstep: out of memory in a coalesced call");
+  } catch (const std::exception& e) {
+    fail_all(CURDLE_EHIP, std::string("lockstep: ") + e.what());
+  }
+}
+
+LockstepRun RunInLockstep(size_t members, size_t group_size, bool constant_time, const std::function<void(size_t)>& job,
+                          const std::function<void(size_t)>& could_not_start) {
+  LockstepRun run;
+  if (group_size == 0) group_size = 1;
+  const int device = curdle_get_device();  // the batch runs where its caller is
+  for (size_t lo = 0; lo < members; lo += group_size) {
+    const size_t m = std::min(group_size, members - lo);
+    Lockstep group(m);
+    std::vector<std::thread> threads;
+    threads.reserve(m);
+    for (size_t j = 0; j < m; j++) {
+      try {
+        threads.emplace_back([&group, &job, lo, j, constant_time, device]() {
+          LockstepScope in_group(group, j);
+          (void)curdle_set_device(device);
+          if (!constant_time) {
+            job(lo + j);
+            return;
+          }
+          ConstantTimeMsmScope msms;
+          SecretOpsScope secret_ops;
+          job(lo + j);
+        });
+      } catch (const std::system_error&) {
+        group.Leave(j);
+        run.not_started++;
+        could_not_start(lo + j);
+      }
+    }
+    for (std::thread& t : threads) t.join();
+    run.groups++;
+    run.device_calls += group.DeviceCalls();
+    run.disagreements += group.Disagreements();
+  }
+  return run;
 }
 
 }  // namespace alg

@@ -11,6 +11,9 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <condition_variable>
+#include <functional>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -217,9 +220,84 @@ unsigned long long PointMulCalls();
 // scalar shared by all; addends may be null.  The independent scalar multiplications that
 // dominate the prover: a batch of at least kScalarMulBatchMin goes to
 // the GPU (curdle_g1_scalar_mul_batch), smaller ones run on the host one by one.
+// Under a SecretOpsScope the scalars are secrets: every size goes to curdle_g1_scalar_mul_batch_ex under
+// CURDLE_G1_MUL_CONSTANT_TIME (which takes no addends), the same records bit for bit.
 static constexpr size_t kScalarMulBatchMin = 24;
 std::vector<G1Affine> ScalarMulBatch(const std::vector<G1Affine>& points, const std::vector<Scalar>& scalars,
                                      const std::vector<G1Affine>* addends = nullptr);
+
+// The third switch: k provers in lockstep.  A Lockstep is a group of `members` threads that all make the same sequence
+// of funnel calls with the same shapes (k Proves over one CRS at one ell do); while a LockstepScope lives on a member's
+// thread, a call of MultiExp, MultiExpBatch, MultiExpShared, ScalarMulBatch -- and PermuteSecret under a SecretOpsScope
+// -- does not go to the device from that thread: it is handed to the group as a request (the funnel, the shapes, the
+// pointers) and the thread waits.  When every LIVE member has handed in its next request, one of the waiting threads
+// checks that funnels, shapes and the two constant-time switches agree (they are read on the member threads), issues
+// ONE coalesced call, member-major -- or as few as fit the primitive's limits, split by whole members -- hands each
+// member its results and wakes them:
+//   the three MSM funnels   one curdle_msm_g1_batch over all members' MSMs (a shared-scalar request is its k MSMs with
+//                           the scalar vector repeated); under a ConstantTimeMsmScope one curdle_msm_g1_ct_batch at 255 bits
+//   ScalarMulBatch          one curdle_g1_scalar_mul_batch over the concatenation with per-point scalars (a member's
+//                           shared scalar is replicated); under a SecretOpsScope, where the scalars are secrets, one
+//                           curdle_g1_scalar_mul_batch_ex under CURDLE_G1_MUL_CONSTANT_TIME (no addends there)
+//   PermuteSecret           one curdle_fr_permute_ct_batch (without a SecretOpsScope: the member's own indexed gather,
+//                           no rendezvous)
+// Results are, bit for bit, those of the member's own call.  A member is live from the group's construction until its
+// LockstepScope dies (an exception leaves through the destructor) or Leave(member) says it will never start: the others
+// then go on without it, and a step that was only waiting for it runs.  Funnels, shapes or switches that disagree, or a
+// failed device call, fail the STEP: every member that handed in a request for it throws the same MsmError, and nobody
+// is left waiting.  Under the constant-time switches every concatenated host copy of scalars, entries and gathered
+// records is explicit_bzero-ed on every way out.  ReadMsmCounters counts a coalesced call once, with all its pairs.
+class Lockstep {
+ public:
+  explicit Lockstep(size_t members);
+  ~Lockstep();
+  Lockstep(const Lockstep&) = delete;
+  Lockstep& operator=(const Lockstep&) = delete;
+  void Leave(size_t member);                  // a member that never gets a scope (its thread could not be started)
+  unsigned long long DeviceCalls() const;     // coalesced calls issued so far
+  unsigned long long Disagreements() const;   // steps failed because funnels, shapes or switches differed
+  struct Request;                             // algebra.cpp
+
+ private:
+  friend class LockstepScope;
+  friend struct LockstepAccess;
+  void Rendezvous(size_t member, Request* r);  // throws MsmError when the step failed
+  void RunStep();
+  mutable std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<Request*> reqs_;   // per member: its request of the current step, or null
+  std::vector<char> live_flag_;
+  size_t live_, arrived_ = 0;
+  unsigned long long step_ = 0, device_calls_ = 0, disagreements_ = 0;
+};
+
+class LockstepScope {
+ public:
+  LockstepScope(Lockstep& group, size_t member);
+  ~LockstepScope();
+  LockstepScope(const LockstepScope&) = delete;
+  LockstepScope& operator=(const LockstepScope&) = delete;
+
+ private:
+  Lockstep* prev_group_;
+  size_t prev_member_;
+};
+
+// k jobs in lockstep: job(i) for i < members, in groups of at most group_size, ONE std::thread per member of a group (a
+// member blocked at the rendezvous cannot be suspended, so no pool) and each under a LockstepScope of its group -- with
+// constant_time also under a ConstantTimeMsmScope and a SecretOpsScope -- and on the device the calling thread has
+// selected.  The calling thread only starts and joins.  A job must not throw.  A member whose thread cannot be started
+// gets could_not_start(i) on the calling thread and leaves its group.  Returns the groups run, the coalesced device
+// calls they made, and the two things that can go wrong without the device's doing: steps at which the members'
+// requests disagreed, and members that could not be started.
+struct LockstepRun {
+  size_t groups = 0;
+  unsigned long long device_calls = 0;
+  unsigned long long disagreements = 0;
+  size_t not_started = 0;
+};
+LockstepRun RunInLockstep(size_t members, size_t group_size, bool constant_time, const std::function<void(size_t)>& job,
+                          const std::function<void(size_t)>& could_not_start);
 
 }  // namespace alg
 }  // namespace curdle

@@ -501,6 +501,52 @@ ShuffleCommit ShufflePermuteCommit(const std::vector<G1Affine>& crsGs, const std
   return out;
 }
 
+ShuffleCommit ShufflePermuteCommitSecret(const std::vector<G1Affine>& crsGs, const std::vector<G1Affine>& crsHs,
+                                         const std::vector<G1Affine>& Rs, const std::vector<G1Affine>& Ss,
+                                         const std::vector<uint32_t>& perm, const Scalar& k, common::Rand& rand) {
+  if (!alg::SecretOpsScope::Active()) throw std::logic_error("ShufflePermuteCommitSecret outside an alg::SecretOpsScope");
+  const size_t ell = perm.size();
+  if (Rs.size() != ell || Ss.size() != ell || crsGs.size() != ell) throw err("shuffling and permuting: lengths differ");
+  static_assert(sizeof(G1Affine) == 3 * sizeof(Scalar), "a point is three of the gather's records");
+  constexpr size_t kRec = 7;  // Ts[t] | Us[t] | t
+  ShuffleCommit out;
+  // The unpermuted k R_i | k S_i reach the host here, which the single flagged step avoids (beside the public Ts | Us they
+  // give the permutation): both copies, `scaled` and `records`, are overwritten on every way out.
+  std::vector<G1Affine> scaled;
+  std::vector<Scalar> records(kRec * ell), gathered, permRange(ell);
+  struct PointWipe {
+    std::vector<G1Affine>& v;
+    ~PointWipe() {
+      if (!v.empty()) explicit_bzero(v.data(), v.size() * sizeof(G1Affine));
+    }
+  } wipe_scaled{scaled};
+  ScalarWipe wipe{{&records, &gathered, &permRange}};
+  scaled = alg::ScalarMulBatch(Concat(Rs, Ss), {k});  // the constant-time multiplication
+  for (size_t t = 0; t < ell; t++) {
+    memcpy(&records[kRec * t], &scaled[t], 96);
+    memcpy(&records[kRec * t + 3], &scaled[ell + t], 96);
+    records[kRec * t + 6] = Scalar::FromU64(t);
+  }
+  std::vector<uint32_t> entries(kRec * ell);
+  struct EntryWipe {
+    std::vector<uint32_t>& v;
+    ~EntryWipe() { explicit_bzero(v.data(), v.size() * sizeof(uint32_t)); }
+  } wipe_entries{entries};
+  for (size_t i = 0; i < ell; i++)
+    for (size_t c = 0; c < kRec; c++) entries[kRec * i + c] = (uint32_t)kRec * perm[i] + (uint32_t)c;
+  gathered = alg::PermuteSecret(records, entries);
+  out.Ts.resize(ell);
+  out.Us.resize(ell);
+  for (size_t i = 0; i < ell; i++) {
+    memcpy(&out.Ts[i], &gathered[kRec * i], 96);
+    memcpy(&out.Us[i], &gathered[kRec * i + 3], 96);
+    permRange[i] = gathered[kRec * i + 6];
+  }
+  out.rs_m = GetFrs(rand, N_BLINDERS);
+  out.M = MultiExpJoined(crsGs, crsHs, permRange, out.rs_m);
+  return out;
+}
+
 // ====================================================== samescalarargument =====
 namespace samescalar {
 static const std::string kPoints = "sameexp_points";

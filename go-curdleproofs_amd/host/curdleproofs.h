@@ -138,6 +138,16 @@ struct ShuffleCommit {
 ShuffleCommit ShufflePermuteCommit(const std::vector<G1Affine>& crsGs, const std::vector<G1Affine>& crsHs,
                                    const std::vector<G1Affine>& Rs, const std::vector<G1Affine>& Ss,
                                    const std::vector<uint32_t>& perm, const Scalar& k, common::Rand& rand);
+// The same step with perm, k and the blinders off the host's branches and addresses, expressed through the funnels of
+// algebra.h; meant to run under an alg::ConstantTimeMsmScope and an alg::SecretOpsScope (it throws std::logic_error
+// without the second), and in a lockstep group the members share each call: k (Rs | Ss) is ONE ScalarMulBatch (the
+// constant-time multiplication), Ts | Us and the permuted range come out of ONE PermuteSecret over 7 ell records of
+// 32 bytes -- element t is (Ts[t], Us[t], t) and the entries are 7 perm[i] + c, plain arithmetic -- and M is ONE MSM
+// over Gs | Hs, so sum perm[i] Gs[i] exists nowhere unblinded.  7 ell <= 4,096.  The same draws (the blinders) and,
+// normalised, the same Ts, Us and M as ShufflePermuteCommit.
+ShuffleCommit ShufflePermuteCommitSecret(const std::vector<G1Affine>& crsGs, const std::vector<G1Affine>& crsHs,
+                                         const std::vector<G1Affine>& Rs, const std::vector<G1Affine>& Ss,
+                                         const std::vector<uint32_t>& perm, const Scalar& k, common::Rand& rand);
 
 // ---- the verifier's deferred checks, described rather than materialised ----
 // Every sub-argument ends in msmAccumulator.AccumulateCheck(C, x, v, rand)

@@ -52,6 +52,8 @@ enum Id {
   STREAM_PLAN,            // streams of pipelined MSMs, read when the context is created: 1 wide (a tail stream per slot), 2 compact (one tail stream: four busy streams); 0 or unset: compact below 16 hardware queues (GPU_MAX_HW_QUEUES), wide from there (stream_plan, msm_plan.hip)
   TRANSCRIPT_MAX_TRIES,   // test hook: lowers the batched transcripts' retry bound (draws of one challenge before the member is handed back with a status) to min(256, value) for value >= 1, so a test can reach the status byte; unset, 0 or above 256: 256.  The single calls ignore it (transcript_max_tries below)
   G1_MUL_CT_PASS,         // curdle_g1_scalar_mul_batch_ex / _device_ex under CURDLE_G1_MUL_CONSTANT_TIME: pairs per pass (one launch of k_g1_mul_ct), rounded down to a multiple of 256, at least 256; unset: 2^20 (g1_mul_ct_api.hip)
+  PROVE_BATCH_GROUP,      // curdle_prove_batch, curdle_whisk_generate_shuffle_proof_batch: members proved in lockstep at a time, one thread each (1..64); unset, 0 or above 64: 64 (proto_api.cpp)
+  PROVE_BATCH_PAIRS,      // test hook: lowers the (point, scalar) pairs or records from which a lockstep group's coalesced call is split by whole members, so a test can reach the split; unset or 0: the primitives' own limits (alg::Lockstep, algebra.cpp)
   COUNT
 };
 // The knob's value, or -1 if it is not set (every knob's valid values are >= 0).

@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <exception>
 #include <new>
@@ -14,6 +15,7 @@
 #include "../../include/curdle_msm.h"
 #include "curdleproofs.h"
 #include "device_accumulator.h"
+#include "knobs.h"
 #include "whisk.h"
 
 using namespace curdle;
@@ -197,6 +199,108 @@ extern "C" int curdle_prove_ct(const curdle_crs* crs, const uint64_t* Rs, const 
   alg::ConstantTimeMsmScope msms;
   alg::SecretOpsScope secret_ops;
   return curdle_prove(crs, Rs, Ss, Ts, Us, ell, M, perm, k, rs_m, rand, proof_out, cap, proof_len);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// curdle_prove_batch: k Proves over one CRS at one ell in lockstep (alg::Lockstep, algebra.h).  Every member runs
+// curdle_prove's body on a thread of its own under a LockstepScope -- under the flag also under the two constant-time
+// scopes, which makes it curdle_prove_ct's -- and the members' funnel calls meet at each step and go to the device as
+// ONE coalesced call.  The results a member gets back are those of its own call, so its proof, its length and its
+// rand's state afterwards are the single call's.
+// ---------------------------------------------------------------------------------------------------------------------
+static std::atomic<unsigned long long> g_prove_batch_stat[4];  // calls | members | groups | coalesced device calls
+
+static size_t ProveBatchGroup() {
+  const long long v = knobs::get(knobs::PROVE_BATCH_GROUP);
+  return v >= 1 && v <= 64 ? (size_t)v : 64;
+}
+
+// The call's verdict over its members' codes.  A member's own failure is CURDLE_EINVAL (Guard: a structural error of the
+// protocol) and leaves the call CURDLE_OK.  What fails the call, each with its own text: a member thread that could not
+// be started, a step at which the members' requests disagreed (the library's fault, not the device's: it reaches the
+// members as an MsmError), and a failed device call.
+static int BatchVerdict(const int* status, size_t k, const char* who, const alg::LockstepRun& run) {
+  char msg[200];
+  if (run.not_started) {
+    snprintf(msg, sizeof(msg), "%s: %zu member thread(s) could not be started", who, run.not_started);
+    return curdle_set_last_error(CURDLE_ENOMEM, msg);
+  }
+  for (size_t i = 0; i < k; i++)
+    if (status[i] != CURDLE_OK && status[i] != CURDLE_EINVAL) {
+      if (run.disagreements)
+        snprintf(msg, sizeof(msg), "%s: the members' requests disagreed at %llu step(s) (funnel, shapes or switches): not a device failure",
+                 who, run.disagreements);
+      else
+        snprintf(msg, sizeof(msg), "%s: a device call failed (member %zu: code %d)", who, i, status[i]);
+      return curdle_set_last_error(status[i], msg);
+    }
+  return CURDLE_OK;
+}
+
+static void CountProveBatch(size_t k, const alg::LockstepRun& run) {
+  g_prove_batch_stat[0].fetch_add(1, std::memory_order_relaxed);
+  g_prove_batch_stat[1].fetch_add(k, std::memory_order_relaxed);
+  g_prove_batch_stat[2].fetch_add(run.groups, std::memory_order_relaxed);
+  g_prove_batch_stat[3].fetch_add(run.device_calls, std::memory_order_relaxed);
+}
+
+// Two members drawing from one generator on two threads would be a race, and no single call's draws.
+static bool DistinctRands(curdle_rand* const* rands, size_t k) {
+  std::vector<const curdle_rand*> v(rands, rands + k);
+  std::sort(v.begin(), v.end());
+  return std::adjacent_find(v.begin(), v.end()) == v.end();
+}
+
+extern "C" int curdle_prove_batch(const curdle_crs* crs, size_t k, size_t ell, const uint64_t* const* Rs,
+                                  const uint64_t* const* Ss, const uint64_t* const* Ts, const uint64_t* const* Us,
+                                  const uint64_t* Ms, const uint32_t* const* perms, const uint64_t* ks, const uint64_t* rs_ms,
+                                  curdle_rand* const* rands, unsigned flags, uint8_t* proofs_out, size_t stride,
+                                  size_t* proof_lens, int* status) {
+  if (flags & ~CURDLE_PROVE_BATCH_CONSTANT_TIME) {
+    char msg[64];
+    snprintf(msg, sizeof(msg), "unknown flag bits 0x%x", flags & ~CURDLE_PROVE_BATCH_CONSTANT_TIME);
+    return curdle_set_last_error(CURDLE_EINVAL, msg);
+  }
+  if (!crs || (k && (!Rs || !Ss || !Ts || !Us || !Ms || !perms || !ks || !rs_ms || !rands || !proofs_out || !proof_lens || !status)))
+    return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  for (size_t i = 0; i < k; i++)
+    if (!Rs[i] || !Ss[i] || !Ts[i] || !Us[i] || !perms[i] || !rands[i])
+      return curdle_set_last_error(CURDLE_EINVAL, "null argument in batch member");
+  if (k && !DistinctRands(rands, k)) return curdle_set_last_error(CURDLE_EINVAL, "two members share one rand");
+  if (ell != crs->crs.Gs.size()) return curdle_set_last_error(CURDLE_EINVAL, "ell does not match the CRS");
+  const bool ct = flags & CURDLE_PROVE_BATCH_CONSTANT_TIME;
+  if (ct) {  // curdle_prove_ct's refusals, in its order
+    if (ell > kProveCtMaxEll)
+      return curdle_set_last_error(CURDLE_EINVAL, "ell exceeds the 4,096 the constant-time prover supports");
+    if (proto::ProverFoldBasesEnabled())
+      return curdle_set_last_error(CURDLE_EINVAL,
+                                   "CURDLE_PROVE_BATCH_CONSTANT_TIME with PROVER_FOLD_BASES set: that prover multiplies H by a "
+                                   "secret inner product on the host");
+    if (k && !ProveCtBackend())
+      return curdle_set_last_error(CURDLE_ENODEV,
+                                   "curdle_prove_batch: the constant-time MSM and the oblivious gather need the device backend and a device");
+  }
+  if (k == 0) return CURDLE_OK;
+  const alg::LockstepRun run = alg::RunInLockstep(
+      k, ProveBatchGroup(), ct,
+      [&](size_t i) {
+        proof_lens[i] = 0;
+        status[i] = curdle_prove(crs, Rs[i], Ss[i], Ts[i], Us[i], ell, Ms + 18 * i, perms[i], ks + 4 * i, rs_ms + 16 * i, rands[i],
+                                 proofs_out + stride * i, stride, &proof_lens[i]);
+        if (status[i] != CURDLE_OK) proof_lens[i] = 0;
+      },
+      [&](size_t i) {
+        proof_lens[i] = 0;
+        status[i] = CURDLE_ENOMEM;
+      });
+  CountProveBatch(k, run);
+  return BatchVerdict(status, k, "curdle_prove_batch", run);
+}
+
+extern "C" int curdle_stat_prove_batch(unsigned long long out[4]) {
+  if (!out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  for (int i = 0; i < 4; i++) out[i] = g_prove_batch_stat[i].load(std::memory_order_relaxed);
+  return CURDLE_OK;
 }
 
 extern "C" int curdle_stat_host_point_mul(unsigned long long* out) {
@@ -559,6 +663,50 @@ extern "C" int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, con
       const whisk::WhiskTracker t = whisk::NewWhiskTracker(Ts[i], Us[i]);
       memcpy(post_trackers_out + 96 * i, &t, 96);
     }
+    return CURDLE_OK;
+  });
+}
+
+// curdle_whisk_generate_shuffle_proof (flags = 0) or curdle_whisk_generate_shuffle_proof_ct (under the flag) for k
+// pre-tracker arrays of one n, in lockstep: whisk::GenerateWhiskShuffleProofBatch.
+extern "C" int curdle_whisk_generate_shuffle_proof_batch(const curdle_crs* crs, size_t k, const uint8_t* const* pre_trackers,
+                                                         size_t n, curdle_rand* const* rands, unsigned flags,
+                                                         uint8_t* post_trackers_out, uint8_t* proofs_out, int* status) {
+  if (flags & ~CURDLE_PROVE_BATCH_CONSTANT_TIME) {
+    char msg[64];
+    snprintf(msg, sizeof(msg), "unknown flag bits 0x%x", flags & ~CURDLE_PROVE_BATCH_CONSTANT_TIME);
+    return curdle_set_last_error(CURDLE_EINVAL, msg);
+  }
+  if (!crs || (k && (!pre_trackers || !rands || !post_trackers_out || !proofs_out || !status)))
+    return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  for (size_t i = 0; i < k; i++)
+    if (!pre_trackers[i] || !rands[i]) return curdle_set_last_error(CURDLE_EINVAL, "null argument in batch member");
+  if (k && !DistinctRands(rands, k)) return curdle_set_last_error(CURDLE_EINVAL, "two members share one rand");
+  const bool ct = flags & CURDLE_PROVE_BATCH_CONSTANT_TIME;
+  if (ct && k && !ProveCtBackend())
+    return curdle_set_last_error(CURDLE_ENODEV,
+                                 "curdle_whisk_generate_shuffle_proof_batch: the constant-time shuffle step and prover need the "
+                                 "device backend and a device");
+  if (k == 0) return CURDLE_OK;
+  return Guard([&]() -> int {
+    std::vector<const whisk::WhiskTracker*> pre(k);
+    std::vector<common::Rand*> rs(k);
+    for (size_t i = 0; i < k; i++) {
+      pre[i] = reinterpret_cast<const whisk::WhiskTracker*>(pre_trackers[i]);
+      rs[i] = &rands[i]->r;
+    }
+    alg::LockstepRun run;
+    std::vector<std::string> what;
+    const std::vector<int> st = whisk::GenerateWhiskShuffleProofBatch(
+        crs->crs, pre, n, rs, ct, ProveBatchGroup(), reinterpret_cast<whisk::WhiskTracker*>(post_trackers_out), proofs_out, &run, &what);
+    for (size_t i = 0; i < k; i++) status[i] = st[i];
+    CountProveBatch(k, run);
+    if (int rc = BatchVerdict(status, k, "curdle_whisk_generate_shuffle_proof_batch", run)) return rc;
+    for (size_t i = 0; i < k; i++)  // the call is CURDLE_OK; curdle_last_error still says why the first failed member failed
+      if (status[i] != CURDLE_OK) {
+        (void)curdle_set_last_error(status[i], what[i].c_str());
+        break;
+      }
     return CURDLE_OK;
   });
 }

@@ -2,7 +2,10 @@
 #include "knobs.h"
 #include "whisk.h"
 
+#include "../../include/curdle_msm.h"
+
 #include <chrono>
+#include <exception>
 #include <future>
 #include <memory>
 
@@ -426,6 +429,111 @@ std::vector<WhiskTracker> GenerateWhiskShuffleProof(const proto::CRS& crs, const
   std::vector<WhiskTracker> post(n);
   for (size_t i = 0; i < n; i++) post[i] = NewWhiskTracker(sc.Ts[i], sc.Us[i]);  // :109-112
   return post;
+}
+
+std::vector<int> GenerateWhiskShuffleProofBatch(const proto::CRS& crs, const std::vector<const WhiskTracker*>& preTrackers,
+                                                size_t n, const std::vector<common::Rand*>& rands, bool constant_time,
+                                                size_t group_size, WhiskTracker* post_out, uint8_t* proofs_out,
+                                                alg::LockstepRun* run, std::vector<std::string>* what) {
+  const size_t k = preTrackers.size();
+  std::vector<std::string> texts(k);
+  struct Member {  // the secrets the single call draws first; under the flag overwritten on every way out
+    std::vector<uint32_t> permutation;
+    Scalar k;
+    bool wipe = false;
+    ~Member() {
+      if (!wipe) return;
+      if (!permutation.empty()) explicit_bzero(permutation.data(), permutation.size() * sizeof(uint32_t));
+      explicit_bzero(&k, sizeof(k));
+    }
+  };
+  std::vector<Member> ms(k);
+  for (size_t i = 0; i < k; i++) {
+    ms[i].wipe = constant_time;
+    rands[i]->GeneratePermutation(ELL, ms[i].permutation);  // :64
+    rands[i]->GetFr(ms[i].k.v);                              // :68
+  }
+  std::vector<int> status(k, CURDLE_EINVAL);
+  if (n != ELL) {  // CheckShuffleSize: the single call's refusal, behind its draws
+    try {
+      CheckShuffleSize(n);
+    } catch (const std::exception& e) {
+      texts.assign(k, e.what());
+    }
+    if (what) *what = texts;
+    return status;
+  }
+  // every member's 2n tracker points in ONE batched decoding
+  proto::PointDecoder dec(/*subgroup_check=*/true);
+  for (size_t i = 0; i < k; i++)
+    for (size_t t = 0; t < n; t++) {
+      dec.Add(preTrackers[i][t].rG);
+      dec.Add(preTrackers[i][t].krG);
+    }
+  dec.Run();
+  std::vector<std::vector<G1Affine>> Rs(k), Ss(k);
+  std::vector<size_t> good;  // the members that go on: a tracker that does not decode is getPoints' error, that member's alone
+  for (size_t i = 0; i < k; i++) {
+    Rs[i].resize(n);
+    Ss[i].resize(n);
+    bool ok = true;
+    for (size_t t = 0; ok && t < n; t++) {  // DecodeTrackers' errors, in its order
+      if (!dec.GetAffine(2 * (i * n + t), &Rs[i][t])) {
+        texts[i] = "getting points: failed to set rG";
+        ok = false;
+      } else if (!dec.GetAffine(2 * (i * n + t) + 1, &Ss[i][t])) {
+        texts[i] = "getting points: failed to set krG";
+        ok = false;
+      }
+    }
+    if (ok) good.push_back(i);
+  }
+  auto code_of = [](const std::exception_ptr& e, std::string* text) {
+    try {
+      std::rethrow_exception(e);
+    } catch (const std::bad_alloc&) {
+      *text = "out of memory";
+      return (int)CURDLE_ENOMEM;
+    } catch (const alg::MsmError& m) {
+      *text = m.what();
+      return m.rc == CURDLE_OK || m.rc == CURDLE_EINVAL ? (int)CURDLE_EHIP : m.rc;
+    } catch (const std::exception& x) {
+      *text = x.what();
+      return (int)CURDLE_EINVAL;
+    } catch (...) {
+      return (int)CURDLE_EINVAL;
+    }
+  };
+  // curdle_prove_ct's refusal, which the single constant-time call meets behind its shuffle step: that prover multiplies
+  // H by a secret inner product on the host.  Read once, here: the members must not disagree about it.
+  const bool refuse_fold_bases = constant_time && proto::ProverFoldBasesEnabled();
+  const alg::LockstepRun r = alg::RunInLockstep(
+      good.size(), group_size, constant_time,
+      [&](size_t g) {
+        const size_t i = good[g];
+        try {
+          proto::ShuffleCommit sc =
+              constant_time ? proto::ShufflePermuteCommitSecret(crs.Gs, crs.Hs, Rs[i], Ss[i], ms[i].permutation, ms[i].k, *rands[i])
+                            : proto::ShufflePermuteCommit(crs.Gs, crs.Hs, Rs[i], Ss[i], ms[i].permutation, ms[i].k, *rands[i]);  // :83
+          if (refuse_fold_bases)
+            throw err("CURDLE_PROVE_MSM_CONSTANT_TIME with PROVER_FOLD_BASES set: that prover multiplies H by a secret inner product on the host");
+          proto::Proof proof = proto::Prove(crs, Rs[i], Ss[i], sc.Ts, sc.Us, sc.M, ms[i].permutation, ms[i].k, sc.rs_m, *rands[i]);  // :88
+          const std::vector<uint8_t> body = proof.Serialize();
+          SerializeShuffleProof(sc.M, body.data(), body.size(), proofs_out + WHISK_SHUFFLE_PROOF_SIZE * i);
+          for (size_t t = 0; t < n; t++) post_out[i * n + t] = NewWhiskTracker(sc.Ts[t], sc.Us[t]);  // :109-112
+          if (constant_time && !sc.rs_m.empty()) explicit_bzero(sc.rs_m.data(), sc.rs_m.size() * sizeof(Scalar));
+          status[i] = CURDLE_OK;
+        } catch (...) {
+          status[i] = code_of(std::current_exception(), &texts[i]);
+        }
+      },
+      [&](size_t g) {
+        status[good[g]] = CURDLE_ENOMEM;
+        texts[good[g]] = "the member's thread could not be started";
+      });
+  if (run) *run = r;
+  if (what) *what = texts;
+  return status;
 }
 
 bool IsValidWhiskTrackerProof(const WhiskTracker& tracker, const uint8_t kComm[G1POINT_SIZE],

@@ -60,6 +60,21 @@ void SerializeShuffleProof(const alg::Point& M, const uint8_t* body, size_t body
 // whisk.go:63 -- returns the post-shuffle trackers, writes the 4,576-byte proof.
 std::vector<WhiskTracker> GenerateWhiskShuffleProof(const proto::CRS& crs, const std::vector<WhiskTracker>& preTrackers,
                                                     common::Rand& rand, uint8_t proof_out[WHISK_SHUFFLE_PROOF_SIZE]);
+// GenerateWhiskShuffleProof for k pre-tracker arrays of one n, in lockstep (alg::Lockstep): per member the draws and their
+// order are the single call's (GeneratePermutation, then GetFr, on the calling thread, member after member), all 2 n k
+// tracker points go through ONE batched decode, then the members run the shuffle step, Prove and the serialisation on
+// threads of their own, in groups of at most group_size, their device calls coalesced step by step.  With
+// constant_time the members run under the two constant-time scopes and the step is proto::ShufflePermuteCommitSecret:
+// curdle_whisk_generate_shuffle_proof_ct's results.  post_out: k n trackers; proofs_out: k proofs of
+// WHISK_SHUFFLE_PROOF_SIZE.  Returns a code per member (CURDLE_OK; CURDLE_EINVAL for an n that is not ELL or a tracker that
+// does not decode, nothing written for that member; a device call's code otherwise) and, in *what when it is given, the
+// text of each failed member's error.  With constant_time and PROVER_FOLD_BASES set every member gets curdle_prove_ct's
+// refusal where the single call meets it: behind the shuffle step and its draws, before any prover work.  Throws what
+// the decode throws.
+std::vector<int> GenerateWhiskShuffleProofBatch(const proto::CRS& crs, const std::vector<const WhiskTracker*>& preTrackers,
+                                                size_t n, const std::vector<common::Rand*>& rands, bool constant_time,
+                                                size_t group_size, WhiskTracker* post_out, uint8_t* proofs_out,
+                                                alg::LockstepRun* run, std::vector<std::string>* what = nullptr);
 // whisk.go:116
 bool IsValidWhiskTrackerProof(const WhiskTracker& tracker, const uint8_t kComm[G1POINT_SIZE],
                               const uint8_t trackerProof[TRACKER_PROOF_SIZE]);

@@ -1209,6 +1209,70 @@ int curdle_prove_ct(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* S
 int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, const uint8_t* pre_trackers, size_t n, curdle_rand* rand,
                                            uint8_t* post_trackers_out, uint8_t* proof_out);
 int curdle_stat_host_point_mul(unsigned long long* out);   /* calls of alg::Point::Mul on the CALLING THREAD */
+/* The oblivious gather for k members of one n in ONE launch (k_permute_ct_seg, csrc/msm_ct_kernels.hip: the single
+ * gathers' body, block (x, j) serving member j): out[j n + i] = in[j n + perm[j n + i]] for i < n, j < k, over 32-byte
+ * records (curdle_fr_permute_ct_batch, _batch_device) or 96-byte records (curdle_g1_permute_ct_batch_device).  An entry
+ * at or above n gives a ZERO record, never another member's: the comparison is against t < n inside the member's own
+ * segment.  Reads are k n^2 records.  Limits: n <= 4,096, k <= 4,096, k n <= 2^20.  k = 0 or n = 0 returns CURDLE_OK
+ * without a device, looks at no pointer and writes nothing.  Refusals, alignment rules, slot hold, staging and wiping
+ * are curdle_fr_permute_ct's over k n records, with k and then k n checked after n, and the host form also overwrites
+ * the INPUT's pinned and device staging (a group's records may be secret); the promise is
+ * curdle_fr_permute_ct's.  curdle_stat_fr_permute_ct moves by (k n, 1) for the 32-byte forms.  It is not a default:
+ * nothing routes to it but curdle_prove_batch and curdle_whisk_generate_shuffle_proof_batch under their flag. */
+int curdle_fr_permute_ct_batch(const uint64_t* in, const uint32_t* perm, size_t n, size_t k, uint64_t* out);
+int curdle_fr_permute_ct_batch_device(const void* d_in, const void* d_perm, size_t n, size_t k, void* d_out, void* stream);
+int curdle_g1_permute_ct_batch_device(const void* d_in, const void* d_perm, size_t n, size_t k, void* d_out, void* stream);
+/* k proofs over one CRS at one ell, generated in lockstep.  Member i's arguments are Rs[i], Ss[i], Ts[i], Us[i] (ell
+ * gnark G1Affine records each), Ms + 18 i, perms[i] (ell entries), ks + 4 i, rs_ms + 16 i and rands[i] (k distinct
+ * generators); its proof goes to proofs_out + stride i (at most stride bytes), its length to proof_lens[i], its code to
+ * status[i].  THE CONTRACT: member i's bytes, its length and the state of rands[i] afterwards are, bit for bit, those
+ * of the single call on member i's arguments -- curdle_prove when flags = 0, curdle_prove_ct under
+ * CURDLE_PROVE_BATCH_CONSTANT_TIME.
+ * How: members run in groups of at most PROVE_BATCH_GROUP (a knob: default and maximum 64, lowered through
+ * curdle_plan_override), one thread per member of a group, each running Prove's body; the device operations of the
+ * members of a group meet at each step and go to the device as ONE coalesced call (alg::Lockstep, host/algebra.h: one
+ * curdle_msm_g1_batch, or under the flag one curdle_msm_g1_ct_batch and one curdle_fr_permute_ct_batch), split by
+ * whole members only where the primitive's limits require it (the knob PROVE_BATCH_PAIRS lowers that cap for tests).
+ * So k constant-time proofs of a group cost about the walks of one.
+ * Refusals happen before any thread starts, with nothing written and nothing drawn, in this order: an undefined flag
+ * bit, a null argument (two members sharing one rand counts as one), ell against the CRS, and under the flag
+ * curdle_prove_ct's own: ell > 4,096, CURDLE_PROVER_FOLD_BASES=1, a backend without the primitives or no device
+ * (CURDLE_ENODEV, no fallback).  k = 0 is CURDLE_OK without a device.
+ * A member that fails on its own gets its code in status[i] and proof_lens[i] = 0, and the others finish; the call
+ * returns CURDLE_OK unless the failure was the device's, which fails every member of that step alike.
+ * WHAT THE FLAG PROMISES: per member what curdle_prove_ct promises, with what it does not promise and what lies outside;
+ * in addition the coalesced staging -- the concatenated host copies of the members' scalars, permutations and gathered
+ * records that the group makes for a call -- is wiped like the single calls' staging, on every way out; the member
+ * threads are the library's own, started and joined inside the call, and the scoped switches live on them alone.
+ * Like curdle_prove_ct it is not a default: nothing routes to it.
+ * curdle_whisk_generate_shuffle_proof_batch is curdle_whisk_generate_shuffle_proof for k pre-tracker arrays of one n
+ * (pre_trackers[i]: n trackers; post_trackers_out + 96 n i and proofs_out + 4,576 i receive member i's results), under
+ * CURDLE_PROVE_BATCH_CONSTANT_TIME curdle_whisk_generate_shuffle_proof_ct: per member the draws and their order are the
+ * single call's (GeneratePermutation, then GetFr), all 2 n k tracker points go through ONE batched decode, the shuffle
+ * steps and the Proves run in lockstep.  Under the flag each member's shuffle step is expressed through the same
+ * funnels: the members share one constant-time multiplication launch over the k 2 n records, one batched gather and
+ * one curdle_msm_g1_ct_batch; the normalised outputs are the flagged single step's bits.  ONE DIFFERENCE from the flagged
+ * single step, which keeps the unpermuted k R_i | k S_i on the device: here they come back to the host between the
+ * multiplication and the gather (beside the public Ts | Us they would give the permutation).  Every copy this call
+ * makes of them -- the members' vectors, the group's concatenations, the gather's pinned and device input staging -- is
+ * overwritten on every way out; the staging of curdle_g1_scalar_mul_batch_ex's output is wiped as that call promises.
+ * A tracker that does not decode, or an n the single call refuses, gives that member the single call's error in
+ * status[i] and leaves the others untouched; under the flag with CURDLE_PROVER_FOLD_BASES=1 every member gets
+ * curdle_prove_ct's refusal (CURDLE_EINVAL, its text) where the single call meets it: behind the shuffle step and its
+ * draws, before any prover work.  The call is then still CURDLE_OK, and curdle_last_error gives the text of the first
+ * failed member's error.  What fails either batch call as a whole says which it was: a member thread that could not
+ * be started (CURDLE_ENOMEM), a step at which the members' requests disagreed, or a failed device call.
+ * curdle_stat_prove_batch: calls | members | groups | coalesced device calls, of both batch calls, completed or not. */
+#define CURDLE_PROVE_BATCH_CONSTANT_TIME 1u
+int curdle_prove_batch(const curdle_crs* crs, size_t k, size_t ell, const uint64_t* const* Rs, const uint64_t* const* Ss,
+                       const uint64_t* const* Ts, const uint64_t* const* Us, const uint64_t* Ms /* k x 18 */,
+                       const uint32_t* const* perms, const uint64_t* ks /* k x 4 */, const uint64_t* rs_ms /* k x 16 */,
+                       curdle_rand* const* rands, unsigned flags, uint8_t* proofs_out, size_t stride, size_t* proof_lens,
+                       int* status);
+int curdle_whisk_generate_shuffle_proof_batch(const curdle_crs* crs, size_t k, const uint8_t* const* pre_trackers, size_t n,
+                                              curdle_rand* const* rands, unsigned flags, uint8_t* post_trackers_out,
+                                              uint8_t* proofs_out, int* status);
+int curdle_stat_prove_batch(unsigned long long out[4]);   /* calls | members | groups | coalesced device calls */
 /* Diagnostics: out[0] points normalised on the device since the library was loaded, out[1] inversion groups run
  * (one Fermat inversion each; at most one per 64 points of a launch). */
 int curdle_stat_normalize(unsigned long long out[2]);
