@@ -41,15 +41,12 @@
 #include <hip/hip_runtime.h>
 
 #include "msm_kernels_common.h"
+#include "g1_walk_ct.h"  // load_fr_lane, select3, store_words_masked
+#include "g1_exit_ct.h"  // to_gnark_ct
 
 namespace curdle {
 
 namespace {
-__device__ __forceinline__ void load_fr_ct(Fr& f, const uint4* __restrict__ src) {
-  const uint4 lo = src[0], hi = src[1];
-  f.l[0] = lo.x; f.l[1] = lo.y; f.l[2] = lo.z; f.l[3] = lo.w;
-  f.l[4] = hi.x; f.l[5] = hi.y; f.l[6] = hi.z; f.l[7] = hi.w;
-}
 // the low 4-bit digit of k, and k >> 4: every window is read from word 0, so no register is indexed by the window
 __device__ __forceinline__ u32 next_digit4(Fr& k) {
   const u32 d = k.l[0] & 0xfu;
@@ -63,16 +60,13 @@ __device__ __forceinline__ void select_or_one(F28& r, u32 m, const F28& a) {
 #pragma unroll
   for (int i = 0; i < d28::N; i++) r.l[i] = (a.l[i] & m) | (d28::kOne(i) & ~m);
 }
-// r = sum ? a : (first ? b : c); sum, first and ~(sum | first) are disjoint masks
-__device__ __forceinline__ void select3(F28& r, u32 sum, const F28& a, u32 first, const F28& b, const F28& c) {
-  const u32 keep = ~(sum | first);
-#pragma unroll
-  for (int i = 0; i < d28::N; i++) r.l[i] = (a.l[i] & sum) | (b.l[i] & first) | (c.l[i] & keep);
-}
 
 // One window's step.  acc: x < 10p, y < 6p, zz, zzz < 2p, limbs normalised; (x2, y2) affine below 2p, normalised.
 // nz = 0 - (d != 0), started = all ones once something was added.  d28::madd's main path (EFD madd-2008-s), then the
 // selection described at the top of the file; the bounds are madd's (X3 < 10p, Y3 < 2p, products < 2p).
+// madd_bit (g1_walk_ct.h) is the same addition and stays a second function: there zz and zzz are SELECTED, here they are
+// multiplied by a selected PP or one.  This kernel sits at 249 of the 256 VGPRs its launch bounds allow, and a shared
+// core would keep pp live across the rest of the addition.
 __device__ __forceinline__ void madd_select(X28& acc, const F28& x2, const F28& y2, u32 nz, u32 started) {
   using namespace d28;
   const u32 sum = nz & started, first = nz & ~started;
@@ -101,33 +95,6 @@ __device__ __forceinline__ void madd_select(X28& acc, const F28& x2, const F28& 
   select3(acc.y, sum, p, first, yn, acc.y);
 }
 
-// d28::to_gnark_msm with a masked canonical step.  d28::canonical_lt2p takes its subtraction under `if (!borrow)`,
-// which this build turned into an exec mask on whether the product's representative reached p: a property of the
-// accumulator's projective coordinates, which are made of the digits.  Here the choice is a select.
-__device__ __forceinline__ void to_gnark_msm_ct(u32* w, const F28& a, u32 role) {
-  using namespace d28;
-  F28 t, c;
-#pragma unroll
-  for (int i = 0; i < N; i++) c.l[i] = role == 0 ? kToExtX16(i) : (role == 1 ? kToExtY64(i) : kToExt(i));
-  mul(t, a, c);
-  u32 d[N], borrow = 0;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    const u32 s = t.l[i] - kP(i) - borrow;
-    borrow = s >> 31;  // limbs are below 2^28 (the top one below 2^31): bit 31 of the difference is the borrow
-    d[i] = i < N - 1 ? s & MASK : s;
-  }
-  const u32 lt = 0u - borrow;  // t < p: keep t
-#pragma unroll
-  for (int i = 0; i < N; i++) t.l[i] = (t.l[i] & lt) | (d[i] & ~lt);
-  pack(w, t);
-}
-
-__device__ __forceinline__ void store12_masked(G1XYZZ* dst, int role, const u32 w[12], u32 m) {
-  uint4* d = reinterpret_cast<uint4*>(reinterpret_cast<u32*>(dst) + 12 * role);
-#pragma unroll
-  for (int i = 0; i < 3; i++) d[i] = make_uint4(w[4 * i] & m, w[4 * i + 1] & m, w[4 * i + 2] & m, w[4 * i + 3] & m);
-}
 }  // namespace
 
 __global__ void __launch_bounds__(kBlock, 2)
@@ -138,10 +105,10 @@ __global__ void __launch_bounds__(kBlock, 2)
   Fr k;
   {
     Fr s;
-    load_fr_ct(s, scalars + 2 * (size_t)i);
+    load_fr_lane(s, scalars + 2 * (size_t)i);
     if (multipliers) {  // a kernel argument: uniform over the launch
       Fr m;
-      load_fr_ct(m, multipliers + 2 * (size_t)i);
+      load_fr_lane(m, multipliers + 2 * (size_t)i);
       f_mul_inl<FrParams>(s, s, m);
     }
     f_from_mont<FrParams>(k, s);
@@ -182,16 +149,17 @@ __global__ void __launch_bounds__(kBlock, 2)
     madd_select(acc, pt.x, pt.y, nz, started);
     started |= nz;
   }
-  u32 w12[12];
-  G1XYZZ* dst = out + i;
-  to_gnark_msm_ct(w12, acc.x, 0);
-  store12_masked(dst, 0, w12, started);
-  to_gnark_msm_ct(w12, acc.y, 1);
-  store12_masked(dst, 1, w12, started);
-  to_gnark_msm_ct(w12, acc.zz, 2);
-  store12_masked(dst, 2, w12, started);
-  to_gnark_msm_ct(w12, acc.zzz, 3);
-  store12_masked(dst, 3, w12, started);
+  // X and Y leave the curve of from_gnark_iso by their own constants (d28::to_gnark_msm's roles), under `started`
+  uint4* dst = reinterpret_cast<uint4*>(out + i);
+  u32 w[12];
+  to_gnark_ct<d28::kToExtX16>(w, acc.x);
+  store_words_masked<3>(dst, w, started);
+  to_gnark_ct<d28::kToExtY64>(w, acc.y);
+  store_words_masked<3>(dst + 3, w, started);
+  to_gnark_ct<d28::kToExt>(w, acc.zz);
+  store_words_masked<3>(dst + 6, w, started);
+  to_gnark_ct<d28::kToExt>(w, acc.zzz);
+  store_words_masked<3>(dst + 9, w, started);
 }
 
 hipError_t launch_fbase_mul_ct(const void* table28, const void* scalars, const void* multipliers, uint32_t n, void* out_xyzz,

@@ -1,7 +1,8 @@
 // ONE complete XYZZ addition by selection: add_ct(acc, b) is d28::add (fp28.h) without a branch, for sums whose
 // operands depend on secrets (k_g1_sum_ct of msm_ct_kernels.hip folds the terms k_i P_i of a constant-time MSM with
 // it).  Device-only; every function is forced inline into its kernel.  The two mask helpers below it,
-// finite_mask and equal_mod_p, are shared with k_tracker_own_ct (tracker_own_ct_kernels.hip).
+// finite_mask and equal_mod_p, are shared with k_tracker_own_ct (tracker_own_ct_kernels.hip); finite_mask with
+// k_g1_mul_ct (g1_mul_ct_kernels.hip) too.
 //
 // What it computes, ALWAYS all of it:
 //     the main path of add-2008-s on (acc, b)                      12 products, 2 squarings

@@ -1,11 +1,12 @@
-// The constant-time walk over a VARIABLE base, shared by k_g1_mul_ct (g1_mul_ct_kernels.hip) and k_tracker_own_ct
-// (tracker_own_ct_kernels.hip): the scalar's load, its bits, the selections and the ONE constant-time mixed addition
-// of the tree for a lane's own affine point.  Device-only; every function is forced inline into its kernel.
+// The constant-time walk over a VARIABLE base, shared by k_g1_mul_ct (g1_mul_ct_kernels.hip), k_msm_ct_walk
+// (msm_ct_kernels.hip) and k_tracker_own_ct (tracker_own_ct_kernels.hip): the scalar's load, its bits, the selections,
+// the ONE constant-time mixed addition of the tree for a lane's own affine point, the walk itself (walk_ct) and the
+// masked store behind it.  k_fbase_mul_ct (fbase_ct_kernels.hip) walks windows of a table on its own and takes
+// load_fr_lane, select3 and store_words_masked from here.  Device-only; every function is forced inline into its kernel.
 //
 // The walk.  The 255 bits of k (r < 2^255) MSB first, a rolled loop.  Every step does ONE XYZZ doubling (d28::dbl,
 // which has no exceptional arm) and ALWAYS one mixed addition of the lane's own affine point (the main path of
-// d28::madd without its three exceptional arms, as madd_select of fbase_ct_kernels.hip); the new accumulator is taken
-// by mask selection:
+// d28::madd without its three exceptional arms); the new accumulator is taken by mask selection:
 //     bit == 0                      keep the doubled accumulator            (the sum is discarded)
 //     bit == 1, nothing added yet   the affine point, zz = zzz = one
 //     otherwise                     the sum
@@ -32,8 +33,8 @@
 // compiler is free to turn a select into a scalar branch on the bit.
 //
 // The multiply-accumulate trap: no product may see a limb the compiler knows.  The
-// initial accumulator is constants, so the bit loop stays rolled (#pragma unroll 1); the constant `one` reaches
-// products only through a select under a lane mask.
+// initial accumulator is constants, so the bit loop of walk_ct stays rolled (#pragma unroll 1); the constant `one`
+// reaches products only through a select under a lane mask.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -95,6 +96,32 @@ __device__ __forceinline__ void madd_bit(X28& acc, const F28& x2, const F28& y2,
   mul2_inl(p, r, q, ny, ppp);  // Y3 = R (Q - X3) - Y1 PPP  (mod p), < 2p
   select3(acc.x, sum, t, first, x2, acc.x);
   select3(acc.y, sum, p, first, y2, acc.y);
+}
+
+// The walk: `steps` bits of k from bit 255 down (the caller dropped bit 255 or shifted k left by 256 - steps; steps is
+// public), one d28::dbl and one madd_bit a step.  acc starts as four ones and is not a point until the returned
+// `started` is all ones; started == 0 is k = 0.  The loop stays rolled: the multiply-accumulate trap at the top.
+__device__ __forceinline__ u32 walk_ct(X28& acc, Fr& k, const F28& x2, const F28& y2, u32 steps) {
+  d28::set_one(acc.x);
+  d28::set_one(acc.y);
+  d28::set_one(acc.zz);
+  d28::set_one(acc.zzz);
+  u32 started = 0;
+#pragma unroll 1
+  for (u32 step = 0; step < steps; step++) {
+    const u32 bit = 0u - next_bit_msb(k);
+    d28::dbl(acc);
+    madd_bit(acc, x2, y2, bit, started);
+    started |= bit;
+  }
+  return started;
+}
+
+// dst[0 .. N16) = the 4 N16 words of w under the lane mask m: what a lane with no result stores is zeros
+template <int N16>
+__device__ __forceinline__ void store_words_masked(uint4* dst, const u32* w, u32 m) {
+#pragma unroll
+  for (int j = 0; j < N16; j++) dst[j] = make_uint4(w[4 * j] & m, w[4 * j + 1] & m, w[4 * j + 2] & m, w[4 * j + 3] & m);
 }
 }  // namespace
 

@@ -28,9 +28,14 @@ void count_msm_ct(size_t pairs, unsigned walks) {
   g_msm_ct_stat[2].fetch_add(1, std::memory_order_relaxed);
 }
 
+int check_scalar_bits(unsigned bits) {
+  if (bits < 1 || bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", bits);
+  return CURDLE_OK;
+}
+
 int check_args(const void* points, const void* scalars, size_t n, unsigned bits, const void* out) {
   if (!out || (n && (!points || !scalars))) return fail(CURDLE_EINVAL, "null argument");
-  if (bits < 1 || bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", bits);
+  if (int rc = check_scalar_bits(bits)) return rc;
   if (n > kMsmCtMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 65,536 pairs", n);
   return CURDLE_OK;
 }
@@ -51,6 +56,27 @@ int sum_and_fetch(Slot& S, size_t m, void* h_out, uint64_t out_jac[18], hipStrea
   HIP_TRY(hipStreamSynchronize(st));
   if (static_cast<const uint32_t*>(h_out)[36]) return fail(CURDLE_EINVAL, "a scalar is not below 2^scalar_bits");
   memcpy(out_jac, h_out, 144);
+  return CURDLE_OK;
+}
+
+// The host forms' n pairs on their way to the device: the slot's buffers, the notes on the WipeList (the scalars' two
+// copies and the term workspace), `fill` writing the scalars (n records of 32 bytes) and then the points (96 bytes each)
+// into the pinned staging it is handed, and the two uploads on st.  Behind it S.scalars and S.points hold the pairs.
+template <class Fill>
+int stage_pairs(Slot& S, WipeList& W, size_t n, hipStream_t st, Fill&& fill) {
+  int r;
+  if ((r = ensure(S.points, n * 96))) return r;
+  if ((r = ensure(S.scalars, n * 32))) return r;
+  if ((r = ensure(S.partials, n * kMsmCtTermBytes))) return r;
+  if ((r = ensure_pinned(S, 0, n * 32 + n * 96))) return r;  // scalars | points
+  W.note_device(S.scalars.p, n * 32);
+  W.note_device(S.partials.p, n * kMsmCtTermBytes);
+  W.note_host(S.h_stage[0], n * 32);
+  uint8_t* h_sc = static_cast<uint8_t*>(S.h_stage[0]);
+  uint8_t* h_pt = h_sc + n * 32;
+  fill(h_sc, h_pt);
+  HIP_TRY(hipMemcpyAsync(S.scalars.p, h_sc, n * 32, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(S.points.p, h_pt, n * 96, hipMemcpyHostToDevice, st));
   return CURDLE_OK;
 }
 
@@ -75,21 +101,13 @@ extern "C" int curdle_msm_g1_ct(const uint64_t* points, const uint64_t* scalars,
     Slot& S = H.slot();
     const hipStream_t st = H.stream();
     int r;
-    if ((r = ensure(S.points, n * 96))) return r;
-    if ((r = ensure(S.scalars, n * 32))) return r;
-    if ((r = ensure(S.partials, n * kMsmCtTermBytes))) return r;
-    if ((r = ensure_pinned(S, 0, n * 32 + n * 96))) return r;  // scalars | points
+    if ((r = stage_pairs(S, W, n, st, [&](uint8_t* h_sc, uint8_t* h_pt) {
+          memcpy(h_sc, scalars, n * 32);
+          memcpy(h_pt, points, n * 96);
+        })))
+      return r;
     if ((r = ensure_pinned(S, 1, kOutBytes))) return r;
-    W.note_device(S.scalars.p, n * 32);
-    W.note_device(S.partials.p, n * kMsmCtTermBytes);
-    W.note_host(S.h_stage[0], n * 32);
-    uint8_t* h_sc = static_cast<uint8_t*>(S.h_stage[0]);
-    uint8_t* h_pt = h_sc + n * 32;
-    memcpy(h_sc, scalars, n * 32);
-    memcpy(h_pt, points, n * 96);
     if ((r = prepare_out(S, st))) return r;
-    HIP_TRY(hipMemcpyAsync(S.scalars.p, h_sc, n * 32, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(S.points.p, h_pt, n * 96, hipMemcpyHostToDevice, st));
     HIP_TRY(launch_msm_ct_walk(S.points.p, S.scalars.p, kMsmCtScalarFr, scalar_bits, (uint32_t)n, S.partials.p, status_word(S), st));
     if ((r = sum_and_fetch(S, n, S.h_stage[1], out_jac, st))) return r;
     count_msm_ct(n, 1);
@@ -149,7 +167,7 @@ struct BatchShape {
 
 // What the batch refuses after the null arguments: scalar_bits, k, offsets that decrease, the total.
 int batch_shape(const size_t* offsets, size_t k, unsigned bits, BatchShape* sh) {
-  if (bits < 1 || bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", bits);
+  if (int rc = check_scalar_bits(bits)) return rc;
   if (k > kMsmCtBatchMax) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
   for (size_t j = 0; j < k; j++)
     if (offsets[j + 1] < offsets[j]) return fail(CURDLE_EINVAL, "offsets decrease at %zu", j);
@@ -203,30 +221,16 @@ int batch_walk_sum_fetch(Slot& S, const BatchShape& sh, const void* d_points, co
   return CURDLE_OK;
 }
 
-// The host forms behind their checks: `fill` writes the scalars (sh.total records of 32 bytes) and then the points
-// (96 bytes each) into the pinned staging it is handed.
+// The host forms behind their checks: `fill` is stage_pairs' over the sh.total pairs.
 template <class Fill>
 int batch_from_host(const BatchShape& sh, unsigned bits, uint64_t* out_jac, const char* what, Fill&& fill) {
-  const size_t n = sh.total;
   SlotHold H(cur(), true, nullptr);
   WipeList W(H.stream());
   H.wipe_on_exit(&W, what);
   return H.run([&]() -> int {
     Slot& S = H.slot();
     const hipStream_t st = H.stream();
-    int r;
-    if ((r = ensure(S.points, n * 96))) return r;
-    if ((r = ensure(S.scalars, n * 32))) return r;
-    if ((r = ensure(S.partials, n * kMsmCtTermBytes))) return r;
-    if ((r = ensure_pinned(S, 0, n * 32 + n * 96))) return r;  // scalars | points
-    W.note_device(S.scalars.p, n * 32);
-    W.note_device(S.partials.p, n * kMsmCtTermBytes);
-    W.note_host(S.h_stage[0], n * 32);
-    uint8_t* h_sc = static_cast<uint8_t*>(S.h_stage[0]);
-    uint8_t* h_pt = h_sc + n * 32;
-    fill(h_sc, h_pt);
-    HIP_TRY(hipMemcpyAsync(S.scalars.p, h_sc, n * 32, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(S.points.p, h_pt, n * 96, hipMemcpyHostToDevice, st));
+    if (int r = stage_pairs(S, W, sh.total, st, fill)) return r;
     return batch_walk_sum_fetch(S, sh, S.points.p, S.scalars.p, bits, out_jac, st);
   });
 }
@@ -278,7 +282,7 @@ extern "C" int curdle_msm_g1_ct_batch_device(const void* d_points, const void* d
 extern "C" int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t k, const uint64_t* scalars, size_t n,
                                       unsigned scalar_bits, uint64_t* out_jac) {
   if (k && (!out_jac || !points_sets || (n && !scalars))) return fail(CURDLE_EINVAL, "null argument");
-  if (scalar_bits < 1 || scalar_bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", scalar_bits);
+  if (int rc = check_scalar_bits(scalar_bits)) return rc;
   if (k > kMsmCtBatchMax) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
   if (k == 0) return CURDLE_OK;
   if (n > kMsmCtMax / k) return fail(CURDLE_EINVAL, "k n = %zu x %zu exceeds the supported 65,536 pairs", k, n);
@@ -341,18 +345,20 @@ int fr_permute_check(const void* in, const void* perm, size_t n, const void* out
   if (n > kShuffleCtMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 4,096 records", n);
   return CURDLE_OK;
 }
-}  // namespace
 
-extern "C" int curdle_fr_permute_ct(const uint64_t* in, const uint32_t* perm, size_t n, uint64_t* out) {
-  if (n == 0) return CURDLE_OK;
-  if (int rc = fr_permute_check(in, perm, n, out)) return rc;
+// The host form of the single gather (m = n) and of the batched one (m = k n): perm | in staged through the first pinned
+// staging, `launch` (the form's own kernel) on the slot's copies, the output back through the second, the counter by
+// (m, 1).  perm's two copies and the output's two copies are always wiped, the input's two only under wipe_input.
+template <class Launch>
+int fr_permute_from_host(const uint64_t* in, const uint32_t* perm, size_t m, bool wipe_input, const char* what, uint64_t* out,
+                         Launch&& launch) {
   SlotHold H(cur(), true, nullptr);
   WipeList W(H.stream());
-  H.wipe_on_exit(&W, "constant-time scalar gather: clearing the permutation and the gathered records");
+  H.wipe_on_exit(&W, what);
   return H.run([&]() -> int {
     Slot& S = H.slot();
     const hipStream_t st = H.stream();
-    const size_t rec = n * 32, perm_pad = (4 * n + 15) / 16 * 16;
+    const size_t rec = m * 32, perm_pad = (4 * m + 15) / 16 * 16;
     int r;
     if ((r = ensure(S.tmp, perm_pad))) return r;    // perm
     if ((r = ensure(S.scalars, rec))) return r;     // in
@@ -360,21 +366,32 @@ extern "C" int curdle_fr_permute_ct(const uint64_t* in, const uint32_t* perm, si
     if ((r = ensure_pinned(S, 0, perm_pad + rec))) return r;  // perm | in
     if ((r = ensure_pinned(S, 1, rec))) return r;             // out
     W.note_device(S.tmp.p, perm_pad);
+    if (wipe_input) W.note_device(S.scalars.p, rec);
     W.note_device(S.sorted.p, rec);
-    W.note_host(S.h_stage[0], perm_pad);
+    W.note_host(S.h_stage[0], wipe_input ? perm_pad + rec : perm_pad);
     W.note_host(S.h_stage[1], rec);
     uint8_t* h = static_cast<uint8_t*>(S.h_stage[0]);
-    memcpy(h, perm, 4 * n);
+    memcpy(h, perm, 4 * m);
     memcpy(h + perm_pad, in, rec);
-    HIP_TRY(hipMemcpyAsync(S.tmp.p, h, 4 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S.tmp.p, h, 4 * m, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(S.scalars.p, h + perm_pad, rec, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_fr_permute_ct(S.scalars.p, static_cast<const uint32_t*>(S.tmp.p), (uint32_t)n, S.sorted.p, st));
+    HIP_TRY(launch(S.scalars.p, static_cast<const uint32_t*>(S.tmp.p), S.sorted.p, st));
     HIP_TRY(hipMemcpyAsync(S.h_stage[1], S.sorted.p, rec, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     memcpy(out, S.h_stage[1], rec);
-    count_fr_permute_ct(n);
+    count_fr_permute_ct(m);
     return CURDLE_OK;
   });
+}
+}  // namespace
+
+extern "C" int curdle_fr_permute_ct(const uint64_t* in, const uint32_t* perm, size_t n, uint64_t* out) {
+  if (n == 0) return CURDLE_OK;
+  if (int rc = fr_permute_check(in, perm, n, out)) return rc;
+  return fr_permute_from_host(in, perm, n, false, "constant-time scalar gather: clearing the permutation and the gathered records",
+                              out, [&](const void* d_in, const uint32_t* d_perm, void* d_out, hipStream_t st) {
+                                return launch_fr_permute_ct(d_in, d_perm, (uint32_t)n, d_out, st);
+                              });
 }
 
 extern "C" int curdle_fr_permute_ct_device(const void* d_in, const void* d_perm, size_t n, void* d_out, void* stream) {
@@ -429,36 +446,12 @@ int permute_batch_device(const void* d_in, const void* d_perm, size_t n, size_t 
 extern "C" int curdle_fr_permute_ct_batch(const uint64_t* in, const uint32_t* perm, size_t n, size_t k, uint64_t* out) {
   if (n == 0 || k == 0) return CURDLE_OK;
   if (int rc = permute_batch_check(in, perm, n, k, out)) return rc;
-  SlotHold H(cur(), true, nullptr);
-  WipeList W(H.stream());
-  H.wipe_on_exit(&W, "constant-time scalar gather batch: clearing the permutations and the gathered records");
-  return H.run([&]() -> int {
-    Slot& S = H.slot();
-    const hipStream_t st = H.stream();
-    const size_t m = k * n, rec = m * 32, perm_pad = (4 * m + 15) / 16 * 16;
-    int r;
-    if ((r = ensure(S.tmp, perm_pad))) return r;    // perm
-    if ((r = ensure(S.scalars, rec))) return r;     // in
-    if ((r = ensure(S.sorted, rec))) return r;      // out
-    if ((r = ensure_pinned(S, 0, perm_pad + rec))) return r;  // perm | in
-    if ((r = ensure_pinned(S, 1, rec))) return r;             // out
-    W.note_device(S.tmp.p, perm_pad);
-    W.note_device(S.scalars.p, rec);  // unlike the single call: a group's input may be secret (the shuffle step's unpermuted records)
-    W.note_device(S.sorted.p, rec);
-    W.note_host(S.h_stage[0], perm_pad + rec);
-    W.note_host(S.h_stage[1], rec);
-    uint8_t* h = static_cast<uint8_t*>(S.h_stage[0]);
-    memcpy(h, perm, 4 * m);
-    memcpy(h + perm_pad, in, rec);
-    HIP_TRY(hipMemcpyAsync(S.tmp.p, h, 4 * m, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(S.scalars.p, h + perm_pad, rec, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_permute_ct_seg(S.scalars.p, static_cast<const uint32_t*>(S.tmp.p), (uint32_t)n, (uint32_t)k, 32, S.sorted.p, st));
-    HIP_TRY(hipMemcpyAsync(S.h_stage[1], S.sorted.p, rec, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(out, S.h_stage[1], rec);
-    count_fr_permute_ct(m);
-    return CURDLE_OK;
-  });
+  // unlike the single call, the input is wiped: a group's input may be secret (the shuffle step's unpermuted records)
+  return fr_permute_from_host(in, perm, k * n, true,
+                              "constant-time scalar gather batch: clearing the permutations and the gathered records", out,
+                              [&](const void* d_in, const uint32_t* d_perm, void* d_out, hipStream_t st) {
+                                return launch_permute_ct_seg(d_in, d_perm, (uint32_t)n, (uint32_t)k, 32, d_out, st);
+                              });
 }
 
 extern "C" int curdle_fr_permute_ct_batch_device(const void* d_in, const void* d_perm, size_t n, size_t k, void* d_out, void* stream) {

@@ -5,8 +5,8 @@
 //
 // k_msm_ct_walk.  One lane per (base, scalar) pair: the walk of g1_walk_ct.h with a PUBLIC step count `bits` (1...255,
 // a kernel argument): the scalar is first shifted left by 256 - bits, one bit a step in a rolled loop whose trip count
-// is the argument alone, and every bit shifted out is OR-ed into the lane's violation word; then `bits` steps of
-// d28::dbl and madd_bit with started |= bit.  The exactness argument of g1_walk_ct.h holds for every prefix of a scalar
+// is the argument alone, and every bit shifted out is OR-ed into the lane's violation word; then walk_ct over `bits`
+// steps.  The exactness argument of g1_walk_ct.h holds for every prefix of a scalar
 // below r, so it holds for the low `bits` bits walked here.  The scalar is a gnark Montgomery fr.Element (32 bytes,
 // f_from_mont in the lane) or a plain uint32 (the shuffle's permutation, so that the host does no field arithmetic on
 // it): a kernel argument says which, and both loads are at addresses made of the lane index.  The violation word goes
@@ -20,9 +20,9 @@
 // reads what another writes.  Addresses and trip counts are functions of m alone.
 //
 // k_msm_ct_finish.  ONE block: the remaining levels (m <= kSumTail, so at most one addition per lane and level) with a
-// barrier between them, then lane 0 normalises term[0] as k_g1_mul_ct does -- one Fermat inversion of zz zzz on the
-// fixed exponent chain of invert28.h -- and writes the 18 words curdle_msm_g1 returns, canonical (x, y, 1) or (1, 1, 0)
-// for infinity, chosen by a mask on zz, through the masked canonical step, and the status word behind them.
+// barrier between them, then lane 0 normalises term[0] as k_g1_mul_ct does -- affine_words_ct of g1_exit_ct.h: one
+// inversion, the masked canonical step -- and writes the 18 words curdle_msm_g1 returns, canonical (x, y, 1) or (1, 1, 0)
+// for infinity, chosen by a mask on zz, and the status word behind them.
 //
 // k_g1_permute_ct.  out[i] = in[perm[i]] over 96-byte records with perm secret: lane i loads its own perm[i] (an
 // address made of the lane index) and walks j = 0 ... n - 1, a public trip count with the address of in[j] made of j,
@@ -58,32 +58,9 @@
 #include "msm_kernels_common.h"
 #include "g1_walk_ct.h"
 #include "g1_add_ct.h"
-#include "invert28.h"
+#include "g1_exit_ct.h"
 
 namespace curdle {
-
-namespace {
-// to_gnark_ct of g1_mul_ct_kernels.hip: d28::to_gnark with a masked canonical step, the choice between t and t - p a
-// select on the borrow, never an exec mask.
-__device__ __forceinline__ void to_gnark_ct(u32* w, const F28& a) {
-  using namespace d28;
-  F28 t, c;
-#pragma unroll
-  for (int i = 0; i < N; i++) c.l[i] = kToExt(i);
-  mul(t, a, c);
-  u32 d[N], borrow = 0;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    const u32 s = t.l[i] - kP(i) - borrow;
-    borrow = s >> 31;  // limbs are below 2^28 (the top one below 2^31): bit 31 of the difference is the borrow
-    d[i] = i < N - 1 ? s & MASK : s;
-  }
-  const u32 lt = 0u - borrow;  // t < p: keep t
-#pragma unroll
-  for (int i = 0; i < N; i++) t.l[i] = (t.l[i] & lt) | (d[i] & ~lt);
-  pack(w, t);
-}
-}  // namespace
 
 __global__ void __launch_bounds__(kBlock, 2)
     k_msm_ct_walk(const uint4* __restrict__ points, const void* __restrict__ scalars, u32 form, u32 bits, u32 n,
@@ -110,38 +87,12 @@ __global__ void __launch_bounds__(kBlock, 2)
   u32 over = 0;
 #pragma unroll 1
   for (u32 s = bits; s < 256; s++) over |= next_bit_msb(k);
-  X28 acc;  // not a point until `started`
-  d28::set_one(acc.x);
-  d28::set_one(acc.y);
-  d28::set_one(acc.zz);
-  d28::set_one(acc.zzz);
-  u32 started = 0;
-#pragma unroll 1
-  for (u32 step = 0; step < bits; step++) {
-    const u32 bit = 0u - next_bit_msb(k);
-    d28::dbl(acc);
-    madd_bit(acc, x2, y2, bit, started);
-    started |= bit;
-  }
+  X28 acc;
+  const u32 started = walk_ct(acc, k, x2, y2, bits);
   // Unconditional, 0 or 1.  The address is made of the lane index (i < 2^31: always word 0) so that it is a per-lane
   // atomic: on a wave-uniform address the compiler first folds the wave's values through v_readlane into SGPRs.
   atomicOr(status + (i >> 31), over);
-  const u32 m = started & finite;
-  const u32* w = reinterpret_cast<const u32*>(&acc);
-  uint4* dst = reinterpret_cast<uint4*>(term + i);
-#pragma unroll
-  for (int j = 0; j < 14; j++) dst[j] = make_uint4(w[4 * j] & m, w[4 * j + 1] & m, w[4 * j + 2] & m, w[4 * j + 3] & m);
-}
-
-__global__ void __launch_bounds__(kBlock, 1) k_g1_sum_ct(X28* term, u32 m) {
-  const u32 h = (m + 1) / 2;
-  const u32 i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= m - h) return;
-  X28 a, b;
-  d28::load(a, term + i);
-  d28::load(b, term + i + h);
-  add_ct(a, b);
-  d28::store(term + i, a);
+  store_words_masked<14>(reinterpret_cast<uint4*>(term + i), reinterpret_cast<const u32*>(&acc), started & finite);
 }
 
 namespace {
@@ -153,7 +104,16 @@ __device__ __forceinline__ void sum_pair(X28* term, u32 i, u32 h) {
   add_ct(a, b);
   d28::store(term + i, a);
 }
+}  // namespace
 
+__global__ void __launch_bounds__(kBlock, 1) k_g1_sum_ct(X28* term, u32 m) {
+  const u32 h = (m + 1) / 2;
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= m - h) return;
+  sum_pair(term, i, h);
+}
+
+namespace {
 // The levels one block runs, m <= kSumTail terms at `term`, with a barrier between them: every lane of the block.
 __device__ __forceinline__ void sum_tail(X28* term, u32 m) {
 #pragma unroll 1
@@ -172,17 +132,8 @@ __device__ __forceinline__ void write_result(const X28* term, u32* out) {
   X28 acc;
   d28::load(acc, term);
   const u32 fin = ~zero_mask(acc.zz);
-  // x = X / zz, y = Y / zzz with one inversion; infinity inverts 0 (which gives 0) and is masked away
-  F28 d, inv, ix, iy;
-  d28::mul(d, acc.zz, acc.zzz);
-  invert(inv, d);
-  d28::mul(ix, inv, acc.zzz);
-  d28::mul(iy, inv, acc.zz);
-  d28::mul(ix, acc.x, ix);
-  d28::mul(iy, acc.y, iy);
   u32 w[24];
-  to_gnark_ct(w, ix);
-  to_gnark_ct(w + 12, iy);
+  affine_words_ct(w, acc);  // infinity inverts 0 (which gives 0) and is masked away
 #pragma unroll
   for (int j = 0; j < 12; j++) {
     const u32 one = FpParams::one(j);  // gnark's Montgomery 1

@@ -13,8 +13,8 @@
 // CURDLE_TRACKER_BAD with no chain (the trackers are public); whether rG or krG is infinity is public too, and is
 // nevertheless folded into masks.  Everything from the key's load to the store is straight-line code under one exec.
 //
-// The walk is k_g1_mul_ct's, from g1_walk_ct.h, on the lane's rG: f_from_mont on the key, bit 255 dropped, 255 rolled
-// steps of d28::dbl and madd_bit with started |= bit.  The exactness argument of g1_walk_ct.h carries over word for
+// The walk is k_g1_mul_ct's, from g1_walk_ct.h, on the lane's rG: f_from_mont on the key, bit 255 dropped, walk_ct over
+// 255 steps.  The exactness argument of g1_walk_ct.h carries over word for
 // word: the decoder's subgroup test (launch_g1_decompress) is what makes rG of prime order r.
 //
 // The end.  There is NO inversion.  The result (X, Y, ZZ, ZZZ) equals the affine krG = (x2, y2) iff x2 ZZ = X and
@@ -67,19 +67,8 @@ __global__ void __launch_bounds__(kBlock, 2)
     f_from_mont<FrParams>(k, s);
   }
   (void)next_bit_msb(k);  // k < r < 2^255: bit 255 is zero, bit 254 is next
-  X28 acc;  // not a point until `started`
-  d28::set_one(acc.x);
-  d28::set_one(acc.y);
-  d28::set_one(acc.zz);
-  d28::set_one(acc.zzz);
-  u32 started = 0;
-#pragma unroll 1
-  for (u32 step = 0; step < 255; step++) {
-    const u32 bit = 0u - next_bit_msb(k);
-    d28::dbl(acc);
-    madd_bit(acc, x2, y2, bit, started);
-    started |= bit;
-  }
+  X28 acc;
+  const u32 started = walk_ct(acc, k, x2, y2, 255);
   // acc == krG without an inversion: x2 ZZ == X and y2 ZZZ == Y
   d28::load_words<24>(pw, points + 6 * (2 * (size_t)t + 1));
   const u32 krg_finite = finite_mask(pw);

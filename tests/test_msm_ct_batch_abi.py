@@ -95,12 +95,21 @@ def test_symbols_and_prototypes(cm):
     for path in glob.glob(os.path.join(csrc, "*.hip")):
         unit = os.path.basename(path)[:-4]
         assert "csrc/%s.hip" % unit in make and "build/%s.o" % unit in make, unit
-    defs = {"void add_ct(": [], "void madd_bit(": [], "u32 equal_mod_p(": []}
+    # the whole constant-time G1 layer has one definition each: the walk, the exit and the small helpers too
+    # ("void affine_words_ct(": the bare name with its parenthesis is also what a call looks like)
+    homes = {"void add_ct(": "g1_add_ct.h", "void madd_bit(": "g1_walk_ct.h", "u32 equal_mod_p(": "g1_add_ct.h",
+             "void to_gnark_ct(": "g1_exit_ct.h", "void affine_words_ct(": "g1_exit_ct.h", "u32 walk_ct(": "g1_walk_ct.h",
+             "void select3(": "g1_walk_ct.h", "void load_fr_lane(": "g1_walk_ct.h", "u32 finite_mask(": "g1_add_ct.h"}
+    defs = {d: [] for d in homes}
+    gone = {"to_gnark_msm_ct": [], "load_fr_ct": []}
     for path in glob.glob(os.path.join(csrc, "*")):
         text = open(path, errors="replace").read()
         for d in defs:
             defs[d] += [os.path.basename(path)] * text.count(d)
-    assert defs == {"void add_ct(": ["g1_add_ct.h"], "void madd_bit(": ["g1_walk_ct.h"], "u32 equal_mod_p(": ["g1_add_ct.h"]}
+        for d in gone:
+            gone[d] += [os.path.basename(path)] * text.count(d)
+    assert defs == {d: [home] for d, home in homes.items()}
+    assert gone == {"to_gnark_msm_ct": [], "load_fr_ct": []}
     # the host layer names the primitive weakly
     alg = re.sub(r"\s+", " ", open(os.path.join(ROOT, "go-curdleproofs_amd", "host", "algebra.cpp")).read())
     for name in ("curdle_msm_g1_ct", "curdle_msm_g1_ct_batch", "curdle_msm_g1_ct_multi"):
