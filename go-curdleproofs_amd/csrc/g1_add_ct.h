@@ -47,6 +47,9 @@ __device__ __forceinline__ u32 finite_mask(const u32* w) {
   return 0u - ((any | (0u - any)) >> 31);
 }
 // all ones iff a - b == 0 mod p; a < 2p, b < 10p, both normalised.  No comparison instruction: masks only.
+// Inside these bounds the difference a - b + 16p is at least 6p, never the integer 0, so for congruent operands the product
+// e below is always p and never 0: the `== 0` leg cannot be reached and is kept for operands outside the contract
+// (tests/g1_ct_model.py asserts it on every call).
 __device__ __forceinline__ u32 equal_mod_p(const F28& a, const F28& b) {
   using namespace d28;
   F28 d, e, c;

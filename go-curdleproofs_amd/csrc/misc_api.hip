@@ -61,12 +61,18 @@ extern "C" int curdle_selftest_op(int op, const uint64_t* in64, size_t n, uint64
   // the widths of every operation live in ONE table (msm_kernels.h), which the launcher and the kernel index too
   const size_t in_w = kSelftestTable[op].in_words, out_w = kSelftestTable[op].out_words;
   if (n > ((size_t)1 << 26)) return fail(CURDLE_EINVAL, "selftest of %zu elements", n);
-  if (op >= 13) {  // raw-limb operations: fp28.h / quad28.h are device headers, there is no host build
+  if (op >= 13) {  // raw-limb operations: fp28.h / quad28.h and the layers on them are device headers, there is no host build
     if (!on_device) return fail(CURDLE_EINVAL, "selftest op %d runs on the device only (fp28.h is a device header)", op);
-    const uint32_t nsel = op == 13 ? kSelftestFieldSels : (op == 14 ? kSelftestPointSels : kSelftestQuadSels);
+    const uint32_t nsel = op == 13 ? kSelftestFieldSels : (op == 14 ? kSelftestPointSels : (op == 15 ? kSelftestQuadSels : kSelftestCtSels));
     for (size_t i = 0; i < n; i++) {
       const uint32_t* s = in + i * in_w;
       if (s[0] >= nsel) return fail(CURDLE_EINVAL, "selftest op %d: element %zu has selector %u (of %u)", op, i, s[0], nsel);
+      if (op == 16) {  // one kernel per selector; mask words are masks; the walk's step count is k_msm_ct_walk's range
+        if (s[0] != in[0]) return fail(CURDLE_EINVAL, "selftest op 16: element %zu has selector %u, element 0 has %u", i, s[0], in[0]);
+        if ((s[0] == 8 || s[0] == 9) && ((s[1] + 1u) > 1u || (s[2] + 1u) > 1u))
+          return fail(CURDLE_EINVAL, "selftest op 16: element %zu has a mask word that is neither 0 nor all ones", i);
+        if (s[0] == 11 && (s[1] < 1 || s[1] > 255)) return fail(CURDLE_EINVAL, "selftest op 16: element %zu walks %u steps (1..255)", i, s[1]);
+      }
       if (op == 15 && s[0] == 3 && (s[2] > 31 || (s[2] < 31 && (s[1] >> (s[2] + 1)) != 0)))
         return fail(CURDLE_EINVAL, "selftest op 15: element %zu has k = %u above bit top = %u", i, s[1], s[2]);
     }
@@ -137,7 +143,8 @@ extern "C" int curdle_selftest_op(int op, const uint64_t* in64, size_t n, uint64
   HIP_TRY(hipMalloc(&d_in.p, n * in_w * 4));
   HIP_TRY(hipMalloc(&d_out.p, n * out_w * 4));
   HIP_TRY(hipMemcpyAsync(d_in.p, in, n * in_w * 4, hipMemcpyHostToDevice, cx.util_stream));
-  HIP_TRY(launch_selftest(op, (const uint32_t*)d_in.p, n, (uint32_t*)d_out.p, cx.util_stream));
+  HIP_TRY(op == 16 ? launch_selftest_ct(in[0], (const uint32_t*)d_in.p, n, (uint32_t*)d_out.p, cx.util_stream)
+                   : launch_selftest(op, (const uint32_t*)d_in.p, n, (uint32_t*)d_out.p, cx.util_stream));
   HIP_TRY(hipMemcpyAsync(out, d_out.p, n * out_w * 4, hipMemcpyDeviceToHost, cx.util_stream));
   HIP_TRY(hipStreamSynchronize(cx.util_stream));
   return CURDLE_OK;

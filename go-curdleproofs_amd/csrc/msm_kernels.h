@@ -186,7 +186,7 @@ struct SelftestOp {
   uint32_t out_words;  // ... written per element
   uint32_t lanes;      // lanes per element: 4 for the lane-distributed (quad) operations
 };
-static constexpr int kSelftestOps = 16;
+static constexpr int kSelftestOps = 17;
 static constexpr SelftestOp kSelftestTable[kSelftestOps] = {
     {24, 12, 1}, {24, 12, 1}, {24, 12, 1}, {24, 12, 1},  // 0..3  Fp mul / add / sub / sqr
     {16, 8, 1},                                           // 4     Fr Montgomery -> canonical
@@ -197,15 +197,20 @@ static constexpr SelftestOp kSelftestTable[kSelftestOps] = {
     {60, 16, 1},                                          // 13    fp28.h field operations on raw limbs
     {116, 56, 1},                                         // 14    fp28.h point operations on raw limbs, one lane
     {116, 56, 4},                                         // 15    quad28.h point operations on raw limbs
+    {116, 60, 1},                                         // 16    the constant-time G1 layer on raw limbs (selftest_ct_kernels.hip)
 };
-// Operations 13..15 read and write the internal 14 x 28-bit limbs directly (no from_gnark / to_gnark on
+// Operations 13..16 read and write the internal 14 x 28-bit limbs directly (no from_gnark / to_gnark on
 // either side).  Word 0 of an element selects the primitive; a selector outside these counts is refused
-// by the host before anything is copied or launched.
+// by the host before anything is copied or launched.  Operation 16 has a kernel per selector: all elements of
+// one call share the selector, its mask words are 0 or all ones and its walk has 1..255 steps, or the host refuses.
 static constexpr uint32_t kSelftestFieldSels = 26;  // op 13
 static constexpr uint32_t kSelftestPointSels = 6;   // op 14
 static constexpr uint32_t kSelftestQuadSels = 4;    // op 15
-// hipErrorInvalidValue for an op outside the table (nothing is launched).
+static constexpr uint32_t kSelftestCtSels = 12;     // op 16
+// hipErrorInvalidValue for an op outside the table, and for op 16, which has its own launcher (nothing is launched).
 hipError_t launch_selftest(int op, const uint32_t* d_in, size_t n, uint32_t* d_out, hipStream_t stream);
+// selftest_ct_kernels.hip: op 16, the kernel of selector `sel` over n elements of the table's widths.
+hipError_t launch_selftest_ct(uint32_t sel, const uint32_t* d_in, size_t n, uint32_t* d_out, hipStream_t stream);
 
 // decode_kernels.hip: n compressed G1 points (48 B each) -> n gnark affine points (24 u32
 // each) + one CURDLE_DECODE_* status byte per point.

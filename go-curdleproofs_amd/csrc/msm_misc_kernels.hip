@@ -296,7 +296,7 @@ __global__ void __launch_bounds__(kBlock, 2)
 }
 
 hipError_t launch_selftest(int op, const uint32_t* d_in, size_t n, uint32_t* d_out, hipStream_t stream) {
-  if (op < 0 || op >= kSelftestOps || !d_in || !d_out) return hipErrorInvalidValue;
+  if (op < 0 || op >= kSelftestOps || op == 16 || !d_in || !d_out) return hipErrorInvalidValue;  // 16: launch_selftest_ct
   if (n == 0) return hipSuccess;
   const SelftestOp& t = kSelftestTable[op];
   const size_t lanes = (size_t)t.lanes * n;

@@ -1477,7 +1477,7 @@ int curdle_synth_points_walk_device(const uint64_t k[4], const uint64_t q[4], si
  *          leaves through 2^388 / 2^390) on plain field elements: in: n x (Fp | Fp), out: n x
  *          (Fp | Fp | 1 if the x image is normalised and below 2p | the same for y); the round trip
  *          is the identity (the host build copies)
- *   op 13..15: the device-internal arithmetic (csrc/fp28.h, csrc/quad28.h) on RAW internal limbs
+ *   op 13..16: the device-internal arithmetic (csrc/fp28.h, csrc/quad28.h, the constant-time G1 layer) on RAW internal limbs
  *          (14 x 28-bit limbs per field element, Montgomery radix 2^392, not reduced; no conversion
  *          on either side), so tests can drive every bound those functions state.  Word 0 of an item
  *          is a selector; an item with an unknown selector makes the call fail with CURDLE_EINVAL
@@ -1493,7 +1493,21 @@ int curdle_synth_points_walk_device(const uint64_t k[4], const uint64_t q[4], si
  *          3 dbl(A)  4 dbl_affine(A.x, A.y)  5 mul_small(B, k)
  *   op 15: the same layout through the quads: sel 0 q28::add(A, B)  1 q28::dbl(A)
  *          2 q28::dbl_outofline(A)  3 q28::mul_small(B, k, top) (top <= 31, k < 2^(top+1))
- * (limbs are passed as uint32 little-endian; 24/16/96/8/24/60/116 in and 12/8/48/10/26/16/56 out per item)
+ *   op 16: the constant-time G1 layer (csrc/g1_walk_ct.h, g1_add_ct.h, g1_exit_ct.h, invert28.h and the fixed-base step
+ *          of fbase_walk_ct.h) on raw limbs, each selector the production function of its header, by the rules of
+ *          13..15 (device only; a bad selector fails before anything is copied or launched).  ALL items of one call
+ *          share the selector (each selector is a kernel of its own): anything else is CURDLE_EINVAL, and so are a
+ *          mask word of sel 8 / 9 that is neither 0 nor 0xffffffff and a step count of sel 11 outside 1..255.
+ *          in: sel | arg0 | arg1 | pad | A (X28) | B (X28), out: 56 words | 4 flag words, unused words zero.
+ *          sel 0 zero_mask(A.x) -> flag 0   1 finite_mask(A's first 24 words) -> flag 0
+ *          2 equal_mod_p(A.x, A.y) -> flag 0 (A.x < 2p, A.y < 10p)
+ *          3 / 4 / 5 to_gnark_ct<kToExt / kToExtX16 / kToExtY64>(A.x) -> 12 gnark words
+ *          6 invert(A.x) -> 14 limbs   7 affine_words_ct(A) -> 24 gnark words
+ *          8 madd_bit(A, B.x, B.y, bit = arg0, started = arg1)   9 madd_select(A, B.x, B.y, nz = arg0, started = arg1)
+ *          10 add_ct(A, B) -> X28
+ *          11 walk_ct: (x2, y2) = (A.x, A.y), the scalar is B's first 8 words (canonical), steps = arg0; the scalar is
+ *          shifted left by 256 - steps as k_msm_ct_walk does it -> X28 | started (flag 0) | over (flag 1)
+ * (limbs are passed as uint32 little-endian; 24/16/96/8/24/60/116 in and 12/8/48/10/26/16/56/60 out per item)
  * on_device = 0 runs the same header code on the host CPU (ops 0..12). */
 int curdle_selftest_op(int op, const uint64_t* in, size_t n, uint64_t* out, int on_device);
 /* Words per item operation `op` reads and writes: the ONE table the entry point above, its launcher

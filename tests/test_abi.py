@@ -130,21 +130,22 @@ def test_selftest_operations_and_raw_limb_operations_share_one_table(cm):
     """curdle_selftest_op's buffer sizes, its launcher's grid and its kernel's indexing come from ONE
     table, which the binding asks for too: an unknown operation is refused before anything is
     allocated or launched (round 3's r3a abort was an operation known to one of them only).  The table
-    has 16 operations; 13..15 (raw internal limbs) are device only and check their selectors first."""
-    shapes = [cm.selftest_shape(op) for op in range(16)]
+    has 17 operations; 13..16 (raw internal limbs) are device only and check their selectors first."""
+    shapes = [cm.selftest_shape(op) for op in range(17)]
     assert shapes[:5] == [(24, 12)] * 4 + [(16, 8)]
     assert shapes[5:11] == [(96, 48)] * 6 and shapes[11] == (8, 10) and shapes[12] == (24, 26)
     assert shapes[13] == (60, 16) and shapes[14] == shapes[15] == (116, 56)   # the raw-limb operations
-    for bad in (-1, 16, 99):
+    assert shapes[16] == (116, 60)                                            # ... and the constant-time G1 layer on them
+    for bad in (-1, 17, 99):
         with pytest.raises(RuntimeError):
             cm.selftest_shape(bad)
     inp = np.zeros((3, 8), dtype=np.uint32)
     out = np.zeros((3, 10), dtype=np.uint32)
     for on_device in (0, 1):
-        assert cm._selftest_op(16, cm._ptr(inp), 3, cm._ptr(out), on_device) == cm.EINVAL
+        assert cm._selftest_op(17, cm._ptr(inp), 3, cm._ptr(out), on_device) == cm.EINVAL
     # the raw-limb operations run fp28.h / quad28.h, device headers: the host build refuses them, and an
     # unknown selector (word 0) is refused before anything is copied or launched, with or without a device
-    for op, nsel in ((13, 26), (14, 6), (15, 4)):
+    for op, nsel in ((13, 26), (14, 6), (15, 4), (16, 12)):
         iw, ow = shapes[op]
         with pytest.raises(RuntimeError, match="device only"):
             cm.selftest_op(op, np.zeros((2, iw), dtype=np.uint32), False)
@@ -156,6 +157,25 @@ def test_selftest_operations_and_raw_limb_operations_share_one_table(cm):
     bad_top[0, :3] = (3, 5, 1)                       # q28::mul_small with k above bit `top`
     with pytest.raises(RuntimeError, match="above bit top"):
         cm.selftest_op(15, bad_top, True)
+    # operation 16 has a kernel per selector: one selector per call, mask words that are masks, 1..255 steps -- refused
+    # before anything is copied or launched, with or without a device
+    mixed = np.zeros((3, 116), dtype=np.uint32)
+    mixed[:, 0] = (10, 10, 2)
+    with pytest.raises(RuntimeError, match="element 2 has selector 2, element 0 has 10"):
+        cm.selftest_op(16, mixed, True)
+    for sel in (8, 9):
+        for word in (1, 2):
+            bad_mask = np.zeros((2, 116), dtype=np.uint32)
+            bad_mask[:, 0] = sel
+            bad_mask[1, word] = 1
+            with pytest.raises(RuntimeError, match="mask word"):
+                cm.selftest_op(16, bad_mask, True)
+    for steps in (0, 256, 1 << 31):
+        bad_steps = np.zeros((2, 116), dtype=np.uint32)
+        bad_steps[:, 0] = 11
+        bad_steps[:, 1] = (9, steps)
+        with pytest.raises(RuntimeError, match="steps"):
+            cm.selftest_op(16, bad_steps, True)
     # the host build of every operation runs on exactly the table's widths
     for op, (iw, ow) in enumerate(shapes):
         if op in (8, 9, 10) or op >= 13:

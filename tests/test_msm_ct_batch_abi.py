@@ -99,7 +99,8 @@ def test_symbols_and_prototypes(cm):
     # ("void affine_words_ct(": the bare name with its parenthesis is also what a call looks like)
     homes = {"void add_ct(": "g1_add_ct.h", "void madd_bit(": "g1_walk_ct.h", "u32 equal_mod_p(": "g1_add_ct.h",
              "void to_gnark_ct(": "g1_exit_ct.h", "void affine_words_ct(": "g1_exit_ct.h", "u32 walk_ct(": "g1_walk_ct.h",
-             "void select3(": "g1_walk_ct.h", "void load_fr_lane(": "g1_walk_ct.h", "u32 finite_mask(": "g1_add_ct.h"}
+             "void select3(": "g1_walk_ct.h", "void load_fr_lane(": "g1_walk_ct.h", "u32 finite_mask(": "g1_add_ct.h",
+             "void madd_select(": "fbase_walk_ct.h"}
     defs = {d: [] for d in homes}
     gone = {"to_gnark_msm_ct": [], "load_fr_ct": []}
     for path in glob.glob(os.path.join(csrc, "*")):
