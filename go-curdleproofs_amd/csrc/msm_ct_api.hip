@@ -185,6 +185,15 @@ int batch_shape(const size_t* offsets, size_t k, unsigned bits, BatchShape* sh) 
   return CURDLE_OK;
 }
 
+}  // namespace
+namespace curdle_api {
+void count_msm_ct_batch(size_t msms, unsigned levels) {
+  g_msm_ct_batch_stat[0].fetch_add(1, std::memory_order_relaxed);
+  g_msm_ct_batch_stat[1].fetch_add(msms, std::memory_order_relaxed);
+  g_msm_ct_batch_stat[2].fetch_add(levels, std::memory_order_relaxed);
+}
+}  // namespace curdle_api
+namespace {
 size_t batch_out_bytes(size_t k) { return 144 * k + 4; }                         // what comes back
 size_t batch_status_offset(size_t k) { return (144 * k + 4 + 15) / 16 * 16; }    // the walk's status word
 
@@ -215,9 +224,7 @@ int batch_walk_sum_fetch(Slot& S, const BatchShape& sh, const void* d_points, co
   g_msm_ct_stat[0].fetch_add(sh.total, std::memory_order_relaxed);
   g_msm_ct_stat[1].fetch_add(1, std::memory_order_relaxed);
   g_msm_ct_stat[2].fetch_add(sh.nonempty, std::memory_order_relaxed);
-  g_msm_ct_batch_stat[0].fetch_add(1, std::memory_order_relaxed);
-  g_msm_ct_batch_stat[1].fetch_add(k, std::memory_order_relaxed);
-  g_msm_ct_batch_stat[2].fetch_add(levels, std::memory_order_relaxed);
+  count_msm_ct_batch(k, levels);
   return CURDLE_OK;
 }
 

@@ -385,6 +385,21 @@ hipError_t launch_fr_permute_ct(const void* in, const uint32_t* perm, uint32_t n
 hipError_t launch_permute_ct_seg(const void* in, const uint32_t* perm, uint32_t n, uint32_t k, uint32_t record_bytes, void* out,
                                  hipStream_t stream);
 
+// msm_ct_bases_kernels.hip: the constant-time MSM over a resident PUBLIC base set, the walk split into chunks of
+// chunk_bits (1...64) bits.
+//   launch_ct_bases_shift: staging_xyzz[(j - 1) n + i] = 2^(chunk_bits j) points[i] for 1 <= j < chunks as gnark-form
+//     G1XYZZ records (192 bytes, ZZ = 0: infinity), what launch_g1_normalize's kNormalizeXyzz reads; points are gnark
+//     G1Affine records.  Public arithmetic.
+//   launch_msm_ct_walk_rows: term[p Cb + j] = (chunk j of scalars[p]) * table[j size + rows[p]] for p < n and
+//     j < Cb = ceil(bits / chunk_bits): launch_msm_ct_walk's walk, status word and term records over chunk_bits steps
+//     (the top chunk: bits - chunk_bits (Cb - 1)).  table: Cb or more rows of `size` gnark G1Affine records; rows: n
+//     device uint32 below size (public; the caller checked them); scalars: Montgomery fr.Elements.  n Cb <= 2^31.
+hipError_t launch_ct_bases_shift(const void* points, uint32_t n, uint32_t chunk_bits, uint32_t chunks, void* staging_xyzz,
+                                 hipStream_t stream);
+hipError_t launch_msm_ct_walk_rows(const void* table, uint32_t size, const uint32_t* rows, const void* scalars,
+                                   uint32_t chunk_bits, uint32_t bits, uint32_t n, void* term, uint32_t* status,
+                                   hipStream_t stream);
+
 // normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion
 // per wave of 64 lanes with 1 or 8 points each (Montgomery's trick over a wave scan).  The forms are those of
 // launch_g1_compress; a denominator (Z, or ZZ ZZZ) that is 0 mod p is infinity.  `in` and `out` are multiples of 16

@@ -98,6 +98,10 @@ SYMBOLS = [
     "curdle_prove_ct", "curdle_whisk_generate_shuffle_proof_ct", "curdle_stat_host_point_mul",
     "curdle_fr_permute_ct_batch", "curdle_fr_permute_ct_batch_device", "curdle_g1_permute_ct_batch_device",
     "curdle_prove_batch", "curdle_whisk_generate_shuffle_proof_batch", "curdle_stat_prove_batch",
+    "curdle_ct_bases_create", "curdle_ct_bases_create_device", "curdle_ct_bases_free", "curdle_ct_bases_size",
+    "curdle_ct_bases_chunk_bits", "curdle_ct_bases_export",
+    "curdle_msm_g1_ct_bases", "curdle_msm_g1_ct_bases_device", "curdle_msm_g1_ct_bases_batch",
+    "curdle_msm_g1_ct_bases_batch_device", "curdle_stat_msm_ct_bases",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -512,6 +516,106 @@ def stat_alg_msm() -> dict:
     out = (C.c_ulonglong * 4)()
     _check(_stat_alg_msm(out))
     return {"bucket_calls": int(out[0]), "bucket_pairs": int(out[1]), "ct_calls": int(out[2]), "ct_pairs": int(out[3])}
+
+
+_ct_bases_create = _sig("curdle_ct_bases_create", C.c_int, _vp, C.c_size_t, C.c_uint, C.POINTER(C.c_void_p))
+_ct_bases_create_device = _sig("curdle_ct_bases_create_device", C.c_int, _vp, C.c_size_t, C.c_uint, C.POINTER(C.c_void_p), _vp)
+_ct_bases_free = _sig("curdle_ct_bases_free", None, _vp)
+_ct_bases_size = _sig("curdle_ct_bases_size", C.c_size_t, _vp)
+_ct_bases_chunk_bits = _sig("curdle_ct_bases_chunk_bits", C.c_uint, _vp)
+_ct_bases_export = _sig("curdle_ct_bases_export", C.c_int, _vp, C.c_uint, _vp)
+_msm_g1_ct_bases = _sig("curdle_msm_g1_ct_bases", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_uint, _vp)
+_msm_g1_ct_bases_device = _sig("curdle_msm_g1_ct_bases_device", C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_uint, _vp, _vp)
+_msm_g1_ct_bases_batch = _sig("curdle_msm_g1_ct_bases_batch", C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_uint, _vp)
+_msm_g1_ct_bases_batch_device = _sig("curdle_msm_g1_ct_bases_batch_device", C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_uint,
+                                     _vp, _vp)
+_stat_msm_ct_bases = _sig("curdle_stat_msm_ct_bases", C.c_int, C.POINTER(C.c_ulonglong))
+
+
+class CtBases:
+    """A resident PUBLIC base set for the constant-time MSM (curdle_ct_bases): the table of the points 2^(c j) P_i, so
+    that a lane walks c bits of a secret scalar instead of scalar_bits.  `points` is uint64[n, 12], or with device=True
+    a raw device pointer and n; chunk_bits is 8, 16, 32, 64 or 0 for the library's choice.  rows (a host array of
+    public indices into the set, or None for 0, 1, ..., n - 1) and offsets always stay host arrays."""
+
+    def __init__(self, points, chunk_bits: int = 0, n: int = None, device: bool = False, stream: int = 0):
+        self._h = C.c_void_p()
+        if device:
+            _check(_ct_bases_create_device(points or None, int(n), int(chunk_bits), C.byref(self._h), stream or None))
+        else:
+            pts = _as_u64(points, 12)
+            _check(_ct_bases_create(_ptr(pts), pts.shape[0] if pts.size else 0, int(chunk_bits), C.byref(self._h)))
+        self.n = int(_ct_bases_size(self._h))
+        self.chunk_bits = int(_ct_bases_chunk_bits(self._h))
+        self.chunks = (255 + self.chunk_bits - 1) // self.chunk_bits
+
+    def free(self):
+        if self._h:
+            _ct_bases_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:       # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def export(self, chunk: int) -> np.ndarray:
+        """Row `chunk` of the table: 2^(chunk_bits chunk) P_i as uint64[n, 12]."""
+        out = np.zeros((self.n, 12), dtype=np.uint64)
+        _check(_ct_bases_export(self._h, int(chunk), _ptr(out)))
+        return out
+
+    @staticmethod
+    def _rows(rows):
+        return None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+
+    def msm(self, scalars, rows=None, scalar_bits: int = 255) -> np.ndarray:
+        """sum_p scalars[p] * P_rows[p] -> uint64[18], bit for bit msm_g1_ct on the same pairs."""
+        sc, r = _as_u64(scalars, 4), self._rows(rows)
+        n = sc.shape[0] if sc.size else 0
+        if r is not None and len(r) != n:
+            raise CurdleError(EINVAL, "len(rows) != len(scalars)")
+        out = np.zeros(18, dtype=np.uint64)
+        _check(_msm_g1_ct_bases(self._h, None if r is None else _ptr(r), _ptr(sc), n, int(scalar_bits), _ptr(out)))
+        return out
+
+    def msm_device(self, d_scalars: int, n: int, rows=None, scalar_bits: int = 255, stream: int = 0) -> np.ndarray:
+        """msm on device-resident scalars (a raw device pointer, a multiple of 16)."""
+        r = self._rows(rows)
+        if r is not None and len(r) != n:
+            raise CurdleError(EINVAL, "len(rows) != n")
+        out = np.zeros(18, dtype=np.uint64)
+        _check(_msm_g1_ct_bases_device(self._h, None if r is None else _ptr(r), d_scalars or None, n, int(scalar_bits), _ptr(out),
+                                       stream or None))
+        return out
+
+    def msm_batch(self, scalars, offsets, rows=None, scalar_bits: int = 255) -> np.ndarray:
+        """k MSMs in one walk: MSM j covers the pairs [offsets[j], offsets[j + 1]) -> uint64[k, 18]."""
+        sc, r = _as_u64(scalars, 4), self._rows(rows)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)  # size_t
+        k = len(offs) - 1
+        out = np.zeros((k, 18), dtype=np.uint64)
+        _check(_msm_g1_ct_bases_batch(self._h, None if r is None else _ptr(r), _ptr(sc), _ptr(offs), k, int(scalar_bits),
+                                      _ptr(out)))
+        return out
+
+    def msm_batch_device(self, d_scalars: int, offsets, rows=None, scalar_bits: int = 255, stream: int = 0) -> np.ndarray:
+        r = self._rows(rows)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        k = len(offs) - 1
+        out = np.zeros((k, 18), dtype=np.uint64)
+        _check(_msm_g1_ct_bases_batch_device(self._h, None if r is None else _ptr(r), d_scalars or None, _ptr(offs), k,
+                                             int(scalar_bits), _ptr(out), stream or None))
+        return out
+
+
+def stat_msm_ct_bases() -> dict:
+    """Constant-time base tables built on a device, MSM calls over them, (pair, chunk) lanes walked and MSMs finished
+    since the library was loaded."""
+    out = (C.c_ulonglong * 4)()
+    _check(_stat_msm_ct_bases(out))
+    return {"tables": int(out[0]), "calls": int(out[1]), "lanes": int(out[2]), "msms": int(out[3])}
 
 
 def msm_g1_device_submit(d_points: int, d_scalars: int, n: int, window_bits: int = 0, win_begin: int = 0,

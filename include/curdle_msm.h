@@ -1090,6 +1090,74 @@ int curdle_msm_g1_ct_batch_device(const void* d_points, const void* d_scalars, c
 int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t k, const uint64_t* scalars, size_t n,
                            unsigned scalar_bits, uint64_t* out_jac);
 int curdle_stat_msm_ct_batch(unsigned long long out[3]);   /* batched calls | MSMs in them | level launches (k_g1_sum_ct_seg) */
+/* -------------------------------------------------------------------------
+ * The constant-time MSM over a RESIDENT, PUBLIC base set, the walk SPLIT INTO CHUNKS.  curdle_msm_g1_ct costs one lane's
+ * chain of scalar_bits doublings and additions however few pairs it has.  Where the bases are public and stay -- a CRS,
+ * the instance vectors of a proof -- the chain can be cut: k = sum_j 2^(c j) d_j with c-bit digits d_j, so
+ * k P = sum_j d_j (2^(c j) P), and the points 2^(c j) P are public arithmetic on public bases, made once and kept.
+ * curdle_ct_bases is the handle of that table; in the MSM over it (csrc/msm_ct_bases_kernels.hip) lane (pair, j) walks
+ * only the c bits of d_j over its own table point, by the walk of curdle_msm_g1_ct, and the terms go through the same
+ * fold (the complete addition: the terms of one pair are multiples of one another and can be equal or opposite) and
+ * the same finish.  The chain is c steps instead of scalar_bits.
+ *
+ * THE HANDLE.  points: n gnark G1Affine records, (0, 0) = infinity.  PRECONDITIONS are curdle_msm_g1_ct's: the bases lie in
+ * the prime-order subgroup and are NOT checked (curdle_g1_check_batch checks points for a caller who needs it).
+ * chunk_bits is 8, 16, 32 or 64; 0 is the library's choice, 16.  The table is C = ceil(255 / chunk_bits) rows of n gnark
+ * G1Affine records: row j holds 2^(chunk_bits j) P_i at table[j n + i], row 0 is the input, infinity stays the all-zero
+ * record in every row.  It is built on the device (k_ct_bases_shift: one lane per base, chunk_bits doublings between
+ * stores; k_g1_normalize writes the rows) and the handle keeps a host copy of the rows.  Limit: n C <= 65,536.  n = 0
+ * gives an empty handle without a device.  Refusals happen before any device work, in this order: a null argument,
+ * chunk_bits, n C, and (the _device form) a device pointer that is not a multiple of 16; each is CURDLE_EINVAL with
+ * *out null; without a device the call returns CURDLE_ENODEV.  The _device form reads d_points behind what the caller
+ * queued on `stream` (as in curdle_msm_g1_device) and keeps nothing of the caller's array.
+ * Lifetime is curdle_fbase's and curdle_dbases': the handle stays usable until it is freed; its device copy is made on
+ * another context at first use there and re-made after curdle_shutdown, both from the host copy; a free during a call
+ * is deferred to that call's end.  THE TABLE IS PUBLIC: nothing of it is wiped, on the device or on the host.
+ * curdle_ct_bases_export copies row `chunk` (n records) to the host, for callers who audit the table; chunk >= C is
+ * CURDLE_EINVAL.
+ *
+ * THE MSM.  out = sum_p scalars[p] * P_rows[p]: the 18 words of curdle_msm_g1_ct and of curdle_msm_g1 on the same pairs,
+ * bit for bit; the batch gives result j per MSM j over the pairs [offsets[j], offsets[j+1]), an empty MSM the infinity
+ * encoding.  rows is always a HOST array of n PUBLIC indices into the base set (for the batch n is offsets[k]); null
+ * means 0, 1, ..., n - 1, which requires n <= the set's size; indices may repeat; an entry at or above the size is
+ * refused on the host before any device work.  The library stages rows itself: it is public and is not wiped.
+ * scalar_bits is ONE public bound for the call, 1...255: Cb = ceil(scalar_bits / chunk_bits) chunks are walked and the
+ * top chunk takes scalar_bits - chunk_bits (Cb - 1) steps.  A scalar at or above 2^scalar_bits ANYWHERE in the call
+ * fails the whole call with CURDLE_EINVAL and EVERY word of out_jac stays untouched: one status word, as in
+ * curdle_msm_g1_ct, and this verdict is the only thing about the scalars the call reveals.
+ * Limits: n Cb <= 65,536 terms per call (one pass), k <= 4,096.  n = 0 returns the infinity encoding and k = 0 writes
+ * nothing, both without a device, as does a batch whose MSMs are all empty.  Refusals happen before any device work, in
+ * this order: a null argument (rows may be null; the scalars when n > 0; for the batch offsets always, out_jac and the
+ * scalars when k > 0), scalar_bits, k, offsets that decrease, the term total, a row index out of range, and (the
+ * _device forms) a device pointer that is not a multiple of 16.  `stream` is as in curdle_msm_g1_device.
+ * One MSM slot is held for the call.  The host forms' scalar staging and its device copy, and in every form the term
+ * workspace, are overwritten on the stream that used them on every way out, as in curdle_msm_g1_ct.  The call's only
+ * device-to-host copy is the results and the status word: one block of 144 k + 4 bytes.
+ * WHAT THE FLAG PROMISES, WHAT IT DOES NOT PROMISE and what is OUTSIDE THE PROMISE are curdle_msm_g1_ct's, word for word.
+ * The instruction stream and the address stream also depend on rows, on chunk_bits and on which table points are
+ * infinity, all of which are public.  It is not a default: nothing in the library routes to these calls yet.
+ * curdle_stat_msm_ct_bases: out[0] tables built on a device, out[1] calls, out[2] (pair, chunk) lanes walked by
+ * k_msm_ct_walk_rows, out[3] MSMs finished that are not empty; completed calls that ran on a device only.  These calls
+ * do not move curdle_stat_msm_ct (k_msm_ct_walk does not run); a batched one moves curdle_stat_msm_ct_batch by
+ * (1, k, the level launches over count Cb terms per MSM).
+ * Cost: profiles/r33_msm_ct_bases.json and DESIGN.md section 0, round 33.
+ * ------------------------------------------------------------------------- */
+typedef struct curdle_ct_bases curdle_ct_bases;
+int curdle_ct_bases_create(const uint64_t* points, size_t n, unsigned chunk_bits, curdle_ct_bases** out);
+int curdle_ct_bases_create_device(const void* d_points, size_t n, unsigned chunk_bits, curdle_ct_bases** out, void* stream);
+void curdle_ct_bases_free(curdle_ct_bases* b);
+size_t curdle_ct_bases_size(const curdle_ct_bases* b);          /* n */
+unsigned curdle_ct_bases_chunk_bits(const curdle_ct_bases* b);  /* c */
+int curdle_ct_bases_export(const curdle_ct_bases* b, unsigned chunk, uint64_t* rows_out /* n x 12 */);
+int curdle_msm_g1_ct_bases(const curdle_ct_bases* b, const uint32_t* rows, const uint64_t* scalars, size_t n,
+                           unsigned scalar_bits, uint64_t out_jac[18]);
+int curdle_msm_g1_ct_bases_device(const curdle_ct_bases* b, const uint32_t* rows, const void* d_scalars, size_t n,
+                                  unsigned scalar_bits, uint64_t out_jac[18], void* stream);
+int curdle_msm_g1_ct_bases_batch(const curdle_ct_bases* b, const uint32_t* rows, const uint64_t* scalars,
+                                 const size_t* offsets, size_t k, unsigned scalar_bits, uint64_t* out_jac);
+int curdle_msm_g1_ct_bases_batch_device(const curdle_ct_bases* b, const uint32_t* rows, const void* d_scalars,
+                                        const size_t* offsets, size_t k, unsigned scalar_bits, uint64_t* out_jac, void* stream);
+int curdle_stat_msm_ct_bases(unsigned long long out[4]);  /* tables built | calls | (pair, chunk) lanes walked | MSMs finished */
 /* curdle_prove with a flags word.  flags = 0 IS curdle_prove.  A bit that is not defined here: CURDLE_EINVAL before
  * anything else is looked at, with proof_out and *proof_len untouched.
  * CURDLE_PROVE_MSM_CONSTANT_TIME: every MSM of the proof -- the prover funnels them through three functions,
