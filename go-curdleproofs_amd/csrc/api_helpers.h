@@ -18,9 +18,7 @@ int generator_table_acquire(Ctx& cx, void** d_table);
 void generator_table_release();
 void count_fbase_ct_pass(size_t n);
 void count_g1_mul_ct_pass(size_t n);
-// What the constant-time MSM over a resident base set (msm_ct_bases_api.hip) borrows from msm_ct_api.hip: the counters
-// of ONE completed batched call that ran the segmented sum (curdle_stat_msm_ct_batch: calls, MSMs, level launches).
-void count_msm_ct_batch(size_t msms, unsigned levels);
+// (What the two constant-time MSM families share has a header of its own, msm_ct_call.h.)
 
 // A free slot, marked as acquire_slot marks it, or -1: never waits, brings no context up and leaves the error text alone.
 int try_acquire_slot(Ctx& cx);

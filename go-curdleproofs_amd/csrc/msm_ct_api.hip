@@ -1,46 +1,135 @@
 // C ABI of the constant-time MSM (msm_ct_kernels.hip): curdle_msm_g1_ct / _device, curdle_stat_msm_ct, the batched forms
-// (curdle_msm_g1_ct_batch / _batch_device / _multi, curdle_stat_msm_ct_batch: further down, with their own notes) and the
-// flagged shuffle step (curdle_shuffle_permute_commit_ex), its first user; that call's host part -- the range check of the
-// permutation and the draw of the blinders -- is in host/proto_api.cpp.
+// (curdle_msm_g1_ct_batch / _batch_device / _multi, curdle_stat_msm_ct_batch), the oblivious gathers and the flagged
+// shuffle step (curdle_shuffle_permute_commit_ex), the MSM's first user; that call's host part -- the range check of the
+// permutation and the draw of the blinders -- is in host/proto_api.cpp.  The unit also holds the definitions of
+// msm_ct_call.h: what these calls share with the MSM over a resident base set (msm_ct_bases_api.hip).
 //
 // A call takes ONE MSM slot, held by a SlotHold (api_helpers.h), for its stream and its buffers.  The terms k_i P_i live
-// in the slot's `partials` buffer, 224 bytes each, and never leave the device: the ONLY device-to-host copy of an MSM is
-// the 160-byte block k_msm_ct_finish wrote (the 18 words of the result and the violation word).  The term workspace is
+// in the slot's `partials` buffer, 224 bytes each, and never leave the device.  The host and the resident form of a call
+// are ONE function with a `resident` flag: single() and batch() behind the extern "C" forwards.  The term workspace is
 // on the call's WipeList in both forms; the host form's scalars go through the slot's pinned staging and a device
-// buffer, both on the list too.  Everything runs on one stream, the caller's if it gave one.  No stream is made here and
-// nothing is allocated once the slot's buffers have grown.
-#include "api_helpers.h"
+// buffer, both on the list too (stage_scalars); the resident form reads the caller's arrays where they are and notes
+// nothing of them.  Everything runs on one stream, the caller's if it gave one.  No stream is made here and nothing is
+// allocated once the slot's buffers have grown.
+//
+// The single call and the shuffle step: k_msm_ct_walk, launch_msm_ct_sum, and the ONLY device-to-host copy of the MSM
+// is the 160-byte block k_msm_ct_finish wrote (the 18 words of the result and the violation word).
+//
+// The batched forms: k MSMs (curdle_msm_g1_ct_batch / _device), or one scalar vector against k base sets
+// (curdle_msm_g1_ct_multi), in ONE launch of k_msm_ct_walk over the concatenated pairs, the segmented sum
+// (k_g1_sum_ct_seg per level, k_msm_ct_finish_seg) and ONE copy back of 144 k + 4 bytes: the k results and the violation
+// word.  That is seg_walk_sum_fetch below, the body the resident-base form runs too with its own walk; the layout of
+// the slot's small buffer and of the second pinned staging is stated at its declaration.  The (begin, count) table is
+// made of `offsets`: public.
+#include "msm_ct_call.h"
 
 #include <algorithm>
 
 namespace {
-constexpr size_t kMsmCtMax = 65536;       // one pass: 256 blocks
 constexpr size_t kShuffleCtMax = 4096;    // the oblivious gather is quadratic
 constexpr size_t kOutBytes = 160;         // 36 words of result, the violation word, three words of padding
 constexpr size_t kStatusOffset = 192;     // the walks' status word, in the same small buffer behind the block
 
 // pairs walked | walk launches | sums finished; completed calls only
 std::atomic<unsigned long long> g_msm_ct_stat[3];
+// batched calls | MSMs in them | level launches (k_g1_sum_ct_seg); completed calls that ran on a device only
+std::atomic<unsigned long long> g_msm_ct_batch_stat[3];
 
-void count_msm_ct(size_t pairs, unsigned walks) {
+void count_msm_ct(size_t pairs, unsigned walks, size_t sums = 1) {
   g_msm_ct_stat[0].fetch_add(pairs, std::memory_order_relaxed);
   g_msm_ct_stat[1].fetch_add(walks, std::memory_order_relaxed);
-  g_msm_ct_stat[2].fetch_add(1, std::memory_order_relaxed);
+  g_msm_ct_stat[2].fetch_add(sums, std::memory_order_relaxed);
 }
 
+size_t round16(size_t v) { return (v + 15) / 16 * 16; }
+}  // namespace
+
+namespace curdle_api {
 int check_scalar_bits(unsigned bits) {
   if (bits < 1 || bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", bits);
   return CURDLE_OK;
 }
 
-int check_args(const void* points, const void* scalars, size_t n, unsigned bits, const void* out) {
-  if (!out || (n && (!points || !scalars))) return fail(CURDLE_EINVAL, "null argument");
+int refuse_scalar_range() { return fail(CURDLE_EINVAL, "a scalar is not below 2^scalar_bits"); }
+
+void count_msm_ct_batch(size_t msms, unsigned levels) {
+  g_msm_ct_batch_stat[0].fetch_add(1, std::memory_order_relaxed);
+  g_msm_ct_batch_stat[1].fetch_add(msms, std::memory_order_relaxed);
+  g_msm_ct_batch_stat[2].fetch_add(levels, std::memory_order_relaxed);
+}
+
+int seg_shape(const size_t* offsets, size_t k, unsigned bits, unsigned stride, TotalText text, SegShape* sh) {
   if (int rc = check_scalar_bits(bits)) return rc;
-  if (n > kMsmCtMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 65,536 pairs", n);
+  if (k > kMsmCtMaxBatch) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
+  for (size_t j = 0; j < k; j++)
+    if (offsets[j + 1] < offsets[j]) return fail(CURDLE_EINVAL, "offsets decrease at %zu", j);
+  sh->k = k;
+  sh->stride = stride;
+  sh->lo = k ? offsets[0] : 0;
+  sh->total = k ? offsets[k] - offsets[0] : 0;
+  if (sh->total > kMsmCtMaxTerms / stride)
+    return text == TotalText::kPairs
+               ? fail(CURDLE_EINVAL, "%zu pairs in all exceed the supported 65,536 pairs", sh->total)
+               : fail(CURDLE_EINVAL, "n Cb = %zu x %u exceeds the supported 65,536 terms of one call", sh->total, stride);
+  sh->seg.resize(2 * k);
+  sh->counts.resize(k);
+  for (size_t j = 0; j < k; j++) {
+    sh->seg[2 * j] = (uint32_t)((offsets[j] - sh->lo) * stride);
+    sh->seg[2 * j + 1] = sh->counts[j] = (uint32_t)((offsets[j + 1] - offsets[j]) * stride);
+    sh->nonempty += offsets[j + 1] != offsets[j];
+  }
   return CURDLE_OK;
 }
 
-// the slot's small buffer: zeroes the status word on st
+int note_terms(Slot& S, WipeList& W, size_t terms) {
+  if (int r = ensure(S.partials, terms * kMsmCtTermBytes)) return r;
+  W.note_device(S.partials.p, terms * kMsmCtTermBytes);
+  return CURDLE_OK;
+}
+
+int stage_scalars(Slot& S, WipeList& W, const void* scalars, size_t n, size_t copies, size_t behind, hipStream_t st) {
+  const size_t run = n * 32, bytes = run * copies;
+  int r;
+  if ((r = ensure(S.scalars, bytes))) return r;
+  if ((r = ensure_pinned(S, 0, bytes + behind))) return r;
+  W.note_device(S.scalars.p, bytes);
+  W.note_host(S.h_stage[0], bytes);
+  for (size_t j = 0; j < copies; j++) memcpy(static_cast<uint8_t*>(S.h_stage[0]) + j * run, scalars, run);
+  HIP_TRY(hipMemcpyAsync(S.scalars.p, S.h_stage[0], bytes, hipMemcpyHostToDevice, st));
+  return CURDLE_OK;
+}
+
+int seg_walk_sum_fetch(SlotHold& H, const SegShape& sh, size_t extra_bytes, uint64_t* out_jac, unsigned* levels, const SegWalk& walk) {
+  Slot& S = H.slot();
+  const hipStream_t st = H.stream();
+  const size_t k = sh.k, back = 144 * k + 4, status_off = round16(back), table_bytes = 8 * k;
+  const size_t extra_off = round16(status_off + table_bytes);
+  int r;
+  if ((r = ensure(S.results, status_off + 16))) return r;
+  if ((r = ensure(S.offsets, table_bytes))) return r;
+  if ((r = ensure_pinned(S, 1, extra_off + extra_bytes))) return r;  // what comes back | the table | the family's: public
+  uint8_t* h_block = static_cast<uint8_t*>(S.h_stage[1]);
+  uint8_t* d_res = static_cast<uint8_t*>(S.results.p);
+  uint32_t* d_status = reinterpret_cast<uint32_t*>(d_res + status_off);
+  memcpy(h_block + status_off, sh.seg.data(), table_bytes);
+  HIP_TRY(hipMemsetAsync(d_status, 0, 16, st));
+  HIP_TRY(hipMemcpyAsync(S.offsets.p, h_block + status_off, table_bytes, hipMemcpyHostToDevice, st));
+  if ((r = walk(d_status, h_block + extra_off, st))) return r;
+  uint32_t lv = 0;
+  HIP_TRY(launch_msm_ct_sum_seg(S.partials.p, S.offsets.p, sh.counts.data(), (uint32_t)k, d_status, d_res, &lv, st));
+  HIP_TRY(hipMemcpyAsync(h_block, d_res, back, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint32_t verdict;
+  memcpy(&verdict, h_block + 144 * k, 4);
+  if (verdict) return refuse_scalar_range();
+  memcpy(out_jac, h_block, 144 * k);
+  *levels = lv;
+  return CURDLE_OK;
+}
+}  // namespace curdle_api
+
+namespace {
+// the slot's small buffer in the single call's layout: zeroes the status word on st
 int prepare_out(Slot& S, hipStream_t st) {
   if (int r = ensure(S.results, 256)) return r;
   HIP_TRY(hipMemsetAsync(static_cast<uint8_t*>(S.results.p) + kStatusOffset, 0, 16, st));
@@ -54,29 +143,24 @@ int sum_and_fetch(Slot& S, size_t m, void* h_out, uint64_t out_jac[18], hipStrea
   HIP_TRY(launch_msm_ct_sum(S.partials.p, (uint32_t)m, status_word(S), S.results.p, st));
   HIP_TRY(hipMemcpyAsync(h_out, S.results.p, kOutBytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (static_cast<const uint32_t*>(h_out)[36]) return fail(CURDLE_EINVAL, "a scalar is not below 2^scalar_bits");
+  if (static_cast<const uint32_t*>(h_out)[36]) return refuse_scalar_range();
   memcpy(out_jac, h_out, 144);
   return CURDLE_OK;
 }
 
-// The host forms' n pairs on their way to the device: the slot's buffers, the notes on the WipeList (the scalars' two
-// copies and the term workspace), `fill` writing the scalars (n records of 32 bytes) and then the points (96 bytes each)
-// into the pinned staging it is handed, and the two uploads on st.  Behind it S.scalars and S.points hold the pairs.
+// The host forms' pairs on their way to the device: `copies` runs of the n scalars (stage_scalars) and, behind them in
+// the same pinned staging, the n x copies points (96 bytes each) that `fill` writes; the term workspace; the two uploads
+// on st.  Behind it S.scalars and S.points hold the pairs.
 template <class Fill>
-int stage_pairs(Slot& S, WipeList& W, size_t n, hipStream_t st, Fill&& fill) {
+int stage_pairs(Slot& S, WipeList& W, const void* scalars, size_t n, size_t copies, hipStream_t st, Fill&& fill) {
+  const size_t m = n * copies;
   int r;
-  if ((r = ensure(S.points, n * 96))) return r;
-  if ((r = ensure(S.scalars, n * 32))) return r;
-  if ((r = ensure(S.partials, n * kMsmCtTermBytes))) return r;
-  if ((r = ensure_pinned(S, 0, n * 32 + n * 96))) return r;  // scalars | points
-  W.note_device(S.scalars.p, n * 32);
-  W.note_device(S.partials.p, n * kMsmCtTermBytes);
-  W.note_host(S.h_stage[0], n * 32);
-  uint8_t* h_sc = static_cast<uint8_t*>(S.h_stage[0]);
-  uint8_t* h_pt = h_sc + n * 32;
-  fill(h_sc, h_pt);
-  HIP_TRY(hipMemcpyAsync(S.scalars.p, h_sc, n * 32, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(S.points.p, h_pt, n * 96, hipMemcpyHostToDevice, st));
+  if ((r = ensure(S.points, m * 96))) return r;
+  if ((r = stage_scalars(S, W, scalars, n, copies, m * 96, st))) return r;
+  if ((r = note_terms(S, W, m))) return r;
+  uint8_t* h_pt = static_cast<uint8_t*>(S.h_stage[0]) + m * 32;
+  fill(h_pt);
+  HIP_TRY(hipMemcpyAsync(S.points.p, h_pt, m * 96, hipMemcpyHostToDevice, st));
   return CURDLE_OK;
 }
 
@@ -85,203 +169,112 @@ unsigned bit_length(size_t v) {
   for (; v; v >>= 1) b++;
   return b;
 }
-}  // namespace
 
-extern "C" int curdle_msm_g1_ct(const uint64_t* points, const uint64_t* scalars, size_t n, unsigned scalar_bits,
-                                uint64_t out_jac[18]) {
-  if (int rc = check_args(points, scalars, n, scalar_bits, out_jac)) return rc;
+// curdle_msm_g1_ct (resident false: the pairs are staged and the scalars' copies wiped) and _device (the caller's arrays
+// are read where they are: nothing of them is copied).
+int single(const void* points, const void* scalars, bool resident, size_t n, unsigned bits, uint64_t out_jac[18], void* stream) {
+  if (!out_jac || (n && (!points || !scalars))) return fail(CURDLE_EINVAL, "null argument");
+  if (int rc = check_scalar_bits(bits)) return rc;
+  if (n > kMsmCtMaxTerms) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 65,536 pairs", n);
   if (n == 0) {
     set_out_infinity(out_jac);
     return CURDLE_OK;
   }
-  SlotHold H(cur(), true, nullptr);
-  WipeList W(H.stream());
-  H.wipe_on_exit(&W, "constant-time MSM: clearing the scalars and the terms");
-  return H.run([&]() -> int {
-    Slot& S = H.slot();
-    const hipStream_t st = H.stream();
-    int r;
-    if ((r = stage_pairs(S, W, n, st, [&](uint8_t* h_sc, uint8_t* h_pt) {
-          memcpy(h_sc, scalars, n * 32);
-          memcpy(h_pt, points, n * 96);
-        })))
-      return r;
-    if ((r = ensure_pinned(S, 1, kOutBytes))) return r;
-    if ((r = prepare_out(S, st))) return r;
-    HIP_TRY(launch_msm_ct_walk(S.points.p, S.scalars.p, kMsmCtScalarFr, scalar_bits, (uint32_t)n, S.partials.p, status_word(S), st));
-    if ((r = sum_and_fetch(S, n, S.h_stage[1], out_jac, st))) return r;
-    count_msm_ct(n, 1);
-    return CURDLE_OK;
-  });
-}
-
-extern "C" int curdle_msm_g1_ct_device(const void* d_points, const void* d_scalars, size_t n, unsigned scalar_bits,
-                                       uint64_t out_jac[18], void* stream) {
-  if (int rc = check_args(d_points, d_scalars, n, scalar_bits, out_jac)) return rc;
-  if (n == 0) {
-    set_out_infinity(out_jac);
-    return CURDLE_OK;
-  }
-  if (!aligned16(d_points) || !aligned16(d_scalars)) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
+  if (resident && (!aligned16(points) || !aligned16(scalars))) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
   SlotHold H(cur(), true, stream);
   WipeList W(H.stream());
-  H.wipe_on_exit(&W, "constant-time MSM: clearing the terms");
+  H.wipe_on_exit(&W, resident ? "constant-time MSM: clearing the terms" : "constant-time MSM: clearing the scalars and the terms");
   return H.run([&]() -> int {
     Slot& S = H.slot();
     const hipStream_t st = H.stream();
     int r;
-    if ((r = ensure(S.partials, n * kMsmCtTermBytes))) return r;
+    if (resident) {
+      if ((r = note_terms(S, W, n))) return r;
+    } else {
+      if ((r = stage_pairs(S, W, scalars, n, 1, st, [&](uint8_t* h_pt) { memcpy(h_pt, points, n * 96); }))) return r;
+      points = S.points.p;
+      scalars = S.scalars.p;
+    }
     if ((r = ensure_pinned(S, 1, kOutBytes))) return r;
-    W.note_device(S.partials.p, n * kMsmCtTermBytes);
     if ((r = prepare_out(S, st))) return r;
-    // the caller's scalars are read where they are: nothing of them is copied
-    HIP_TRY(launch_msm_ct_walk(d_points, d_scalars, kMsmCtScalarFr, scalar_bits, (uint32_t)n, S.partials.p, status_word(S), st));
+    HIP_TRY(launch_msm_ct_walk(points, scalars, kMsmCtScalarFr, bits, (uint32_t)n, S.partials.p, status_word(S), st));
     if ((r = sum_and_fetch(S, n, S.h_stage[1], out_jac, st))) return r;
     count_msm_ct(n, 1);
     return CURDLE_OK;
   });
 }
 
-extern "C" int curdle_stat_msm_ct(unsigned long long out[3]) { return read_stats(out, g_msm_ct_stat, 3); }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The batched forms: k MSMs (curdle_msm_g1_ct_batch / _device), or one scalar vector against k base sets
-// (curdle_msm_g1_ct_multi), in ONE launch of k_msm_ct_walk over the concatenated pairs, the segmented sum
-// (k_g1_sum_ct_seg per level, k_msm_ct_finish_seg) and ONE copy back of 144 k + 4 bytes: the k results and the violation
-// word.  The slot's small buffer holds, in this order, the results, the word the finish kernel copies the violation word
-// to, and -- from the next multiple of 16 -- the walk's status word; the table of (begin, count) goes through the second
-// pinned staging (behind the block that comes back) into the slot's `offsets` buffer.  It is made of `offsets`: public.
-// ---------------------------------------------------------------------------------------------------------------------
-namespace {
-constexpr size_t kMsmCtBatchMax = 4096;  // MSMs of one call
-
-// batched calls | MSMs in them | level launches (k_g1_sum_ct_seg); completed calls that ran on a device only
-std::atomic<unsigned long long> g_msm_ct_batch_stat[3];
-
-struct BatchShape {
-  size_t k = 0, lo = 0, total = 0;
-  std::vector<uint32_t> seg;     // (begin, count) per MSM, begin relative to the call's first pair
-  std::vector<uint32_t> counts;  // count per MSM
-  size_t nonempty = 0;
-};
-
-// What the batch refuses after the null arguments: scalar_bits, k, offsets that decrease, the total.
-int batch_shape(const size_t* offsets, size_t k, unsigned bits, BatchShape* sh) {
-  if (int rc = check_scalar_bits(bits)) return rc;
-  if (k > kMsmCtBatchMax) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
-  for (size_t j = 0; j < k; j++)
-    if (offsets[j + 1] < offsets[j]) return fail(CURDLE_EINVAL, "offsets decrease at %zu", j);
-  sh->k = k;
-  sh->lo = k ? offsets[0] : 0;
-  sh->total = k ? offsets[k] - offsets[0] : 0;
-  if (sh->total > kMsmCtMax) return fail(CURDLE_EINVAL, "%zu pairs in all exceed the supported 65,536 pairs", sh->total);
-  sh->seg.resize(2 * k);
-  sh->counts.resize(k);
-  for (size_t j = 0; j < k; j++) {
-    sh->seg[2 * j] = (uint32_t)(offsets[j] - sh->lo);
-    sh->seg[2 * j + 1] = sh->counts[j] = (uint32_t)(offsets[j + 1] - offsets[j]);
-    sh->nonempty += offsets[j + 1] != offsets[j];
-  }
-  return CURDLE_OK;
-}
-
-}  // namespace
-namespace curdle_api {
-void count_msm_ct_batch(size_t msms, unsigned levels) {
-  g_msm_ct_batch_stat[0].fetch_add(1, std::memory_order_relaxed);
-  g_msm_ct_batch_stat[1].fetch_add(msms, std::memory_order_relaxed);
-  g_msm_ct_batch_stat[2].fetch_add(levels, std::memory_order_relaxed);
-}
-}  // namespace curdle_api
-namespace {
-size_t batch_out_bytes(size_t k) { return 144 * k + 4; }                         // what comes back
-size_t batch_status_offset(size_t k) { return (144 * k + 4 + 15) / 16 * 16; }    // the walk's status word
-
-// On the call's stream, behind the scalars and the points: the status word, the table, the walk, the sum, the copy, the
-// wait, the verdict.  h_block: pinned, batch_out_bytes(k) and the table behind it (from the next multiple of 16).
-int batch_walk_sum_fetch(Slot& S, const BatchShape& sh, const void* d_points, const void* d_scalars, unsigned bits,
-                         uint64_t* out_jac, hipStream_t st) {
-  const size_t k = sh.k, status_off = batch_status_offset(k), table_bytes = 8 * k;
-  int r;
-  if ((r = ensure(S.results, status_off + 16))) return r;
-  if ((r = ensure(S.offsets, table_bytes))) return r;
-  if ((r = ensure_pinned(S, 1, status_off + table_bytes))) return r;
-  uint8_t* h_block = static_cast<uint8_t*>(S.h_stage[1]);
-  uint8_t* d_res = static_cast<uint8_t*>(S.results.p);
-  uint32_t* d_status = reinterpret_cast<uint32_t*>(d_res + status_off);
-  memcpy(h_block + status_off, sh.seg.data(), table_bytes);
-  HIP_TRY(hipMemsetAsync(d_status, 0, 16, st));
-  HIP_TRY(hipMemcpyAsync(S.offsets.p, h_block + status_off, table_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(launch_msm_ct_walk(d_points, d_scalars, kMsmCtScalarFr, bits, (uint32_t)sh.total, S.partials.p, d_status, st));
-  uint32_t levels = 0;
-  HIP_TRY(launch_msm_ct_sum_seg(S.partials.p, S.offsets.p, sh.counts.data(), (uint32_t)k, d_status, d_res, &levels, st));
-  HIP_TRY(hipMemcpyAsync(h_block, d_res, batch_out_bytes(k), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  uint32_t verdict;
-  memcpy(&verdict, h_block + 144 * k, 4);
-  if (verdict) return fail(CURDLE_EINVAL, "a scalar is not below 2^scalar_bits");
-  memcpy(out_jac, h_block, 144 * k);
-  g_msm_ct_stat[0].fetch_add(sh.total, std::memory_order_relaxed);
-  g_msm_ct_stat[1].fetch_add(1, std::memory_order_relaxed);
-  g_msm_ct_stat[2].fetch_add(sh.nonempty, std::memory_order_relaxed);
-  count_msm_ct_batch(k, levels);
-  return CURDLE_OK;
-}
-
-// The host forms behind their checks: `fill` is stage_pairs' over the sh.total pairs.
-template <class Fill>
-int batch_from_host(const BatchShape& sh, unsigned bits, uint64_t* out_jac, const char* what, Fill&& fill) {
-  SlotHold H(cur(), true, nullptr);
+// One batched call behind its checks, sh.total > 0: the slot, the wipe, `stage` (a host form's stage_pairs, a resident
+// form's note_terms), the shared body with ONE k_msm_ct_walk over all pairs, the counters.  d_points, d_scalars: the
+// call's first pair in the caller's device arrays, or null for what `stage` left in S.points and S.scalars.
+template <class Stage>
+int batch_run(const SegShape& sh, unsigned bits, uint64_t* out_jac, const char* what, void* stream, const void* d_points,
+              const void* d_scalars, Stage&& stage) {
+  SlotHold H(cur(), true, stream);
   WipeList W(H.stream());
   H.wipe_on_exit(&W, what);
   return H.run([&]() -> int {
     Slot& S = H.slot();
-    const hipStream_t st = H.stream();
-    if (int r = stage_pairs(S, W, sh.total, st, fill)) return r;
-    return batch_walk_sum_fetch(S, sh, S.points.p, S.scalars.p, bits, out_jac, st);
+    int r;
+    if ((r = stage(S, W, H.stream()))) return r;
+    if (!d_points) d_points = S.points.p, d_scalars = S.scalars.p;
+    unsigned levels = 0;
+    if ((r = seg_walk_sum_fetch(H, sh, 0, out_jac, &levels, [&](uint32_t* d_status, uint8_t*, hipStream_t st) -> int {
+          HIP_TRY(launch_msm_ct_walk(d_points, d_scalars, kMsmCtScalarFr, bits, (uint32_t)sh.total, S.partials.p, d_status, st));
+          return CURDLE_OK;
+        })))
+      return r;
+    count_msm_ct(sh.total, 1, sh.nonempty);
+    count_msm_ct_batch(sh.k, levels);
+    return CURDLE_OK;
   });
 }
-}  // namespace
 
-extern "C" int curdle_msm_g1_ct_batch(const uint64_t* points, const uint64_t* scalars, const size_t* offsets, size_t k,
-                                      unsigned scalar_bits, uint64_t* out_jac) {
+// curdle_msm_g1_ct_batch (resident false) and _batch_device.
+int batch(const void* points, const void* scalars, bool resident, const size_t* offsets, size_t k, unsigned bits, uint64_t* out_jac,
+          void* stream) {
   if (!offsets || (k && (!out_jac || !points || !scalars))) return fail(CURDLE_EINVAL, "null argument");
-  BatchShape sh;
-  if (int rc = batch_shape(offsets, k, scalar_bits, &sh)) return rc;
+  SegShape sh;
+  if (int rc = seg_shape(offsets, k, bits, 1, TotalText::kPairs, &sh)) return rc;
   if (k == 0) return CURDLE_OK;
+  if (resident && (!aligned16(points) || !aligned16(scalars))) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
   if (sh.total == 0) {
     for (size_t j = 0; j < k; j++) set_out_infinity(out_jac + 18 * j);
     return CURDLE_OK;
   }
-  return batch_from_host(sh, scalar_bits, out_jac, "batched constant-time MSM: clearing the scalars and the terms",
-                         [&](uint8_t* h_sc, uint8_t* h_pt) {
-                           memcpy(h_sc, scalars + 4 * sh.lo, sh.total * 32);
-                           memcpy(h_pt, points + 12 * sh.lo, sh.total * 96);
-                         });
+  // the call's first pair (96 and 32 bytes a record keep the alignment)
+  const uint8_t* pts = static_cast<const uint8_t*>(points) + 96 * sh.lo;
+  const uint8_t* sc = static_cast<const uint8_t*>(scalars) + 32 * sh.lo;
+  if (resident)  // the caller's arrays are read where they are
+    return batch_run(sh, bits, out_jac, "batched constant-time MSM: clearing the terms", stream, pts, sc,
+                     [&](Slot& S, WipeList& W, hipStream_t) { return note_terms(S, W, sh.total); });
+  return batch_run(sh, bits, out_jac, "batched constant-time MSM: clearing the scalars and the terms", nullptr, nullptr, nullptr,
+                   [&](Slot& S, WipeList& W, hipStream_t st) {
+                     return stage_pairs(S, W, sc, sh.total, 1, st, [&](uint8_t* h_pt) { memcpy(h_pt, pts, sh.total * 96); });
+                   });
+}
+}  // namespace
+
+extern "C" int curdle_msm_g1_ct(const uint64_t* points, const uint64_t* scalars, size_t n, unsigned scalar_bits,
+                                uint64_t out_jac[18]) {
+  return single(points, scalars, false, n, scalar_bits, out_jac, nullptr);
+}
+
+extern "C" int curdle_msm_g1_ct_device(const void* d_points, const void* d_scalars, size_t n, unsigned scalar_bits,
+                                       uint64_t out_jac[18], void* stream) {
+  return single(d_points, d_scalars, true, n, scalar_bits, out_jac, stream);
+}
+
+extern "C" int curdle_stat_msm_ct(unsigned long long out[3]) { return read_stats(out, g_msm_ct_stat, 3); }
+
+extern "C" int curdle_msm_g1_ct_batch(const uint64_t* points, const uint64_t* scalars, const size_t* offsets, size_t k,
+                                      unsigned scalar_bits, uint64_t* out_jac) {
+  return batch(points, scalars, false, offsets, k, scalar_bits, out_jac, nullptr);
 }
 
 extern "C" int curdle_msm_g1_ct_batch_device(const void* d_points, const void* d_scalars, const size_t* offsets, size_t k,
                                              unsigned scalar_bits, uint64_t* out_jac, void* stream) {
-  if (!offsets || (k && (!out_jac || !d_points || !d_scalars))) return fail(CURDLE_EINVAL, "null argument");
-  BatchShape sh;
-  if (int rc = batch_shape(offsets, k, scalar_bits, &sh)) return rc;
-  if (k == 0) return CURDLE_OK;
-  if (!aligned16(d_points) || !aligned16(d_scalars)) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
-  if (sh.total == 0) {
-    for (size_t j = 0; j < k; j++) set_out_infinity(out_jac + 18 * j);
-    return CURDLE_OK;
-  }
-  SlotHold H(cur(), true, stream);
-  WipeList W(H.stream());
-  H.wipe_on_exit(&W, "batched constant-time MSM: clearing the terms");
-  return H.run([&]() -> int {
-    Slot& S = H.slot();
-    if (int r = ensure(S.partials, sh.total * kMsmCtTermBytes)) return r;
-    W.note_device(S.partials.p, sh.total * kMsmCtTermBytes);
-    // the caller's arrays are read where they are, from the call's first pair (96 and 32 bytes a record keep the alignment)
-    return batch_walk_sum_fetch(S, sh, static_cast<const uint8_t*>(d_points) + 96 * sh.lo,
-                                static_cast<const uint8_t*>(d_scalars) + 32 * sh.lo, scalar_bits, out_jac, H.stream());
-  });
+  return batch(d_points, d_scalars, true, offsets, k, scalar_bits, out_jac, stream);
 }
 
 // One scalar vector against k base sets: the vector is replicated k times in the pinned staging (a host copy of public
@@ -290,9 +283,9 @@ extern "C" int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t
                                       unsigned scalar_bits, uint64_t* out_jac) {
   if (k && (!out_jac || !points_sets || (n && !scalars))) return fail(CURDLE_EINVAL, "null argument");
   if (int rc = check_scalar_bits(scalar_bits)) return rc;
-  if (k > kMsmCtBatchMax) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
+  if (k > kMsmCtMaxBatch) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
   if (k == 0) return CURDLE_OK;
-  if (n > kMsmCtMax / k) return fail(CURDLE_EINVAL, "k n = %zu x %zu exceeds the supported 65,536 pairs", k, n);
+  if (n > kMsmCtMaxTerms / k) return fail(CURDLE_EINVAL, "k n = %zu x %zu exceeds the supported 65,536 pairs", k, n);
   if (n == 0) {
     for (size_t j = 0; j < k; j++) set_out_infinity(out_jac + 18 * j);
     return CURDLE_OK;
@@ -301,16 +294,14 @@ extern "C" int curdle_msm_g1_ct_multi(const uint64_t* const* points_sets, size_t
     if (!points_sets[j]) return fail(CURDLE_EINVAL, "null argument: base set %zu", j);
   std::vector<size_t> offsets(k + 1);
   for (size_t j = 0; j <= k; j++) offsets[j] = j * n;
-  BatchShape sh;
-  if (int rc = batch_shape(offsets.data(), k, scalar_bits, &sh)) return rc;
-  return batch_from_host(sh, scalar_bits, out_jac,
-                         "constant-time MSM over k base sets: clearing the replicated scalars and the terms",
-                         [&](uint8_t* h_sc, uint8_t* h_pt) {
-                           for (size_t j = 0; j < k; j++) {
-                             memcpy(h_sc + j * n * 32, scalars, n * 32);
-                             memcpy(h_pt + j * n * 96, points_sets[j], n * 96);
-                           }
-                         });
+  SegShape sh;
+  if (int rc = seg_shape(offsets.data(), k, scalar_bits, 1, TotalText::kPairs, &sh)) return rc;
+  return batch_run(sh, scalar_bits, out_jac, "constant-time MSM over k base sets: clearing the replicated scalars and the terms",
+                   nullptr, nullptr, nullptr, [&](Slot& S, WipeList& W, hipStream_t st) {
+                     return stage_pairs(S, W, scalars, n, k, st, [&](uint8_t* h_pt) {
+                       for (size_t j = 0; j < k; j++) memcpy(h_pt + j * n * 96, points_sets[j], n * 96);
+                     });
+                   });
 }
 
 extern "C" int curdle_stat_msm_ct_batch(unsigned long long out[3]) { return read_stats(out, g_msm_ct_batch_stat, 3); }

@@ -10,13 +10,15 @@
 // keeps the staging within the constant-time MSM's term workspace (65,536 records of no more than 224 bytes).  The
 // table is PUBLIC: nothing of it is wiped.
 //
-// The MSM.  The single call is the batch of one MSM: ONE body (rows_walk_sum_fetch) behind the checks.  On the call's
-// one stream: the public tables -- (begin Cb, count Cb) per MSM and the row indices -- go up through the second pinned
-// staging, k_msm_ct_walk_rows writes the n Cb terms into the slot's `partials`, the segmented sum of msm_ct_kernels.hip
-// folds and finishes each MSM's run and ONE block of 144 k + 4 bytes comes back: the results and the violation word.
-// The host forms stage the scalars through the first pinned staging and a device buffer; both, and the term workspace
-// in every form, are on the call's WipeList.
-#include "api_helpers.h"
+// The MSM.  The single call is the batch of one MSM: ONE body (rows_call) behind the checks, and that body is the
+// segmented call of msm_ct_call.h (seg_walk_sum_fetch, which curdle_msm_g1_ct_batch runs too) with this family's walk.
+// On the call's one stream: the public tables -- (begin Cb, count Cb) per MSM and, behind it, the row indices -- go up
+// through the second pinned staging, k_msm_ct_walk_rows writes the n Cb terms into the slot's `partials`, the segmented
+// sum of msm_ct_kernels.hip folds and finishes each MSM's run and ONE block of 144 k + 4 bytes comes back: the results
+// and the violation word.  The host forms stage the scalars through the first pinned staging and a device buffer
+// (stage_scalars); both, and the term workspace in every form, are on the call's WipeList.  The tables are public and
+// are not.
+#include "msm_ct_call.h"
 
 #include <algorithm>
 
@@ -29,8 +31,6 @@ struct curdle_ct_bases {
 };
 
 namespace {
-constexpr size_t kTermMax = 65536;   // terms of one call, and records of one table: one pass
-constexpr size_t kBatchMax = 4096;   // MSMs of one call
 // The library's choice for chunk_bits = 0.  Measured (profiles/r33_msm_ct_bases.json; 255 bits, c = 8 / 16 / 32 / 64):
 // 256 pairs 1.26 / 1.34 / 1.61 / 2.11 ms, 2,048 pairs 1.97 / 1.71 / 1.79 / 2.25 ms against 5.7 ms for curdle_msm_g1_ct_device.
 // 8 wins by less than 0.2 ms at small calls, loses at 2,048 pairs, doubles the table and halves the pairs one call may
@@ -84,7 +84,7 @@ int check_create(size_t n, unsigned chunk_bits, unsigned* c) {
   *c = chunk_bits ? chunk_bits : kDefaultChunkBits;
   if (*c != 8 && *c != 16 && *c != 32 && *c != 64)
     return fail(CURDLE_EINVAL, "chunk_bits = %u is not 8, 16, 32, 64 or 0 (the library's choice)", chunk_bits);
-  if (n > kTermMax / chunks_of(255, *c))
+  if (n > kMsmCtMaxTerms / chunks_of(255, *c))
     return fail(CURDLE_EINVAL, "n C = %zu x %u exceeds the supported 65,536 table records", n, chunks_of(255, *c));
   return CURDLE_OK;
 }
@@ -120,47 +120,24 @@ int create(size_t n, unsigned c, curdle_ct_bases** out, Fill&& fill) {
 
 // The shape of a call behind its null arguments, in the order the header states: scalar_bits, k, offsets that
 // decrease, the term total, a row index out of range.  The single call is offsets = {0, n}, k = 1.
-struct Shape {
-  size_t k = 0, lo = 0, total = 0, nonempty = 0;
-  unsigned cb = 0;               // chunks walked: ceil(scalar_bits / c)
-  std::vector<uint32_t> seg;     // (begin Cb, count Cb) per MSM, begin relative to the call's first pair
-  std::vector<uint32_t> counts;  // count Cb per MSM
-};
-
-int shape_of(const curdle_ct_bases* b, const uint32_t* rows, const size_t* offsets, size_t k, unsigned bits, bool batch, Shape* sh) {
-  if (bits < 1 || bits > 255) return fail(CURDLE_EINVAL, "scalar_bits = %u is not in 1...255", bits);
-  if (batch && k > kBatchMax) return fail(CURDLE_EINVAL, "k = %zu exceeds the supported 4,096 MSMs of one call", k);
-  for (size_t j = 0; j < k; j++)
-    if (offsets[j + 1] < offsets[j]) return fail(CURDLE_EINVAL, "offsets decrease at %zu", j);
-  sh->k = k;
-  sh->cb = chunks_of(bits, b->c);
-  sh->lo = k ? offsets[0] : 0;
-  const size_t hi = k ? offsets[k] : 0;
-  sh->total = hi - sh->lo;
-  if (sh->total > kTermMax / sh->cb)
-    return fail(CURDLE_EINVAL, "n Cb = %zu x %u exceeds the supported 65,536 terms of one call", sh->total, sh->cb);
+// seg_shape (msm_ct_call.h) runs all but the last with a pair counting Cb = ceil(scalar_bits / c) terms.
+int shape_of(const curdle_ct_bases* b, const uint32_t* rows, const size_t* offsets, size_t k, unsigned bits, SegShape* sh) {
+  // (a scalar_bits out of range is refused before the stride is looked at)
+  if (int rc = seg_shape(offsets, k, bits, chunks_of(bits, b->c), TotalText::kTerms, sh)) return rc;
+  const size_t hi = sh->lo + sh->total;
   if (rows) {
     for (size_t p = sh->lo; p < hi; p++)
       if (rows[p] >= b->n) return fail(CURDLE_EINVAL, "rows[%zu] = %u is not below the %zu resident bases", p, rows[p], b->n);
   } else if (sh->total && hi > b->n) {
     return fail(CURDLE_EINVAL, "rows is null and the pairs end at %zu, beyond the %zu resident bases", hi, b->n);
   }
-  sh->seg.resize(2 * k);
-  sh->counts.resize(k);
-  for (size_t j = 0; j < k; j++) {
-    sh->seg[2 * j] = (uint32_t)((offsets[j] - sh->lo) * sh->cb);
-    sh->seg[2 * j + 1] = sh->counts[j] = (uint32_t)((offsets[j + 1] - offsets[j]) * sh->cb);
-    sh->nonempty += offsets[j + 1] != offsets[j];
-  }
   return CURDLE_OK;
 }
 
-size_t round16(size_t v) { return (v + 15) / 16 * 16; }
-
 // One call behind its checks, sh.total > 0.  scalars: the call's FIRST pair's, in host memory (resident false: staged
 // and wiped here) or in device memory (read where they are).  rows: the caller's array from index 0, or null.
-int rows_walk_sum_fetch(const curdle_ct_bases* bases, const uint32_t* rows, const void* scalars, bool resident, const Shape& sh,
-                        unsigned bits, bool batch, uint64_t* out_jac, void* stream) {
+int rows_call(const curdle_ct_bases* bases, const uint32_t* rows, const void* scalars, bool resident, const SegShape& sh,
+              unsigned bits, bool batch, uint64_t* out_jac, void* stream) {
   Ctx& cx = cur();
   curdle_ct_bases* b = const_cast<curdle_ct_bases*>(bases);
   void* d_table = nullptr;
@@ -171,50 +148,30 @@ int rows_walk_sum_fetch(const curdle_ct_bases* bases, const uint32_t* rows, cons
                               : "constant-time MSM over resident bases: clearing the scalars and the terms");
   const int rc = H.run([&]() -> int {
     Slot& S = H.slot();
-    const hipStream_t st = H.stream();
-    const size_t k = sh.k, n = sh.total, terms = n * sh.cb;
-    // the slot's small buffer: k results | the word the finish copies the verdict to | from the next 16: the status word
-    const size_t status_off = round16(144 * k + 4), seg_bytes = 8 * k, rows_off = round16(status_off + seg_bytes);
+    const size_t n = sh.total;
     int r;
-    if ((r = ensure(S.partials, terms * kMsmCtTermBytes))) return r;
-    if ((r = ensure(S.results, status_off + 16))) return r;
-    if ((r = ensure(S.offsets, seg_bytes))) return r;
-    if ((r = ensure(S.tmp, 4 * n))) return r;
-    if ((r = ensure_pinned(S, 1, rows_off + 4 * n))) return r;  // what comes back | the segments | the rows: public
-    W.note_device(S.partials.p, terms * kMsmCtTermBytes);
+    if ((r = note_terms(S, W, sh.terms()))) return r;
+    if ((r = ensure(S.tmp, 4 * n))) return r;  // the rows on the device
     const void* d_scalars = scalars;
     if (!resident) {
-      if ((r = ensure(S.scalars, n * 32))) return r;
-      if ((r = ensure_pinned(S, 0, n * 32))) return r;
-      W.note_device(S.scalars.p, n * 32);
-      W.note_host(S.h_stage[0], n * 32);
-      memcpy(S.h_stage[0], scalars, n * 32);
-      HIP_TRY(hipMemcpyAsync(S.scalars.p, S.h_stage[0], n * 32, hipMemcpyHostToDevice, st));
+      if ((r = stage_scalars(S, W, scalars, n, 1, 0, H.stream()))) return r;
       d_scalars = S.scalars.p;
     }
-    uint8_t* h_block = static_cast<uint8_t*>(S.h_stage[1]);
-    uint8_t* d_res = static_cast<uint8_t*>(S.results.p);
-    uint32_t* d_status = reinterpret_cast<uint32_t*>(d_res + status_off);
-    uint32_t* h_rows = reinterpret_cast<uint32_t*>(h_block + rows_off);
-    memcpy(h_block + status_off, sh.seg.data(), seg_bytes);
-    for (size_t p = 0; p < n; p++) h_rows[p] = rows ? rows[sh.lo + p] : (uint32_t)(sh.lo + p);
-    HIP_TRY(hipMemsetAsync(d_status, 0, 16, st));
-    HIP_TRY(hipMemcpyAsync(S.offsets.p, h_block + status_off, seg_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(S.tmp.p, h_rows, 4 * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_msm_ct_walk_rows(d_table, (uint32_t)b->n, static_cast<const uint32_t*>(S.tmp.p), d_scalars, b->c, bits,
-                                    (uint32_t)n, S.partials.p, d_status, st));
-    uint32_t levels = 0;
-    HIP_TRY(launch_msm_ct_sum_seg(S.partials.p, S.offsets.p, sh.counts.data(), (uint32_t)k, d_status, d_res, &levels, st));
-    HIP_TRY(hipMemcpyAsync(h_block, d_res, 144 * k + 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    uint32_t verdict;
-    memcpy(&verdict, h_block + 144 * k, 4);
-    if (verdict) return fail(CURDLE_EINVAL, "a scalar is not below 2^scalar_bits");
-    memcpy(out_jac, h_block, 144 * k);
+    unsigned levels = 0;
+    // this family's part: the row list (public, not wiped) through the pinned bytes behind the table, and the walk
+    if ((r = seg_walk_sum_fetch(H, sh, 4 * n, out_jac, &levels, [&](uint32_t* d_status, uint8_t* h_extra, hipStream_t st) -> int {
+          uint32_t* h_rows = reinterpret_cast<uint32_t*>(h_extra);
+          for (size_t p = 0; p < n; p++) h_rows[p] = rows ? rows[sh.lo + p] : (uint32_t)(sh.lo + p);
+          HIP_TRY(hipMemcpyAsync(S.tmp.p, h_rows, 4 * n, hipMemcpyHostToDevice, st));
+          HIP_TRY(launch_msm_ct_walk_rows(d_table, (uint32_t)b->n, static_cast<const uint32_t*>(S.tmp.p), d_scalars, b->c, bits,
+                                          (uint32_t)n, S.partials.p, d_status, st));
+          return CURDLE_OK;
+        })))
+      return r;
     g_stat[1].fetch_add(1, std::memory_order_relaxed);
-    g_stat[2].fetch_add(terms, std::memory_order_relaxed);
+    g_stat[2].fetch_add(sh.terms(), std::memory_order_relaxed);
     g_stat[3].fetch_add(sh.nonempty, std::memory_order_relaxed);
-    if (batch) count_msm_ct_batch(k, levels);
+    if (batch) count_msm_ct_batch(sh.k, levels);
     return CURDLE_OK;
   });
   bases_release(b);
@@ -225,21 +182,21 @@ int single(const curdle_ct_bases* b, const uint32_t* rows, const void* scalars, 
            uint64_t out_jac[18], void* stream) {
   if (!b || !out_jac || (n && !scalars)) return fail(CURDLE_EINVAL, "null argument");
   const size_t offsets[2] = {0, n};
-  Shape sh;
-  if (int rc = shape_of(b, rows, offsets, 1, bits, false, &sh)) return rc;
+  SegShape sh;
+  if (int rc = shape_of(b, rows, offsets, 1, bits, &sh)) return rc;
   if (n == 0) {
     set_out_infinity(out_jac);
     return CURDLE_OK;
   }
   if (resident && !aligned16(scalars)) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
-  return rows_walk_sum_fetch(b, rows, scalars, resident, sh, bits, false, out_jac, stream);
+  return rows_call(b, rows, scalars, resident, sh, bits, false, out_jac, stream);
 }
 
 int batch(const curdle_ct_bases* b, const uint32_t* rows, const void* scalars, bool resident, const size_t* offsets, size_t k,
           unsigned bits, uint64_t* out_jac, void* stream) {
   if (!b || !offsets || (k && (!out_jac || !scalars))) return fail(CURDLE_EINVAL, "null argument");
-  Shape sh;
-  if (int rc = shape_of(b, rows, offsets, k, bits, true, &sh)) return rc;
+  SegShape sh;
+  if (int rc = shape_of(b, rows, offsets, k, bits, &sh)) return rc;
   if (k == 0) return CURDLE_OK;
   if (resident && !aligned16(scalars)) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
   if (sh.total == 0) {
@@ -247,7 +204,7 @@ int batch(const curdle_ct_bases* b, const uint32_t* rows, const void* scalars, b
     return CURDLE_OK;
   }
   // the call's first pair (32 bytes a record keep the alignment)
-  return rows_walk_sum_fetch(b, rows, static_cast<const uint8_t*>(scalars) + 32 * sh.lo, resident, sh, bits, true, out_jac, stream);
+  return rows_call(b, rows, static_cast<const uint8_t*>(scalars) + 32 * sh.lo, resident, sh, bits, true, out_jac, stream);
 }
 }  // namespace
 

@@ -15,7 +15,8 @@
 // k_msm_ct_walk_rows.  The grid is (ceil(n / kBlock), Cb), Cb = ceil(bits / c) the chunks a scalar below 2^bits has;
 // blockIdx.y = j is the chunk: block-uniform and public.  Lane p loads rows[p] (a PUBLIC index list the host checked
 // against the set's size) and the record table[j size + rows[p]] -- addresses made of public values only -- and its
-// scalar at an address made of the lane index.  The bits at or above `bits` are shifted out into the violation word
+// scalar at an address made of the lane index; the rest is msm_ct_lane (msm_ct_lane.h), the lane k_msm_ct_walk runs
+// too.  The bits at or above `bits` are shifted out into the violation word
 // with k_msm_ct_walk's loop (every chunk's lane of a pair ORs the same word), then the bits between the chunk's top and
 // `bits` are shifted out by the same rolled loop, whose trip count is a function of j, c and bits alone; walk_ct over
 // the chunk's step count -- c, or bits - c (Cb - 1) for the top chunk -- leaves d_j (2^(c j) P) and the lane stores it
@@ -33,6 +34,7 @@
 #include "msm_kernels_common.h"
 #include "g1_walk_ct.h"
 #include "g1_add_ct.h"  // finite_mask
+#include "msm_ct_lane.h"
 
 namespace curdle {
 
@@ -66,28 +68,15 @@ __global__ void __launch_bounds__(kBlock, 2)
   const u32 j = blockIdx.y, cb = gridDim.y;                 // the chunk and the chunk count: public
   const u32 steps = j + 1 < cb ? c : bits - c * (cb - 1);   // the top chunk is the short one
   const u32 skip = bits - (c * j + steps);                  // the bits between the chunk's top and `bits`
-  u32 pw[24];
-  d28::load_words<24>(pw, table + 6 * ((size_t)j * size + rows[p]));  // an address made of public values
-  const u32 finite = finite_mask(pw);                                  // public
-  F28 x2, y2;
-  d28::from_gnark(x2, pw);
-  d28::from_gnark(y2, pw + 12);
   Fr k;
   {
     Fr s;
     load_fr_lane(s, scalars + 2 * (size_t)p);  // an address made of the lane index
     f_from_mont<FrParams>(k, s);
   }
-  // k << (256 - bits): a set bit at or above `bits` is the violation; then the chunks above this one go
-  u32 over = 0;
-#pragma unroll 1
-  for (u32 s = bits; s < 256; s++) over |= next_bit_msb(k);
-#pragma unroll 1
-  for (u32 s = 0; s < skip; s++) (void)next_bit_msb(k);
-  X28 acc;
-  const u32 started = walk_ct(acc, k, x2, y2, steps);
-  atomicOr(status + (p >> 31), over);  // unconditional, 0 or 1, a per-lane atomic: see k_msm_ct_walk
-  store_words_masked<14>(reinterpret_cast<uint4*>(term + ((size_t)p * cb + j)), reinterpret_cast<const u32*>(&acc), started & finite);
+  // the record's address is made of public values; the status word's of the lane index (p < 2^31: always word 0)
+  msm_ct_lane(table + 6 * ((size_t)j * size + rows[p]), k, bits, skip, steps, reinterpret_cast<uint4*>(term + ((size_t)p * cb + j)),
+              status + (p >> 31));
 }
 
 hipError_t launch_ct_bases_shift(const void* points, uint32_t n, uint32_t chunk_bits, uint32_t chunks, void* staging_xyzz,

@@ -3,7 +3,8 @@
 // bucket addresses and large-bucket queue are all functions of the scalars, in the manner of k_g1_mul_ct
 // (g1_mul_ct_kernels.hip).  Seven kernels; the rule of what may depend on a secret is the one of g1_walk_ct.h.
 //
-// k_msm_ct_walk.  One lane per (base, scalar) pair: the walk of g1_walk_ct.h with a PUBLIC step count `bits` (1...255,
+// k_msm_ct_walk.  One lane per (base, scalar) pair; behind the scalar's load the lane is msm_ct_lane (msm_ct_lane.h),
+// shared with k_msm_ct_walk_rows.  The walk of g1_walk_ct.h with a PUBLIC step count `bits` (1...255,
 // a kernel argument): the scalar is first shifted left by 256 - bits, one bit a step in a rolled loop whose trip count
 // is the argument alone, and every bit shifted out is OR-ed into the lane's violation word; then walk_ct over `bits`
 // steps.  The exactness argument of g1_walk_ct.h holds for every prefix of a scalar
@@ -59,6 +60,7 @@
 #include "g1_walk_ct.h"
 #include "g1_add_ct.h"
 #include "g1_exit_ct.h"
+#include "msm_ct_lane.h"
 
 namespace curdle {
 
@@ -67,12 +69,6 @@ __global__ void __launch_bounds__(kBlock, 2)
                   X28* __restrict__ term, u32* status) {
   const u32 i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  u32 pw[24];
-  d28::load_words<24>(pw, points + 6 * (size_t)i);
-  const u32 finite = finite_mask(pw);  // public
-  F28 x2, y2;
-  d28::from_gnark(x2, pw);
-  d28::from_gnark(y2, pw + 12);
   Fr k;
   if (form == kMsmCtScalarU32) {  // a kernel argument: wave-uniform and public
 #pragma unroll
@@ -83,16 +79,8 @@ __global__ void __launch_bounds__(kBlock, 2)
     load_fr_lane(s, static_cast<const uint4*>(scalars) + 2 * (size_t)i);
     f_from_mont<FrParams>(k, s);
   }
-  // k << (256 - bits): the trip count is the argument alone; a set bit at or above `bits` is the violation
-  u32 over = 0;
-#pragma unroll 1
-  for (u32 s = bits; s < 256; s++) over |= next_bit_msb(k);
-  X28 acc;
-  const u32 started = walk_ct(acc, k, x2, y2, bits);
-  // Unconditional, 0 or 1.  The address is made of the lane index (i < 2^31: always word 0) so that it is a per-lane
-  // atomic: on a wave-uniform address the compiler first folds the wave's values through v_readlane into SGPRs.
-  atomicOr(status + (i >> 31), over);
-  store_words_masked<14>(reinterpret_cast<uint4*>(term + i), reinterpret_cast<const u32*>(&acc), started & finite);
+  // all `bits` bits in one walk; the status word's address is made of the lane index (i < 2^31: always word 0)
+  msm_ct_lane(points + 6 * (size_t)i, k, bits, 0, bits, reinterpret_cast<uint4*>(term + i), status + (i >> 31));
 }
 
 namespace {

@@ -113,17 +113,28 @@ def test_symbols_and_prototypes(cm):
     for unit in ("msm_ct_bases_kernels", "msm_ct_bases_api"):
         assert make.count("csrc/%s.hip" % unit) == 1 and make.count("build/%s.o" % unit) == 1, unit
     kernels = open(os.path.join(csrc, "msm_ct_bases_kernels.hip")).read()
-    for k in ("k_ct_bases_shift(", "k_msm_ct_walk_rows(", "walk_ct(acc, k, x2, y2, steps)", "load_fr_lane(", "d28::dbl(acc)",
-              '#include "g1_walk_ct.h"'):
+    for k in ("k_ct_bases_shift(", "k_msm_ct_walk_rows(", "msm_ct_lane(", "load_fr_lane(", "d28::dbl(acc)",
+              '#include "g1_walk_ct.h"', '#include "msm_ct_lane.h"'):
         assert k in kernels, k
-    assert "asm" not in kernels and "__shared__" not in kernels and kernels.count("atomicOr(") == 1
+    # the lane behind the addresses is the one k_msm_ct_walk runs: the walk and the ONE atomic OR are there, once
+    lane = open(os.path.join(csrc, "msm_ct_lane.h")).read()
+    assert "walk_ct(acc, k, x2, y2, steps)" in lane and "store_words_masked<14>(" in lane
+    both = kernels + lane
+    assert "asm" not in both and "__shared__" not in both and both.count("atomicOr(") == 1
+    assert "atomicOr(" not in open(os.path.join(csrc, "msm_ct_kernels.hip")).read()
     api = open(os.path.join(csrc, "msm_ct_bases_api.hip")).read()
-    for k in ("launch_msm_ct_sum_seg(", "launch_g1_normalize(", "kNormalizeXyzz", "ResidentCopy", "SlotHold", "WipeList"):
+    for k in ("seg_walk_sum_fetch(", "launch_g1_normalize(", "kNormalizeXyzz", "ResidentCopy", "SlotHold", "WipeList"):
         assert k in api, k
-    # one definition of each function of the constant-time G1 layer in the tree
+    # ONE segmented call body: over all the C ABI units the segmented sum is launched from exactly one place
+    apis = "".join(open(p).read() for p in glob.glob(os.path.join(csrc, "*_api.hip")))
+    assert apis.count("launch_msm_ct_sum_seg(") == 1
+    # one definition of each function of the constant-time G1 layer in the tree, and one place for each refusal text the
+    # two MSM families share
     homes = {"void add_ct(": "g1_add_ct.h", "void madd_bit(": "g1_walk_ct.h", "u32 walk_ct(": "g1_walk_ct.h",
              "void affine_words_ct(": "g1_exit_ct.h", "void load_fr_lane(": "g1_walk_ct.h", "u32 finite_mask(": "g1_add_ct.h",
-             "u32 next_bit_msb(": "g1_walk_ct.h"}
+             "u32 next_bit_msb(": "g1_walk_ct.h", "void msm_ct_lane(": "msm_ct_lane.h",
+             "offsets decrease at": "msm_ct_api.hip", "is not in 1...255": "msm_ct_api.hip",
+             "a scalar is not below 2^scalar_bits": "msm_ct_api.hip"}
     defs = {d: [] for d in homes}
     for path in glob.glob(os.path.join(csrc, "*")):
         text = open(path, errors="replace").read()
