@@ -10,8 +10,12 @@
 // keeps the staging within the constant-time MSM's term workspace (65,536 records of no more than 224 bytes).  The
 // table is PUBLIC: nothing of it is wiped.
 //
-// The MSM.  The single call is the batch of one MSM: ONE body (rows_call) behind the checks, and that body is the
+// The MSM.  The single call is the batch of one MSM, and a call over one handle is the call over up to four sets
+// (curdle_msm_g1_ct_bases_sets_batch: the prover's funnel calls mix CRS points and instance points) with one set: ONE
+// body (rows_call) behind the checks, and that body is the
 // segmented call of msm_ct_call.h (seg_walk_sum_fetch, which curdle_msm_g1_ct_batch runs too) with this family's walk.
+// The sets reach the walk as a kernel argument (CtRowSets: table, size and first index of each); every handle of a call
+// is acquired before the device work and released behind it (SetsHold).
 // On the call's one stream: the public tables -- (begin Cb, count Cb) per MSM and, behind it, the row indices -- go up
 // through the second pinned staging, k_msm_ct_walk_rows writes the n Cb terms into the slot's `partials`, the segmented
 // sum of msm_ct_kernels.hip folds and finishes each MSM's run and ONE block of 144 k + 4 bytes comes back: the results
@@ -121,27 +125,56 @@ int create(size_t n, unsigned c, curdle_ct_bases** out, Fill&& fill) {
 // The shape of a call behind its null arguments, in the order the header states: scalar_bits, k, offsets that
 // decrease, the term total, a row index out of range.  The single call is offsets = {0, n}, k = 1.
 // seg_shape (msm_ct_call.h) runs all but the last with a pair counting Cb = ceil(scalar_bits / c) terms.
-int shape_of(const curdle_ct_bases* b, const uint32_t* rows, const size_t* offsets, size_t k, unsigned bits, SegShape* sh) {
+// n: the records the call's sets hold in all, c: their one chunk width.
+int shape_of(size_t n, unsigned c, const uint32_t* rows, const size_t* offsets, size_t k, unsigned bits, SegShape* sh) {
   // (a scalar_bits out of range is refused before the stride is looked at)
-  if (int rc = seg_shape(offsets, k, bits, chunks_of(bits, b->c), TotalText::kTerms, sh)) return rc;
+  if (int rc = seg_shape(offsets, k, bits, chunks_of(bits, c), TotalText::kTerms, sh)) return rc;
   const size_t hi = sh->lo + sh->total;
   if (rows) {
     for (size_t p = sh->lo; p < hi; p++)
-      if (rows[p] >= b->n) return fail(CURDLE_EINVAL, "rows[%zu] = %u is not below the %zu resident bases", p, rows[p], b->n);
-  } else if (sh->total && hi > b->n) {
-    return fail(CURDLE_EINVAL, "rows is null and the pairs end at %zu, beyond the %zu resident bases", hi, b->n);
+      if (rows[p] >= n) return fail(CURDLE_EINVAL, "rows[%zu] = %u is not below the %zu resident bases", p, rows[p], n);
+  } else if (sh->total && hi > n) {
+    return fail(CURDLE_EINVAL, "rows is null and the pairs end at %zu, beyond the %zu resident bases", hi, n);
   }
   return CURDLE_OK;
 }
 
-// One call behind its checks, sh.total > 0.  scalars: the call's FIRST pair's, in host memory (resident false: staged
-// and wiped here) or in device memory (read where they are).  rows: the caller's array from index 0, or null.
-int rows_call(const curdle_ct_bases* bases, const uint32_t* rows, const void* scalars, bool resident, const SegShape& sh,
-              unsigned bits, bool batch, uint64_t* out_jac, void* stream) {
+// The handles of one call, each a user of its ResidentCopy from acquire() until this dies: every set is acquired before
+// the call's device work and released behind it on every way out, so a free during the call is deferred for each.
+struct SetsHold {
+  curdle_ct_bases* held[kCtRowSetsMax] = {};
+  size_t n_held = 0;
+  CtRowSets desc = {};
+  // This context's copies, made on first use; an empty set has none and covers no index.
+  int acquire(Ctx& cx, const curdle_ct_bases* const* sets, size_t n_sets) {
+    uint32_t first = 0;
+    for (size_t s = 0; s < (size_t)kCtRowSetsMax; s++) {
+      desc.first[s] = first;
+      if (s >= n_sets) continue;
+      curdle_ct_bases* b = const_cast<curdle_ct_bases*>(sets[s]);
+      void* d_table = nullptr;
+      if (int rc = bases_acquire(cx, b, &d_table)) return rc;
+      held[n_held++] = b;
+      desc.table[s] = d_table;
+      desc.size[s] = (uint32_t)b->n;
+      first += (uint32_t)b->n;
+    }
+    return CURDLE_OK;
+  }
+  ~SetsHold() {
+    while (n_held) bases_release(held[--n_held]);
+  }
+};
+
+// One call behind its checks, sh.total > 0, over n_sets handles at one chunk width (the single-handle calls: one set).
+// scalars: the call's FIRST pair's, in host memory (resident false: staged and wiped here) or in device memory (read
+// where they are).  rows: the caller's array from index 0, or null.
+int rows_call(const curdle_ct_bases* const* sets, size_t n_sets, const uint32_t* rows, const void* scalars, bool resident,
+              const SegShape& sh, unsigned bits, bool batch, uint64_t* out_jac, void* stream) {
   Ctx& cx = cur();
-  curdle_ct_bases* b = const_cast<curdle_ct_bases*>(bases);
-  void* d_table = nullptr;
-  if (int rc = bases_acquire(cx, b, &d_table)) return rc;  // this context's copy, made on first use
+  const unsigned c = sets[0]->c;
+  SetsHold held;
+  if (int rc = held.acquire(cx, sets, n_sets)) return rc;
   SlotHold H(cx, true, stream);
   WipeList W(H.stream());
   H.wipe_on_exit(&W, resident ? "constant-time MSM over resident bases: clearing the terms"
@@ -163,8 +196,8 @@ int rows_call(const curdle_ct_bases* bases, const uint32_t* rows, const void* sc
           uint32_t* h_rows = reinterpret_cast<uint32_t*>(h_extra);
           for (size_t p = 0; p < n; p++) h_rows[p] = rows ? rows[sh.lo + p] : (uint32_t)(sh.lo + p);
           HIP_TRY(hipMemcpyAsync(S.tmp.p, h_rows, 4 * n, hipMemcpyHostToDevice, st));
-          HIP_TRY(launch_msm_ct_walk_rows(d_table, (uint32_t)b->n, static_cast<const uint32_t*>(S.tmp.p), d_scalars, b->c, bits,
-                                          (uint32_t)n, S.partials.p, d_status, st));
+          HIP_TRY(launch_msm_ct_walk_rows(held.desc, static_cast<const uint32_t*>(S.tmp.p), d_scalars, c, bits, (uint32_t)n,
+                                          S.partials.p, d_status, st));
           return CURDLE_OK;
         })))
       return r;
@@ -174,7 +207,6 @@ int rows_call(const curdle_ct_bases* bases, const uint32_t* rows, const void* sc
     if (batch) count_msm_ct_batch(sh.k, levels);
     return CURDLE_OK;
   });
-  bases_release(b);
   return rc;
 }
 
@@ -183,20 +215,23 @@ int single(const curdle_ct_bases* b, const uint32_t* rows, const void* scalars, 
   if (!b || !out_jac || (n && !scalars)) return fail(CURDLE_EINVAL, "null argument");
   const size_t offsets[2] = {0, n};
   SegShape sh;
-  if (int rc = shape_of(b, rows, offsets, 1, bits, &sh)) return rc;
+  if (int rc = shape_of(b->n, b->c, rows, offsets, 1, bits, &sh)) return rc;
   if (n == 0) {
     set_out_infinity(out_jac);
     return CURDLE_OK;
   }
   if (resident && !aligned16(scalars)) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
-  return rows_call(b, rows, scalars, resident, sh, bits, false, out_jac, stream);
+  return rows_call(&b, 1, rows, scalars, resident, sh, bits, false, out_jac, stream);
 }
 
-int batch(const curdle_ct_bases* b, const uint32_t* rows, const void* scalars, bool resident, const size_t* offsets, size_t k,
-          unsigned bits, uint64_t* out_jac, void* stream) {
-  if (!b || !offsets || (k && (!out_jac || !scalars))) return fail(CURDLE_EINVAL, "null argument");
+// The batch behind the null checks of its handles, over n_sets of them at one chunk width: what the single-handle batch
+// and the batch over several sets share from the shape on.  A call with pairs needs `rows` when it has several sets.
+int batch_over(const curdle_ct_bases* const* sets, size_t n_sets, const uint32_t* rows, const void* scalars, bool resident,
+               const size_t* offsets, size_t k, unsigned bits, uint64_t* out_jac, void* stream) {
+  size_t n = 0;
+  for (size_t s = 0; s < n_sets; s++) n += sets[s]->n;
   SegShape sh;
-  if (int rc = shape_of(b, rows, offsets, k, bits, &sh)) return rc;
+  if (int rc = shape_of(n, sets[0]->c, rows, offsets, k, bits, &sh)) return rc;
   if (k == 0) return CURDLE_OK;
   if (resident && !aligned16(scalars)) return fail(CURDLE_EINVAL, "device pointers must be multiples of 16");
   if (sh.total == 0) {
@@ -204,7 +239,30 @@ int batch(const curdle_ct_bases* b, const uint32_t* rows, const void* scalars, b
     return CURDLE_OK;
   }
   // the call's first pair (32 bytes a record keep the alignment)
-  return rows_call(b, rows, static_cast<const uint8_t*>(scalars) + 32 * sh.lo, resident, sh, bits, true, out_jac, stream);
+  return rows_call(sets, n_sets, rows, static_cast<const uint8_t*>(scalars) + 32 * sh.lo, resident, sh, bits, true, out_jac, stream);
+}
+
+int batch(const curdle_ct_bases* b, const uint32_t* rows, const void* scalars, bool resident, const size_t* offsets, size_t k,
+          unsigned bits, uint64_t* out_jac, void* stream) {
+  if (!b || !offsets || (k && (!out_jac || !scalars))) return fail(CURDLE_EINVAL, "null argument");
+  return batch_over(&b, 1, rows, scalars, resident, offsets, k, bits, out_jac, stream);
+}
+
+// curdle_msm_g1_ct_bases_sets_batch / _device: the null arguments (a null set is looked for among the first four only:
+// nothing beyond CURDLE_CT_BASES_MAX_SETS is read), the set count, one chunk width, then the single-handle batch's order.
+// rows: needed as soon as a pair would be read, i.e. when the offsets span any.
+int sets_batch(const curdle_ct_bases* const* sets, size_t n_sets, const uint32_t* rows, const void* scalars, bool resident,
+               const size_t* offsets, size_t k, unsigned bits, uint64_t* out_jac, void* stream) {
+  if (!sets || !offsets || (k && (!out_jac || !scalars))) return fail(CURDLE_EINVAL, "null argument");
+  for (size_t s = 0; s < std::min<size_t>(n_sets, CURDLE_CT_BASES_MAX_SETS); s++)
+    if (!sets[s]) return fail(CURDLE_EINVAL, "null argument: sets[%zu]", s);
+  if (k && k <= kMsmCtMaxBatch && !rows && offsets[k] > offsets[0]) return fail(CURDLE_EINVAL, "null argument: rows, and the call has pairs");
+  if (n_sets < 1 || n_sets > CURDLE_CT_BASES_MAX_SETS)
+    return fail(CURDLE_EINVAL, "n_sets = %zu is not in 1...%d", n_sets, CURDLE_CT_BASES_MAX_SETS);
+  for (size_t s = 1; s < n_sets; s++)
+    if (sets[s]->c != sets[0]->c)
+      return fail(CURDLE_EINVAL, "the sets' chunk_bits differ: sets[%zu] has %u, sets[0] has %u", s, sets[s]->c, sets[0]->c);
+  return batch_over(sets, n_sets, rows, scalars, resident, offsets, k, bits, out_jac, stream);
 }
 }  // namespace
 
@@ -275,6 +333,18 @@ extern "C" int curdle_msm_g1_ct_bases_batch_device(const curdle_ct_bases* b, con
                                                    const size_t* offsets, size_t k, unsigned scalar_bits, uint64_t* out_jac,
                                                    void* stream) {
   return batch(b, rows, d_scalars, true, offsets, k, scalar_bits, out_jac, stream);
+}
+
+extern "C" int curdle_msm_g1_ct_bases_sets_batch(const curdle_ct_bases* const* sets, size_t n_sets, const uint32_t* rows,
+                                                 const uint64_t* scalars, const size_t* offsets, size_t k, unsigned scalar_bits,
+                                                 uint64_t* out_jac) {
+  return sets_batch(sets, n_sets, rows, scalars, false, offsets, k, scalar_bits, out_jac, nullptr);
+}
+
+extern "C" int curdle_msm_g1_ct_bases_sets_batch_device(const curdle_ct_bases* const* sets, size_t n_sets, const uint32_t* rows,
+                                                        const void* d_scalars, const size_t* offsets, size_t k,
+                                                        unsigned scalar_bits, uint64_t* out_jac, void* stream) {
+  return sets_batch(sets, n_sets, rows, d_scalars, true, offsets, k, scalar_bits, out_jac, stream);
 }
 
 extern "C" int curdle_stat_msm_ct_bases(unsigned long long out[4]) { return read_stats(out, g_stat, 4); }

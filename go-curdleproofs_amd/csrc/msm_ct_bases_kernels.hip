@@ -13,8 +13,12 @@
 // multiply-accumulate trap of g1_walk_ct.h: the initial zz and zzz are constants).
 //
 // k_msm_ct_walk_rows.  The grid is (ceil(n / kBlock), Cb), Cb = ceil(bits / c) the chunks a scalar below 2^bits has;
-// blockIdx.y = j is the chunk: block-uniform and public.  Lane p loads rows[p] (a PUBLIC index list the host checked
-// against the set's size) and the record table[j size + rows[p]] -- addresses made of public values only -- and its
+// blockIdx.y = j is the chunk: block-uniform and public.  The ONE walk kernel of the family: the call's base sets -- up
+// to four tables at one c, set s covering the indices [first_s, first_s + size_s) -- arrive by value (CtRowSets), and a
+// call over one handle is the one-set case.  Lane p loads rows[p] (a PUBLIC index list the host checked against the
+// sets' total), finds its set by three compares against the public first_s (selects, no indexed read of the argument;
+// an empty set shares its first index with the next one and is never chosen) and loads the record
+// table_s[j size_s + rows[p] - first_s] -- addresses made of public values only -- and its
 // scalar at an address made of the lane index; the rest is msm_ct_lane (msm_ct_lane.h), the lane k_msm_ct_walk runs
 // too.  The bits at or above `bits` are shifted out into the violation word
 // with k_msm_ct_walk's loop (every chunk's lane of a pair ORs the same word), then the bits between the chunk's top and
@@ -61,13 +65,24 @@ __global__ void __launch_bounds__(kBlock, 2)
 }
 
 __global__ void __launch_bounds__(kBlock, 2)
-    k_msm_ct_walk_rows(const uint4* __restrict__ table, u32 size, const u32* __restrict__ rows, const uint4* __restrict__ scalars,
-                       u32 c, u32 bits, u32 n, X28* __restrict__ term, u32* status) {
+    k_msm_ct_walk_rows(const CtRowSets sets, const u32* __restrict__ rows, const uint4* __restrict__ scalars, u32 c, u32 bits, u32 n,
+                       X28* __restrict__ term, u32* status) {
   const u32 p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= n) return;
   const u32 j = blockIdx.y, cb = gridDim.y;                 // the chunk and the chunk count: public
   const u32 steps = j + 1 < cb ? c : bits - c * (cb - 1);   // the top chunk is the short one
   const u32 skip = bits - (c * j + steps);                  // the bits between the chunk's top and `bits`
+  // the lane's set: the last one whose first index is not above the row -- public values, three compares
+  const u32 row = rows[p];
+  const uint4* table = static_cast<const uint4*>(sets.table[0]);
+  u32 size = sets.size[0], first = sets.first[0];
+#pragma unroll
+  for (int s = 1; s < kCtRowSetsMax; s++) {
+    const bool in = row >= sets.first[s];
+    table = in ? static_cast<const uint4*>(sets.table[s]) : table;
+    size = in ? sets.size[s] : size;
+    first = in ? sets.first[s] : first;
+  }
   Fr k;
   {
     Fr s;
@@ -75,7 +90,7 @@ __global__ void __launch_bounds__(kBlock, 2)
     f_from_mont<FrParams>(k, s);
   }
   // the record's address is made of public values; the status word's of the lane index (p < 2^31: always word 0)
-  msm_ct_lane(table + 6 * ((size_t)j * size + rows[p]), k, bits, skip, steps, reinterpret_cast<uint4*>(term + ((size_t)p * cb + j)),
+  msm_ct_lane(table + 6 * ((size_t)j * size + (row - first)), k, bits, skip, steps, reinterpret_cast<uint4*>(term + ((size_t)p * cb + j)),
               status + (p >> 31));
 }
 
@@ -88,15 +103,17 @@ hipError_t launch_ct_bases_shift(const void* points, uint32_t n, uint32_t chunk_
   return hipGetLastError();
 }
 
-hipError_t launch_msm_ct_walk_rows(const void* table, uint32_t size, const uint32_t* rows, const void* scalars,
-                                   uint32_t chunk_bits, uint32_t bits, uint32_t n, void* term, uint32_t* status,
-                                   hipStream_t stream) {
+hipError_t launch_msm_ct_walk_rows(const CtRowSets& sets, const uint32_t* rows, const void* scalars, uint32_t chunk_bits,
+                                   uint32_t bits, uint32_t n, void* term, uint32_t* status, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   if (bits < 1 || bits > 255 || chunk_bits < 1 || chunk_bits > 64) return hipErrorInvalidValue;
   const u32 cb = (bits + chunk_bits - 1) / chunk_bits;
   if ((u64)n * cb > ((u64)1 << 31)) return hipErrorInvalidValue;  // the term index is 32 bits
-  hipLaunchKernelGGL(k_msm_ct_walk_rows, dim3(cdiv(n, kBlock), cb), dim3(kBlock), 0, stream, (const uint4*)table, (u32)size,
-                     rows, (const uint4*)scalars, (u32)chunk_bits, (u32)bits, (u32)n, (X28*)term, status);
+  for (int s = 0; s < kCtRowSetsMax; s++) {  // the ranges lie behind each other and a set with records has a table
+    if (sets.first[s] != (s ? sets.first[s - 1] + sets.size[s - 1] : 0) || (sets.size[s] && !sets.table[s])) return hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(k_msm_ct_walk_rows, dim3(cdiv(n, kBlock), cb), dim3(kBlock), 0, stream, sets, rows, (const uint4*)scalars,
+                     (u32)chunk_bits, (u32)bits, (u32)n, (X28*)term, status);
   return hipGetLastError();
 }
 

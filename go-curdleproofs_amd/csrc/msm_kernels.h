@@ -390,15 +390,23 @@ hipError_t launch_permute_ct_seg(const void* in, const uint32_t* perm, uint32_t 
 //   launch_ct_bases_shift: staging_xyzz[(j - 1) n + i] = 2^(chunk_bits j) points[i] for 1 <= j < chunks as gnark-form
 //     G1XYZZ records (192 bytes, ZZ = 0: infinity), what launch_g1_normalize's kNormalizeXyzz reads; points are gnark
 //     G1Affine records.  Public arithmetic.
-//   launch_msm_ct_walk_rows: term[p Cb + j] = (chunk j of scalars[p]) * table[j size + rows[p]] for p < n and
-//     j < Cb = ceil(bits / chunk_bits): launch_msm_ct_walk's walk, status word and term records over chunk_bits steps
-//     (the top chunk: bits - chunk_bits (Cb - 1)).  table: Cb or more rows of `size` gnark G1Affine records; rows: n
-//     device uint32 below size (public; the caller checked them); scalars: Montgomery fr.Elements.  n Cb <= 2^31.
+//   launch_msm_ct_walk_rows: term[p Cb + j] = (chunk j of scalars[p]) * table_s[j size_s + rows[p] - first_s] for p < n
+//     and j < Cb = ceil(bits / chunk_bits), s the set whose range [first_s, first_s + size_s) holds rows[p]:
+//     launch_msm_ct_walk's walk, status word and term records over chunk_bits steps (the top chunk:
+//     bits - chunk_bits (Cb - 1)).  sets: up to four tables of Cb or more rows of size_s gnark G1Affine records each, all
+//     at one chunk_bits, laid behind each other in the index space (CtRowSets: a kernel argument by value); rows: n
+//     device uint32 below the sets' total (public; the caller checked them); scalars: Montgomery fr.Elements.
+//     n Cb <= 2^31.
+static constexpr int kCtRowSetsMax = 4;
+struct CtRowSets {
+  const void* table[kCtRowSetsMax];  // null for an empty set: never read
+  uint32_t size[kCtRowSetsMax];      // records a row of the set's table holds
+  uint32_t first[kCtRowSetsMax];     // B_s = size_0 + ... + size_(s-1); the total for s beyond the call's sets
+};
 hipError_t launch_ct_bases_shift(const void* points, uint32_t n, uint32_t chunk_bits, uint32_t chunks, void* staging_xyzz,
                                  hipStream_t stream);
-hipError_t launch_msm_ct_walk_rows(const void* table, uint32_t size, const uint32_t* rows, const void* scalars,
-                                   uint32_t chunk_bits, uint32_t bits, uint32_t n, void* term, uint32_t* status,
-                                   hipStream_t stream);
+hipError_t launch_msm_ct_walk_rows(const CtRowSets& sets, const uint32_t* rows, const void* scalars, uint32_t chunk_bits,
+                                   uint32_t bits, uint32_t n, void* term, uint32_t* status, hipStream_t stream);
 
 // normalize_kernels.hip: n points in memory -> n gnark G1Affine records (96 bytes; infinity: all zero), ONE inversion
 // per wave of 64 lanes with 1 or 8 points each (Montgomery's trick over a wave scan).  The forms are those of

@@ -102,6 +102,9 @@ SYMBOLS = [
     "curdle_ct_bases_chunk_bits", "curdle_ct_bases_export",
     "curdle_msm_g1_ct_bases", "curdle_msm_g1_ct_bases_device", "curdle_msm_g1_ct_bases_batch",
     "curdle_msm_g1_ct_bases_batch_device", "curdle_stat_msm_ct_bases",
+    "curdle_msm_g1_ct_bases_sets_batch", "curdle_msm_g1_ct_bases_sets_batch_device",
+    "curdle_prover_ct_create", "curdle_prover_ct_free", "curdle_prover_ct_prove", "curdle_prover_ct_whisk_shuffle_proof",
+    "curdle_stat_alg_msm_resident",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -608,6 +611,41 @@ class CtBases:
         _check(_msm_g1_ct_bases_batch_device(self._h, None if r is None else _ptr(r), d_scalars or None, _ptr(offs), k,
                                              int(scalar_bits), _ptr(out), stream or None))
         return out
+
+
+CT_BASES_MAX_SETS = 4                                  # CURDLE_CT_BASES_MAX_SETS
+_msm_g1_ct_bases_sets_batch = _sig("curdle_msm_g1_ct_bases_sets_batch", C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t,
+                                   C.c_uint, _vp)
+_msm_g1_ct_bases_sets_batch_device = _sig("curdle_msm_g1_ct_bases_sets_batch_device", C.c_int, _vp, C.c_size_t, _vp, _vp, _vp,
+                                          C.c_size_t, C.c_uint, _vp, _vp)
+
+
+def _set_handles(sets):
+    return (C.c_void_p * max(1, len(sets)))(*[s._h for s in sets])
+
+
+def msm_g1_ct_bases_sets_batch(sets, rows, scalars, offsets, scalar_bits: int = 255) -> np.ndarray:
+    """CtBases.msm_batch over up to four CtBases of one chunk_bits in one call (curdle_msm_g1_ct_bases_sets_batch): rows
+    index the concatenation of the sets -> uint64[k, 18], bit for bit the batch over one handle of the concatenated
+    points."""
+    sc, r = _as_u64(scalars, 4), CtBases._rows(rows)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    k = len(offs) - 1
+    out = np.zeros((k, 18), dtype=np.uint64)
+    _check(_msm_g1_ct_bases_sets_batch(_set_handles(sets), len(sets), None if r is None else _ptr(r), _ptr(sc), _ptr(offs), k,
+                                       int(scalar_bits), _ptr(out)))
+    return out
+
+
+def msm_g1_ct_bases_sets_batch_device(sets, rows, d_scalars: int, offsets, scalar_bits: int = 255, stream: int = 0) -> np.ndarray:
+    """msm_g1_ct_bases_sets_batch on device-resident scalars (a raw device pointer, a multiple of 16)."""
+    r = CtBases._rows(rows)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    k = len(offs) - 1
+    out = np.zeros((k, 18), dtype=np.uint64)
+    _check(_msm_g1_ct_bases_sets_batch_device(_set_handles(sets), len(sets), None if r is None else _ptr(r), d_scalars or None,
+                                              _ptr(offs), k, int(scalar_bits), _ptr(out), stream or None))
+    return out
 
 
 def stat_msm_ct_bases() -> dict:
@@ -1523,6 +1561,65 @@ def whisk_generate_shuffle_proof_ct(crs: CRS, pre_trackers, rand: Rand):
     _check(_whisk_gen_shuffle_ct(crs._h, _ptr(pre), len(pre_trackers), rand._h, _ptr(post), _ptr(proof)))
     pb = post.tobytes()
     return [pb[96 * i: 96 * (i + 1)] for i in range(len(pre_trackers))], proof.tobytes()
+
+
+_prover_ct_create = _sig("curdle_prover_ct_create", C.c_int, _vp, C.c_uint, C.POINTER(C.c_void_p))
+_prover_ct_free = _sig("curdle_prover_ct_free", None, _vp)
+_prover_ct_prove = _sig("curdle_prover_ct_prove", C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
+                        C.c_size_t, C.POINTER(C.c_size_t))
+_prover_ct_whisk = _sig("curdle_prover_ct_whisk_shuffle_proof", C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, _vp)
+_stat_alg_msm_resident = _sig("curdle_stat_alg_msm_resident", C.c_int, C.POINTER(C.c_ulonglong))
+
+
+class ProverCt:
+    """A constant-time prover over one CRS (curdle_prover_ct): the CRS's points live in a constant-time base table made
+    once, and every MSM of a Prove walks chunk_bits steps over resident tables instead of 255.  prove() and
+    whisk_shuffle_proof() give prove_ct's and whisk_generate_shuffle_proof_ct's bytes and draws.  The CRS must outlive
+    the handle (this object keeps a reference)."""
+
+    def __init__(self, crs: CRS, chunk_bits: int = 0):
+        self._h = C.c_void_p()
+        self.crs = crs
+        _check(_prover_ct_create(crs._h, int(chunk_bits), C.byref(self._h)))
+
+    def free(self):
+        if self._h:
+            _prover_ct_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:       # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def prove(self, Rs, Ss, Ts, Us, M, perm, k, rs_m, rand: Rand) -> bytes:
+        Rs, Ss, Ts, Us = (_as_u64(a, 12) for a in (Rs, Ss, Ts, Us))
+        M, k, rs_m = _as_u64(M), _as_u64(k), _as_u64(rs_m)
+        perm = np.ascontiguousarray(perm, dtype=np.uint32)
+        cap = 1 << 16
+        buf = np.zeros(cap, dtype=np.uint8)
+        n = C.c_size_t(0)
+        _check(_prover_ct_prove(self._h, _ptr(Rs), _ptr(Ss), _ptr(Ts), _ptr(Us), self.crs.ell, _ptr(M), _ptr(perm), _ptr(k),
+                                _ptr(rs_m), rand._h, _ptr(buf), cap, C.byref(n)))
+        return bytes(buf[: n.value])
+
+    def whisk_shuffle_proof(self, pre_trackers, rand: Rand):
+        pre = _bytes_arr(b"".join(pre_trackers))
+        post = np.zeros(96 * len(pre_trackers), dtype=np.uint8)
+        proof = np.zeros(WHISK_SHUFFLE_PROOF_SIZE, dtype=np.uint8)
+        _check(_prover_ct_whisk(self._h, _ptr(pre), len(pre_trackers), rand._h, _ptr(post), _ptr(proof)))
+        pb = post.tobytes()
+        return [pb[96 * i: 96 * (i + 1)] for i in range(len(pre_trackers))], proof.tobytes()
+
+
+def stat_alg_msm_resident() -> dict:
+    """The funnel's calls under an alg::ResidentBasesScope: those that went to the MSM over resident tables and their
+    pairs, and those that took the unchunked constant-time path and their pairs."""
+    out = (C.c_ulonglong * 4)()
+    _check(_stat_alg_msm_resident(out))
+    return {"resident_calls": int(out[0]), "resident_pairs": int(out[1]), "fallback_calls": int(out[2]),
+            "fallback_pairs": int(out[3])}
 
 
 _whisk_gen_shuffle_batch = _sig("curdle_whisk_generate_shuffle_proof_batch", C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp,

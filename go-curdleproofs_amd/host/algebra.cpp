@@ -9,10 +9,12 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <stdexcept>
 #include <system_error>
 #include <thread>
+#include <unordered_map>
 
 #include "../../include/curdle_msm.h"
 
@@ -35,6 +37,16 @@ extern "C" int curdle_fr_permute_ct_batch(const uint64_t* in, const uint32_t* pe
 extern "C" int curdle_g1_scalar_mul_batch_ex(const uint64_t* points, const uint64_t* scalars, size_t n_scalars,
                                              const uint64_t* addends, size_t n, unsigned flags, uint64_t* out_affine)
     __attribute__((weak));
+
+// The constant-time base tables and the MSM over several of them (csrc/msm_ct_bases_api.hip), weak like the names above:
+// alg::ResidentBases and the route under an alg::ResidentBasesScope need them, and ResidentBasesScope::Available() says
+// whether they are linked.
+extern "C" int curdle_ct_bases_create(const uint64_t* points, size_t n, unsigned chunk_bits, curdle_ct_bases** out)
+    __attribute__((weak));
+extern "C" void curdle_ct_bases_free(curdle_ct_bases* b) __attribute__((weak));
+extern "C" int curdle_msm_g1_ct_bases_sets_batch(const curdle_ct_bases* const* sets, size_t n_sets, const uint32_t* rows,
+                                                 const uint64_t* scalars, const size_t* offsets, size_t k,
+                                                 unsigned scalar_bits, uint64_t* out_jac) __attribute__((weak));
 
 namespace curdle {
 namespace alg {
@@ -403,20 +415,155 @@ static int no_ct_backend() {
   return curdle_set_last_error(CURDLE_ENODEV, "the constant-time MSM is not part of this backend: no device code to run it on");
 }
 
+// ------------------------------------------------------------ the fourth switch ---
+static_assert(sizeof(G1Affine) == 96, "a base record is a gnark G1Affine");
+struct ResidentBases::Impl {
+  using Key = std::array<uint64_t, 12>;
+  struct Hash {
+    size_t operator()(const Key& k) const {
+      uint64_t h = 0x9e3779b97f4a7c15ull;
+      for (uint64_t w : k) h = (h ^ w) * 0xff51afd7ed558ccdull + (h >> 29);
+      return (size_t)h;
+    }
+  };
+  std::unordered_map<Key, uint32_t, Hash> rows;
+  static Key KeyOf(const G1Affine& p) {
+    Key k;
+    memcpy(k.data(), &p, 96);
+    return k;
+  }
+};
+
+static thread_local ResidentBases* t_resident = nullptr;
+static std::atomic<unsigned long long> g_resident_counters[4];
+
+ResidentBases::ResidentBases(unsigned chunk_bits) : chunk_bits_(ChunkBitsOf(chunk_bits)), map_(new Impl()) {
+  if (chunk_bits_ != 8 && chunk_bits_ != 16 && chunk_bits_ != 32 && chunk_bits_ != 64) {
+    delete map_;
+    throw MsmError("resident bases: chunk_bits is not 8, 16, 32, 64 or 0", CURDLE_EINVAL);
+  }
+}
+
+ResidentBases::~ResidentBases() {
+  for (size_t s = 0; s < handles_.size(); s++)
+    if (owned_[s] && curdle_ct_bases_free) curdle_ct_bases_free(static_cast<curdle_ct_bases*>(const_cast<void*>(handles_[s])));
+  delete map_;
+}
+
+void ResidentBases::Index(const std::vector<G1Affine>& points) {
+  for (size_t i = 0; i < points.size(); i++) map_->rows.emplace(Impl::KeyOf(points[i]), (uint32_t)(rows_ + i));  // the first occurrence wins
+  rows_ += points.size();
+}
+
+void ResidentBases::Add(const std::vector<G1Affine>& points) {
+  if (handles_.size() >= kMaxSets) throw MsmError("resident bases: a registry holds at most four sets", CURDLE_EINVAL);
+  if (!ResidentBasesScope::Available()) {
+    const int rc = curdle_set_last_error(CURDLE_ENODEV, "the constant-time base tables are not part of this backend: no device code to run them on");
+    throw msm_error(rc);
+  }
+  curdle_ct_bases* h = nullptr;
+  const int rc = curdle_ct_bases_create(reinterpret_cast<const uint64_t*>(points.data()), points.size(), chunk_bits_, &h);
+  if (rc != CURDLE_OK) throw msm_error(rc);
+  handles_.push_back(h);
+  owned_.push_back(1);
+  Index(points);
+}
+
+void ResidentBases::AddShared(const void* handle, const std::vector<G1Affine>& points) {
+  if (handles_.size() >= kMaxSets) throw MsmError("resident bases: a registry holds at most four sets", CURDLE_EINVAL);
+  handles_.push_back(handle);
+  owned_.push_back(0);
+  Index(points);
+}
+
+bool ResidentBases::Find(const G1Affine& p, uint32_t* row) const {
+  const auto it = map_->rows.find(Impl::KeyOf(p));
+  if (it == map_->rows.end()) return false;
+  *row = it->second;
+  return true;
+}
+
+ResidentBasesScope::ResidentBasesScope(ResidentBases& bases) : prev_(t_resident) { t_resident = &bases; }
+ResidentBasesScope::~ResidentBasesScope() { t_resident = prev_; }
+ResidentBases* ResidentBasesScope::Active() { return t_resident && !t_resident->Declined() ? t_resident : nullptr; }
+bool ResidentBasesScope::Available() { return curdle_ct_bases_create && curdle_ct_bases_free && curdle_msm_g1_ct_bases_sets_batch; }
+
+void ReadResidentCounters(unsigned long long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_resident_counters[i].load(std::memory_order_relaxed);
+}
+
+namespace {
+template <class T>
+struct WipeOnExit {  // a concatenated copy of secrets does not outlive the call that made it
+  std::vector<T>& v;
+  bool on;
+  ~WipeOnExit() {
+    if (on && !v.empty()) explicit_bzero(v.data(), v.size() * sizeof(T));
+  }
+};
+
+struct BaseRun {
+  const G1Affine* p;
+  size_t n;
+};
+constexpr size_t kResidentMaxTerms = 65536, kResidentMaxMsms = 4096;  // curdle_msm_g1_ct_bases_sets_batch's limits
+
+// The registry this call consults: the thread's, under a ConstantTimeMsmScope and outside a lockstep group.
+ResidentBases* resident_registry(bool ct) { return ct && !t_lockstep ? t_resident : nullptr; }
+
+// Whether a call of `msms` MSMs over the base runs goes to the resident tables, and then its row list: the shape fits
+// one pass and every base is a resident record.  Public shapes and public points only.
+bool resident_rows(const ResidentBases* rb, const std::vector<BaseRun>& runs, size_t msms, std::vector<uint32_t>* rows) {
+  if (!rb || !rb->Sets() || !ResidentBasesScope::Available() || msms > kResidentMaxMsms) return false;
+  size_t pairs = 0, cap = kResidentMaxTerms;
+  for (const BaseRun& r : runs) pairs += r.n;
+  const long long knob = knobs::get(knobs::PROVE_RESIDENT_TERMS);
+  if (knob > 0 && (size_t)knob < cap) cap = (size_t)knob;
+  if (pairs > cap / rb->Chunks()) return false;
+  rows->resize(pairs);
+  size_t q = 0;
+  for (const BaseRun& r : runs)
+    for (size_t i = 0; i < r.n; i++)
+      if (!rb->Find(r.p[i], &(*rows)[q++])) return false;
+  return true;
+}
+
+int resident_call(const ResidentBases* rb, const std::vector<uint32_t>& rows, const uint64_t* scalars, const size_t* offsets,
+                  size_t k, uint64_t* out) {
+  return curdle_msm_g1_ct_bases_sets_batch(reinterpret_cast<const curdle_ct_bases* const*>(rb->Handles()), rb->Sets(), rows.data(),
+                                           scalars, offsets, k, kCtScalarBits, out);
+}
+
+// A successful constant-time call under an active registry: which of the two routes it took.
+void count_resident(const ResidentBases* rb, bool resident, size_t pairs) {
+  if (!rb) return;
+  g_resident_counters[resident ? 0 : 2].fetch_add(1, std::memory_order_relaxed);
+  g_resident_counters[resident ? 1 : 3].fetch_add(pairs, std::memory_order_relaxed);
+}
+}  // namespace
+
 Point MultiExp(const std::vector<G1Affine>& points, const std::vector<Scalar>& scalars) {
   if (points.size() != scalars.size()) throw std::runtime_error("computing msm: len(points) != len(scalars)");
   if (t_lockstep) return LockstepMsms(Lockstep::Request::kMultiExp, {{points.data(), scalars.data(), points.size()}})[0];
   const bool ct = t_msm_ct;
+  const ResidentBases* rb = resident_registry(ct);
+  std::vector<uint32_t> rows;
+  const bool resident = resident_rows(rb, {{points.data(), points.size()}}, 1, &rows);
   const uint64_t* P = reinterpret_cast<const uint64_t*>(points.data());
   const uint64_t* S = reinterpret_cast<const uint64_t*>(scalars.data());
   uint64_t out[18];
   int rc;
-  if (!ct)
+  if (!ct) {
     rc = curdle_msm_g1(P, S, points.size(), out);
-  else
+  } else if (resident) {
+    const size_t off[2] = {0, points.size()};
+    rc = resident_call(rb, rows, S, off, 1, out);
+  } else {
     rc = curdle_msm_g1_ct ? curdle_msm_g1_ct(P, S, points.size(), kCtScalarBits, out) : no_ct_backend();
+  }
   if (rc != CURDLE_OK) throw msm_error(rc);
   count_msm(ct, points.size());
+  count_resident(rb, resident, points.size());
   return Point::FromJac(out);
 }
 
@@ -435,7 +582,12 @@ std::vector<Point> MultiExpBatch(const std::vector<const std::vector<G1Affine>*>
     for (size_t j = 0; j < k; j++) msms[j] = {points[j]->data(), scalars[j]->data(), points[j]->size()};
     return LockstepMsms(Lockstep::Request::kMultiExpBatch, std::move(msms));
   }
-  std::vector<G1Affine> P(off[k]);
+  const ResidentBases* rb = resident_registry(ct);
+  std::vector<uint32_t> rows;
+  std::vector<BaseRun> runs(k);
+  for (size_t j = 0; j < k; j++) runs[j] = {points[j]->data(), points[j]->size()};
+  const bool resident = resident_rows(rb, runs, k, &rows);
+  std::vector<G1Affine> P(resident ? 0 : off[k]);  // the resident call names its bases by row
   std::vector<Scalar> S(off[k]);
   struct Clear {  // the concatenated copy of the scalars does not outlive a constant-time call
     std::vector<Scalar>& v;
@@ -445,7 +597,7 @@ std::vector<Point> MultiExpBatch(const std::vector<const std::vector<G1Affine>*>
     }
   } clear{S, ct};
   for (size_t j = 0; j < k; j++) {
-    std::copy(points[j]->begin(), points[j]->end(), P.begin() + off[j]);
+    if (!resident) std::copy(points[j]->begin(), points[j]->end(), P.begin() + off[j]);
     std::copy(scalars[j]->begin(), scalars[j]->end(), S.begin() + off[j]);
   }
   std::vector<uint64_t> out(18 * k);
@@ -454,10 +606,13 @@ std::vector<Point> MultiExpBatch(const std::vector<const std::vector<G1Affine>*>
   int rc;
   if (!ct)
     rc = curdle_msm_g1_batch(Pw, Sw, off.data(), k, out.data());
+  else if (resident)
+    rc = resident_call(rb, rows, Sw, off.data(), k, out.data());
   else
     rc = curdle_msm_g1_ct_batch ? curdle_msm_g1_ct_batch(Pw, Sw, off.data(), k, kCtScalarBits, out.data()) : no_ct_backend();
   if (rc != CURDLE_OK) throw msm_error(rc);
   count_msm(ct, off[k]);
+  count_resident(rb, resident, off[k]);
   std::vector<Point> res(k);
   for (size_t j = 0; j < k; j++) res[j] = Point::FromJac(out.data() + 18 * j);
   return res;
@@ -483,14 +638,32 @@ std::vector<Point> MultiExpShared(const std::vector<const std::vector<G1Affine>*
     return LockstepMsms(Lockstep::Request::kMultiExpShared, std::move(msms));
   }
   const uint64_t* Sw = reinterpret_cast<const uint64_t*>(scalars.data());
+  const ResidentBases* rb = resident_registry(ct);
+  std::vector<uint32_t> rows;
+  std::vector<BaseRun> runs(k);
+  for (size_t j = 0; j < k; j++) runs[j] = {sets[j]->data(), sets[j]->size()};
+  const bool resident = resident_rows(rb, runs, k, &rows);
   int rc;
-  if (!ct)
+  if (!ct) {
     rc = curdle_msm_g1_multi(ptrs.data(), k, Sw, scalars.size(), out.data());
-  else
+  } else if (resident) {
+    // one batch of k MSMs: the scalar vector once per set, in a copy that does not outlive the call
+    const size_t n = scalars.size();
+    std::vector<Scalar> S(k * n);
+    WipeOnExit<Scalar> wipe{S, true};
+    std::vector<size_t> off(k + 1, 0);
+    for (size_t j = 0; j < k; j++) {
+      std::copy(scalars.begin(), scalars.end(), S.begin() + j * n);
+      off[j + 1] = off[j] + n;
+    }
+    rc = resident_call(rb, rows, reinterpret_cast<const uint64_t*>(S.data()), off.data(), k, out.data());
+  } else {
     rc = curdle_msm_g1_ct_multi ? curdle_msm_g1_ct_multi(ptrs.data(), k, Sw, scalars.size(), kCtScalarBits, out.data())
                                 : no_ct_backend();
+  }
   if (rc != CURDLE_OK) throw msm_error(rc);
   count_msm(ct, k * scalars.size());
+  count_resident(rb, resident, k * scalars.size());
   std::vector<Point> res(k);
   for (size_t j = 0; j < k; j++) res[j] = Point::FromJac(out.data() + 18 * j);
   return res;
@@ -637,15 +810,6 @@ void Lockstep::Rendezvous(size_t member, Request* r) {
 }
 
 namespace {
-template <class T>
-struct WipeOnExit {  // a concatenated copy of secrets does not outlive the coalesced call
-  std::vector<T>& v;
-  bool on;
-  ~WipeOnExit() {
-    if (on && !v.empty()) explicit_bzero(v.data(), v.size() * sizeof(T));
-  }
-};
-
 // Members per coalesced call: as many whole members as fit `cap` units (and `cap_members`), at least one -- a member
 // that alone is too large for the primitive gets the primitive's own refusal, as its single call would.
 size_t members_per_call(size_t unit, size_t cap, size_t cap_members) {

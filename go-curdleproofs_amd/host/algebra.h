@@ -283,6 +283,77 @@ class LockstepScope {
   size_t prev_member_;
 };
 
+// The fourth switch: the constant-time MSMs over RESIDENT tables of PUBLIC bases.  Every base of the prover's MSMs is
+// public and known before its scalars exist -- a CRS point, a record of the instance vectors, the point at infinity,
+// the aggregates R and S -- so it can live in a curdle_ct_bases table (csrc/msm_ct_bases_api.hip), over which a lane walks
+// chunk_bits steps instead of 255.
+//
+// ResidentBases is the registry of such tables for one Prove: an ordered list of at most kMaxSets sets at one
+// chunk_bits, and an index of every 96-byte G1Affine record by value -- a hash map from the record to its global row
+// (set s covers the rows [B_s, B_s + n_s)), the first occurrence wins, the all-zero record (infinity) included.  The
+// points are public, so hashing them is fine; nothing about a scalar ever reaches the map.  Add creates a table and
+// owns it; AddShared names a table someone else owns (the prover handle's CRS set) and only indexes it.  Not
+// thread-safe: one registry per call.
+class ResidentBases {
+ public:
+  static constexpr size_t kMaxSets = 4;  // CURDLE_CT_BASES_MAX_SETS
+  // 0 is the library's choice, 16; the width in force is what every table is created with, so 0 never reaches a creator.
+  static unsigned ChunkBitsOf(unsigned chunk_bits) { return chunk_bits ? chunk_bits : 16; }
+  explicit ResidentBases(unsigned chunk_bits);
+  ~ResidentBases();                             // frees the sets Add made
+  ResidentBases(const ResidentBases&) = delete;
+  ResidentBases& operator=(const ResidentBases&) = delete;
+  // A new set over `points`.  Throws MsmError: a fifth set (CURDLE_EINVAL), a backend without the tables
+  // (CURDLE_ENODEV), or curdle_ct_bases_create's own refusal.
+  void Add(const std::vector<G1Affine>& points);
+  // A set over `points` whose table `handle` (a curdle_ct_bases* over exactly these points at this registry's
+  // chunk_bits) belongs to the caller and outlives the registry.
+  void AddShared(const void* handle, const std::vector<G1Affine>& points);
+  // A registry that declines: it stays empty, ResidentBasesScope::Active() does not name it (so the prover changes
+  // nothing), and the funnel only counts the calls under its scope as having taken the old path.  What a prover handle
+  // runs under when a Prove's instance vectors do not fit a table.
+  void Decline() { declined_ = true; }
+  bool Declined() const { return declined_; }
+  size_t Sets() const { return handles_.size(); }
+  size_t Rows() const { return rows_; }
+  unsigned ChunkBits() const { return chunk_bits_; }                       // the width in force
+  unsigned Chunks() const { return (255 + chunk_bits_ - 1) / chunk_bits_; }  // C = Cb at 255 bits
+  bool Find(const G1Affine& p, uint32_t* row) const;            // the record's global row
+  const void* const* Handles() const { return handles_.data(); }
+
+ private:
+  struct Impl;
+  void Index(const std::vector<G1Affine>& points);
+  unsigned chunk_bits_;
+  bool declined_ = false;
+  size_t rows_ = 0;
+  std::vector<const void*> handles_;
+  std::vector<char> owned_;
+  Impl* map_;
+};
+
+// While one lives on a thread that is also under a ConstantTimeMsmScope and NOT in a LockstepScope, MultiExp,
+// MultiExpBatch and MultiExpShared resolve every base of a call to a row of `bases`; if all resolve, the call's terms
+// fit one pass (pairs x Cb <= 65,536, or the knob PROVE_RESIDENT_TERMS when a test lowered it) and it has at most 4,096
+// MSMs, the call is ONE curdle_msm_g1_ct_bases_sets_batch at 255 bits (MultiExpShared repeats the scalar vector per set in
+// a concatenated copy that is cleared on every way out).  Otherwise the call takes the path it takes without this
+// scope, untouched.  The route depends on shapes and public points only.  Same results, bit for bit.
+class ResidentBasesScope {
+ public:
+  explicit ResidentBasesScope(ResidentBases& bases);
+  ~ResidentBasesScope();
+  ResidentBasesScope(const ResidentBasesScope&) = delete;
+  ResidentBasesScope& operator=(const ResidentBasesScope&) = delete;
+  static ResidentBases* Active();  // the registry this thread's MSMs consult, or null (also for one that declines)
+  static bool Available();         // the backend has the tables and the call over several of them
+
+ private:
+  ResidentBases* prev_;
+};
+// resident calls | their pairs | calls under an active scope (and a ConstantTimeMsmScope, outside a lockstep group) that
+// took the old path | their pairs; counted when the call they made succeeded.
+void ReadResidentCounters(unsigned long long out[4]);
+
 // k jobs in lockstep: job(i) for i < members, in groups of at most group_size, ONE std::thread per member of a group (a
 // member blocked at the rendezvous cannot be suspended, so no pool) and each under a LockstepScope of its group -- with
 // constant_time also under a ConstantTimeMsmScope and a SecretOpsScope -- and on the device the calling thread has

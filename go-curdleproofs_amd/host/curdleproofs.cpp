@@ -718,7 +718,11 @@ Proof Prove(std::vector<G1Affine> Gs, std::vector<G1Affine> Gs_prime, const Poin
     else
       coefGp.assign(N, Scalar::One());
   }
-  const G1Affine H_affine = H.Affine();
+  // Under an alg::ResidentBasesScope H = beta Hcrs, made mid-proof, is in no table; Hcrs is.  s H = (s beta) Hcrs: the
+  // rounds push Hcrs with s beta instead -- the same group element, the same canonical result, the same proof bytes.
+  const bool h_by_crs = !fold_bases && alg::ResidentBasesScope::Active() != nullptr;
+  const G1Affine H_affine = h_by_crs ? AffineOf(Hcrs) : H.Affine();
+  const Scalar H_scale = h_by_crs ? beta : Scalar::One();
   while (n > 1) {  // :101-173
     n /= 2;
     const std::vector<Scalar> c_L(cs.begin(), cs.begin() + n), c_R(cs.begin() + n, cs.begin() + 2 * n);
@@ -752,9 +756,9 @@ Proof Prove(std::vector<G1Affine> Gs, std::vector<G1Affine> Gs_prime, const Poin
       // ... and H's multiples <c_L, d_R> H and <c_R, d_L> H (:113, :130) ride along as one more
       // pair of their MSM instead of a 255-step scalar multiplication on the host each
       G_R.push_back(H_affine);
-      s_cL.push_back(alg::InnerProduct(c_L, d_R));
+      s_cL.push_back(h_by_crs ? alg::InnerProduct(c_L, d_R) * H_scale : alg::InnerProduct(c_L, d_R));
       G_L.push_back(H_affine);
-      s_cR.push_back(alg::InnerProduct(c_R, d_L));
+      s_cR.push_back(h_by_crs ? alg::InnerProduct(c_R, d_L) * H_scale : alg::InnerProduct(c_R, d_L));
       ms = alg::MultiExpBatch({&G_R, &Gp_L, &G_L, &Gp_R}, {&s_cL, &s_dR, &s_cR, &s_dL});
     }
     const Point L_C = fold_bases ? ms[0] + H.Mul(alg::InnerProduct(c_L, d_R)) : ms[0];
@@ -1329,6 +1333,9 @@ Proof Prove(const CRS& crs, const std::vector<G1Affine>& Rs, const std::vector<G
     proof.R = rs[0];
     proof.S = rs[1];
   }
+  // R and S are public (public challenges over public points) and bases of the MSMs below: under an
+  // alg::ResidentBasesScope they become the late set.  One that is infinity is the zero record, resident already.
+  if (alg::ResidentBases* resident = alg::ResidentBasesScope::Active()) resident->Add({AffineOf(proof.R), AffineOf(proof.S)});
   if (secret_ops) {
     CommitPairSecret(crs.Gt, crs.Gu, crs.H, proof.R, proof.S, k, r_t, r_u, &proof.T, &proof.U);
   } else {

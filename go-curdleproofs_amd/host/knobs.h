@@ -54,6 +54,7 @@ enum Id {
   G1_MUL_CT_PASS,         // curdle_g1_scalar_mul_batch_ex / _device_ex under CURDLE_G1_MUL_CONSTANT_TIME: pairs per pass (one launch of k_g1_mul_ct), rounded down to a multiple of 256, at least 256; unset: 2^20 (g1_mul_ct_api.hip)
   PROVE_BATCH_GROUP,      // curdle_prove_batch, curdle_whisk_generate_shuffle_proof_batch: members proved in lockstep at a time, one thread each (1..64); unset, 0 or above 64: 64 (proto_api.cpp)
   PROVE_BATCH_PAIRS,      // test hook: lowers the (point, scalar) pairs or records from which a lockstep group's coalesced call is split by whole members, so a test can reach the split; unset or 0: the primitives' own limits (alg::Lockstep, algebra.cpp)
+  PROVE_RESIDENT_TERMS,   // test hook: lowers the terms (pairs x chunks) up to which a funnel call under an alg::ResidentBasesScope goes to the resident tables, so a test can reach the old path beside the new one; unset, 0 or above 65,536: the primitive's own limit (algebra.cpp)
   COUNT
 };
 // The knob's value, or -1 if it is not set (every knob's valid values are >= 0).

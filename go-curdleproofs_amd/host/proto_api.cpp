@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <atomic>
 #include <exception>
+#include <memory>
 #include <new>
 #include <stdexcept>
 #include <thread>
@@ -199,6 +200,112 @@ extern "C" int curdle_prove_ct(const curdle_crs* crs, const uint64_t* Rs, const 
   alg::ConstantTimeMsmScope msms;
   alg::SecretOpsScope secret_ops;
   return curdle_prove(crs, Rs, Ss, Ts, Us, ell, M, perm, k, rs_m, rand, proof_out, cap, proof_len);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// curdle_prover_ct: curdle_prove_ct over resident tables.  The handle owns ONE curdle_ct_bases over the CRS's points --
+// Gs | Hs | H | Gt | Gu | one all-zero record (the point at infinity, which the same-multiscalar bases pad with) -- made
+// once; a Prove runs curdle_prove_ct's body under one more scope, an alg::ResidentBasesScope whose registry is
+// {the handle's CRS set, this call's Rs | Ss | Ts | Us} and later {R, S} (curdleproofs.cpp), so every funnel call
+// resolves to rows and is one curdle_msm_g1_ct_bases_sets_batch.  The table names are weak, as in host/algebra.cpp.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int curdle_ct_bases_create(const uint64_t* points, size_t n, unsigned chunk_bits, curdle_ct_bases** out)
+    __attribute__((weak));
+extern "C" void curdle_ct_bases_free(curdle_ct_bases* b) __attribute__((weak));
+
+struct curdle_prover_ct {
+  const curdle_crs* crs = nullptr;
+  unsigned c = 0, chunks = 0;    // chunk_bits in force and C = ceil(255 / c)
+  std::vector<G1Affine> points;  // what the table holds, in its order
+  curdle_ct_bases* table = nullptr;
+};
+
+static constexpr size_t kCtBasesMaxRecords = 65536;  // curdle_ct_bases_create's limit on n C
+
+extern "C" int curdle_prover_ct_create(const curdle_crs* crs, unsigned chunk_bits, curdle_prover_ct** out) {
+  if (out) *out = nullptr;
+  if (!crs || !out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  const unsigned c = alg::ResidentBases::ChunkBitsOf(chunk_bits);
+  if (c != 8 && c != 16 && c != 32 && c != 64) {
+    char msg[96];
+    snprintf(msg, sizeof(msg), "chunk_bits = %u is not 8, 16, 32, 64 or 0 (the library's choice)", chunk_bits);
+    return curdle_set_last_error(CURDLE_EINVAL, msg);
+  }
+  const unsigned chunks = (255 + c - 1) / c;
+  const proto::CRS& k = crs->crs;
+  const size_t n = k.Gs.size() + k.Hs.size() + 4;
+  if (n > kCtBasesMaxRecords / chunks) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "the CRS is too large for one table: (ell + 8) C = %zu x %u exceeds 65,536 records", n, chunks);
+    return curdle_set_last_error(CURDLE_EINVAL, msg);
+  }
+  if (!alg::ResidentBasesScope::Available() || !ProveCtBackend())
+    return curdle_set_last_error(CURDLE_ENODEV,
+                                 "curdle_prover_ct_create: the constant-time base tables and prover need the device backend and a device");
+  return Guard([&]() -> int {
+    std::unique_ptr<curdle_prover_ct> p(new curdle_prover_ct());
+    p->crs = crs;
+    p->c = c;
+    p->chunks = chunks;
+    p->points = k.Gs;
+    p->points.insert(p->points.end(), k.Hs.begin(), k.Hs.end());
+    p->points.push_back(k.H.Affine());
+    p->points.push_back(k.Gt.Affine());
+    p->points.push_back(k.Gu.Affine());
+    G1Affine zero;
+    memset(&zero, 0, sizeof(zero));
+    p->points.push_back(zero);
+    if (int rc = curdle_ct_bases_create(reinterpret_cast<const uint64_t*>(p->points.data()), p->points.size(), c, &p->table)) return rc;
+    *out = p.release();
+    return CURDLE_OK;
+  });
+}
+
+extern "C" void curdle_prover_ct_free(curdle_prover_ct* p) {
+  if (!p) return;
+  if (p->table && curdle_ct_bases_free) curdle_ct_bases_free(p->table);
+  delete p;
+}
+
+extern "C" int curdle_prover_ct_prove(curdle_prover_ct* p, const uint64_t* Rs, const uint64_t* Ss, const uint64_t* Ts,
+                                      const uint64_t* Us, size_t ell, const uint64_t M[18], const uint32_t* perm,
+                                      const uint64_t k[4], const uint64_t rs_m[16], curdle_rand* rand, uint8_t* proof_out,
+                                      size_t cap, size_t* proof_len) {
+  // curdle_prove_ct's refusals, in its order
+  if (!p || !Rs || !Ss || !Ts || !Us || !M || !perm || !k || !rs_m || !rand || !proof_len)
+    return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  const curdle_crs* crs = p->crs;
+  if (ell != crs->crs.Gs.size()) return curdle_set_last_error(CURDLE_EINVAL, "ell does not match the CRS");
+  if (ell > kProveCtMaxEll)
+    return curdle_set_last_error(CURDLE_EINVAL, "ell exceeds the 4,096 the constant-time prover supports");
+  if (proto::ProverFoldBasesEnabled())
+    return curdle_set_last_error(CURDLE_EINVAL,
+                                 "CURDLE_PROVE_MSM_CONSTANT_TIME with PROVER_FOLD_BASES set: that prover multiplies H by a "
+                                 "secret inner product on the host");
+  if (!ProveCtBackend())
+    return curdle_set_last_error(CURDLE_ENODEV,
+                                 "curdle_prove_ct: the constant-time MSM and the oblivious gather need the device backend and a device");
+  // Before anything is drawn from rand: this call's registry.  The CRS set is the handle's, shared and read-only; the
+  // instance vectors are this call's set, freed with the registry on every way out.  A public decision on ell: instance
+  // vectors beyond one table (4 ell C > 65,536) leave the registry empty and declining, and the call runs exactly as
+  // curdle_prove_ct.
+  return Guard([&]() -> int {
+    alg::ResidentBases registry(p->c);
+    if (4 * ell > kCtBasesMaxRecords / p->chunks) {
+      registry.Decline();
+    } else {
+      registry.AddShared(p->table, p->points);
+      std::vector<G1Affine> inst(4 * ell);
+      const uint64_t* parts[4] = {Rs, Ss, Ts, Us};
+      for (int i = 0; i < 4; i++)
+        if (ell) memcpy(inst.data() + i * ell, parts[i], ell * 96);
+      registry.Add(inst);
+    }
+    alg::ConstantTimeMsmScope msms;
+    alg::SecretOpsScope secret_ops;
+    alg::ResidentBasesScope resident(registry);
+    return curdle_prove(crs, Rs, Ss, Ts, Us, ell, M, perm, k, rs_m, rand, proof_out, cap, proof_len);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -616,8 +723,9 @@ extern "C" int curdle_whisk_generate_shuffle_proof(const curdle_crs* crs, const 
 // addresses: the draws and their order are the unflagged call's, the decode is public, the shuffle step runs under
 // CURDLE_SHUFFLE_CONSTANT_TIME and the proof through curdle_prove_ct.  This call's own copies of k, the permutation and
 // rs_m are overwritten on every way out.
-extern "C" int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, const uint8_t* pre_trackers, size_t n,
-                                                      curdle_rand* rand, uint8_t* post_trackers_out, uint8_t* proof_out) {
+// `prover`: null for curdle_prove_ct, or the handle whose curdle_prover_ct_prove makes the proof; nothing else differs.
+static int WhiskShuffleProofCt(const curdle_crs* crs, curdle_prover_ct* prover, const uint8_t* pre_trackers, size_t n,
+                               curdle_rand* rand, uint8_t* post_trackers_out, uint8_t* proof_out) {
   if (!crs || !pre_trackers || !rand || !post_trackers_out || !proof_out)
     return curdle_set_last_error(CURDLE_EINVAL, "null argument");
   if (!curdle_shuffle_permute_commit_ex || !ProveCtBackend())
@@ -655,8 +763,10 @@ extern "C" int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, con
     if (rc != CURDLE_OK) return rc;
     std::vector<uint8_t> body(whisk::WHISK_SHUFFLE_PROOF_SIZE);
     size_t body_len = 0;
-    rc = curdle_prove_ct(crs, R64, S64, T64, U64, n, M, s.permutation.data(), s.k, s.rs_m, rand, body.data(), body.size(),
-                         &body_len);  // :88
+    rc = prover ? curdle_prover_ct_prove(prover, R64, S64, T64, U64, n, M, s.permutation.data(), s.k, s.rs_m, rand, body.data(),
+                                         body.size(), &body_len)
+                : curdle_prove_ct(crs, R64, S64, T64, U64, n, M, s.permutation.data(), s.k, s.rs_m, rand, body.data(), body.size(),
+                                  &body_len);  // :88
     if (rc != CURDLE_OK) return rc;
     whisk::SerializeShuffleProof(Point::FromJac(M), body.data(), body_len, proof_out);
     for (size_t i = 0; i < n; i++) {  // :109-112
@@ -665,6 +775,23 @@ extern "C" int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, con
     }
     return CURDLE_OK;
   });
+}
+
+extern "C" int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, const uint8_t* pre_trackers, size_t n,
+                                                      curdle_rand* rand, uint8_t* post_trackers_out, uint8_t* proof_out) {
+  return WhiskShuffleProofCt(crs, nullptr, pre_trackers, n, rand, post_trackers_out, proof_out);
+}
+
+// curdle_whisk_generate_shuffle_proof_ct with its Prove through the handle; the shuffle step is unchanged.
+extern "C" int curdle_prover_ct_whisk_shuffle_proof(curdle_prover_ct* p, const uint8_t* pre_trackers, size_t n, curdle_rand* rand,
+                                                    uint8_t* post_trackers_out, uint8_t* proof_out) {
+  return WhiskShuffleProofCt(p ? p->crs : nullptr, p, pre_trackers, n, rand, post_trackers_out, proof_out);
+}
+
+extern "C" int curdle_stat_alg_msm_resident(unsigned long long out[4]) {
+  if (!out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  alg::ReadResidentCounters(out);
+  return CURDLE_OK;
 }
 
 // curdle_whisk_generate_shuffle_proof (flags = 0) or curdle_whisk_generate_shuffle_proof_ct (under the flag) for k

@@ -1135,7 +1135,8 @@ int curdle_stat_msm_ct_batch(unsigned long long out[3]);   /* batched calls | MS
  * device-to-host copy is the results and the status word: one block of 144 k + 4 bytes.
  * WHAT THE FLAG PROMISES, WHAT IT DOES NOT PROMISE and what is OUTSIDE THE PROMISE are curdle_msm_g1_ct's, word for word.
  * The instruction stream and the address stream also depend on rows, on chunk_bits and on which table points are
- * infinity, all of which are public.  It is not a default: nothing in the library routes to these calls yet.
+ * infinity, all of which are public.  It is not a default: nothing in the library routes to these calls yet unless the
+ * caller asks for it by making a curdle_prover_ct (below), whose Proves send their MSMs to the sets form.
  * curdle_stat_msm_ct_bases: out[0] tables built on a device, out[1] calls, out[2] (pair, chunk) lanes walked by
  * k_msm_ct_walk_rows, out[3] MSMs finished that are not empty; completed calls that ran on a device only.  These calls
  * do not move curdle_stat_msm_ct (k_msm_ct_walk does not run); a batched one moves curdle_stat_msm_ct_batch by
@@ -1158,6 +1159,37 @@ int curdle_msm_g1_ct_bases_batch(const curdle_ct_bases* b, const uint32_t* rows,
 int curdle_msm_g1_ct_bases_batch_device(const curdle_ct_bases* b, const uint32_t* rows, const void* d_scalars,
                                         const size_t* offsets, size_t k, unsigned scalar_bits, uint64_t* out_jac, void* stream);
 int curdle_stat_msm_ct_bases(unsigned long long out[4]);  /* tables built | calls | (pair, chunk) lanes walked | MSMs finished */
+/* The batch over UP TO FOUR resident sets in one call: a prover's MSM mixes bases of several public sets -- a CRS, made
+ * once and kept, and the instance vectors of one proof -- and re-building the first inside a combined table per proof
+ * would throw away what the handle is for.
+ * sets: n_sets handles, 1 ... CURDLE_CT_BASES_MAX_SETS, all of one chunk_bits.  rows is a HOST array of PUBLIC indices
+ * into the concatenation of the sets: set s covers [B_s, B_s + n_s) with B_0 = 0 and B_(s+1) = B_s + n_s; an empty set
+ * covers nothing; rows may not be null when the call has pairs.
+ * Result j is, bit for bit, what curdle_msm_g1_ct_bases_batch returns for the same rows, scalars and offsets over ONE
+ * handle created from the concatenated points at the same chunk_bits -- and therefore what curdle_msm_g1_ct_batch and
+ * curdle_msm_g1_batch return on those pairs.  Everything else is curdle_msm_g1_ct_bases_batch's: the limits (n Cb <= 65,536
+ * terms, k <= 4,096), the one status word, out_jac untouched on a violation, the slot hold, the staging and the wiping,
+ * the counters (curdle_stat_msm_ct_bases and curdle_stat_msm_ct_batch move exactly as for the single-handle batch on the
+ * same pairs) and the promise: WHAT THE FLAG PROMISES, WHAT IT DOES NOT PROMISE and what is OUTSIDE THE PROMISE are
+ * curdle_msm_g1_ct's, word for word.  The ONE walk kernel, k_msm_ct_walk_rows, takes the sets as an argument by value (table,
+ * size and first index of each) and a call over one handle is its one-set case: a lane finds its set by at most three
+ * compares of rows[p] against the B_s.  Addresses, branch conditions and loop counts stay functions of public values
+ * only: rows, the sets' sizes, the chunk index, chunk_bits and scalar_bits.
+ * Refusals happen before any device work, in this order: a null argument (sets, any sets[s] of the first four, offsets;
+ * out_jac and the scalars when k > 0; rows when the offsets span a pair), n_sets = 0 or above 4, sets whose chunk_bits
+ * differ, then the single-handle batch's order: scalar_bits, k, offsets that decrease, the term total, a row index at
+ * or above B_(n_sets), and (the _device form) a device pointer that is not a multiple of 16.
+ * Every handle of a call is held from before its device work to behind it: a free during the call is deferred, for
+ * each of them, as for one handle.
+ * Cost: the single-handle batch's on the same pairs: 1.383 against 1.385 ms at 256 pairs, 1.815 against 1.823 ms at 2,048
+ * (profiles/r35_prove_ct_resident.json). */
+#define CURDLE_CT_BASES_MAX_SETS 4
+int curdle_msm_g1_ct_bases_sets_batch(const curdle_ct_bases* const* sets, size_t n_sets, const uint32_t* rows,
+                                      const uint64_t* scalars, const size_t* offsets, size_t k,
+                                      unsigned scalar_bits, uint64_t* out_jac);
+int curdle_msm_g1_ct_bases_sets_batch_device(const curdle_ct_bases* const* sets, size_t n_sets, const uint32_t* rows,
+                                             const void* d_scalars, const size_t* offsets, size_t k,
+                                             unsigned scalar_bits, uint64_t* out_jac, void* stream);
 /* curdle_prove with a flags word.  flags = 0 IS curdle_prove.  A bit that is not defined here: CURDLE_EINVAL before
  * anything else is looked at, with proof_out and *proof_len untouched.
  * CURDLE_PROVE_MSM_CONSTANT_TIME: every MSM of the proof -- the prover funnels them through three functions,
@@ -1277,6 +1309,60 @@ int curdle_prove_ct(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* S
 int curdle_whisk_generate_shuffle_proof_ct(const curdle_crs* crs, const uint8_t* pre_trackers, size_t n, curdle_rand* rand,
                                            uint8_t* post_trackers_out, uint8_t* proof_out);
 int curdle_stat_host_point_mul(unsigned long long* out);   /* calls of alg::Point::Mul on the CALLING THREAD */
+/* -------------------------------------------------------------------------
+ * A CONSTANT-TIME PROVER HANDLE: curdle_prove_ct over resident base tables.  Every base of the prover's MSMs is public
+ * and known before its scalars exist -- a CRS point, a record of Rs | Ss | Ts | Us, the point at infinity, the
+ * aggregates R and S, and H_beta = beta H, a public multiple of a CRS point -- so each of the proof's MSMs can be the
+ * chunked walk of curdle_msm_g1_ct_bases_sets_batch (chunk_bits steps a lane) instead of a lone 255-step chain.
+ * These are new entry points, not new flag bits; curdle_prove_ct, curdle_prove_ex, curdle_prove_batch and every other
+ * entry point keep their behaviour and their counters, and nothing becomes a default.
+ *
+ * curdle_prover_ct_create builds ONE table over Gs | Hs | H | Gt | Gu | one all-zero record of the CRS, by
+ * curdle_ct_bases_create: ell + 8 records.  chunk_bits: 0 is the library's 16; 8, 16, 32 and 64 are accepted as there.
+ * Lifetime, the copy on another context and the re-creation after curdle_shutdown are curdle_ct_bases's own.  THE CRS MUST
+ * OUTLIVE THE HANDLE.  Refusals, in this order, with *out null: a null argument, chunk_bits, a CRS too large for one
+ * table ((ell + 8) C > 65,536, C = ceil(255 / chunk_bits)), and no device or a backend without the primitives:
+ * CURDLE_ENODEV, no fallback.  curdle_prover_ct_free(NULL) does nothing.
+ *
+ * curdle_prover_ct_prove: the contract is curdle_prove_ct's, word for word, with the handle in the CRS's place: the same
+ * refusals in the same order (proof_out and *proof_len untouched, nothing drawn from rand), the same promise and what is
+ * outside it, the same proof bytes, rand in the same state afterwards.  The body is curdle_prove_ct's under one more
+ * scoped switch on the calling thread (alg::ResidentBasesScope): a registry of resident sets that starts as {the
+ * handle's CRS set, this call's Rs | Ss | Ts | Us} -- the second made before the first MSM and before anything is drawn
+ * from rand -- and receives {R, S} as a late set right after they exist.  Under it
+ *   - MultiExp, MultiExpBatch and MultiExpShared resolve every base of a call to a row by the record's value (a hash
+ *     map over PUBLIC points; nothing about a scalar reaches it) and make one curdle_msm_g1_ct_bases_sets_batch at 255
+ *     bits; a call with a base that does not resolve, or too large for one pass, takes curdle_prove_ct's path;
+ *   - the inner-product argument pushes H with the scalar s beta where it pushed H_beta = beta H with s: the same group
+ *     element, the same canonical result.
+ * The route depends on shapes and public points only.  If 4 ell C > 65,536 (ell > 1,024 at chunk_bits 16) the instance
+ * vectors do not fit a table and the call runs exactly as curdle_prove_ct, with nothing resident: a public decision on
+ * ell.  The per-call sets are freed on every way out.  The handle may be used by several threads at once: each call has
+ * its own registry, and the CRS set is shared and read-only.
+ * curdle_prover_ct_whisk_shuffle_proof is curdle_whisk_generate_shuffle_proof_ct with its Prove in that form; the
+ * shuffle step is unchanged.
+ * The instruction stream and the address stream also depend on the row lists, on chunk_bits and on which table points
+ * are infinity, all of which are public.
+ * curdle_stat_alg_msm_resident: out[0] funnel calls that went to the resident tables, out[1] their pairs, out[2] calls
+ * under an active scope that took the old path, out[3] their pairs; curdle_stat_alg_msm's constant-time half counts both
+ * routes.  Per proof through a handle: out[2] moves by 0, out[0] by curdle_stat_alg_msm's constant-time calls,
+ * curdle_stat_msm_ct does not move, curdle_stat_msm_ct_bases' tables move by 2 (the instance set and the late set) and
+ * curdle_stat_host_point_mul by 2.  The knob PROVE_RESIDENT_TERMS (curdle_plan_override) lowers the per-call term cap
+ * for tests; 0 or a value above 65,536 means "not set".
+ * Cost: 40.7 / 46.9 ms a Prove at ell = 124 / 252 against curdle_prove_ct's 143.0 / 154.8 ms in the same process, 3.0 / 3.6 ms
+ * for the creation, the Whisk form 52.5 against 154.9 ms; about half of a Prove is the 24 / 26 calls' one-lane finish
+ * (profiles/r35_prove_ct_resident.json and DESIGN.md section 0, round 35).
+ * ------------------------------------------------------------------------- */
+typedef struct curdle_prover_ct curdle_prover_ct;
+int  curdle_prover_ct_create(const curdle_crs* crs, unsigned chunk_bits, curdle_prover_ct** out);
+void curdle_prover_ct_free(curdle_prover_ct* p);
+int  curdle_prover_ct_prove(curdle_prover_ct* p, const uint64_t* Rs, const uint64_t* Ss, const uint64_t* Ts,
+                            const uint64_t* Us, size_t ell, const uint64_t M[18], const uint32_t* perm,
+                            const uint64_t k[4], const uint64_t rs_m[16], curdle_rand* rand,
+                            uint8_t* proof_out, size_t cap, size_t* proof_len);
+int  curdle_prover_ct_whisk_shuffle_proof(curdle_prover_ct* p, const uint8_t* pre_trackers, size_t n, curdle_rand* rand,
+                                          uint8_t* post_trackers_out, uint8_t* proof_out);
+int  curdle_stat_alg_msm_resident(unsigned long long out[4]);  /* resident calls | their pairs | old-path calls under a scope | their pairs */
 /* The oblivious gather for k members of one n in ONE launch (k_permute_ct_seg, csrc/msm_ct_kernels.hip: the single
  * gathers' body, block (x, j) serving member j): out[j n + i] = in[j n + perm[j n + i]] for i < n, j < k, over 32-byte
  * records (curdle_fr_permute_ct_batch, _batch_device) or 96-byte records (curdle_g1_permute_ct_batch_device).  An entry
