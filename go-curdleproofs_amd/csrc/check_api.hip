@@ -8,7 +8,8 @@
 #include "../host/batch_check.h"
 
 namespace {
-std::atomic<unsigned long long> g_check_paths[2];  // checks begun on a decode context | run to the end through an MSM slot
+// checks begun on a decode context | run to the end through an MSM slot (the four batch calls below always are)
+std::atomic<unsigned long long> g_check_paths[2];
 
 constexpr size_t kCheckMax = (size_t)1 << 27;
 
@@ -190,6 +191,7 @@ extern "C" int curdle_g1_check_batch(const uint64_t* points, size_t n, int subgr
   if (n && (!points || !status)) return fail(CURDLE_EINVAL, "null argument");
   if (n == 0) return CURDLE_OK;
   if (n > kCheckMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^27 points", n);
+  g_check_paths[1].fetch_add(1, std::memory_order_relaxed);
   return check_through_slot(cur(), &points, &n, 1, nullptr, n, subgroup_check, status, nullptr);
 }
 
@@ -197,6 +199,7 @@ extern "C" int curdle_g1_check_batch_device(const void* d_points, size_t n, int 
   if (n && (!d_points || !status)) return fail(CURDLE_EINVAL, "null argument");
   if (n == 0) return CURDLE_OK;
   if (n > kCheckMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^27 points", n);
+  g_check_paths[1].fetch_add(1, std::memory_order_relaxed);
   return check_through_slot(cur(), nullptr, nullptr, 0, d_points, n, subgroup_check, status, stream);
 }
 
@@ -204,6 +207,7 @@ extern "C" int curdle_g1_check_jac_batch(const uint64_t* jac_points, size_t n, i
   if (n && (!jac_points || !status)) return fail(CURDLE_EINVAL, "null argument");
   if (n == 0) return CURDLE_OK;
   if (n > kCheckMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^27 points", n);
+  g_check_paths[1].fetch_add(1, std::memory_order_relaxed);
   return check_through_slot(cur(), &jac_points, &n, 1, nullptr, n, subgroup_check, status, nullptr, true);
 }
 
@@ -211,6 +215,7 @@ extern "C" int curdle_g1_check_jac_batch_device(const void* d_jac_points, size_t
   if (n && (!d_jac_points || !status)) return fail(CURDLE_EINVAL, "null argument");
   if (n == 0) return CURDLE_OK;
   if (n > kCheckMax) return fail(CURDLE_EINVAL, "n = %zu exceeds the supported 2^27 points", n);
+  g_check_paths[1].fetch_add(1, std::memory_order_relaxed);
   return check_through_slot(cur(), nullptr, nullptr, 0, d_jac_points, n, subgroup_check, status, stream, true);
 }
 

@@ -105,6 +105,7 @@ SYMBOLS = [
     "curdle_msm_g1_ct_bases_sets_batch", "curdle_msm_g1_ct_bases_sets_batch_device",
     "curdle_prover_ct_create", "curdle_prover_ct_free", "curdle_prover_ct_prove", "curdle_prover_ct_whisk_shuffle_proof",
     "curdle_stat_alg_msm_resident",
+    "curdle_crs_from_points", "curdle_crs_from_bytes", "curdle_crs_export_points", "curdle_crs_to_bytes",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -1028,8 +1029,41 @@ def synth_points_walk_device(k: int, q: int, n: int, d_out: int) -> None:
 # ---------------------------------------------------------------------------
 # Protocol layers (host restatement of curdleproof.Prove / Verify; include/curdle_msm.h)
 # ---------------------------------------------------------------------------
+CRS_N_BLINDERS = 4                                    # CURDLE_CRS_N_BLINDERS
+CRS_MAX_ELL = 1 << 20                                 # CURDLE_CRS_MAX_ELL
+CRS_TRUSTED = 1                                       # CURDLE_CRS_TRUSTED
+CRS_GS, CRS_HS, CRS_H, CRS_GT, CRS_GU, CRS_GSUM, CRS_HSUM = range(7)      # CURDLE_CRS_GS ... CURDLE_CRS_HSUM
+CRS_FIELDS = ("Gs", "Hs", "H", "Gt", "Gu", "Gsum", "Hsum")
+CRS_DUPLICATE, CRS_SUM_MISMATCH = 16, 17              # CURDLE_CRS_DUPLICATE, CURDLE_CRS_SUM_MISMATCH
+
+
+class CrsPoints(C.Structure):                         # curdle_crs_points
+    _fields_ = [("Gs", _vp), ("ell", C.c_size_t), ("Hs", _vp), ("H", _vp), ("Gt", _vp), ("Gu", _vp), ("Gsum", _vp),
+                ("Hsum", _vp)]
+
+
+class CrsFaultRecord(C.Structure):                    # curdle_crs_fault
+    _fields_ = [("field", C.c_int), ("index", C.c_size_t), ("reason", C.c_int)]
+
+
+class CrsFault(CurdleError):
+    """A validated CRS import found a fault: which field (CRS_GS ... CRS_HSUM), which index within Gs or Hs, and why
+    (a CURDLE_DECODE_* code, CRS_DUPLICATE or CRS_SUM_MISMATCH)."""
+
+    def __init__(self, code: int, msg: str, field: int, index: int, reason: int):
+        super().__init__(code, msg)
+        self.field, self.index, self.reason = field, index, reason
+
+
+_crs_from_points = _sig("curdle_crs_from_points", C.c_int, C.POINTER(CrsPoints), C.c_uint, C.POINTER(_vp),
+                        C.POINTER(CrsFaultRecord))
+_crs_from_bytes = _sig("curdle_crs_from_bytes", C.c_int, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(CrsFaultRecord))
+_crs_export_points = _sig("curdle_crs_export_points", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+_crs_to_bytes = _sig("curdle_crs_to_bytes", C.c_int, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t))
+
+
 class CRS:
-    """curdleproof.CRS from GenerateCRS(ell, rand) (crs.go:20)."""
+    """curdleproof.CRS: from GenerateCRS(ell, rand) (crs.go:20), or imported with from_points / from_bytes."""
 
     def __init__(self, ell: int, rand: Rand):
         self._h = _crs_generate(ell, rand._h)
@@ -1041,6 +1075,53 @@ class CRS:
         h, self._h = getattr(self, "_h", None), None
         if h and _crs_free is not None:
             _crs_free(h)
+
+    @classmethod
+    def _imported(cls, rc: int, handle, fault: CrsFaultRecord) -> "CRS":
+        if rc != OK:
+            if fault.field >= 0:
+                raise CrsFault(rc, last_error(), fault.field, fault.index, fault.reason)
+            raise CurdleError(rc, last_error())
+        crs = cls.__new__(cls)
+        crs._h = handle.value
+        crs.ell = _crs_size(crs._h)
+        return crs
+
+    @classmethod
+    def from_points(cls, Gs, Hs, H, Gt, Gu, Gsum, Hsum, flags: int = 0) -> "CRS":
+        """curdle_crs_from_points: Gs uint64[ell, 12], Hs uint64[4, 12], H / Gt / Gu uint64[18] (G1Jac, any Z), Gsum /
+        Hsum uint64[12].  Validated on the GPU (CrsFault names the first fault) unless flags = CRS_TRUSTED."""
+        Gs, Hs, Gsum, Hsum = _as_u64(Gs, 12), _as_u64(Hs, 12), _as_u64(Gsum, 12), _as_u64(Hsum, 12)
+        H, Gt, Gu = _as_u64(H, 18), _as_u64(Gt, 18), _as_u64(Gu, 18)
+        if Hs.size != 12 * CRS_N_BLINDERS:
+            raise ValueError(f"Hs holds {CRS_N_BLINDERS} points")
+        pts = CrsPoints(_ptr(Gs), Gs.size // 12, _ptr(Hs), _ptr(H), _ptr(Gt), _ptr(Gu), _ptr(Gsum), _ptr(Hsum))
+        handle, fault = _vp(), CrsFaultRecord(-1, 0, 0)
+        rc = _crs_from_points(C.byref(pts), int(flags), C.byref(handle), C.byref(fault))
+        return cls._imported(rc, handle, fault)
+
+    @classmethod
+    def from_bytes(cls, data: bytes) -> "CRS":
+        """curdle_crs_from_bytes: the library's own wire form, 48 (ell + 9) bytes; always validated on the GPU."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        handle, fault = _vp(), CrsFaultRecord(-1, 0, 0)
+        rc = _crs_from_bytes(_ptr(buf) if buf.size else None, buf.size, C.byref(handle), C.byref(fault))
+        return cls._imported(rc, handle, fault)
+
+    def points(self) -> dict:
+        """curdle_crs_export_points: the seven fields by name, in the layouts from_points takes (H, Gt, Gu with Z = 1)."""
+        out = {"Gs": np.zeros((self.ell, 12), np.uint64), "Hs": np.zeros((CRS_N_BLINDERS, 12), np.uint64),
+               "H": np.zeros(18, np.uint64), "Gt": np.zeros(18, np.uint64), "Gu": np.zeros(18, np.uint64),
+               "Gsum": np.zeros(12, np.uint64), "Hsum": np.zeros(12, np.uint64)}
+        _check(_crs_export_points(self._h, *(_ptr(out[k]) for k in CRS_FIELDS)))
+        return out
+
+    def to_bytes(self) -> bytes:
+        """curdle_crs_to_bytes: 48 (ell + 9) bytes."""
+        buf = np.zeros(48 * (self.ell + CRS_N_BLINDERS + 5), dtype=np.uint8)
+        n = C.c_size_t(0)
+        _check(_crs_to_bytes(self._h, _ptr(buf), buf.size, C.byref(n)))
+        return bytes(buf[: n.value])
 
 
 SHUFFLE_CONSTANT_TIME = 1                             # CURDLE_SHUFFLE_CONSTANT_TIME
@@ -1248,7 +1329,8 @@ def verify_checked(crs: CRS, proof: bytes, Rs, Ss, Ts, Us, M, rand: Rand) -> boo
 
 
 def stat_check_paths() -> dict:
-    """Checked verifications so far whose point check ran beside the verification / ran to its end first."""
+    """Checked verifications so far whose point check ran beside the verification / ran to its end first; the second
+    also counts every g1_check_batch / g1_check_jac_batch call (a validated CRS.from_points makes one of each)."""
     out = (C.c_ulonglong * 2)()
     _check(_stat_check_paths(out))
     return {"beside": int(out[0]), "first": int(out[1])}

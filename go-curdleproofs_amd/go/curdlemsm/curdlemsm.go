@@ -659,3 +659,96 @@ func VerifyBatchChecked(batch []BatchInstance, verify func(i int) (bool, error))
 	}
 	return oks, faults, nil
 }
+
+// CRS is a handle on a curdleproof.CRS inside the library (curdle_crs): what curdle_verify*, curdle_prove*, the
+// constant-time prover handle and the curdle_whisk_*shuffle* calls take.  UNVERIFIED like the rest of this file: never
+// compiled.
+type CRS struct{ h *C.curdle_crs }
+
+// CRSFault says which point of an imported CRS failed its validation: Field is 0..6 for Gs, Hs, H, Gt, Gu, Gsum, Hsum,
+// Index counts within Gs or Hs, Reason is a Decode* status, 16 (two equal generators) or 17 (a sum that is not the sum).
+type CRSFault struct {
+	Field  int
+	Index  int
+	Reason int
+	Text   string
+}
+
+func (f *CRSFault) Error() string { return "curdlemsm: CRS: " + f.Text }
+
+// NewCRSFromFields hands the fields of a curdleproof.CRS (crs.go:10-18) to the library in gnark's layouts, with no copy
+// on the Go side.  This package cannot name curdleproof.CRS itself: common imports curdlemsm (INTEGRATION.md section 2)
+// and the root package imports common, so the wrapper that takes the struct, NewCRS, lives in the sub-package
+// curdlemsm/curdlecrs.  trusted = false checks every point on the GPU (range, curve, subgroup), then that no two
+// generators are equal and that Gsum and Hsum are the sums; a *CRSFault names the first failure.  trusted = true takes
+// the fields as they are and needs no GPU: for a CRS this process generated itself.  The slices are only read and no
+// pointer is kept.  UNVERIFIED: never compiled.
+func NewCRSFromFields(Gs, Hs []bls12381.G1Affine, H, Gt, Gu *bls12381.G1Jac, Gsum, Hsum *bls12381.G1Affine, trusted bool) (*CRS, error) {
+	if len(Gs) == 0 || len(Hs) != C.CURDLE_CRS_N_BLINDERS || H == nil || Gt == nil || Gu == nil || Gsum == nil || Hsum == nil {
+		return nil, errors.New("curdlemsm: NewCRSFromFields: Gs is empty, Hs does not hold 4 points, or a field is nil")
+	}
+	var pin runtime.Pinner // the struct handed to C holds Go pointers: pin what they point to for the call
+	defer pin.Unpin()
+	for _, p := range []any{&Gs[0], &Hs[0], H, Gt, Gu, Gsum, Hsum} {
+		pin.Pin(p)
+	}
+	in := C.curdle_crs_points{
+		Gs: (*C.uint64_t)(unsafe.Pointer(&Gs[0])), ell: C.size_t(len(Gs)), Hs: (*C.uint64_t)(unsafe.Pointer(&Hs[0])),
+		H: (*C.uint64_t)(unsafe.Pointer(H)), Gt: (*C.uint64_t)(unsafe.Pointer(Gt)), Gu: (*C.uint64_t)(unsafe.Pointer(Gu)),
+		Gsum: (*C.uint64_t)(unsafe.Pointer(Gsum)), Hsum: (*C.uint64_t)(unsafe.Pointer(Hsum)),
+	}
+	var flags C.uint
+	if trusted {
+		flags = C.CURDLE_CRS_TRUSTED
+	}
+	return importCRS(func(out **C.curdle_crs, fault *C.curdle_crs_fault) C.int {
+		return C.curdle_crs_from_points(&in, flags, out, fault)
+	})
+}
+
+// CRSFromBytes imports the library's own wire form (the reference defines none): Gs, Hs, H, Gt, Gu, Gsum, Hsum as
+// 48-byte compressed points, 48 (ell + 9) bytes.  Always validated on the GPU.  UNVERIFIED: never compiled.
+func CRSFromBytes(data []byte) (*CRS, error) {
+	if len(data) == 0 {
+		return nil, errors.New("curdlemsm: CRSFromBytes: no bytes")
+	}
+	return importCRS(func(out **C.curdle_crs, fault *C.curdle_crs_fault) C.int {
+		return C.curdle_crs_from_bytes((*C.uint8_t)(unsafe.Pointer(&data[0])), C.size_t(len(data)), out, fault)
+	})
+}
+
+func importCRS(call func(out **C.curdle_crs, fault *C.curdle_crs_fault) C.int) (*CRS, error) {
+	c := &CRS{}
+	fault := C.curdle_crs_fault{field: -1}
+	if err := locked(func() C.int { return call(&c.h, &fault) }); err != nil {
+		if fault.field >= 0 {
+			return nil, &CRSFault{Field: int(fault.field), Index: int(fault.index), Reason: int(fault.reason), Text: err.Error()}
+		}
+		return nil, err
+	}
+	runtime.SetFinalizer(c, func(c *CRS) { c.Free() })
+	return c, nil
+}
+
+// Bytes is the wire form CRSFromBytes reads.
+func (c *CRS) Bytes() ([]byte, error) {
+	out := make([]byte, 48*(c.Size()+9))
+	var n C.size_t
+	if err := locked(func() C.int {
+		return C.curdle_crs_to_bytes(c.h, (*C.uint8_t)(unsafe.Pointer(&out[0])), C.size_t(len(out)), &n)
+	}); err != nil {
+		return nil, err
+	}
+	return out[:int(n)], nil
+}
+
+// Size is ell, the number of Gs.
+func (c *CRS) Size() int { return int(C.curdle_crs_size(c.h)) }
+
+// Free releases the handle; nothing that was made over it (a constant-time prover handle) may be used afterwards.
+func (c *CRS) Free() {
+	if c.h != nil {
+		C.curdle_crs_free(c.h)
+		c.h = nil
+	}
+}

@@ -479,6 +479,22 @@ CRS GenerateCRS(size_t size, common::Rand& rand) {
   return crs;
 }
 
+CRS CRSFromPoints(std::vector<G1Affine> Gs, std::vector<G1Affine> Hs, const Point& H, const Point& Gt, const Point& Gu,
+                  const G1Affine& Gsum, const G1Affine& Hsum) {
+  CRS crs;
+  crs.Gs = std::move(Gs);
+  crs.Hs = std::move(Hs);
+  crs.H = Point::FromAffine(H.Affine());
+  crs.Gt = Point::FromAffine(Gt.Affine());
+  crs.Gu = Point::FromAffine(Gu.Affine());
+  crs.Gsum = Gsum;
+  crs.Hsum = Hsum;
+  crs.GsumTable = std::make_shared<const alg::FixedBase>(crs.Gsum);
+  crs.HsumTable = std::make_shared<const alg::FixedBase>(crs.Hsum);
+  crs.device = std::make_shared<DeviceCrs>();
+  return crs;
+}
+
 ShuffleCommit ShufflePermuteCommit(const std::vector<G1Affine>& crsGs, const std::vector<G1Affine>& crsHs,
                                    const std::vector<G1Affine>& Rs, const std::vector<G1Affine>& Ss,
                                    const std::vector<uint32_t>& perm, const Scalar& k, common::Rand& rand) {

@@ -128,6 +128,10 @@ struct CRS {
   std::shared_ptr<class DeviceCrs> device;
 };
 CRS GenerateCRS(size_t size, common::Rand& rand);  // crs.go:20
+// The struct filled in by hand, as a caller of the reference fills it (crs.go:10-18): the fields as given, H, Gt and Gu
+// normalised to Z = 1 as GenerateCRS leaves them, the derived members made the way GenerateCRS makes them.  Checks nothing.
+CRS CRSFromPoints(std::vector<G1Affine> Gs, std::vector<G1Affine> Hs, const Point& H, const Point& Gt, const Point& Gu,
+                  const G1Affine& Gsum, const G1Affine& Hsum);
 
 // common.ShufflePermuteCommit (common/util.go:45)
 struct ShuffleCommit {

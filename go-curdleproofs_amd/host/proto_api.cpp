@@ -71,6 +71,231 @@ extern "C" curdle_crs* curdle_crs_generate(size_t ell, curdle_rand* rand) {
 extern "C" void curdle_crs_free(curdle_crs* c) { delete c; }
 extern "C" size_t curdle_crs_size(const curdle_crs* c) { return c ? c->crs.Gs.size() : 0; }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// curdle_crs_from_points / _from_bytes / _export_points / _to_bytes: a CRS no curdle_rand produced.  The rule of a
+// validated import is stated in include/curdle_msm.h; its per-point half is the device's (the three batched calls
+// below, weak as host/algebra.cpp names device entry points: a host-only link builds and answers CURDLE_ENODEV), the
+// duplicates and the sums are host work on ell + 7 public points.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int curdle_g1_check_batch(const uint64_t* points, size_t n, int subgroup_check, uint8_t* status) __attribute__((weak));
+extern "C" int curdle_g1_check_jac_batch(const uint64_t* jac_points, size_t n, int subgroup_check, uint8_t* status)
+    __attribute__((weak));
+extern "C" int curdle_g1_decompress_batch(const uint8_t* in, size_t n, int subgroup_check, uint64_t* out_affine, uint8_t* status)
+    __attribute__((weak));
+
+namespace {
+static_assert(proto::N_BLINDERS == CURDLE_CRS_N_BLINDERS, "the header's count of blinders");
+constexpr size_t kCrsSingles = 5;  // H, Gt, Gu, Gsum, Hsum
+
+struct CrsFields {  // the seven fields in wire order; Gs | Hs back to back
+  std::vector<G1Affine> gens;  // ell + N_BLINDERS
+  size_t ell = 0;
+  Point H, Gt, Gu;
+  G1Affine Gsum, Hsum;
+};
+
+// Where record `wire` of Gs | Hs | H | Gt | Gu | Gsum | Hsum lies, as the fault and the error text name it.
+void CrsWhere(size_t wire, size_t ell, int* field, size_t* index) {
+  if (wire < ell) {
+    *field = CURDLE_CRS_GS;
+    *index = wire;
+  } else if (wire < ell + proto::N_BLINDERS) {
+    *field = CURDLE_CRS_HS;
+    *index = wire - ell;
+  } else {
+    *field = CURDLE_CRS_H + (int)(wire - ell - proto::N_BLINDERS);
+    *index = 0;
+  }
+}
+std::string CrsName(size_t wire, size_t ell) {
+  static const char* const kField[7] = {"Gs", "Hs", "H", "Gt", "Gu", "Gsum", "Hsum"};
+  int field;
+  size_t index;
+  CrsWhere(wire, ell, &field, &index);
+  char buf[40];
+  if (field <= CURDLE_CRS_HS)
+    snprintf(buf, sizeof(buf), "%s[%zu]", kField[field], index);
+  else
+    snprintf(buf, sizeof(buf), "%s", kField[field]);
+  return buf;
+}
+int CrsFault(size_t wire, size_t ell, int reason, const std::string& why, curdle_crs_fault* fault) {
+  if (fault) {
+    CrsWhere(wire, ell, &fault->field, &fault->index);
+    fault->reason = reason;
+  }
+  return curdle_set_last_error(CURDLE_EINVAL, (CrsName(wire, ell) + ": " + why).c_str());
+}
+
+// The handle over the fields as they stand, and "no fault".
+int CrsHandle(const CrsFields& f, curdle_crs** out, curdle_crs_fault* fault) {
+  std::unique_ptr<curdle_crs> c(new curdle_crs());
+  c->crs = proto::CRSFromPoints(std::vector<G1Affine>(f.gens.begin(), f.gens.begin() + f.ell),
+                                std::vector<G1Affine>(f.gens.begin() + f.ell, f.gens.end()), f.H, f.Gt, f.Gu, f.Gsum, f.Hsum);
+  *out = c.release();
+  if (fault) *fault = curdle_crs_fault{-1, 0, 0};
+  return CURDLE_OK;
+}
+
+// Steps 2 (the verdict over the device's status bytes, in wire order), 3 and 4 of a validated import, then the handle.
+int CrsFinishValidated(CrsFields& f, const std::vector<uint8_t>& status, bool from_bytes, curdle_crs** out, curdle_crs_fault* fault) {
+  const size_t ell = f.ell, n_gen = ell + proto::N_BLINDERS + 3;
+  for (size_t w = 0; w < status.size(); w++) {
+    const uint8_t st = status[w];
+    if (st == CURDLE_DECODE_OK || (st == CURDLE_DECODE_INFINITY && w >= n_gen)) continue;
+    const char* why = "invalid point";
+    switch (st) {
+      case CURDLE_DECODE_INFINITY: why = "the point at infinity is no generator"; break;
+      case CURDLE_DECODE_BAD_ENCODING:
+        why = from_bytes ? "not a valid compressed encoding" : "not a field element (a coordinate is not below p)";
+        break;
+      case CURDLE_DECODE_NOT_ON_CURVE: why = "not on the curve"; break;
+      case CURDLE_DECODE_NOT_IN_SUBGROUP: why = "not in the prime-order subgroup"; break;
+    }
+    return CrsFault(w, ell, st, why, fault);
+  }
+  // duplicates: the canonical 96-byte records of the ell + 7 generators, sorted with their wire index; within a run of
+  // equal records the second is the later point of the run's first pair, and the earliest such point is the fault
+  std::vector<G1Affine> gen = f.gens;
+  gen.push_back(f.H.Affine());
+  gen.push_back(f.Gt.Affine());
+  gen.push_back(f.Gu.Affine());
+  std::vector<size_t> order(n_gen);
+  for (size_t i = 0; i < n_gen; i++) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    const int c = memcmp(&gen[a], &gen[b], sizeof(G1Affine));
+    return c ? c < 0 : a < b;
+  });
+  size_t later = n_gen, earlier = 0;
+  for (size_t i = 1; i < n_gen; i++)
+    if (!memcmp(&gen[order[i - 1]], &gen[order[i]], sizeof(G1Affine)) &&
+        (i < 2 || memcmp(&gen[order[i - 2]], &gen[order[i]], sizeof(G1Affine))) && order[i] < later) {
+      later = order[i];
+      earlier = order[i - 1];
+    }
+  if (later < n_gen)
+    return CrsFault(later, ell, CURDLE_CRS_DUPLICATE,
+                    "equal to " + CrsName(earlier, ell) + ": a known relation between generators", fault);
+  // the sums, as GenerateCRS makes them (crs.go:41-48)
+  Point gs = Point::Infinity(), hs = Point::Infinity();
+  for (size_t i = 0; i < ell; i++) gs = gs + Point::FromAffine(f.gens[i]);
+  for (size_t i = ell; i < ell + proto::N_BLINDERS; i++) hs = hs + Point::FromAffine(f.gens[i]);
+  const G1Affine gsum = gs.Affine(), hsum = hs.Affine();
+  if (memcmp(&gsum, &f.Gsum, sizeof(G1Affine))) return CrsFault(n_gen, ell, CURDLE_CRS_SUM_MISMATCH, "not the sum of Gs", fault);
+  if (memcmp(&hsum, &f.Hsum, sizeof(G1Affine))) return CrsFault(n_gen + 1, ell, CURDLE_CRS_SUM_MISMATCH, "not the sum of Hs", fault);
+  return CrsHandle(f, out, fault);
+}
+
+int CrsNoDevice(const char* who) {
+  return curdle_set_last_error(CURDLE_ENODEV, (std::string(who) + ": the point checks of a validated import need the device backend").c_str());
+}
+}  // namespace
+
+extern "C" int curdle_crs_from_points(const curdle_crs_points* in, unsigned flags, curdle_crs** out, curdle_crs_fault* fault) {
+  if (out) *out = nullptr;
+  if (!in || !out || !in->Gs || !in->Hs || !in->H || !in->Gt || !in->Gu || !in->Gsum || !in->Hsum)
+    return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  if (flags & ~CURDLE_CRS_TRUSTED) {
+    char msg[64];
+    snprintf(msg, sizeof(msg), "unknown flag bits 0x%x", flags & ~CURDLE_CRS_TRUSTED);
+    return curdle_set_last_error(CURDLE_EINVAL, msg);
+  }
+  const size_t ell = in->ell;
+  if (ell == 0 || ell > CURDLE_CRS_MAX_ELL) return curdle_set_last_error(CURDLE_EINVAL, "ell must be 1 ... 2^20 (CURDLE_CRS_MAX_ELL)");
+  if (!(flags & CURDLE_CRS_TRUSTED) && (!curdle_g1_check_batch || !curdle_g1_check_jac_batch)) return CrsNoDevice("curdle_crs_from_points");
+  return Guard([&]() -> int {
+    CrsFields f;
+    f.ell = ell;
+    f.gens = Affines(in->Gs, ell);
+    f.gens.resize(ell + proto::N_BLINDERS);
+    memcpy(f.gens.data() + ell, in->Hs, proto::N_BLINDERS * sizeof(G1Affine));
+    f.H = Point::FromJac(in->H);
+    f.Gt = Point::FromJac(in->Gt);
+    f.Gu = Point::FromJac(in->Gu);
+    memcpy(&f.Gsum, in->Gsum, sizeof(G1Affine));
+    memcpy(&f.Hsum, in->Hsum, sizeof(G1Affine));
+    if (flags & CURDLE_CRS_TRUSTED) return CrsHandle(f, out, fault);
+    // Gs | Hs | Gsum | Hsum staged contiguously for one affine check; H | Gt | Gu, as given, for one Jacobian check
+    const size_t n_gens = ell + proto::N_BLINDERS;
+    std::vector<G1Affine> affine = f.gens;
+    affine.push_back(f.Gsum);
+    affine.push_back(f.Hsum);
+    uint64_t jac[3 * 18];
+    memcpy(jac, in->H, 144);
+    memcpy(jac + 18, in->Gt, 144);
+    memcpy(jac + 36, in->Gu, 144);
+    std::vector<uint8_t> st_affine(affine.size(), 0xff);
+    uint8_t st_jac[3] = {0xff, 0xff, 0xff};
+    if (int rc = curdle_g1_check_batch(reinterpret_cast<const uint64_t*>(affine.data()), affine.size(), 1, st_affine.data())) return rc;
+    if (int rc = curdle_g1_check_jac_batch(jac, 3, 1, st_jac)) return rc;
+    std::vector<uint8_t> status(st_affine.begin(), st_affine.begin() + n_gens);  // into wire order
+    status.insert(status.end(), st_jac, st_jac + 3);
+    status.insert(status.end(), st_affine.begin() + n_gens, st_affine.end());
+    return CrsFinishValidated(f, status, /*from_bytes=*/false, out, fault);
+  });
+}
+
+extern "C" int curdle_crs_from_bytes(const uint8_t* in, size_t len, curdle_crs** out, curdle_crs_fault* fault) {
+  if (out) *out = nullptr;
+  if (!in || !out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  const size_t fixed = proto::N_BLINDERS + kCrsSingles;
+  if (len % 48 || len / 48 <= fixed || len / 48 - fixed > CURDLE_CRS_MAX_ELL) {
+    char msg[112];
+    snprintf(msg, sizeof(msg), "len = %zu is not 48 (ell + 9) for an ell of 1 ... 2^20 (CURDLE_CRS_MAX_ELL)", len);
+    return curdle_set_last_error(CURDLE_EINVAL, msg);
+  }
+  if (!curdle_g1_decompress_batch) return CrsNoDevice("curdle_crs_from_bytes");
+  return Guard([&]() -> int {
+    const size_t n = len / 48, ell = n - fixed, n_gens = ell + proto::N_BLINDERS;
+    std::vector<G1Affine> pts(n);
+    std::vector<uint8_t> status(n, 0xff);
+    if (int rc = curdle_g1_decompress_batch(in, n, 1, reinterpret_cast<uint64_t*>(pts.data()), status.data())) return rc;
+    CrsFields f;  // an invalid record decodes to (0, 0); its status is looked at before any of this is used
+    f.ell = ell;
+    f.gens.assign(pts.begin(), pts.begin() + n_gens);
+    f.H = Point::FromAffine(pts[n_gens]);
+    f.Gt = Point::FromAffine(pts[n_gens + 1]);
+    f.Gu = Point::FromAffine(pts[n_gens + 2]);
+    f.Gsum = pts[n_gens + 3];
+    f.Hsum = pts[n_gens + 4];
+    return CrsFinishValidated(f, status, /*from_bytes=*/true, out, fault);
+  });
+}
+
+extern "C" int curdle_crs_export_points(const curdle_crs* crs, uint64_t* Gs, uint64_t* Hs, uint64_t H[18], uint64_t Gt[18],
+                                        uint64_t Gu[18], uint64_t Gsum[12], uint64_t Hsum[12]) {
+  if (!crs || !Gs || !Hs || !H || !Gt || !Gu || !Gsum || !Hsum) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  const proto::CRS& k = crs->crs;
+  if (!k.Gs.empty()) memcpy(Gs, k.Gs.data(), k.Gs.size() * sizeof(G1Affine));
+  if (!k.Hs.empty()) memcpy(Hs, k.Hs.data(), k.Hs.size() * sizeof(G1Affine));
+  k.H.Jac(H);
+  k.Gt.Jac(Gt);
+  k.Gu.Jac(Gu);
+  memcpy(Gsum, &k.Gsum, sizeof(G1Affine));
+  memcpy(Hsum, &k.Hsum, sizeof(G1Affine));
+  return CURDLE_OK;
+}
+
+extern "C" int curdle_crs_to_bytes(const curdle_crs* crs, uint8_t* out, size_t cap, size_t* len) {
+  if (!crs || !len) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  const proto::CRS& k = crs->crs;
+  const size_t n_gens = k.Gs.size() + k.Hs.size(), need = 48 * (n_gens + kCrsSingles);
+  *len = need;
+  if (!out) return curdle_set_last_error(CURDLE_EINVAL, "null argument");
+  if (cap < need) return curdle_set_last_error(CURDLE_EINVAL, "CRS buffer too small");
+  return Guard([&]() {
+    alg::CompressAffineBatch(k.Gs.data(), k.Gs.size(), out);
+    alg::CompressAffineBatch(k.Hs.data(), k.Hs.size(), out + 48 * k.Gs.size());
+    uint8_t* p = out + 48 * n_gens;
+    k.H.Compressed(p);
+    k.Gt.Compressed(p + 48);
+    k.Gu.Compressed(p + 96);
+    alg::CompressAffine(k.Gsum, p + 144);
+    alg::CompressAffine(k.Hsum, p + 192);
+    return CURDLE_OK;
+  });
+}
+
 extern "C" int curdle_shuffle_permute_commit(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, size_t ell,
                                              const uint32_t* perm, const uint64_t k[4], curdle_rand* rand,
                                              uint64_t* Ts_out, uint64_t* Us_out, uint64_t M_out[18],

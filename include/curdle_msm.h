@@ -311,6 +311,79 @@ typedef struct curdle_crs curdle_crs;
 curdle_crs* curdle_crs_generate(size_t ell, curdle_rand* rand);   /* GenerateCRS, crs.go:20           */
 void curdle_crs_free(curdle_crs* crs);
 size_t curdle_crs_size(const curdle_crs* crs);
+/* A CRS that no curdle_rand produced: the caller's points, or their bytes.  In the reference CRS is a struct of public
+ * fields (crs.go:10-18) that the caller fills in and passes; a Whisk deployment uses one fixed, published CRS.  The
+ * handle that comes out is indistinguishable from a generated one -- H, Gt and Gu stored with Z = 1 as GenerateCRS
+ * leaves them, the fixed-base tables of Gsum and Hsum built from the stored sums, a fresh resident copy for the device
+ * accumulator -- and goes to every entry point that takes a curdle_crs; curdle_crs_free and curdle_crs_size apply.
+ *
+ * WIRE FORM (curdle_crs_from_bytes / curdle_crs_to_bytes).  THE REFERENCE DEFINES NO CRS SERIALISATION (crs.go has
+ * none): this form is THIS LIBRARY'S OWN.  It is the struct's fields in declaration order -- Gs, Hs, H, Gt, Gu, Gsum,
+ * Hsum -- each point in gnark's 48-byte compressed encoding with nothing in between: 48 (ell + 9) bytes, and ell is
+ * read from the length.
+ *
+ * A VALIDATED import (curdle_crs_from_bytes always; curdle_crs_from_points without CURDLE_CRS_TRUSTED) checks, in
+ * this order:
+ *   1. before any device work: a null argument (a null field of curdle_crs_points included), a flag bit that is not
+ *      defined here, ell = 0 or ell > CURDLE_CRS_MAX_ELL; for bytes a len that is not 48 (ell + 9) for an ell in that
+ *      range.  CURDLE_EINVAL, *out = NULL, *fault NOT written.
+ *   2. every point ON THE GPU, with the subgroup test: from_points by one curdle_g1_check_batch over
+ *      Gs | Hs | Gsum | Hsum and one curdle_g1_check_jac_batch over H | Gt | Gu, from_bytes by one
+ *      curdle_g1_decompress_batch over all ell + 9 records.  The first status that is not CURDLE_DECODE_OK, in wire
+ *      order, is the fault, with that CURDLE_DECODE_* code as its reason.  CURDLE_DECODE_INFINITY is a fault for Gs,
+ *      Hs, H, Gt and Gu (a generator at infinity is no generator) and none, here, for Gsum and Hsum.  No host
+ *      fallback: without a device CURDLE_ENODEV, as the check calls themselves answer.
+ *   3. duplicates among Gs | Hs | H | Gt | Gu as group elements (H, Gt, Gu normalised on the host first): two equal
+ *      points are a known relation between generators.  The fault names the LATER point in wire order, reason
+ *      CURDLE_CRS_DUPLICATE; curdle_last_error names both.
+ *   4. the sums: Gs and Hs summed as GenerateCRS sums them (crs.go:41-48) against Gsum, then Hsum, (0, 0) being
+ *      infinity.  Reason CURDLE_CRS_SUM_MISMATCH, index 0.
+ * On a fault: CURDLE_EINVAL, *out = NULL, *fault (if not null) filled, and curdle_last_error reads like the checked
+ * verifier's texts -- "Gs[17]: not in the prime-order subgroup".  On success *out receives the handle and *fault (if
+ * not null) is {-1, 0, 0}.
+ *
+ * CURDLE_CRS_TRUSTED (from_points only): only the refusals of step 1 apply.  The fields are taken as they are -- an
+ * inconsistent Gsum included, which is what the reference does with a hand-filled struct --, nothing is sent to a
+ * device, no counter moves, and the call works on a machine without a GPU.  That every point lies in G1 is then the
+ * CALLER'S PRECONDITION, as it is for the bases of curdle_msm_g1.  For a caller who generated the CRS itself. */
+#define CURDLE_CRS_N_BLINDERS 4
+#define CURDLE_CRS_MAX_ELL ((size_t)1 << 20)
+#define CURDLE_CRS_TRUSTED 1u           /* from_points only: take the fields as they are, check nothing, no device */
+/* which field a fault names, in WIRE ORDER */
+#define CURDLE_CRS_GS 0
+#define CURDLE_CRS_HS 1
+#define CURDLE_CRS_H 2
+#define CURDLE_CRS_GT 3
+#define CURDLE_CRS_GU 4
+#define CURDLE_CRS_GSUM 5
+#define CURDLE_CRS_HSUM 6
+/* reasons beyond CURDLE_DECODE_* (1..4) */
+#define CURDLE_CRS_DUPLICATE 16
+#define CURDLE_CRS_SUM_MISMATCH 17
+typedef struct {            /* gnark's in-memory layouts, unchanged: what cgo hands over */
+  const uint64_t* Gs;       /* ell x 12, G1Affine */
+  size_t ell;
+  const uint64_t* Hs;       /* CURDLE_CRS_N_BLINDERS x 12 */
+  const uint64_t* H;        /* 18, G1Jac, any Z */
+  const uint64_t* Gt;       /* 18 */
+  const uint64_t* Gu;       /* 18 */
+  const uint64_t* Gsum;     /* 12 */
+  const uint64_t* Hsum;     /* 12 */
+} curdle_crs_points;
+typedef struct {
+  int field;                /* CURDLE_CRS_GS ... CURDLE_CRS_HSUM; -1: no fault */
+  size_t index;             /* within Gs or Hs; 0 for the single points */
+  int reason;               /* CURDLE_DECODE_* or CURDLE_CRS_DUPLICATE / CURDLE_CRS_SUM_MISMATCH */
+} curdle_crs_fault;
+int curdle_crs_from_points(const curdle_crs_points* in, unsigned flags, curdle_crs** out, curdle_crs_fault* fault);
+int curdle_crs_from_bytes(const uint8_t* in, size_t len, curdle_crs** out, curdle_crs_fault* fault);
+/* The handle's fields in the layouts of curdle_crs_points (Gs: curdle_crs_size(crs) x 12; H, Gt, Gu with Z = 1, or
+ * (1, 1, 0) for infinity) and in the wire form.  Host code, no device needed; a null argument: CURDLE_EINVAL.
+ * curdle_crs_to_bytes sets *len to the needed 48 (ell + 9) even when cap is too small (CURDLE_EINVAL then), as
+ * curdle_prove does for its proof. */
+int curdle_crs_export_points(const curdle_crs* crs, uint64_t* Gs, uint64_t* Hs, uint64_t H[18], uint64_t Gt[18],
+                             uint64_t Gu[18], uint64_t Gsum[12], uint64_t Hsum[12]);
+int curdle_crs_to_bytes(const curdle_crs* crs, uint8_t* out, size_t cap, size_t* len);
 /* common.ShufflePermuteCommit, common/util.go:45 */
 int curdle_shuffle_permute_commit(const curdle_crs* crs, const uint64_t* Rs, const uint64_t* Ss, size_t ell,
                                   const uint32_t* perm, const uint64_t k[4], curdle_rand* rand,
@@ -1460,7 +1533,10 @@ int curdle_verify_batch_checked(const curdle_crs* crs, size_t k, const uint8_t* 
  * out[2] chunks checked. */
 int curdle_stat_batch_checked(unsigned long long out[3]);
 /* Diagnostics: checked verifications since the library was loaded whose point check out[0] ran on a decode
- * context beside the verification, out[1] found every decode context taken and ran to its end first. */
+ * context beside the verification, out[1] found every decode context taken and ran to its end first.  out[1] also
+ * counts every curdle_g1_check_batch / _jac_batch call (host or _device form) that reached the device: such a check
+ * always runs to its end before the call returns.  A validated curdle_crs_from_points moves it by two, a TRUSTED one
+ * moves nothing. */
 int curdle_stat_check_paths(unsigned long long out[2]);
 
 /* ------------------------------------------------------------------------------------------------
