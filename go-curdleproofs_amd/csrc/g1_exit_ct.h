@@ -6,8 +6,9 @@
 // turned into an exec mask on whether the product's representative reached p: a property of the accumulator's projective
 // coordinates, which are made of the secret's digits.  Here the choice between t and t - p is a select on the borrow.
 //
-// The affine exit.  ONE Fermat inversion of zz zzz on the fixed exponent chain of invert28.h (the exponent is p - 2 for
-// every lane: its window switch is wave-uniform and public), x = X zzz / (zz zzz), y = Y zz / (zz zzz), and both
+// The affine exit.  ONE inversion of zz zzz -- by default the Fermat one on the fixed exponent chain of invert28.h (the
+// exponent is p - 2 for every lane: its window switch is wave-uniform and public); under InvertDivsteps the division
+// steps of invert_ds.h, which k_msm_ct_finish_ds / _seg_ds take --, x = X zzz / (zz zzz), y = Y zz / (zz zzz), and both
 // coordinates through the masked canonical step.  A record that is not a point (nothing added yet, or infinity) inverts
 // whatever it holds -- 0 gives 0 -- and the CALLER masks the words away.
 #pragma once
@@ -15,6 +16,7 @@
 
 #include "msm_kernels_common.h"
 #include "invert28.h"
+#include "invert_ds.h"
 
 namespace curdle {
 
@@ -41,11 +43,22 @@ __device__ __forceinline__ void to_gnark_ct(u32* w, const F28& a) {
   pack(w, t);
 }
 
+// The exit's inversion, a template parameter of affine_words_ct.  Both take a product (normalised, below 2p) and give
+// the Montgomery form of its inverse under the same bounds, 0 for 0 and for p.
+struct InvertFermat {  // the fixed exponent chain of invert28.h: what every kernel took before there was a choice
+  static __device__ __forceinline__ void run(F28& y, const F28& d) { invert(y, d); }
+};
+struct InvertDivsteps {  // the division steps of invert_ds.h
+  // The violation word is dropped: invert_ds takes the canonical representative first, and no value below p sets it.
+  static __device__ __forceinline__ void run(F28& y, const F28& d) { (void)invert_ds(y, d); }
+};
+
 // w = the canonical gnark record (x | y) of acc: x = X / zz, y = Y / zzz with one inversion
+template <class Inv = InvertFermat>
 __device__ __forceinline__ void affine_words_ct(u32 w[24], const X28& acc) {
   F28 d, inv, ix, iy;
   d28::mul(d, acc.zz, acc.zzz);
-  invert(inv, d);
+  Inv::run(inv, d);
   d28::mul(ix, inv, acc.zzz);
   d28::mul(iy, inv, acc.zz);
   d28::mul(ix, acc.x, ix);

@@ -1,7 +1,7 @@
 // Constant-time multi-scalar multiplication: sum_i k_i P_i with an instruction stream and an address stream that do
 // not depend on the scalars.  The twin of the bucket MSM (msm_sort_kernels.hip, msm_accumulate_kernel.hip), whose sort,
 // bucket addresses and large-bucket queue are all functions of the scalars, in the manner of k_g1_mul_ct
-// (g1_mul_ct_kernels.hip).  Seven kernels; the rule of what may depend on a secret is the one of g1_walk_ct.h.
+// (g1_mul_ct_kernels.hip).  Seven kernels and two second builds of the finish; the rule of what may depend on a secret is the one of g1_walk_ct.h.
 //
 // k_msm_ct_walk.  One lane per (base, scalar) pair; behind the scalar's load the lane is msm_ct_lane (msm_ct_lane.h),
 // shared with k_msm_ct_walk_rows.  The walk of g1_walk_ct.h with a PUBLIC step count `bits` (1...255,
@@ -51,11 +51,17 @@
 // out + 36 j; an empty segment (public) gives the infinity encoding; the status word follows the k results.  Per
 // segment the order of additions is exactly k_g1_sum_ct's and k_msm_ct_finish's on that segment alone.
 //
+// k_msm_ct_finish_ds, k_msm_ct_finish_seg_ds.  The two finish kernels with the exit's inversion by division steps
+// (invert_ds.h) in place of the Fermat chain: ONE body each with its Fermat twin (finish_block, finish_seg_block), ONE
+// sum_tail and ONE write_result, the inversion a template parameter; the words out are the same.  The launchers take
+// them under knob CT_FINISH_DIVSTEPS (finish_on_divsteps below).
+//
 // Plain loads and stores, one atomic OR, no LDS, no inline assembly beyond the field layer's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "../host/knobs.h"
 #include "msm_kernels_common.h"
 #include "g1_walk_ct.h"
 #include "g1_add_ct.h"
@@ -115,13 +121,14 @@ __device__ __forceinline__ void sum_tail(X28* term, u32 m) {
   }
 }
 
-// One lane: *term normalised into the 36 words curdle_msm_g1 returns.
+// One lane: *term normalised into the 36 words curdle_msm_g1 returns.  Inv: the exit's inversion (g1_exit_ct.h).
+template <class Inv>
 __device__ __forceinline__ void write_result(const X28* term, u32* out) {
   X28 acc;
   d28::load(acc, term);
   const u32 fin = ~zero_mask(acc.zz);
   u32 w[24];
-  affine_words_ct(w, acc);  // infinity inverts 0 (which gives 0) and is masked away
+  affine_words_ct<Inv>(w, acc);  // infinity inverts 0 (which gives 0) and is masked away
 #pragma unroll
   for (int j = 0; j < 12; j++) {
     const u32 one = FpParams::one(j);  // gnark's Montgomery 1
@@ -130,30 +137,18 @@ __device__ __forceinline__ void write_result(const X28* term, u32* out) {
     out[24 + j] = one & fin;
   }
 }
-}  // namespace
-
-__global__ void __launch_bounds__(kBlock, 1) k_msm_ct_finish(X28* term, u32 m, const u32* status, u32* out) {
+// The block of k_msm_ct_finish and of k_msm_ct_finish_ds: the tail, then lane 0 writes the result and the status word.
+template <class Inv>
+__device__ __forceinline__ void finish_block(X28* term, u32 m, const u32* status, u32* out) {
   sum_tail(term, m);
   if (threadIdx.x != 0) return;
-  write_result(term, out);
+  write_result<Inv>(term, out);
   out[36] = *status;
 }
 
-// seg[j] = (begin_j, count_j), public.  `level` counts the launches before this one.
-__global__ void __launch_bounds__(kBlock, 1) k_g1_sum_ct_seg(X28* term, const uint2* __restrict__ seg, u32 level) {
-  const uint2 s = seg[blockIdx.y];  // a wave-uniform address
-  u32 m = s.y;
-#pragma unroll 1
-  for (u32 l = 0; l < level && m > kMsmCtSumTail; l++) m = (m + 1) / 2;
-  if (m <= kMsmCtSumTail) return;
-  const u32 h = (m + 1) / 2;
-  const u32 i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= m - h) return;
-  sum_pair(term + s.x, i, h);
-}
-
-__global__ void __launch_bounds__(kBlock, 1)
-    k_msm_ct_finish_seg(X28* term, const uint2* __restrict__ seg, const u32* status, u32* out) {
+// Block j of k_msm_ct_finish_seg and of k_msm_ct_finish_seg_ds.
+template <class Inv>
+__device__ __forceinline__ void finish_seg_block(X28* term, const uint2* __restrict__ seg, const u32* status, u32* out) {
   const uint2 s = seg[blockIdx.x];  // a wave-uniform address
   u32* res = out + 36 * (size_t)blockIdx.x;
   if (blockIdx.x == 0 && threadIdx.x == 0) out[36 * (size_t)gridDim.x] = *status;
@@ -171,7 +166,40 @@ __global__ void __launch_bounds__(kBlock, 1)
   while (m > kMsmCtSumTail) m = (m + 1) / 2;  // where the level launches left the segment
   sum_tail(term + s.x, m);
   if (threadIdx.x != 0) return;
-  write_result(term + s.x, res);
+  write_result<Inv>(term + s.x, res);
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock, 1) k_msm_ct_finish(X28* term, u32 m, const u32* status, u32* out) {
+  finish_block<InvertFermat>(term, m, status, out);
+}
+
+// The same block with the division-step exit (invert_ds.h): the same words out.
+__global__ void __launch_bounds__(kBlock, 1) k_msm_ct_finish_ds(X28* term, u32 m, const u32* status, u32* out) {
+  finish_block<InvertDivsteps>(term, m, status, out);
+}
+
+// seg[j] = (begin_j, count_j), public.  `level` counts the launches before this one.
+__global__ void __launch_bounds__(kBlock, 1) k_g1_sum_ct_seg(X28* term, const uint2* __restrict__ seg, u32 level) {
+  const uint2 s = seg[blockIdx.y];  // a wave-uniform address
+  u32 m = s.y;
+#pragma unroll 1
+  for (u32 l = 0; l < level && m > kMsmCtSumTail; l++) m = (m + 1) / 2;
+  if (m <= kMsmCtSumTail) return;
+  const u32 h = (m + 1) / 2;
+  const u32 i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= m - h) return;
+  sum_pair(term + s.x, i, h);
+}
+
+__global__ void __launch_bounds__(kBlock, 1)
+    k_msm_ct_finish_seg(X28* term, const uint2* __restrict__ seg, const u32* status, u32* out) {
+  finish_seg_block<InvertFermat>(term, seg, status, out);
+}
+
+__global__ void __launch_bounds__(kBlock, 1)
+    k_msm_ct_finish_seg_ds(X28* term, const uint2* __restrict__ seg, const u32* status, u32* out) {
+  finish_seg_block<InvertDivsteps>(term, seg, status, out);
 }
 
 namespace {
@@ -241,6 +269,25 @@ hipError_t launch_msm_ct_walk(const void* points, const void* scalars, int scala
   return hipGetLastError();
 }
 
+namespace {
+// finish launches on division steps | on Fermat
+std::atomic<unsigned long long> g_finish_launches[2];
+
+// Which build a finish launcher takes, counted as a launch of that build.  Knob CT_FINISH_DIVSTEPS: 1 always the _ds kernels, 0 never; unset: the
+// library's rule, which is kCtFinishDivstepsDefault (msm_kernels.h) for every shape.
+bool finish_on_divsteps() {
+  const long long knob = knobs::get(knobs::CT_FINISH_DIVSTEPS);
+  const bool ds = knob < 0 ? kCtFinishDivstepsDefault : knob != 0;
+  g_finish_launches[ds ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+  return ds;
+}
+}  // namespace
+
+void msm_ct_finish_launches(unsigned long long out[2]) {
+  out[0] = g_finish_launches[0].load(std::memory_order_relaxed);
+  out[1] = g_finish_launches[1].load(std::memory_order_relaxed);
+}
+
 hipError_t launch_msm_ct_sum(void* term, uint32_t m, const uint32_t* status, void* out40, hipStream_t stream) {
   if (m == 0) return hipErrorInvalidValue;
   while (m > kMsmCtSumTail) {
@@ -249,7 +296,10 @@ hipError_t launch_msm_ct_sum(void* term, uint32_t m, const uint32_t* status, voi
     if (hipError_t e = hipGetLastError()) return e;
     m = h;
   }
-  hipLaunchKernelGGL(k_msm_ct_finish, dim3(1), dim3(kBlock), 0, stream, (X28*)term, (u32)m, status, (u32*)out40);
+  if (finish_on_divsteps())
+    hipLaunchKernelGGL(k_msm_ct_finish_ds, dim3(1), dim3(kBlock), 0, stream, (X28*)term, (u32)m, status, (u32*)out40);
+  else
+    hipLaunchKernelGGL(k_msm_ct_finish, dim3(1), dim3(kBlock), 0, stream, (X28*)term, (u32)m, status, (u32*)out40);
   return hipGetLastError();
 }
 
@@ -270,7 +320,10 @@ hipError_t launch_msm_ct_sum_seg(void* term, const void* seg, const uint32_t* co
     if (hipError_t e = hipGetLastError()) return e;
   }
   if (levels) *levels = level;
-  hipLaunchKernelGGL(k_msm_ct_finish_seg, dim3(k), dim3(kBlock), 0, stream, (X28*)term, (const uint2*)seg, status, (u32*)out);
+  if (finish_on_divsteps())
+    hipLaunchKernelGGL(k_msm_ct_finish_seg_ds, dim3(k), dim3(kBlock), 0, stream, (X28*)term, (const uint2*)seg, status, (u32*)out);
+  else
+    hipLaunchKernelGGL(k_msm_ct_finish_seg, dim3(k), dim3(kBlock), 0, stream, (X28*)term, (const uint2*)seg, status, (u32*)out);
   return hipGetLastError();
 }
 

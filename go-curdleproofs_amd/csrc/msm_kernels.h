@@ -384,6 +384,22 @@ hipError_t launch_g1_permute_ct(const void* in, const uint32_t* perm, uint32_t n
 hipError_t launch_fr_permute_ct(const void* in, const uint32_t* perm, uint32_t n, void* out, hipStream_t stream);
 hipError_t launch_permute_ct_seg(const void* in, const uint32_t* perm, uint32_t n, uint32_t k, uint32_t record_bytes, void* out,
                                  hipStream_t stream);
+// The finish of launch_msm_ct_sum and launch_msm_ct_sum_seg exists in two builds with the same words out: the exit's
+// inversion on the Fermat chain (k_msm_ct_finish, k_msm_ct_finish_seg) or on division steps (k_msm_ct_finish_ds,
+// k_msm_ct_finish_seg_ds).  Knob CT_FINISH_DIVSTEPS chooses (1 / 0); unset, the library's rule is this constant: true since
+// the measurement of round 37 put the _ds finish below the Fermat one by more than the sum of both arms' spreads at 1 x 256
+// and 4,096 x 16 terms and in a handle Prove at ell = 124 (profiles/r37_invert_ds.json).
+// msm_ct_finish_launches: out[0] finish launches on division steps, out[1] on Fermat.
+static constexpr bool kCtFinishDivstepsDefault = true;
+void msm_ct_finish_launches(unsigned long long out[2]);
+
+// fp_invert_kernels.hip: out[i] = in[i]^-1 in Fp for i < n <= kFpInvertPass, 0 -> 0, one lane per element, by division
+// steps (invert_ds.h) or, fermat != 0, by the exponent chain of invert28.h: the same words.  Items are gnark fp.Elements
+// (48 bytes, canonical in and out) or, raw != 0, the 14 limbs of fp28.h (56 bytes; normalised and below 2p in, canonical
+// out).  An item out of range ORs 1 into *status (which the caller zeroes first) without a branch.  in and out are
+// multiples of 16 and out may be in.  Neither the instruction stream nor the address stream depends on the elements.
+static constexpr uint32_t kFpInvertPass = 1u << 20;
+hipError_t launch_fp_invert(const void* in, uint32_t n, void* out, int fermat, int raw, uint32_t* status, hipStream_t stream);
 
 // msm_ct_bases_kernels.hip: the constant-time MSM over a resident PUBLIC base set, the walk split into chunks of
 // chunk_bits (1...64) bits.

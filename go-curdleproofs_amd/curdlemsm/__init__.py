@@ -106,6 +106,7 @@ SYMBOLS = [
     "curdle_prover_ct_create", "curdle_prover_ct_free", "curdle_prover_ct_prove", "curdle_prover_ct_whisk_shuffle_proof",
     "curdle_stat_alg_msm_resident",
     "curdle_crs_from_points", "curdle_crs_from_bytes", "curdle_crs_export_points", "curdle_crs_to_bytes",
+    "curdle_fp_invert_batch", "curdle_fp_invert_batch_device", "curdle_stat_fp_invert",
 ]
 
 _u64p = C.POINTER(C.c_uint64)
@@ -2323,6 +2324,45 @@ def stat_g1_mul_ct() -> dict:
     out = (C.c_ulonglong * 2)()
     _check(_stat_g1_mul_ct(out))
     return {"scalars": int(out[0]), "launches": int(out[1])}
+
+
+_fp_invert_batch = _sig("curdle_fp_invert_batch", C.c_int, _vp, C.c_size_t, _vp, C.c_uint)
+_fp_invert_batch_device = _sig("curdle_fp_invert_batch_device", C.c_int, _vp, C.c_size_t, _vp, C.c_uint, _vp)
+_stat_fp_invert = _sig("curdle_stat_fp_invert", C.c_int, C.POINTER(C.c_ulonglong))
+
+FP_INVERT_FERMAT = 1                                  # CURDLE_FP_INVERT_FERMAT
+FP_INVERT_RAW28 = 2                                   # CURDLE_FP_INVERT_RAW28
+
+
+def fp_invert_batch(elements, flags: int = 0, out=None) -> np.ndarray:
+    """out[i] = elements[i]^-1 in Fp on the GPU, 0 -> 0, constant time in the elements (curdle_fp_invert_batch).
+    elements: (n, 6) uint64 gnark fp.Elements (Montgomery, canonical), or under FP_INVERT_RAW28 (n, 7) uint64 holding
+    the 14 uint32 limbs of the internal field layer.  flags: 0 inverts by division steps, FP_INVERT_FERMAT by the
+    exponent chain (bit-identical).  out: an array to write into (it may be `elements`); a new one by default.  An
+    element out of range raises CurdleError(EINVAL) and leaves `out` untouched."""
+    cols = 7 if int(flags) & FP_INVERT_RAW28 else 6
+    elements = _as_u64(elements, cols)
+    n = elements.shape[0] if elements.size else 0
+    if out is None:
+        out = np.zeros((n, cols), dtype=np.uint64)
+    _check(_fp_invert_batch(_ptr(elements), n, _ptr(out), int(flags)))
+    return out
+
+
+def fp_invert_batch_device(d_in: int, n: int, d_out: int, flags: int = 0, stream=None) -> None:
+    """The same for n elements resident in device memory at d_in (curdle_fp_invert_batch_device): the inverses are
+    written to d_out (which may be d_in) in the stream's order and are complete when the call returns.  Both pointers
+    are multiples of 16.  After CurdleError(EINVAL) for an element out of range d_out's contents are unspecified."""
+    _check(_fp_invert_batch_device(d_in or None, n, d_out or None, int(flags), stream or None))
+
+
+def stat_fp_invert() -> dict:
+    """Completed calls of fp_invert_batch / _device and their elements, and the finish launches of the constant-time
+    MSM by the inversion their exit took (division steps under knob CT_FINISH_DIVSTEPS, or the Fermat chain), since
+    the library was loaded."""
+    out = (C.c_ulonglong * 4)()
+    _check(_stat_fp_invert(out))
+    return {"calls": int(out[0]), "elements": int(out[1]), "finish_divsteps": int(out[2]), "finish_fermat": int(out[3])}
 
 
 def stat_normalize() -> dict:

@@ -16,7 +16,7 @@ const char* const kNames[COUNT] = {
     "ACC_PRIO", "REDUCE_PRIO", "AUX_PRIO", "HOST_FOLD", "MAX_LARGE", "BATCH_CHECKERS", "TRANSCRIPT_LANES", "GPU_PRELUDE",
     "TRACKER_DEVICE_HASH", "NORMALIZE_LANE_POINTS", "TRACKER_OWN_PAIRS", "FBASE_PASS", "TRANSCRIPT_SHEET",
     "STREAM_PLAN", "TRANSCRIPT_MAX_TRIES", "G1_MUL_CT_PASS", "PROVE_BATCH_GROUP", "PROVE_BATCH_PAIRS",
-    "PROVE_RESIDENT_TERMS"};
+    "PROVE_RESIDENT_TERMS", "CT_FINISH_DIVSTEPS"};
 std::atomic<long long> g_val[COUNT];
 std::once_flag g_once;
 void load() {

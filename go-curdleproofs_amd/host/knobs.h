@@ -55,6 +55,7 @@ enum Id {
   PROVE_BATCH_GROUP,      // curdle_prove_batch, curdle_whisk_generate_shuffle_proof_batch: members proved in lockstep at a time, one thread each (1..64); unset, 0 or above 64: 64 (proto_api.cpp)
   PROVE_BATCH_PAIRS,      // test hook: lowers the (point, scalar) pairs or records from which a lockstep group's coalesced call is split by whole members, so a test can reach the split; unset or 0: the primitives' own limits (alg::Lockstep, algebra.cpp)
   PROVE_RESIDENT_TERMS,   // test hook: lowers the terms (pairs x chunks) up to which a funnel call under an alg::ResidentBasesScope goes to the resident tables, so a test can reach the old path beside the new one; unset, 0 or above 65,536: the primitive's own limit (algebra.cpp)
+  CT_FINISH_DIVSTEPS,     // the finish of the constant-time MSM (k_msm_ct_finish / _seg): 1 always the builds whose exit inverts by division steps (k_msm_ct_finish_ds / _seg_ds, csrc/invert_ds.h), 0 never; unset: the library's rule (kCtFinishDivstepsDefault, csrc/msm_kernels.h).  The results are bit-identical either way
   COUNT
 };
 // The knob's value, or -1 if it is not set (every knob's valid values are >= 0).

@@ -1089,6 +1089,55 @@ int curdle_g1_scalar_mul_batch_device_ex(const void* d_points, const void* d_sca
  * NOT in curdle_stat_normalize: it runs no normalisation kernel. */
 int curdle_stat_g1_mul_ct(unsigned long long out[2]);
 /* -------------------------------------------------------------------------
+ * Batched inversion in Fp, CONSTANT TIME in the elements: out[i] = in[i]^-1 for i < n, and 0 gives 0 (gnark's
+ * fp.Element.Inverse; for a whole vector, what fp.BatchInvert returns).  Items are gnark fp.Elements: 48 bytes,
+ * Montgomery, canonical, in and out.  One lane per element (k_fp_invert, csrc/fp_invert_kernels.hip), one launch per
+ * 2^20 elements, and the inversion is Bernstein-Yang's division steps (csrc/invert_ds.h): from (delta, f, g) = (1, p, x)
+ * a FIXED 1,110 steps -- the paper's bound for 381 bits is 1,101 -- of shifts, additions and masks on the low bits, in 37
+ * batches of 30, each followed by one 2 x 2 matrix on the full-width values; the step's two cases are taken by masks.
+ * out may be in (a lane reads its item before it writes it and touches no other).
+ * flags: CURDLE_FP_INVERT_FERMAT takes the exponent chain x^(p-2) of the point kernels (csrc/invert28.h) instead: the
+ * control, bit-identical results.  CURDLE_FP_INVERT_RAW28 is a diagnostic form: items are the 14 uint32 limbs of the
+ * library's internal field layer (csrc/fp28.h: 28 bits a limb, Montgomery radix 2^392), 56 bytes, normalised and below
+ * 2p going in, canonical coming out -- the form in which the exit of the constant-time MSM calls the inversion.  A bit
+ * that is not defined here: CURDLE_EINVAL.
+ * An element at or above p (raw form: a value at or above 2p, or a limb at or above 2^28) makes the call fail with
+ * CURDLE_EINVAL and, in the host form, out untouched (the _device form has written d_out by then: its contents are
+ * unspecified): the lanes OR a violation word into one status word, without a branch, and the host reads that word.
+ * THIS VERDICT IS THE ONLY THING ABOUT THE ELEMENTS THE CALL REVEALS.
+ * Refusals happen before any device work, in this order: an unknown flag bit, a null pointer with n > 0, n > 2^24, and
+ * (the _device form) device pointers that are not multiples of 16.  n = 0 then returns CURDLE_OK without a device.  No
+ * host fallback: without a device the call fails with CURDLE_ENODEV.  `stream` is as in curdle_msm_g1_device (the
+ * caller's stream, or NULL for the library's); the call returns when its work is done.  One MSM slot is held for the call.
+ * The host form stages the elements through pinned memory into a device buffer, inverts them there and brings them back
+ * only behind a clean verdict; the buffer and both stagings are overwritten on the stream that used them before it
+ * returns on every path.  The device form copies nothing but the status word.
+ * WHAT THE FLAG PROMISES (with or without a flag: both inversions are constant-time forms): the kernel's instruction
+ * stream (every branch, every exec mask beyond the end-of-array guard, every loop count) and its address stream (every
+ * load, store and atomic address) are independent of the values of the elements; they depend on n, flags and the
+ * pointers.  The host only copies the elements and never looks at them; of what the device computed it reads the
+ * violation word and the result.
+ * WHAT IT DOES NOT PROMISE: anything about data-dependent power draw and clock behaviour of the chip (a multiplier fed
+ * zeros draws less), which is not addressed.
+ * OUTSIDE THE PROMISE: the result itself and the verdict on the range; whatever the caller does with the elements
+ * before and after.
+ * curdle_stat_fp_invert: out[0] completed calls that ran on a device, out[1] elements in them; out[2] and out[3] count
+ * the finish launches of the constant-time MSM (k_msm_ct_finish / _seg, every caller of curdle_msm_g1_ct and its
+ * batched and resident-base forms) whose exit inverted by division steps (k_msm_ct_finish_ds / _seg_ds) and on the
+ * Fermat chain.  The knob CT_FINISH_DIVSTEPS (curdle_plan_override) chooses: 1 always division steps, 0 never; unset,
+ * the library's rule, which is division steps since round 37 measured them.  The result is bit for bit the same either
+ * way.
+ * Cost: an instruction count, NOT a measurement, of about 25 to 30 thousand 32/64-bit integer instructions per element
+ * against about 265 thousand for the Fermat chain; measured (profiles/r37_invert_ds.json) 0.11 / 0.16 / 0.86 / 12.0 ms at
+ * n = 64 / 4,096 / 65,536 / 2^20 against 0.50 / 0.54 / 1.27 / 13.6 ms under CURDLE_FP_INVERT_FERMAT; the finish kernel
+ * 0.34 against 0.80 ms over one segment of 256 terms and 3.93 against 11.03 ms over 4,096 segments of 16.
+ * ------------------------------------------------------------------------- */
+#define CURDLE_FP_INVERT_FERMAT 1u   /* the existing chain of invert28.h: the control, bit-identical results */
+#define CURDLE_FP_INVERT_RAW28  2u   /* diagnostic: items are 14 u32 internal limbs (radix 2^392), normalised, < 2p */
+int curdle_fp_invert_batch(const uint64_t* in, size_t n, uint64_t* out, unsigned flags);
+int curdle_fp_invert_batch_device(const void* d_in, size_t n, void* d_out, unsigned flags, void* stream);
+int curdle_stat_fp_invert(unsigned long long out[4]);
+/* -------------------------------------------------------------------------
  * Constant-time MSM for SECRET scalars: out = sum_i scalars[i] * points[i], the result bit for bit the 18 words
  * curdle_msm_g1 returns on the same input (canonical (x, y, 1), or its encoding of infinity).  curdle_msm_g1 is NOT
  * constant time in the scalars: its sort, its bucket addresses and its large-bucket queue are functions of them.  Here
